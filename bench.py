@@ -46,7 +46,14 @@ def parse_args(argv=None):
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the other BASELINE configs (one 640x480 frame, 8x1920x1080 n=4000 extract+match, the 1241x376 tracking loop) and the realistic-density stream")
     ap.add_argument("--pipelined-streams", type=int, default=2)
     ap.add_argument("--cpu-budget", type=float, default=12.0)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32/float64, <= 64 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def launch_ranks(args):
@@ -174,6 +181,50 @@ def cpu_baseline(frames, nfeatures, budget_s=12.0, all_cores_s=8.0):
         out["all_cores"] = {"value": tot[0] / el2, "unit": "keypoints/s", "cores": ncore,
                             "sample": "%d frames in %.1f s on %d threads; %.1f frames/s" % (tot[1], el2, ncore, tot[1] / el2)}
     return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, layout, blocks, ranges, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what a caller of the timed path receives for the stream, frame by frame in stream order, as .npy files.
+    `blocks[r]` is rank r's flat result block (my-slam_amd/shard.py), `ranges[r]` the (lo, hi) of the stream it owns.
+      keypoints.npy    float32 [N, 7]   x, y, size, angle, response, octave, class_id of every keypoint (the two ints by value)
+      descriptors.npy  float32 [N, 32]  the 32 descriptor bytes by value
+      matches.npy      float32 [N]      index of the matched keypoint in the previous frame, -1 = none
+      frame_index.npy, keypoint_counts.npy, match_counts.npy  float64 [F]  per dumped frame
+    When every frame at full capacity could exceed `limit` bytes, a fixed seeded sample of frames is written (the sample
+    depends only on the stream length and the capacity, never on the results)."""
+    import numpy as np
+    cap = layout.cap
+    frames = [(lo + j - 1, r, j) for r, (lo, hi) in enumerate(ranges) for j in range(1, hi - lo + 1)]
+    per_frame = cap * (7 + 32 + 1) * 4 + 3 * 8
+    keep = max(1, min(len(frames), limit // per_frame))
+    if keep < len(frames):
+        pick = np.sort(np.random.default_rng(0).choice(len(frames), keep, replace=False))
+        frames = [frames[i] for i in pick]
+    host = {}
+    kps, desc, m12, fidx, nk, nm = [], [], [], [], [], []
+    for f, r, j in frames:
+        if r not in host:
+            host[r] = layout.views(blocks[r].cpu())
+        kv, dv, mv, cv, nv = host[r]
+        n = int(cv[j])
+        k = kv[j, :n].numpy()
+        kf = k.copy()
+        kf[:, 5:7] = k.view(np.int32)[:, 5:7]          # octave, class_id: int32 in the 28-byte record
+        kps.append(kf)
+        desc.append(dv[j, :n].numpy().astype(np.float32))
+        m12.append(mv[j, :n].numpy().astype(np.float32))
+        fidx.append(f); nk.append(n); nm.append(int(nv[j]))
+    out = {"keypoints": np.concatenate(kps).astype(np.float32), "descriptors": np.concatenate(desc),
+           "matches": np.concatenate(m12), "frame_index": np.array(fidx, np.float64),
+           "keypoint_counts": np.array(nk, np.float64), "match_counts": np.array(nm, np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "frames": len(frames), "of_frames": sum(hi - lo for lo, hi in ranges),
+            "bytes": int(sum(a.nbytes for a in out.values()))}
 
 
 class DevicePath:
@@ -632,6 +683,13 @@ def main():
         gathered_ok = gk == nk_all
         if not gathered_ok:
             raise SystemExit("gathered block holds %d keypoints, the ranks produced %d" % (gk, nk_all))
+    dumped = None
+    if args.dump_outputs and rank == 0:   # the last timed step's result, before the profiling passes below run the extractor again
+        last = (step_no[0] - 1) % nslot
+        if comm_on:
+            dumped = dump_outputs(args.dump_outputs, layout, gather_bufs[last], ranges)
+        else:
+            dumped = dump_outputs(args.dump_outputs, layout, [path.bufs[last]], [(lo, hi)])
 
     # ---- per-stage GPU time (HIP events on the launch stream, inside the library) ----
     roof = None
@@ -777,6 +835,8 @@ def main():
         }
         if gathered_ok is not None:
             out["gathered_on_rank0"] = gathered_ok
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if force_comm:
             kv, dv, _, cv, _ = layout.views(path.bufs[(step_no[0] - 1) % nslot])
             out["forced_comm"] = {"backend": backend, "world_size": 1,

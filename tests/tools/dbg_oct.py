@@ -1,5 +1,5 @@
 import sys, os
-sys.path.insert(0, "/root/repo/tests"); sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import conftest, oracle_lib as O
 import my_slam_amd as M, my_slam_amd.synth as synth
