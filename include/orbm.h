@@ -328,8 +328,11 @@ int orbm_fuse_sim3(orbm_matcher *m, int n_mp, const uint8_t *use, const float *p
  * searches and the agreement check (:1188-1323).  One MapPoint slot per key-frame feature (n_mp1 == n1, n_mp2 == n2).
  * use1[i] = pMP && !vbAlreadyMatched1[i] && !isBad() && orbm_project_points_sim3's ok && the distance-invariance test (:1152-1183);
  * proj_u1 / proj_v1 = its projection into key frame 2, pred_level1 = PredictScale(dist3D, pKF2); use2 / proj_*2 / pred_level2 the
- * reverse.  Both grids are built by the call (slot 1 of the handle holds key frame 1's afterwards).  match12[i1] = the feature of
- * KF2 whose MapPoint goes into vpMatches12[i1], or -1; *nfound = the return value.
+ * reverse.  Once the arguments are valid the call ends in one of two states: both grids are built and slot 1 of the handle holds key
+ * frame 1's (orbm_grid_count() == n1), or the handle holds no grid (orbm_grid_count() == -1).  The second is the state after an
+ * empty side (n1 == 0 or n2 == 0), after a side without a usable MapPoint (every use1 or every use2 zero: nothing can match both
+ * ways) and after an error; the grid of an earlier call never survives it.  match12[i1] = the feature of KF2 whose MapPoint goes
+ * into vpMatches12[i1], or -1; *nfound = the return value.
  */
 int orbm_search_by_sim3(orbm_matcher *m,
                         int n_mp1, const uint8_t *use1, const float *proj_u1, const float *proj_v1, const int32_t *pred_level1,

@@ -162,6 +162,7 @@ def _bind_matcher(L):
     L.orbm_best2_batch_device.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.orbm_match_batch_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, vp, vp, vp]
     L.orbm_grid_build.argtypes = [vp, vp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float]
+    L.orbm_grid_count.argtypes = [vp]
     L.orbm_features_in_area.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int]
     L.orbm_search_area_best2.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp]
     L.orbm_search_area_best2_device.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
@@ -212,7 +213,7 @@ def _bind_matcher(L):
     L.orbm_last_error.restype = C.c_char_p
     for name in ("orbm_create", "orbm_distance", "orbm_best2", "orbm_distances", "orbm_best2_batch_device",
                  "orbm_match_batch_device", "orbm_rot_filter", "orbm_three_maxima", "orbm_grid_build",
-                 "orbm_features_in_area", "orbm_search_area_best2", "orbm_search_area_best2_device"):
+                 "orbm_features_in_area", "orbm_search_area_best2", "orbm_search_area_best2_device", "orbm_grid_count"):
         getattr(L, name).restype = C.c_int
 
 
@@ -506,6 +507,10 @@ class ORBmatcher:
         kps_un = np.ascontiguousarray(kps_un, KP_DTYPE)
         self._grid_n = len(kps_un)
         _mchk(self.L.orbm_grid_build(self.h, _p(kps_un), len(kps_un), min_x, max_x, min_y, max_y))
+
+    def grid_count(self):
+        """Keypoints in the handle's grid (frame or key frame), -1 when it holds none."""
+        return self.L.orbm_grid_count(self.h)
 
     @staticmethod
     def _windows(x, y, r, min_level, max_level):

@@ -487,6 +487,9 @@ extern "C" int orbm_search_by_sim3(orbm_matcher *m,
     if (n_mp1 != n1 || n_mp2 != n2) return mfail(ORBX_E_INVALID, "one MapPoint slot per key-frame feature: n_mp1 = %d / n1 = %d, n_mp2 = %d / n2 = %d", n_mp1, n1, n_mp2, n2);
     *nfound = 0;
     for (int i = 0; i < n_mp1; i++) match12[i] = -1;
+    // from here on the call leaves either both grids built (slot 1 = key frame 1) or no grid at all: an early return must not leave
+    // the grid of an earlier call behind, which a caller that relabels the slot by its keypoint count would take for key frame 1's
+    m->grid_ok = false; m->grid2_ok = false;
     if (n1 == 0 || n2 == 0) return ORBX_OK;
     KfQueries Q1, Q2;                                // Q1: MapPoints of key frame 1 searched in key frame 2 (:1148-1225); Q2: the reverse (:1228-1305)
     rc = Q1.build(n_mp1, use1, proj_u1, proj_v1, nullptr, pred_level1, mp_desc1, scale_factors2, nlevels2, th);
@@ -496,7 +499,6 @@ extern "C" int orbm_search_by_sim3(orbm_matcher *m,
     const int nq1 = (int)Q1.src.size(), nq2 = (int)Q2.src.size();
     if (nq1 == 0 || nq2 == 0) return ORBX_OK;       // a match needs both directions
     MHIPCHK(hipSetDevice(m->device));
-    m->grid_ok = false; m->grid2_ok = false;
     rc = orbm_grow(m, 2 * std::max(nq1, nq2), std::max(n1, n2), 0);
     if (rc != ORBX_OK) return rc;
     rc = orbm_arena_begin(m);

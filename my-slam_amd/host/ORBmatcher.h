@@ -414,6 +414,7 @@ public:
                                     pKF2->mDescriptors.ptr<unsigned char>(), N2, &g2, pKF2->mvScaleFactors.data(), (int)pKF2->mvScaleFactors.size(), th,
                                     S.match_.data(), &nf)))
             return 0;
+        // keep this check: a call with nothing to search returns without building grids and leaves none (count -1), not key frame 1's
         if (orbm_grid_count(h_.m) == N1) { h_.gridKind = 1; h_.gridFrame = (unsigned long)pKF1->mnId; h_.gridKeys = (const void *)pKF1->mvKeysUn.data(); h_.gridN = N1; }
         for (int i1 = 0; i1 < N1; i1++)
             if (S.match_[i1] >= 0) vpMatches12[i1] = vpMapPoints2[S.match_[i1]];               // :1319

@@ -10,6 +10,7 @@
 //   src/LoopClosing.cc:590,600   ORBmatcher matcher(0.8); matcher.Fuse(pKF,cvScw,mvpLoopMapPoints,4,vpReplacePoints)
 // For the two Fuse variants the object graph after the call (key-frame slots, bad flags, observation counts, replacement links) is
 // compared with a model that replays src/ORBmatcher.cc:952-971 / :1082-1096 on the C ABI's match table.
+// The last block drives this thread's pooled handle through Fuse(X), an empty SearchBySim3 and Fuse(KF1) (row Fuse(KF,after-empty-Sim3)).
 // The Frame / KeyFrame / MapPoint classes are the minimal ones of tests/cxx/slam_shims/ (an ORB-SLAM2 tree brings its own).
 // usage: mapping_callsites frames.u8 layer.u8 W H vocabulary.txt      (frames.u8 = two W x H frames, layer.u8 = depth layer per pixel)
 // prints one line per call site: <name> <result> <1 if equal to the C ABI>.
@@ -88,10 +89,10 @@ struct Flat {                        // the MapPoints of a list as arrays (what 
 
 // a light model of the object graph for replaying Fuse's bookkeeping (src/ORBmatcher.cc:952-971; MapPoint::Replace, AddObservation)
 struct Model {
-    struct MP { bool bad; int obs; map<int, int> in; MapPoint *replaced; };      // in: key frame (0 / 1) -> slot
+    struct MP { bool bad; int obs; map<int, int> in; MapPoint *replaced; };      // in: key frame (0 / 1 / 2) -> slot
     map<MapPoint *, MP> mp;
-    vector<MapPoint *> slot[2];
-    vector<float> uright[2];
+    vector<MapPoint *> slot[3];
+    vector<float> uright[3];
     void add_obs(MapPoint *p, int kf, int idx) { MP &m = mp[p]; if (m.in.count(kf)) return; m.in[kf] = idx; m.obs += uright[kf][idx] >= 0 ? 2 : 1; }
     void replace(MapPoint *a, MapPoint *b)      // a->Replace(b)
     {
@@ -127,7 +128,7 @@ int main(int argc, char **argv)
     auto report = [&](const char *name, int nm, bool same) { printf("%s %d %d\n", name, nm, same ? 1 : 0); nfail += !same; };
 
     // ---- the two key frames: frame 0 at the origin, frame 1 a baseline further along +x; MapPoints = back-projected keypoints ----
-    Side sd[2];
+    Side sd[3];                                       // [2]: the mirrored key frame X of the last block
     vector<float> logSf(1);
     for (int s = 0; s < 2; s++) {
         cv::Mat im(H, W, CV_8UC1, raw.data() + (size_t)s * W * H, W);
@@ -321,12 +322,13 @@ int main(int argc, char **argv)
     }
     auto graph_equals_model = [&]() {
         bool same = true;
-        for (int s = 0; s < 2 && same; s++)
+        for (int s = 0; s < 3 && same; s++)
             for (int i = 0; i < (int)M.slot[s].size() && same; i++) same = sd[s].kf->GetMapPoint(i) == M.slot[s][i];
         for (auto &e : M.mp) {
             if (!same) break;
             same = e.first->isBad() == e.second.bad && e.first->Observations() == e.second.obs && e.first->GetReplaced() == e.second.replaced &&
-                   e.first->IsInKeyFrame(sd[0].kf) == (e.second.in.count(0) != 0) && e.first->IsInKeyFrame(sd[1].kf) == (e.second.in.count(1) != 0);
+                   e.first->IsInKeyFrame(sd[0].kf) == (e.second.in.count(0) != 0) && e.first->IsInKeyFrame(sd[1].kf) == (e.second.in.count(1) != 0) &&
+                   (!sd[2].kf || e.first->IsInKeyFrame(sd[2].kf) == (e.second.in.count(2) != 0));
         }
         return same;
     };
@@ -381,16 +383,11 @@ int main(int argc, char **argv)
     }
 
     // ================= LocalMapping::SearchInNeighbors (src/LocalMapping.cc:485-516) =================
-    for (int dir = 0; dir < 2; dir++) {
+    // the points fused into key frame b (sd[b]) by a fresh ORBmatcher on this thread's pooled handle, against orbm_fuse on a grid built
+    // for the call in `ref` and the model's replay of :842-850 / :952-971
+    auto fuse_into = [&](int b, const vector<MapPoint *> &vpMapPointMatches, int *nFusedOut) {
         ORBmatcher matcher;
-        const int a = dir, b = 1 - dir;                       // points of key frame a fused into key frame b
         KeyFrame *pKFi = sd[b].kf;
-        vector<MapPoint*> vpMapPointMatches = sd[a].kf->GetMapPointMatches();
-        if (dir == 1) {                                        // vpFuseCandidates: no NULLs, no bad points (:497-512)
-            vector<MapPoint *> c;
-            for (MapPoint *p : vpMapPointMatches) if (p && !p->isBad()) c.push_back(p);
-            vpMapPointMatches = c;
-        }
         const int n = (int)vpMapPointMatches.size(), nB = sd[b].kf->N;
         Flat f;
         f.from(vpMapPointMatches);
@@ -424,8 +421,69 @@ int main(int argc, char **argv)
             wantFused++;
         }
         int nFused = matcher.Fuse(pKFi,vpMapPointMatches);
-        bool same = nFused == wantFused && graph_equals_model();
+        *nFusedOut = nFused;
+        return nFused == wantFused && graph_equals_model();
+    };
+    for (int dir = 0; dir < 2; dir++) {
+        const int a = dir, b = 1 - dir;                       // points of key frame a fused into key frame b
+        vector<MapPoint*> vpMapPointMatches = sd[a].kf->GetMapPointMatches();
+        if (dir == 1) {                                        // vpFuseCandidates: no NULLs, no bad points (:497-512)
+            vector<MapPoint *> c;
+            for (MapPoint *p : vpMapPointMatches) if (p && !p->isBad()) c.push_back(p);
+            vpMapPointMatches = c;
+        }
+        int nFused = 0;
+        const bool same = fuse_into(b, vpMapPointMatches, &nFused);
         report(dir == 0 ? "Fuse(KF,points)" : "Fuse(KF,candidates)", nFused, same);
+    }
+
+    // ================= one thread's handle through Fuse(X), an empty SearchBySim3 and Fuse(KF1) =================
+    // X = key frame 1 mirrored (x -> W-1-x): the same N, the same descriptors, other cells.  Fuse(X, ...) leaves X's grid in the pooled
+    // handle; SearchBySim3 with every slot of vpMatches12 taken has nothing to search (nq1 == 0) and must not leave that grid behind
+    // labelled as key frame 1's, or the next Fuse(KF1, ...) on this thread searches X's cells.  The points: fresh MapPoints at key
+    // frame 1's points (another key frame's triangulation of them), so that they are neither in key frame 1 nor in X.
+    {
+        KeyFrame *pKF1 = mpCurrentKeyFrame;
+        vector<cv::KeyPoint> mirrored = pKF1->mvKeysUn;
+        for (cv::KeyPoint &kp : mirrored) kp.pt.x = (float)(W - 1) - kp.pt.x;
+        sd[2] = sd[0];
+        sd[2].kf = new KeyFrame(20, mirrored, pKF1->mvuRight, pKF1->mDescriptors, pKF1->mFeatVec, vector<MapPoint *>(N1, static_cast<MapPoint *>(NULL)), fx, fy,
+                                cx, cy, bf, Frame::mfGridElementWidthInv, Frame::mfGridElementHeightInv, Frame::mnMinX, Frame::mnMinY, Frame::mnMaxX,
+                                Frame::mnMaxY, pKF1->mvScaleFactors, pKF1->mvLevelSigma2, pKF1->mvInvLevelSigma2, pKF1->mfLogScaleFactor);
+        cv::Mat Tcw = eye4();
+        for (int r = 0; r < 4; r++) for (int c = 0; c < 4; c++) Tcw.at<float>(r, c) = sd[0].T[4 * r + c];
+        sd[2].kf->SetPose(Tcw);
+        sd[2].kf->SetCameraCenter(pKF1->GetCameraCenter());
+        sd[2].mps = sd[2].kf->GetMapPointMatches();
+        M.slot[2] = sd[2].mps; M.uright[2] = sd[2].kf->mvuRight;
+        vector<MapPoint *> points;
+        for (MapPoint *p : pKF1->GetMapPointMatches()) {
+            if (!p || p->isBad()) continue;
+            MapPoint *q = new MapPoint(p->GetWorldPos(), p->GetDescriptor(), 1, p->MaxDistance() / pKF1->mvScaleFactors[nLevels - 1], p->MaxDistance());
+            const cv::Mat N = p->GetNormal();
+            q->SetNormal(N.at<float>(0), N.at<float>(1), N.at<float>(2));
+            Model::MP m; m.bad = false; m.obs = 1; m.replaced = nullptr; M.mp[q] = m;
+            points.push_back(q);
+        }
+        int nX = 0, nFused = 0;
+        bool same = fuse_into(2, points, &nX);
+        {
+            ORBmatcher matcher(0.75,true);
+            vector<MapPoint *> vpMatches12(N1, static_cast<MapPoint *>(NULL));
+            vector<MapPoint *> kf2 = pKF2->GetMapPointMatches();
+            for (int k = 0, j = 0; k < N1; k++, j++) {             // every slot taken: vbAlreadyMatched1 is all true
+                while (!kf2[j % N2]) j++;
+                vpMatches12[k] = kf2[j % N2];
+            }
+            const vector<MapPoint *> before = vpMatches12;
+            cv::Mat R(3, 3, CV_32F), t(3, 1, CV_32F);
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) R.at<float>(r, c) = r == c ? 1.f : 0.f;
+            t.at<float>(0) = base; t.at<float>(1) = 0.f; t.at<float>(2) = 0.f;
+            const int nfound = matcher.SearchBySim3(pKF1,pKF2,vpMatches12,1.0f,R,t,7.5);
+            same = same && nfound == 0 && vpMatches12 == before;
+        }
+        same = fuse_into(0, points, &nFused) && same;
+        report("Fuse(KF,after-empty-Sim3)", nFused, same);
     }
 
     orbm_destroy(ref);

@@ -111,7 +111,9 @@ def test_tracking_callsites_equal_cabi(orbx, synth, tmp_path):
 def test_mapping_callsites_equal_cabi(orbx, synth, tmp_path):
     """The reference's LocalMapping / LoopClosing call expressions (SearchForTriangulation, Fuse x 2, SearchByBoW(KF, KF), SearchBySim3,
     SearchByProjection(KF, Scw)) on the drop-in class == direct C-ABI calls (which tests/test_kf_matchers.py ties to the oracle); for
-    the Fuse variants the object graph after the call equals a replay of the reference's bookkeeping on the C ABI's match table."""
+    the Fuse variants the object graph after the call equals a replay of the reference's bookkeeping on the C ABI's match table.
+    Fuse(KF,after-empty-Sim3): one thread's pooled handle through Fuse(X) (X = key frame 1 mirrored, same N), a SearchBySim3 with
+    nothing to search, and Fuse(key frame 1), which must search key frame 1's grid and not the one X left in the handle."""
     import test_vocabulary as TV
     exe = _build(orbx, "mapping_callsites.cc", str(tmp_path / "mapping_callsites"))
     W, H = 1241, 376
@@ -123,7 +125,7 @@ def test_mapping_callsites_equal_cabi(orbx, synth, tmp_path):
     assert p.returncode == 0, p.stdout + p.stderr
     rows = {ln.split()[0]: ln.split()[1:] for ln in p.stdout.splitlines() if ln.strip()}
     want = {"SearchForTriangulation": 40, "SearchByBoW(KF,KF)": 30, "SearchBySim3": 100, "SearchByProjection(KF,Scw)": 100, "Fuse(KF,Scw)": 100,
-            "Fuse(KF,points)": 100, "Fuse(KF,candidates)": 20}
+            "Fuse(KF,points)": 100, "Fuse(KF,candidates)": 20, "Fuse(KF,after-empty-Sim3)": 100}
     for name, floor in want.items():
         assert name in rows, p.stdout
         assert int(rows[name][1]) == 1, "%s differs from the C ABI\n%s" % (name, p.stdout)
