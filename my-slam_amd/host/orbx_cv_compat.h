@@ -1,6 +1,7 @@
 // orbx_cv_compat.h -- the handful of OpenCV 3.1.0 core types the adapters use, for hosts WITHOUT OpenCV
 // (this image has none).  With OpenCV present the adapters include the real headers and this file is not
-// used.  It is NOT a stand-in for building the reference: it exists so that my-slam_amd/host/*.h can be
+// used.  It is not the stand-in the reference is built on (that is oracle/ref/cv_shim/, test infrastructure that
+// pins the extractor to the reference's own ORBextractor.cc -- DESIGN.md section 2): it exists so that my-slam_amd/host/*.h can be
 // compiled and exercised by this repo's own tests THROUGH THE SAME CODE PATH a maintainer compiles against
 // OpenCV: the adapters are written against OpenCV's API (InputArray::getMat(), OutputArray::create(),
 // unqualified CV_8U ...), and this header models exactly those calls:

@@ -1,6 +1,6 @@
 /*
  * orb_oracle.c -- CPU restatement of the reference ORB front-end (see orb_oracle.h header note:
- * TEST INFRASTRUCTURE ONLY; PARITY UNPINNED at the OpenCV 3.1.0 boundary).
+ * TEST INFRASTRUCTURE ONLY; the reference's own logic is pinned by oracle/ref/, the OpenCV 3.1.0 primitives are not).
  *
  * Build: gcc -O2 -std=c11 -ffp-contract=off -fno-fast-math (strict IEEE fp32).
  * All file:line citations are relative to /root/reference.

@@ -5,11 +5,12 @@
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg use it, as the checker
  * and as the reported CPU baseline ("kind": "port").
  *
- * PARITY UNPINNED: the reference (WChen09/My-SLAM) ships no tests, fixtures or golden vectors for
- * this path and cannot be built here (needs OpenCV 3.1.0, absent; writing stand-in
- * headers for it is not allowed).  Four of the stages' arithmetic lives in OpenCV 3.1.0 (resize,
- * FAST, GaussianBlur, fastAtan2/cvRound), restated here from its published algorithm; every such
- * decision point is marked "OpenCV 3.1.0:" in orb_oracle.c.  The reference's own logic is restated
+ * The reference (WChen09/My-SLAM) ships no tests, fixtures or golden vectors for this path (SURVEY.md
+ * F5).  The extraction path is pinned to the reference's own src/ORBextractor.cc, built unmodified on
+ * the OpenCV shim of oracle/ref/ (tests/test_reference_pin_cpu.py).  Four of the stages' arithmetic
+ * lives in OpenCV 3.1.0 (resize, FAST, GaussianBlur, fastAtan2/cvRound), restated here from its
+ * published algorithm; the shim calls these same primitives, so they remain the project's reading.
+ * Every such decision point is marked "OpenCV 3.1.0:" in orb_oracle.c.  The reference's own logic is restated
  * line by line with file:line citations (paths relative to /root/reference).
  */
 #ifndef ORB_ORACLE_H

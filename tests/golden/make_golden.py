@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Generate tests/golden/*.npz from the oracle (CPU restatement) on seeded synthetic frames.
 
-PARITY UNPINNED: the reference ships no fixtures and cannot be built here (no OpenCV 3.1.0), so these
-vectors freeze the ORACLE's behaviour (regression pin + GPU-box fixture), not the reference's.
+The reference ships no fixtures.  These vectors freeze the oracle's behaviour (regression pin + GPU-box fixture);
+tests/test_reference_pin_cpu.py checks that each extraction fixture is also what the reference's own
+src/ORBextractor.cc computes (built on the OpenCV shim of oracle/ref/, which shares the oracle's OpenCV primitives).
 Run from the repo root:  python tests/golden/make_golden.py
 """
 import hashlib
