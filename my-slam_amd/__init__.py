@@ -101,6 +101,7 @@ def lib():
     _bind_matcher(L)
     _bind_voc(L)
     _bind_pose(L)
+    _bind_kfdb(L)
     _lib = L
     return L
 
@@ -120,6 +121,26 @@ def _bind_voc(L):
     L.orbv_score_l1.restype = C.c_double
     L.orbv_last_error.restype = C.c_char_p
     for name in ("orbv_load_text", "orbv_info", "orbv_transform_features", "orbv_bow_vector", "orbv_feature_vector"):
+        getattr(L, name).restype = C.c_int
+
+
+def _bind_kfdb(L):
+    vp, ip, u64 = C.c_void_p, C.POINTER(C.c_int), C.c_uint64
+    if not hasattr(L, "orbk_create"):
+        return
+    L.orbk_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.orbk_destroy.argtypes = [vp]
+    L.orbk_destroy.restype = None
+    L.orbk_add.argtypes = [vp, u64, vp, vp, C.c_int]
+    L.orbk_erase.argtypes = [vp, u64]
+    L.orbk_clear.argtypes = [vp]
+    L.orbk_size.argtypes = [vp]
+    L.orbk_score.argtypes = [vp, vp, vp, C.c_int, vp, C.c_int, ip]
+    L.orbk_query_begin.argtypes = [vp, C.c_int, u64, vp, vp, C.c_int, vp, C.c_int, C.c_float, vp, vp, C.c_int, ip]
+    L.orbk_query_end.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, ip]
+    L.orbk_last_error.restype = C.c_char_p
+    for name in ("orbk_create", "orbk_add", "orbk_erase", "orbk_clear", "orbk_size", "orbk_score", "orbk_query_begin",
+                 "orbk_query_end"):
         getattr(L, name).restype = C.c_int
 
 
@@ -828,6 +849,100 @@ class ORBVocabulary:
 
     def score(self, bow1, bow2):
         return self.L.orbv_score_l1(_p(bow1[0]), _p(bow1[1]), len(bow1[0]), _p(bow2[0]), _p(bow2[1]), len(bow2[0]))
+
+
+ORBK_RELOC, ORBK_LOOP = 0, 1
+ORBK_RECORD = np.dtype([("id", "<u8"), ("words", "<i4"), ("first", "<i4"), ("score", "<f8")])
+assert ORBK_RECORD.itemsize == 24
+
+
+def _kchk(rc):
+    if rc != ORBX_OK:
+        raise OrbxError(rc, lib().orbk_last_error().decode())
+
+
+def _bow(bow):
+    ids, vals = bow
+    return np.ascontiguousarray(ids, np.int32), np.ascontiguousarray(vals, np.float64)
+
+
+class KeyFrameDatabase:
+    """ORB_SLAM2::KeyFrameDatabase (src/KeyFrameDatabase.cc) over include/orbk.h.  Keyframes are ids with a BowVector
+    (ascending word ids, values); covis maps an id to its GetBestCovisibilityKeyFrames(10), in order."""
+
+    def __init__(self, nwords, scoring=0, device=0, max_keyframes=1024, max_entries=1 << 20):
+        self.L = lib()
+        self.h = C.c_void_p()
+        _kchk(self.L.orbk_create(C.byref(self.h), device, nwords, scoring, max_keyframes, max_entries))
+
+    def close(self):
+        if getattr(self, "h", None) is not None and self.h:
+            self.L.orbk_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def add(self, kf_id, bow):
+        ids, vals = _bow(bow)
+        _kchk(self.L.orbk_add(self.h, kf_id, _p(ids), _p(vals), len(ids)))
+
+    def erase(self, kf_id):
+        _kchk(self.L.orbk_erase(self.h, kf_id))
+
+    def clear(self):
+        _kchk(self.L.orbk_clear(self.h))
+
+    def __len__(self):
+        n = self.L.orbk_size(self.h)
+        _kchk(min(n, 0))
+        return n
+
+    def score(self, bow):
+        """One record (id, words, first, score) per live keyframe sharing a word with bow, in add order."""
+        ids, vals = _bow(bow)
+        n = C.c_int(max(len(self), 1))
+        while True:         # another thread may add keyframes after the size is read: retry with the count the call needs
+            out = np.zeros(max(n.value, 1), ORBK_RECORD)
+            rc = self.L.orbk_score(self.h, _p(ids), _p(vals), len(ids), _p(out), len(out), C.byref(n))
+            if rc != ORBX_E_CAPACITY:
+                break
+        _kchk(rc)
+        return out[:n.value].copy()
+
+    def query_begin(self, kind, query_id, bow, connected=(), min_score=0.0, cap=None):
+        """Phase 1: returns lScoreAndMatch as (ids uint64, si float32) in encounter order.  With cap given, a scored list
+        longer than cap raises ORBX_E_CAPACITY (and changes no state); without it the buffer grows to what the call needs."""
+        ids, vals = _bow(bow)
+        conn = np.ascontiguousarray(list(connected), np.uint64)
+        n = C.c_int(max(len(self), 1) if cap is None else cap)
+        while True:         # a capacity error commits no state, so the retry is the same query
+            c = n.value if cap is None else cap
+            sc = np.zeros(max(c, 1), np.uint64); si = np.zeros(max(c, 1), np.float32)
+            rc = self.L.orbk_query_begin(self.h, kind, query_id, _p(ids), _p(vals), len(ids), _p(conn), len(conn),
+                                         min_score, _p(sc), _p(si), c, C.byref(n))
+            if rc != ORBX_E_CAPACITY or cap is not None:
+                break
+        _kchk(rc)
+        return sc[:n.value].copy(), si[:n.value].copy()
+
+    def query_end(self, kind, scored, covis):
+        """Phase 2: covis maps each scored id to its ordered neighbour ids; returns the candidate ids."""
+        nb = [list(covis.get(int(k), ())) for k in scored]
+        off = np.zeros(len(nb) + 1, np.int32)
+        off[1:] = np.cumsum([len(x) for x in nb]) if nb else []
+        nb_ids = np.ascontiguousarray([x for l in nb for x in l], np.uint64)
+        out = np.zeros(max(len(scored), 1), np.uint64)
+        n = C.c_int()
+        _kchk(self.L.orbk_query_end(self.h, kind, _p(off), _p(nb_ids), _p(out), len(out), C.byref(n)))
+        return [int(x) for x in out[:n.value]]
+
+    def DetectRelocalizationCandidates(self, query_id, bow, covis):
+        sc, _ = self.query_begin(ORBK_RELOC, query_id, bow)
+        return self.query_end(ORBK_RELOC, sc, covis)
+
+    def DetectLoopCandidates(self, query_id, bow, connected, min_score, covis):
+        sc, _ = self.query_begin(ORBK_LOOP, query_id, bow, connected, min_score)
+        return self.query_end(ORBK_LOOP, sc, covis)
 
 
 def UndistortKeyPoints(kps, fx, fy, cx, cy, dist_coef):
