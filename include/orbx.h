@@ -154,6 +154,12 @@ int orbx_stage_ms_ring(orbx_extractor *h, float *ms, int max_calls);
  * `right` are the two extractor handles of the stereo rig (src/Frame.cc:78-81); the pyramids of their last
  * orbx_extract call (mvImagePyramid) are read in place.  Inputs are that call's keypoints/descriptors
  * (host); mb = mbf/fx, mbf as in Frame.  Outputs mvuRight / mvDepth (nl floats, -1 = no match).
+ * Which pyramid a handle exposes is that of its last extraction call: the frame of orbx_extract or of
+ * orbx_extract_begin/end, and FRAME 0 of orbx_extract_batch / orbx_extract_batch_device.  Levels >= 1 are frame 0's
+ * slot of the handle's own pyramid; level 0 is read where that call read frame 0: the handle's upload buffer for the
+ * host entry points, but the CALLER's device buffer for orbx_extract_batch_device, which must therefore hold the same
+ * bytes until this call returns.  Both handles need the same nlevels (else ORBX_E_INVALID) and the same level sizes
+ * (else ORBX_E_SHAPE); nr >= 2^22 returns ORBX_E_CAPACITY before anything is allocated or launched.
  */
 int orbx_stereo_matches(orbx_extractor *left, orbx_extractor *right,
                         const orbx_keypoint *kl, const uint8_t *dl, int nl,

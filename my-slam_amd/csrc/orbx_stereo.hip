@@ -153,6 +153,7 @@ extern "C" int orbx_stereo_matches(orbx_extractor *left, orbx_extractor *right,
                                    float mb, float mbf, float *u_right, float *depth)
 {
     if (!left || !right || nl < 0 || nr < 0) return ORBX_E_INVALID;
+    if (nr >= (1 << 22)) return ORBX_E_CAPACITY;                  // k_stereo's key is dist << 22 | iR
     if (nl == 0) return ORBX_OK;
     if (!kl || !dl || !u_right || !depth || (nr > 0 && (!kr || !dr))) return ORBX_E_INVALID;
     StereoLevels lv;

@@ -4,10 +4,14 @@
  * operation forwards to the oracle's primitive (oracle/orb_oracle.h), so the reference's own
  * ORBextractor.cc runs unmodified on top of the project's reading of OpenCV 3.1.0's arithmetic.
  *
- * TEST INFRASTRUCTURE ONLY: linked into oracle/_ref/ref_orbx (oracle/ref/ref_orbx.cc), never
- * into the library.  Scope:
- *   - Mat: single-channel 8-bit only, reference counted, with ROI views (operator()(Rect),
- *     rowRange, colRange, adjustROI).  A view keeps its parent buffer alive.
+ * TEST INFRASTRUCTURE ONLY: linked into oracle/_ref/ref_orbx (oracle/ref/ref_orbx.cc) and
+ * oracle/_ref/ref_stereo (oracle/ref/ref_stereo.cc), never into the library.  Scope:
+ *   - Mat: single-channel 8-bit or 32-bit float, reference counted, with ROI views (operator()(Rect),
+ *     rowRange, colRange, row, adjustROI).  A view keeps its parent buffer alive.  An ROI outside
+ *     the matrix aborts, as OpenCV's CV_Assert does.
+ *   - what Frame::ComputeStereoMatches uses on float windows: convertTo(CV_32F), at<float>,
+ *     Mat::ones, scalar * Mat and Mat - Mat (evaluated at once: MatExpr is not modelled), and
+ *     norm(a, b, NORM_L1) (a double sum of |a - b|).
  *   - copyMakeBorder treats its source as an isolated image (BORDER_ISOLATED or not); the
  *     driver only hands the extractor whole images.
  *   - KeyPointsFilter::retainBest is only reached from ComputeKeyPointsOld, which the
@@ -34,12 +38,15 @@ typedef unsigned char uchar;
 
 #define CV_8U 0
 #define CV_8UC1 0
+#define CV_32F 5
+#define CV_32FC1 5
 #define CV_PI 3.1415926535897932384626433832795
 
 namespace cv {
 
 enum { BORDER_REFLECT_101 = 4, BORDER_DEFAULT = 4, BORDER_ISOLATED = 16 };
 enum { INTER_LINEAR = 1 };
+enum { NORM_L1 = 2 };
 
 /* GaussianBlur's column rounding (ORO_BLUR_SCALAR or ORO_BLUR_X86_SIMD); set by the driver */
 void shim_set_blur_mode(int mode);
@@ -114,35 +121,44 @@ public:
     uchar *data;
     size_t step;
 
-    Mat() : rows(0), cols(0), data(0), step(0), whole_rows_(0), whole_cols_(0), buf_() {}
+    Mat() : rows(0), cols(0), data(0), step(0), type_(CV_8UC1), whole_rows_(0), whole_cols_(0), buf_() {}
     Mat(int r, int c, int type) : Mat() { create(r, c, type); }
     Mat(Size sz, int type) : Mat() { create(sz.height, sz.width, type); }
     /* user data: not owned */
     Mat(int r, int c, int type, void *ptr, size_t step_ = 0)
-        : rows(r), cols(c), data((uchar *)ptr), step(step_ ? step_ : (size_t)c), whole_rows_(r), whole_cols_(c),
-          base_((uchar *)ptr), buf_()
+        : rows(r), cols(c), data((uchar *)ptr), step(step_ ? step_ : (size_t)c * elem(type)), type_(type), whole_rows_(r),
+          whole_cols_(c), base_((uchar *)ptr), buf_()
     {
-        (void)type;
+        check_type(type);
     }
 
     static MatZeros zeros(int r, int c, int type) { MatZeros z = {r, c, type}; return z; }
+    static Mat ones(int r, int c, int type)
+    {
+        if (type != CV_32F) { std::fprintf(stderr, "cv_shim: Mat::ones is CV_32F only\n"); std::abort(); }
+        Mat m(r, c, type);
+        for (int y = 0; y < r; y++)
+            for (int x = 0; x < c; x++) m.at<float>(y, x) = 1.0f;
+        return m;
+    }
 
     /* MatExpr assignment: evaluated into this matrix, which is reallocated only on a size change */
     Mat &operator=(const MatZeros &z)
     {
         create(z.rows, z.cols, z.type);
-        for (int y = 0; y < rows; y++) std::memset(ptr(y), 0, (size_t)cols);
+        for (int y = 0; y < rows; y++) std::memset(ptr(y), 0, (size_t)cols * elemSize());
         return *this;
     }
 
     void create(int r, int c, int type)
     {
-        if (type != CV_8UC1) { std::fprintf(stderr, "cv_shim: only CV_8UC1\n"); std::abort(); }
-        if (data && r == rows && c == cols) return;
+        check_type(type);
+        if (data && r == rows && c == cols && type == type_) return;
         release();
-        rows = r; cols = c; step = (size_t)c;
+        type_ = type;
+        rows = r; cols = c; step = (size_t)c * elem(type);
         whole_rows_ = r; whole_cols_ = c;
-        size_t n = (size_t)r * (size_t)c;
+        size_t n = (size_t)r * step;
         buf_ = std::shared_ptr<std::vector<uchar> >(new std::vector<uchar>(n ? n : 1));
         data = buf_->data();
         base_ = data;
@@ -150,27 +166,39 @@ public:
     void create(Size sz, int type) { create(sz.height, sz.width, type); }
     void release() { buf_.reset(); data = 0; rows = cols = 0; step = 0; }
     bool empty() const { return data == 0 || rows == 0 || cols == 0; }
-    int type() const { return CV_8UC1; }
-    size_t step1() const { return step; }
+    int type() const { return type_; }
+    size_t elemSize() const { return elem(type_); }
+    size_t step1() const { return step / elemSize(); }
     size_t total() const { return (size_t)rows * cols; }
     Size size() const { return Size(cols, rows); }
-    bool isContinuous() const { return step == (size_t)cols || rows == 1; }
+    bool isContinuous() const { return step == (size_t)cols * elemSize() || rows == 1; }
 
     uchar *ptr(int y = 0) { return data + (size_t)y * step; }
     const uchar *ptr(int y = 0) const { return data + (size_t)y * step; }
-    template <typename T> T &at(int y, int x) { return *(T *)(data + (size_t)y * step + x); }
-    template <typename T> const T &at(int y, int x) const { return *(const T *)(data + (size_t)y * step + x); }
+    template <typename T> T &at(int y, int x) { return *(T *)(data + (size_t)y * step + (size_t)x * sizeof(T)); }
+    template <typename T> const T &at(int y, int x) const { return *(const T *)(data + (size_t)y * step + (size_t)x * sizeof(T)); }
 
     Mat operator()(const Rect &r) const
     {
         check_range(r.y, r.y + r.height, rows); check_range(r.x, r.x + r.width, cols);
         Mat m(*this);
-        m.data = data + (size_t)r.y * step + r.x;
+        m.data = data + (size_t)r.y * step + (size_t)r.x * elemSize();
         m.rows = r.height; m.cols = r.width;
         return m;
     }
     Mat rowRange(int a, int b) const { return (*this)(Rect(0, a, cols, b - a)); }
     Mat colRange(int a, int b) const { return (*this)(Rect(a, 0, b - a, rows)); }
+    Mat row(int y) const { return rowRange(y, y + 1); }
+
+    /* into a new CV_32F matrix (from 8-bit or float), then assigned to dst (which may be this matrix) */
+    void convertTo(Mat &dst, int rtype) const
+    {
+        if (rtype != CV_32F) { std::fprintf(stderr, "cv_shim: convertTo is CV_32F only\n"); std::abort(); }
+        Mat out(rows, cols, CV_32F);
+        for (int y = 0; y < rows; y++)
+            for (int x = 0; x < cols; x++) out.at<float>(y, x) = type_ == CV_32F ? at<float>(y, x) : (float)ptr(y)[x];
+        dst = out;
+    }
 
     /* grows or shrinks the view inside its parent buffer, clipped to the parent */
     Mat &adjustROI(int dtop, int dbottom, int dleft, int dright)
@@ -186,27 +214,68 @@ public:
 
     Mat clone() const
     {
-        Mat m(rows, cols, CV_8UC1);
-        for (int y = 0; y < rows; y++) std::memcpy(m.ptr(y), ptr(y), (size_t)cols);
+        Mat m(rows, cols, type_);
+        for (int y = 0; y < rows; y++) std::memcpy(m.ptr(y), ptr(y), (size_t)cols * elemSize());
         return m;
     }
     void copyTo(Mat &dst) const
     {
-        if (dst.data == data && dst.step == step && dst.rows == rows && dst.cols == cols) return;
+        if (dst.data == data && dst.step == step && dst.rows == rows && dst.cols == cols && dst.type_ == type_) return;
         Mat tmp = clone();
-        dst.create(rows, cols, CV_8UC1);
-        for (int y = 0; y < rows; y++) std::memcpy(dst.ptr(y), tmp.ptr(y), (size_t)cols);
+        dst.create(rows, cols, type_);
+        for (int y = 0; y < rows; y++) std::memcpy(dst.ptr(y), tmp.ptr(y), (size_t)cols * elemSize());
     }
 
 private:
+    static size_t elem(int type) { return type == CV_32F ? 4 : 1; }
+    static void check_type(int type)
+    {
+        if (type != CV_8UC1 && type != CV_32F) { std::fprintf(stderr, "cv_shim: only CV_8UC1 and CV_32F\n"); std::abort(); }
+    }
     static void check_range(int a, int b, int n)
     {
         if (a < 0 || b < a || b > n) { std::fprintf(stderr, "cv_shim: ROI [%d,%d) outside [0,%d)\n", a, b, n); std::abort(); }
     }
+    int type_;
     int whole_rows_, whole_cols_;
     uchar *base_ = 0;
     std::shared_ptr<std::vector<uchar> > buf_;
 };
+
+/* scalar * Mat and Mat - Mat on CV_32F: each element rounded to float once, as saturate_cast<float> does */
+inline Mat operator*(double s, const Mat &m)
+{
+    if (m.type() != CV_32F) { std::fprintf(stderr, "cv_shim: scalar * Mat is CV_32F only\n"); std::abort(); }
+    Mat out(m.rows, m.cols, CV_32F);
+    for (int y = 0; y < m.rows; y++)
+        for (int x = 0; x < m.cols; x++) out.at<float>(y, x) = (float)(s * (double)m.at<float>(y, x));
+    return out;
+}
+
+inline Mat operator-(const Mat &a, const Mat &b)
+{
+    if (a.type() != CV_32F || b.type() != CV_32F || a.rows != b.rows || a.cols != b.cols) {
+        std::fprintf(stderr, "cv_shim: Mat - Mat needs two CV_32F matrices of one size\n");
+        std::abort();
+    }
+    Mat out(a.rows, a.cols, CV_32F);
+    for (int y = 0; y < a.rows; y++)
+        for (int x = 0; x < a.cols; x++) out.at<float>(y, x) = a.at<float>(y, x) - b.at<float>(y, x);
+    return out;
+}
+
+/* NORM_L1 of a - b for CV_32F: the differences in float, their absolute values summed in double */
+inline double norm(const Mat &a, const Mat &b, int normType)
+{
+    if (normType != NORM_L1 || a.type() != CV_32F || b.type() != CV_32F || a.rows != b.rows || a.cols != b.cols) {
+        std::fprintf(stderr, "cv_shim: norm is NORM_L1 of two CV_32F matrices of one size only\n");
+        std::abort();
+    }
+    double s = 0;
+    for (int y = 0; y < a.rows; y++)
+        for (int x = 0; x < a.cols; x++) s += std::fabs((double)(a.at<float>(y, x) - b.at<float>(y, x)));
+    return s;
+}
 
 class _InputArray {
 public:

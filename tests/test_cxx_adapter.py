@@ -23,7 +23,7 @@ def _build(orbx, src, out):
 
 
 def test_adapters_compile_and_link(orbx, tmp_path):
-    for src in ("adapter_check.cc", "tracking_callsites.cc", "mapping_callsites.cc"):
+    for src in ("adapter_check.cc", "tracking_callsites.cc", "mapping_callsites.cc", "stereo_callsites.cc"):
         exe = _build(orbx, src, str(tmp_path / src[:-3]))
         assert subprocess.run([exe, "compile-only"]).returncode == 0
 
@@ -130,3 +130,41 @@ def test_mapping_callsites_equal_cabi(orbx, synth, tmp_path):
         assert name in rows, p.stdout
         assert int(rows[name][1]) == 1, "%s differs from the C ABI\n%s" % (name, p.stdout)
         assert int(rows[name][0]) >= floor, "%s: only %s\n%s" % (name, rows[name][0], p.stdout)
+
+
+@pytest.mark.gpu
+def test_stereo_callsites_equal_cabi(orbx, tmp_path):
+    """The stereo route on the drop-in classes: a Frame shaped like src/Frame.cc:61-117 (left and right extraction on two
+    std::threads) whose ComputeStereoMatches is INTEGRATION.md section 3b verbatim.  mvuRight / mvDepth equal a direct C-ABI call
+    (checked in the program) and the oracle on the same keypoints, descriptors and pyramids (checked here)."""
+    import oracle_lib as O
+    import stereo_cases as S
+    exe = _build(orbx, "stereo_callsites.cc", str(tmp_path / "stereo_callsites"))
+    W, H = 640, 480
+    left, right, _ = S.stereo_scene(181, W, H)
+    np.concatenate([left.ravel(), right.ravel()]).tofile(tmp_path / "pair.u8")
+    out = tmp_path / "out.bin"
+    p = subprocess.run([exe, str(tmp_path / "pair.u8"), str(W), str(H), str(out)], capture_output=True, text=True)
+    assert p.returncode == 0, p.stdout + p.stderr
+    row = p.stdout.split()
+    assert row[0] == "stereo" and int(row[3]) == 1, p.stdout
+    b = out.read_bytes()
+    N, Nr = np.frombuffer(b[:8], np.int32)
+    o = 8
+    take = lambda n: b[o:o + n]
+    kl = np.frombuffer(take(28 * N), O.KP_DTYPE); o += 28 * N
+    kr = np.frombuffer(take(28 * Nr), O.KP_DTYPE); o += 28 * Nr
+    dl = np.frombuffer(take(32 * N), np.uint8).reshape(N, 32); o += 32 * N
+    dr = np.frombuffer(take(32 * Nr), np.uint8).reshape(Nr, 32); o += 32 * Nr
+    u = np.frombuffer(take(4 * N), np.float32); o += 4 * N
+    d = np.frombuffer(take(4 * N), np.float32); o += 4 * N
+    assert o == len(b)
+    okl, odl, _ = O.Extractor(1000).extract(left)
+    okr, odr, _ = O.Extractor(1000).extract(right)
+    assert kl.tobytes() == okl.tobytes() and kr.tobytes() == okr.tobytes()
+    assert np.array_equal(dl, odl) and np.array_equal(dr, odr)
+    mb, mbf = S.rig(500.0)
+    ex = O.Extractor(1000)
+    ou, od = O.stereo_matches(ex, kl, dl, kr, dr, ex.pyramid(left), ex.pyramid(right), mb, mbf)
+    assert u.tobytes() == ou.tobytes() and d.tobytes() == od.tobytes()
+    assert int(row[2]) > 0.3 * N
