@@ -344,6 +344,36 @@ int orbm_search_by_sim3(orbm_matcher *m,
                         const orbx_keypoint *kps2, const uint8_t *desc2, int n2, const orbm_kf_grid *grid2, const float *scale_factors2,
                         int nlevels2, float th, int32_t *match12, int *nfound);
 
+/*
+ * ---- MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) for a batch of MapPoints in one call ----
+ * The reference calls the method once per MapPoint, in loops over all MapPoints of a key frame (src/LocalMapping.cc:141-163,
+ * :444, :519-532, src/LoopClosing.cc:533, src/Tracking.cc:541, 677, 1124).  Here the batch is a CSR: point p owns the rows
+ * off[p] .. off[p+1]-1 of desc (32 bytes each), given in the iteration order of its mObservations with bad key frames left out
+ * (:261-267) -- the order is part of the input, ties go to the first row.  Per point, with N rows:
+ *   dist[i][j] = DescriptorDistance(row i, row j), dist[i][i] = 0 (:276-285);
+ *   median[i]  = element (N-1)/2 (the lower middle for even N) of row i of dist sorted ascending, own 0 included (:292-294);
+ *   best[p]    = the first i with the smallest median[i] (:288-301), best_median[p] = that median; both -1 for an empty run
+ *                (the reference returns with mDescriptor untouched, :256, :269).
+ * mDescriptor = row best[p] of the point is the caller's to store.  best_median may be NULL.  n_points == 0 is ORBX_OK.  There is
+ * no limit on N: runs of up to 256 rows are served from LDS, longer ones from global memory, spread over N / 256 workgroups.
+ * Argument checks come before any device work (ORBX_E_INVALID: negative count, NULL off / best / desc, off[0] != 0, off not
+ * monotone).  A batch whose runs all have N <= 2 needs no arithmetic (best = 0, or -1): it is answered on the host without a launch
+ * and without touching the handle, which may then be NULL.  Every other batch needs the GPU: with a NULL handle it fails with
+ * ORBX_E_HIP where there is no HIP device ("no CPU path", as orbm_create does) and with ORBX_E_INVALID where there is one.
+ * The call keeps its own scratch block in the handle and grows it on demand; the grid and the other buffers of the handle are
+ * not touched, whatever the batch size.
+ *
+ * orbm_distinctive_descriptors_device takes device pointers (d_desc 16-byte aligned) and the two facts the launch plan needs
+ * from the host: total_rows = off[n_points] and max_run >= the longest run (classes above max_run are not launched, so a
+ * max_run that is too small leaves their points unanswered; a larger one only costs empty launches).  d_off is trusted to be
+ * monotone from 0.  Asynchronous on hip_stream (NULL = the handle's stream), nothing is synchronised -- except that the first
+ * call with more points than any call before allocates scratch (not possible inside a stream capture: warm up once).
+ */
+int orbm_distinctive_descriptors(orbm_matcher *m, int n_points, const int32_t *off, const uint8_t *desc,
+                                 int32_t *best, int32_t *best_median);
+int orbm_distinctive_descriptors_device(orbm_matcher *m, int n_points, const int32_t *d_off, const uint8_t *d_desc,
+                                        int total_rows, int max_run, int32_t *d_best, int32_t *d_best_median, void *hip_stream);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12. */
 int orbm_three_maxima(const int32_t *hist_sizes, int L, int32_t ind[3]);
 int orbm_rot_filter(const float *angle_q, const float *angle_t, int32_t *match12, int nq);

@@ -227,6 +227,9 @@ def _bind_matcher(L):
     L.orbm_fuse_sim3.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, C.c_int, f, vp, vp]
     L.orbm_search_by_sim3.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp,
                                       vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, vp, vp, C.c_int, f, vp, vp]
+    L.orbm_distinctive_descriptors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.orbm_distinctive_descriptors_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.orbm_distinctive_descriptors.restype = L.orbm_distinctive_descriptors_device.restype = C.c_int
     for name in ("orbm_reserve", "orbm_grid_build_kf", "orbm_sim3_decompose", "orbm_sim3_relative", "orbm_project_points_kf",
                  "orbm_project_points_sim3", "orbm_search_by_projection_sim3", "orbm_search_by_bow_kf", "orbm_search_for_triangulation",
                  "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_search_by_bow"):
@@ -502,6 +505,23 @@ class ORBmatcher:
             out = np.zeros(nq * nt, np.int32)
         _mchk(self.L.orbm_distances(self.h, _p(q), nq, _p(t), nt, _p(cand_off), _p(cand_idx), _p(out)))
         return out
+
+    def distinctive_descriptors(self, off, desc):
+        """MapPoint::ComputeDistinctiveDescriptors (src/MapPoint.cc:242-307) for a batch of MapPoints: point p owns the rows
+        off[p]:off[p+1] of desc, in the order of its observations.  Returns (best, best_median), int32 per point: the row
+        whose median distance to the point's rows is the smallest (the first such row), and that median; -1 for an empty run."""
+        off = np.ascontiguousarray(off, np.int32).reshape(-1)
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        if len(off) < 1 or (len(off) > 1 and int(off[-1]) != len(desc)):
+            raise OrbxError(ORBX_E_INVALID, "off has %d entries ending at %s, desc has %d rows" % (len(off), off[-1:], len(desc)))
+        n = len(off) - 1
+        best, med = np.full(n, -1, np.int32), np.full(n, -1, np.int32)
+        _mchk(self.L.orbm_distinctive_descriptors(self.h, n, _p(off), _p(desc), _p(best), _p(med)))
+        return best, med
+
+    def distinctive_descriptors_device(self, n_points, d_off, d_desc, total_rows, max_run, d_best, d_best_median=None, stream=None):
+        """The same on raw device pointers; nothing is synchronised.  total_rows = off[n_points], max_run >= the longest run."""
+        _mchk(self.L.orbm_distinctive_descriptors_device(self.h, n_points, d_off, d_desc, total_rows, max_run, d_best, d_best_median, stream))
 
     def match_dense(self, q, kq, t, kt, th=None):
         """Dense SearchByBoW-style acceptance + rotation filter on host buffers (via best2)."""

@@ -310,6 +310,7 @@ extern "C" void orbm_destroy(orbm_matcher *m)
     (void)hipFree(m->d_qf); (void)hipFree(m->d_qi); (void)hipFree(m->d_skip);
     if (m->stream) (void)hipStreamDestroy(m->stream);
     (void)hipHostFree(m->h_pin); (void)hipHostFree(m->arena); (void)hipFree(m->d_arena);
+    (void)hipFree(m->d_dd);
     delete m;
 }
 

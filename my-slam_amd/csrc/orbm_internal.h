@@ -101,6 +101,7 @@ struct orbm_matcher {
     uint8_t *d_arena = nullptr;     // device mirror of the arena: inputs staged with orbm_stage_in() go up in ONE copy
     struct Pend { void *dst; const void *src; size_t bytes; };
     Pend pend[8]; int npend = 0;
+    uint8_t *d_dd = nullptr; size_t dd_bytes = 0;      // orbm_mappoint.hip: scratch of orbm_distinctive_descriptors (lazy, its own block)
 };
 // workspace growth (orbm.hip): the reference's matcher has no size limit, so entry points grow the handle instead of refusing
 int orbm_grow(orbm_matcher *m, long long need_q, long long need_t, long long need_pairs);

@@ -43,34 +43,13 @@
 #include "orbx_cv_compat.h"
 #endif
 #include "../../include/orbm.h"
+#include "orbm_pool.h"
 
 #include "MapPoint.h"
 #include "KeyFrame.h"
 #include "Frame.h"
 
 namespace ORB_SLAM2 {
-
-namespace orbm_detail {
-struct Scratch {                                 // marshalling buffers: they stay with the pooled handle, so a call allocates nothing once warm
-    std::vector<uint8_t> u8_, in_, has_, desc_;
-    std::vector<float> f0_, f1_, f2_, f3_, f4_, f5_, f6_, g0_, g1_, g2_, g3_;
-    std::vector<uint8_t> v8_, w8_, desc2_;
-    std::vector<int32_t> i0_, i1_, i2_, j0_, j1_, j2_, obs_, match_;
-    std::vector<orbx_keypoint> kp_;
-};
-struct PooledHandle {
-    orbm_matcher *m = nullptr; Scratch *s = nullptr;
-    unsigned long gridFrame = ~0ul; const void *gridKeys = nullptr; int gridN = -1; int gridKind = -1;   // which frame's (0) / key frame's (1) grid the handle holds
-};
-struct HandlePool {                              // one per thread: handles are not re-entrant, threads never share one
-    std::vector<PooledHandle> idle;
-    ~HandlePool() { for (auto &h : idle) { orbm_destroy(h.m); delete h.s; } }
-    static HandlePool &tls() { static thread_local HandlePool p; return p; }
-};
-inline int &pool_device() { static int d = 0; return d; }
-inline int &pool_max_descriptors() { static int n = 8192; return n; }
-inline int &pool_max_pairs() { static int n = 1 << 22; return n; }
-}  // namespace orbm_detail
 
 class ORBmatcher {
 public:
