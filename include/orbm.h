@@ -374,7 +374,10 @@ int orbm_distinctive_descriptors(orbm_matcher *m, int n_points, const int32_t *o
 int orbm_distinctive_descriptors_device(orbm_matcher *m, int n_points, const int32_t *d_off, const uint8_t *d_desc,
                                         int total_rows, int max_run, int32_t *d_best, int32_t *d_best_median, void *hip_stream);
 
-/* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12. */
+/* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
+ * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
+ * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts
+ * there.  match12 is then partly filtered and must not be used. */
 int orbm_three_maxima(const int32_t *hist_sizes, int L, int32_t ind[3]);
 int orbm_rot_filter(const float *angle_q, const float *angle_t, int32_t *match12, int nq);
 

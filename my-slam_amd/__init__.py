@@ -532,6 +532,8 @@ class ORBmatcher:
             aq = np.ascontiguousarray(kq["angle"], np.float32)
             at = np.ascontiguousarray(kt["angle"], np.float32)
             n = self.L.orbm_rot_filter(_p(aq), _p(at), _p(m), len(m))
+            if n < 0:
+                _mchk(n)
         else:
             n = int((m >= 0).sum())
         return n, m

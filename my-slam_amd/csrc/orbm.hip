@@ -68,27 +68,6 @@ int orbm_d2h(orbm_matcher *m, void *host, const void *dev, size_t bytes, hipStre
     MHIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
     return ORBX_OK;
 }
-void *orbm_stage_in(orbm_matcher *m, const void *host, size_t bytes)
-{
-    if (!m->d_arena) { m->arena_want += (bytes + 63) & ~(size_t)63; return nullptr; }
-    void *p = arena_take(m, bytes);
-    if (!p) return nullptr;
-    memcpy(p, host, bytes);
-    return m->d_arena + ((uint8_t *)p - m->arena);
-}
-int orbm_flush_in(orbm_matcher *m, size_t from, hipStream_t s)
-{
-    if (m->arena_used > from)
-        MHIPCHK(hipMemcpyAsync(m->d_arena + from, m->arena + from, m->arena_used - from, hipMemcpyHostToDevice, s));
-    return ORBX_OK;
-}
-void *orbm_d2h_tmp(orbm_matcher *m, const void *dev, size_t bytes, hipStream_t s)
-{
-    void *p = arena_take(m, bytes);
-    if (!p) return nullptr;
-    if (hipMemcpyAsync(p, dev, bytes, hipMemcpyDeviceToHost, s) != hipSuccess) return nullptr;
-    return p;
-}
 int orbm_d2h_split(orbm_matcher *m, void *const *host, const size_t *parts, int nparts, const void *dev, hipStream_t s)
 {
     size_t total = 0;
@@ -98,8 +77,7 @@ int orbm_d2h_split(orbm_matcher *m, void *const *host, const size_t *parts, int 
     if (!p) {     // no room in the arena this call: one copy per part
         size_t o = 0;
         for (int i = 0; i < nparts; i++) {
-            int rc = orbm_d2h(m, host[i], (const uint8_t *)dev + o, parts[i], s);
-            if (rc != ORBX_OK) return rc;
+            MTRY(orbm_d2h(m, host[i], (const uint8_t *)dev + o, parts[i], s));
             o += parts[i];
         }
         return ORBX_OK;
@@ -307,9 +285,8 @@ extern "C" void orbm_destroy(orbm_matcher *m)
     (void)hipFree(m->d_q); (void)hipFree(m->d_t); (void)hipFree(m->d_off); (void)hipFree(m->d_idx);
     (void)hipFree(m->d_out); (void)hipFree(m->d_part);
     orbm_grid_free(m->grid); orbm_grid_free(m->grid2);
-    (void)hipFree(m->d_qf); (void)hipFree(m->d_qi); (void)hipFree(m->d_skip);
     if (m->stream) (void)hipStreamDestroy(m->stream);
-    (void)hipHostFree(m->h_pin); (void)hipHostFree(m->arena); (void)hipFree(m->d_arena);
+    (void)hipHostFree(m->arena); (void)hipFree(m->d_arena);
     (void)hipFree(m->d_dd);
     delete m;
 }
@@ -365,7 +342,6 @@ extern "C" int orbm_reserve(orbm_matcher *m, int max_queries, int max_train, int
         (void)hipFree(m->d_t); m->d_t = nullptr;
         MHIPCHK(hipMalloc((void **)&m->d_t, (size_t)nt * 32));
         orbm_grid_free(m->grid); orbm_grid_free(m->grid2); m->grid_ok = false; m->grid2_ok = false;     // sized by max_train
-        (void)hipFree(m->d_skip); m->d_skip = nullptr;
     }
     if (np > m->max_pairs) {
         (void)hipFree(m->d_idx); m->d_idx = nullptr;
@@ -434,21 +410,20 @@ extern "C" int orbm_best2(orbm_matcher *m, const uint8_t *q, int nq, const uint8
 {
     if (!m) return mfail(ORBX_E_INVALID, "NULL handle");
     if (nq < 0 || nt < 0) return mfail(ORBX_E_INVALID, "nq=%d nt=%d", nq, nt);
-    { int rc_ = orbm_grow(m, nq, nt, cand_off && nq > 0 ? cand_off[nq] : 0); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_grow(m, nq, nt, cand_off && nq > 0 ? cand_off[nq] : 0));
     if (nq == 0) return ORBX_OK;
     if (!q || !best_idx || !best_d || !second_d || (nt > 0 && !t)) return mfail(ORBX_E_INVALID, "NULL buffer");
     MHIPCHK(hipSetDevice(m->device));
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    { int rc_ = orbm_h2d(m, m->d_q, q, (size_t)nq * 32, s); if (rc_ != ORBX_OK) return rc_; }
-    if (nt > 0) { int rc_ = orbm_h2d(m, m->d_t, t, (size_t)nt * 32, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_h2d(m, m->d_q, q, (size_t)nq * 32, s));
+    if (nt > 0) MTRY(orbm_h2d(m, m->d_t, t, (size_t)nt * 32, s));
     int32_t *o_bi = m->d_out, *o_bd = m->d_out + nq, *o_sd = m->d_out + 2 * (size_t)nq;
     if (cand_off) {
         int total = 0;
-        int rc = check_csr(cand_off, cand_idx, nq, nt, m->max_pairs, &total);
-        if (rc != ORBX_OK) return rc;
-        { int rc_ = orbm_h2d(m, m->d_off, cand_off, ((size_t)nq + 1) * 4, s); if (rc_ != ORBX_OK) return rc_; }
-        if (total > 0) { int rc_ = orbm_h2d(m, m->d_idx, cand_idx, (size_t)total * 4, s); if (rc_ != ORBX_OK) return rc_; }
+        MTRY(check_csr(cand_off, cand_idx, nq, nt, m->max_pairs, &total));
+        MTRY(orbm_h2d(m, m->d_off, cand_off, ((size_t)nq + 1) * 4, s));
+        if (total > 0) MTRY(orbm_h2d(m, m->d_idx, cand_idx, (size_t)total * 4, s));
         hipLaunchKernelGGL(k_best2_csr, dim3((nq + 3) / 4), dim3(M_THREADS), 0, s, m->d_q, nq, m->d_t, m->d_off, m->d_idx, o_bi, o_bd, o_sd);
     } else {
         const int S = m->dense_popcount ? pick_splits(nq, 1, nt) : orbm_mfma_splits(nq, nt, 1);
@@ -462,10 +437,10 @@ extern "C" int orbm_best2(orbm_matcher *m, const uint8_t *q, int nq, const uint8
         hipLaunchKernelGGL(k_merge_best2, dim3((nq + M_THREADS - 1) / M_THREADS), dim3(M_THREADS), 0, s, m->d_part, S, nq, o_bi, o_bd, o_sd);
     }
     MHIPCHK(hipGetLastError());
-    { int rc_ = orbm_d2h(m, best_idx, o_bi, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_d2h(m, best_d, o_bd, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_d2h(m, second_d, o_sd, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_d2h(m, best_idx, o_bi, (size_t)nq * 4, s));
+    MTRY(orbm_d2h(m, best_d, o_bd, (size_t)nq * 4, s));
+    MTRY(orbm_d2h(m, second_d, o_sd, (size_t)nq * 4, s));
+    MTRY(orbm_sync(m, s));
     return ORBX_OK;
 }
 
@@ -474,23 +449,22 @@ extern "C" int orbm_distances(orbm_matcher *m, const uint8_t *q, int nq, const u
 {
     if (!m) return mfail(ORBX_E_INVALID, "NULL handle");
     if (nq < 0 || nt < 0) return mfail(ORBX_E_INVALID, "nq=%d nt=%d", nq, nt);
-    { int rc_ = orbm_grow(m, nq, nt, cand_off && nq > 0 ? cand_off[nq] : (long long)nq * nt); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_grow(m, nq, nt, cand_off && nq > 0 ? cand_off[nq] : (long long)nq * nt));
     if (nq == 0 || nt == 0) return ORBX_OK;
     if (!q || !t || !dist) return mfail(ORBX_E_INVALID, "NULL buffer");
     MHIPCHK(hipSetDevice(m->device));
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    { int rc_ = orbm_h2d(m, m->d_q, q, (size_t)nq * 32, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, m->d_t, t, (size_t)nt * 32, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_h2d(m, m->d_q, q, (size_t)nq * 32, s));
+    MTRY(orbm_h2d(m, m->d_t, t, (size_t)nt * 32, s));
     long long total;
     if (cand_off) {
         int tot = 0;
-        int rc = check_csr(cand_off, cand_idx, nq, nt, m->max_pairs, &tot);
-        if (rc != ORBX_OK) return rc;
+        MTRY(check_csr(cand_off, cand_idx, nq, nt, m->max_pairs, &tot));
         total = tot;
         if (total == 0) return ORBX_OK;
-        { int rc_ = orbm_h2d(m, m->d_off, cand_off, ((size_t)nq + 1) * 4, s); if (rc_ != ORBX_OK) return rc_; }
-        { int rc_ = orbm_h2d(m, m->d_idx, cand_idx, (size_t)total * 4, s); if (rc_ != ORBX_OK) return rc_; }
+        MTRY(orbm_h2d(m, m->d_off, cand_off, ((size_t)nq + 1) * 4, s));
+        MTRY(orbm_h2d(m, m->d_idx, cand_idx, (size_t)total * 4, s));
         hipLaunchKernelGGL(k_dist_csr, dim3((unsigned)((total + M_THREADS - 1) / M_THREADS)), dim3(M_THREADS), 0, s,
                            m->d_q, nq, m->d_t, m->d_off, m->d_idx, (int)total, m->d_out);
     } else {
@@ -501,8 +475,8 @@ extern "C" int orbm_distances(orbm_matcher *m, const uint8_t *q, int nq, const u
                            m->d_q, nq, m->d_t, nt, m->d_out);
     }
     MHIPCHK(hipGetLastError());
-    { int rc_ = orbm_d2h(m, dist, m->d_out, (size_t)total * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_d2h(m, dist, m->d_out, (size_t)total * 4, s));
+    MTRY(orbm_sync(m, s));
     return ORBX_OK;
 }
 
@@ -538,8 +512,7 @@ extern "C" int orbm_match_batch_device(orbm_matcher *m, const uint8_t *d_q, cons
     // (The acceptance as the tail of the LAST workgroup of a pair inside the match launch -- arrival counter, agent-scope release /
     // acquire -- was built and measured in round 3: identical tables, 76.7 us against 22.9 + 6.6: every workgroup's release is an L2
     // write-back on this multi-XCD part.  It stays a launch of its own.)
-    int rc = launch_dense_batch(m, d_q, d_nq, d_t, d_nt, cap, nbatch, s, &S);
-    if (rc != ORBX_OK) return rc;
+    MTRY(launch_dense_batch(m, d_q, d_nq, d_t, d_nt, cap, nbatch, s, &S));
     const uint2 *part = m->d_part;
     if (S > ORBM_PREMERGE_SPLITS) {
         uint2 *merged = m->d_part + (size_t)S * nbatch * cap;
@@ -575,8 +548,7 @@ extern "C" int orbm_best2_batch_device(orbm_matcher *m, const uint8_t *d_q, cons
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;
     int S = 1;
-    int rc = launch_dense_batch(m, d_q, d_nq, d_t, d_nt, cap, nbatch, s, &S);
-    if (rc != ORBX_OK) return rc;
+    MTRY(launch_dense_batch(m, d_q, d_nq, d_t, d_nt, cap, nbatch, s, &S));
     hipLaunchKernelGGL(k_merge_batch, dim3((cap + M_THREADS - 1) / M_THREADS, nbatch), dim3(M_THREADS), 0, s,
                        m->d_part, S, d_nq, cap, d_best_idx, d_best_d, d_second_d);
     MHIPCHK(hipGetLastError());
@@ -666,39 +638,25 @@ __global__ __launch_bounds__(M_THREADS) void k_bow_select(
     }
 }
 
-// ---- host helpers (ComputeThreeMaxima :1601-1642, histogram fill/cull :236-246,:266-284) ----
+// ---- host helpers ----
 // rotation histogram + ComputeThreeMaxima cull of SearchByBoW (:236-246, :266-284) on a finished match table
 static int bow_rotation_cull(const orbx_keypoint *kps_kf, const orbx_keypoint *kps_f, int n_f, int check_orientation,
                              int32_t *match_f, int *nmatches)
 {
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    std::vector<int> bin_of((size_t)n_f, -1);
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    RotHist rot;
     int nm = 0;
     for (int i = 0; i < n_f; i++) {
         if (match_f[i] < 0) continue;
         nm++;
-        if (!check_orientation) continue;
-        float rot = kps_kf[match_f[i]].angle - kps_f[i].angle;
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == ORBM_HISTO_LENGTH) bin = 0;
-        if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");   // the reference asserts
-        bin_of[i] = bin;
-        hist[bin]++;
+        if (check_orientation) MTRY(rot.add(kps_kf[match_f[i]].angle, kps_f[i].angle, i));
     }
-    if (check_orientation) {
-        int32_t ind[3];
-        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-        for (int i = 0; i < n_f; i++)
-            if (bin_of[i] >= 0 && bin_of[i] != ind[0] && bin_of[i] != ind[1] && bin_of[i] != ind[2]) { match_f[i] = -1; nm--; }
-    }
+    if (check_orientation) rot.cull([&](int i) { match_f[i] = -1; nm--; });
     *nmatches = nm;
     return ORBX_OK;
 }
 
-// Returns 1 when the GPU selection does not apply (a node with more than BOW_MAX_NODE_FEATURES frame features, staging larger
-// than the handle's buffers, ORBM_BOW_HOST_SELECT=1 in the environment): the caller then takes the host-selection path.
+// Returns 1 when the GPU selection does not apply (a node with more than BOW_MAX_NODE_FEATURES frame features, a match table larger
+// than the handle's result buffer, ORBM_BOW_HOST_SELECT=1 in the environment): the caller then takes the host-selection path.
 static int search_by_bow_device(orbm_matcher *m,
                                 const uint8_t *desc_kf, const orbx_keypoint *kps_kf, int n_kf, const uint8_t *valid_kf,
                                 const int32_t *fv_kf_node, const int32_t *fv_kf_off, const int32_t *fv_kf_idx, int fv_kf_n,
@@ -709,7 +667,7 @@ static int search_by_bow_device(orbm_matcher *m,
     static const bool force_host = [] { const char *e = getenv("ORBM_BOW_HOST_SELECT"); return e && e[0] == '1'; }();
     if (force_host) return 1;
     const int nki = fv_kf_off[fv_kf_n], nfi = fv_f_off[fv_f_n];
-    if (nki < 0 || nfi < 0 || n_kf > m->max_q) return 1;
+    if (nki < 0 || nfi < 0) return 1;
     std::vector<int4> pairs;
     for (int a = 0, b = 0; a < fv_kf_n && b < fv_f_n;) {       // merge-join of the ascending node lists (:178-262)
         if (fv_kf_node[a] == fv_f_node[b]) {
@@ -726,63 +684,24 @@ static int search_by_bow_device(orbm_matcher *m,
         if (fv_kf_idx[c] < 0 || fv_kf_idx[c] >= n_kf) return mfail(ORBX_E_INVALID, "key-frame feature index %d outside [0,%d)", fv_kf_idx[c], n_kf);
     for (int c = 0; c < nfi; c++)
         if (fv_f_idx[c] < 0 || fv_f_idx[c] >= n_f) return mfail(ORBX_E_INVALID, "frame feature index %d outside [0,%d)", fv_f_idx[c], n_f);
-    // device ints: [kf_idx | f_idx | pairs (16-byte aligned) | valid bytes] in d_idx, match table in d_out
-    const size_t i_kf = 0, i_f = i_kf + (size_t)nki, i_pairs = (i_f + (size_t)nfi + 3) & ~(size_t)3, i_valid = i_pairs + 4 * (size_t)np;
-    const size_t n_ints = i_valid + (valid_kf ? ((size_t)n_kf + 3) / 4 : 0);
-    const size_t out_ints = std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs);
-    if (n_ints > (size_t)std::max(m->max_pairs, 1) || (size_t)n_f > out_ints) return 1;
+    if ((size_t)n_f > std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs)) return 1;     // the match table lives in d_out
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = m->stream;
-    {   // usual path: everything staged in the pinned arena, one copy up, one kernel, one copy back
-        int rc_ = orbm_arena_begin(m);
-        if (rc_ != ORBX_OK) return rc_;
-        const size_t mark = m->arena_used;
-        const uint8_t *dq = (const uint8_t *)orbm_stage_in(m, desc_kf, (size_t)n_kf * 32), *dt = (const uint8_t *)orbm_stage_in(m, desc_f, (size_t)n_f * 32);
-        const int32_t *dki = (const int32_t *)orbm_stage_in(m, fv_kf_idx, (size_t)nki * 4), *dfi = (const int32_t *)orbm_stage_in(m, fv_f_idx, (size_t)nfi * 4);
-        const int4 *dp = (const int4 *)orbm_stage_in(m, pairs.data(), (size_t)np * 16);
-        const uint8_t *dv = valid_kf ? (const uint8_t *)orbm_stage_in(m, valid_kf, (size_t)n_kf) : nullptr;
-        if (dq && dt && dki && dfi && dp && (dv || !valid_kf)) {
-            rc_ = orbm_flush_in(m, mark, s);
-            if (rc_ != ORBX_OK) return rc_;
-            hipLaunchKernelGGL(k_bow_select, dim3((np + M_THREADS / 64 - 1) / (M_THREADS / 64)), dim3(M_THREADS), 0, s,
-                               dq, dt, dki, dfi, dp, np, dv, nnratio, th, m->d_out);
-            MHIPCHK(hipGetLastError());
-            const int32_t *out = (const int32_t *)orbm_d2h_tmp(m, m->d_out, (size_t)n_f * 4, s);
-            if (out) {
-                rc_ = orbm_sync(m, s);
-                if (rc_ != ORBX_OK) return rc_;
-                for (int k = 0; k < np; k++)         // the kernel wrote the entries of the paired nodes only
-                    for (int c = pairs[k].z; c < pairs[k].w; c++) match_f[fv_f_idx[c]] = out[fv_f_idx[c]];
-                return bow_rotation_cull(kps_kf, kps_f, n_f, check_orientation, match_f, nmatches);
-            }
-            MHIPCHK(hipStreamSynchronize(s));      // no room for the result this call: take the slower path below
-        }
-    }
-    const size_t o_q = 0, o_t = o_q + (size_t)n_kf * 32, o_i = o_t + (size_t)n_f * 32, o_m = o_i + n_ints * 4, need = o_m + (size_t)n_f * 4;
-    if (need > m->h_pin_bytes) {
-        MHIPCHK(hipStreamSynchronize(s));
-        (void)hipHostFree(m->h_pin); m->h_pin = nullptr; m->h_pin_bytes = 0;
-        MHIPCHK(hipHostMalloc((void **)&m->h_pin, need + need / 2, hipHostMallocDefault));
-        m->h_pin_bytes = need + need / 2;
-    }
-    memcpy(m->h_pin + o_q, desc_kf, (size_t)n_kf * 32);
-    memcpy(m->h_pin + o_t, desc_f, (size_t)n_f * 32);
-    int32_t *hi = reinterpret_cast<int32_t *>(m->h_pin + o_i);
-    memcpy(hi + i_kf, fv_kf_idx, (size_t)nki * 4);
-    memcpy(hi + i_f, fv_f_idx, (size_t)nfi * 4);
-    memcpy(hi + i_pairs, pairs.data(), (size_t)np * 16);
-    if (valid_kf) memcpy(hi + i_valid, valid_kf, (size_t)n_kf);
-    MHIPCHK(hipMemcpyAsync(m->d_q, m->h_pin + o_q, (size_t)n_kf * 32, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemcpyAsync(m->d_t, m->h_pin + o_t, (size_t)n_f * 32, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemcpyAsync(m->d_idx, hi, n_ints * 4, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemsetAsync(m->d_out, 0xFF, (size_t)n_f * 4, s));        // match table = -1
+    MTRY(orbm_arena_begin(m));
+    InBlock in(m);                                  // one copy up, one kernel, one copy back
+    const int pq = in.add(desc_kf, (size_t)n_kf * 32), pt = in.add(desc_f, (size_t)n_f * 32);
+    const int pki = in.add(fv_kf_idx, (size_t)nki * 4), pfi = in.add(fv_f_idx, (size_t)nfi * 4);
+    const int pp = in.add(pairs.data(), (size_t)np * 16), pv = in.add(valid_kf, valid_kf ? (size_t)n_kf : 0);
+    MTRY(in.upload(s));
     hipLaunchKernelGGL(k_bow_select, dim3((np + M_THREADS / 64 - 1) / (M_THREADS / 64)), dim3(M_THREADS), 0, s,
-                       m->d_q, m->d_t, m->d_idx + i_kf, m->d_idx + i_f, reinterpret_cast<const int4 *>(m->d_idx + i_pairs), np,
-                       valid_kf ? reinterpret_cast<const uint8_t *>(m->d_idx + i_valid) : (const uint8_t *)nullptr, nnratio, th, m->d_out);
+                       in.at<uint8_t>(pq), in.at<uint8_t>(pt), in.at<int32_t>(pki), in.at<int32_t>(pfi), in.at<int4>(pp), np,
+                       in.at<uint8_t>(pv), nnratio, th, m->d_out);
     MHIPCHK(hipGetLastError());
-    MHIPCHK(hipMemcpyAsync(m->h_pin + o_m, m->d_out, (size_t)n_f * 4, hipMemcpyDeviceToHost, s));
-    MHIPCHK(hipStreamSynchronize(s));
-    memcpy(match_f, m->h_pin + o_m, (size_t)n_f * 4);
+    std::vector<int32_t> out((size_t)n_f);
+    MTRY(orbm_d2h(m, out.data(), m->d_out, (size_t)n_f * 4, s));
+    MTRY(orbm_sync(m, s));
+    for (int k = 0; k < np; k++)         // the kernel wrote the entries of the paired nodes only
+        for (int c = pairs[k].z; c < pairs[k].w; c++) match_f[fv_f_idx[c]] = out[fv_f_idx[c]];
     return bow_rotation_cull(kps_kf, kps_f, n_f, check_orientation, match_f, nmatches);
 }
 
@@ -802,8 +721,8 @@ static int search_by_bow_impl(orbm_matcher *m,
     if (n_kf == 0 || n_f == 0 || fv_kf_n == 0 || fv_f_n == 0) return ORBX_OK;
     if (!desc_kf || !kps_kf || !desc_f || !kps_f || !fv_kf_node || !fv_kf_off || !fv_kf_idx || !fv_f_node || !fv_f_off || !fv_f_idx)
         return mfail(ORBX_E_INVALID, "NULL buffer");
-    { int rc_ = orbm_grow(m, n_kf, n_f, 0); if (rc_ != ORBX_OK) return rc_; }
-    {   // selection on the GPU when every matched node fits a wave's registers and the staging fits the handle's buffers
+    MTRY(orbm_grow(m, n_kf, n_f, 0));
+    {   // selection on the GPU when every matched node fits a wave's registers
         int rc = search_by_bow_device(m, desc_kf, kps_kf, n_kf, valid_kf, fv_kf_node, fv_kf_off, fv_kf_idx, fv_kf_n, desc_f, kps_f, n_f,
                                       fv_f_node, fv_f_off, fv_f_idx, fv_f_n, nnratio, th, check_orientation, match_f, nmatches);
         if (rc != 1) return rc;    // 1 = not applicable: distances on the GPU, selection on the host (below)
@@ -832,60 +751,43 @@ static int search_by_bow_impl(orbm_matcher *m,
     }
     const int nq = (int)qs.size();
     if (nq == 0 || pairs == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, 0, 0, pairs); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_grow(m, 0, 0, pairs));                 // the distances come back through d_out
     // Usual case (both frames below 65536 features): the key frame's descriptor block goes up as it is and every pair is
     // (key-frame feature << 16 | frame feature).  Otherwise the query descriptors are compacted and the kernel finds a
     // pair's query by binary search over the offsets.
     const bool packed16 = n_kf < 65536 && n_f < 65536;
-    const int nq_up = packed16 ? n_kf : nq;
-    { int rc_ = orbm_grow(m, nq_up, 0, 0); if (rc_ != ORBX_OK) return rc_; }
-    // pinned staging block: [query descriptors | n_f x 32 frame descriptors | nq+1 offsets | pairs indices | pairs distances]
-    MHIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    const size_t o_q = 0, o_t = o_q + (size_t)nq_up * 32, o_off = o_t + (size_t)n_f * 32, o_idx = o_off + ((size_t)nq + 1) * 4;
-    const size_t o_dist = o_idx + (size_t)pairs * 4, need = o_dist + (size_t)pairs * 4;
-    if (need > m->h_pin_bytes) {
-        MHIPCHK(hipStreamSynchronize(s));
-        (void)hipHostFree(m->h_pin); m->h_pin = nullptr; m->h_pin_bytes = 0;
-        MHIPCHK(hipHostMalloc((void **)&m->h_pin, need + need / 2, hipHostMallocDefault));
-        m->h_pin_bytes = need + need / 2;
+    std::vector<uint8_t> qd;
+    if (!packed16) {
+        qd.resize((size_t)nq * 32);
+        for (int i = 0; i < nq; i++) memcpy(&qd[(size_t)i * 32], desc_kf + (size_t)qs[i].kf * 32, 32);
     }
-    if (packed16) memcpy(m->h_pin + o_q, desc_kf, (size_t)n_kf * 32);
-    else for (int i = 0; i < nq; i++) memcpy(m->h_pin + o_q + (size_t)i * 32, desc_kf + (size_t)qs[i].kf * 32, 32);
-    memcpy(m->h_pin + o_t, desc_f, (size_t)n_f * 32);
-    int32_t *idx = reinterpret_cast<int32_t *>(m->h_pin + o_idx);
-    const int32_t *dist = reinterpret_cast<const int32_t *>(m->h_pin + o_dist);
+    std::vector<int32_t> idx((size_t)pairs), dist((size_t)pairs);
     for (int i = 0; i < nq; i++) {
         const int b = qs[i].f_node;
         const uint32_t hi = packed16 ? (uint32_t)qs[i].kf << 16 : 0u;
-        int32_t *dst = idx + off[i];
+        int32_t *dst = idx.data() + off[i];
         for (int c = fv_f_off[b]; c < fv_f_off[b + 1]; c++) {
             const int fi = fv_f_idx[c];
             if (fi < 0 || fi >= n_f) return mfail(ORBX_E_INVALID, "frame feature index %d outside [0,%d)", fi, n_f);
             *dst++ = (int32_t)(hi | (uint32_t)fi);
         }
     }
-    MHIPCHK(hipMemcpyAsync(m->d_q, m->h_pin + o_q, (size_t)nq_up * 32, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemcpyAsync(m->d_t, m->h_pin + o_t, (size_t)n_f * 32, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemcpyAsync(m->d_idx, m->h_pin + o_idx, (size_t)pairs * 4, hipMemcpyHostToDevice, s));
-    if (packed16) {
+    MHIPCHK(hipSetDevice(m->device));
+    hipStream_t s = m->stream;
+    MTRY(orbm_arena_begin(m));
+    InBlock in(m);
+    const int pq = packed16 ? in.add(desc_kf, (size_t)n_kf * 32) : in.add(qd.data(), qd.size()), pt = in.add(desc_f, (size_t)n_f * 32);
+    const int pi = in.add(idx.data(), (size_t)pairs * 4), po = in.add(off.data(), packed16 ? 0 : ((size_t)nq + 1) * 4);
+    MTRY(in.upload(s));
+    if (packed16)
         hipLaunchKernelGGL(k_dist_pairs16, dim3((unsigned)((pairs + M_THREADS - 1) / M_THREADS)), dim3(M_THREADS), 0, s,
-                           m->d_q, m->d_t, reinterpret_cast<const uint32_t *>(m->d_idx), (int)pairs, m->d_out);
-    } else {
-        memcpy(m->h_pin + o_off, off.data(), ((size_t)nq + 1) * 4);
-        MHIPCHK(hipMemcpyAsync(m->d_off, m->h_pin + o_off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(k_dist_csr, dim3((unsigned)((pairs + M_THREADS - 1) / M_THREADS)), dim3(M_THREADS), 0, s,
-                           m->d_q, nq, m->d_t, m->d_off, m->d_idx, (int)pairs, m->d_out);
-    }
+                           in.at<uint8_t>(pq), in.at<uint8_t>(pt), in.at<uint32_t>(pi), (int)pairs, m->d_out);
+    else
+        orbm_launch_dist_csr(in.at<uint8_t>(pq), nq, in.at<uint8_t>(pt), in.at<int32_t>(po), in.at<int32_t>(pi), (int)pairs, m->d_out, s);
     MHIPCHK(hipGetLastError());
-    MHIPCHK(hipMemcpyAsync(m->h_pin + o_dist, m->d_out, (size_t)pairs * 4, hipMemcpyDeviceToHost, s));
-    MHIPCHK(hipStreamSynchronize(s));
-    // sequential selection (:199-246)
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    std::vector<int> bin_of((size_t)n_f, -1);
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
-    int nm = 0;
-    for (int i = 0; i < nq; i++) {
+    MTRY(orbm_d2h(m, dist.data(), m->d_out, (size_t)pairs * 4, s));
+    MTRY(orbm_sync(m, s));
+    for (int i = 0; i < nq; i++) {                   // sequential selection (:199-232)
         int best1 = 256, best2 = 256, bestF = -1;
         for (int c = off[i]; c < off[i + 1]; c++) {
             const int fi = packed16 ? (int)((uint32_t)idx[c] & 0xFFFFu) : idx[c];
@@ -894,28 +796,9 @@ static int search_by_bow_impl(orbm_matcher *m,
             if (d < best1) { best2 = best1; best1 = d; bestF = fi; }
             else if (d < best2) best2 = d;
         }
-        if (best1 <= th && (float)best1 < nnratio * (float)best2) {
-            match_f[bestF] = qs[i].kf;
-            if (check_orientation) {
-                float rot = kps_kf[qs[i].kf].angle - kps_f[bestF].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int)roundf(rot * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-                if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");   // the reference asserts
-                bin_of[bestF] = bin;
-                hist[bin]++;
-            }
-            nm++;
-        }
+        if (best1 <= th && (float)best1 < nnratio * (float)best2) match_f[bestF] = qs[i].kf;
     }
-    if (check_orientation) {
-        int32_t ind[3];
-        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-        for (int i = 0; i < n_f; i++)
-            if (bin_of[i] >= 0 && bin_of[i] != ind[0] && bin_of[i] != ind[1] && bin_of[i] != ind[2]) { match_f[i] = -1; nm--; }
-    }
-    *nmatches = nm;
-    return ORBX_OK;
+    return bow_rotation_cull(kps_kf, kps_f, n_f, check_orientation, match_f, nmatches);
 }
 
 extern "C" int orbm_search_by_bow(orbm_matcher *m,
@@ -987,23 +870,13 @@ extern "C" int orbm_three_maxima(const int32_t *histo, int L, int32_t ind[3])
 extern "C" int orbm_rot_filter(const float *angle_q, const float *angle_t, int32_t *match12, int nq)
 {
     if (nq < 0 || (nq > 0 && (!angle_q || !angle_t || !match12))) return mfail(ORBX_E_INVALID, "bad argument");
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    std::vector<int> bins(nq, -1);
+    RotHist rot;
     int nmatches = 0;
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
     for (int i = 0; i < nq; i++) {
         if (match12[i] < 0) continue;
-        float rot = angle_q[i] - angle_t[match12[i]];
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int)roundf(rot * factor);
-        if (bin == ORBM_HISTO_LENGTH) bin = 0;
-        bins[i] = bin;
-        hist[bin]++;
+        MTRY(rot.add(angle_q[i], angle_t[match12[i]], i));
         nmatches++;
     }
-    int32_t ind[3];
-    orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-    for (int i = 0; i < nq; i++)
-        if (bins[i] >= 0 && bins[i] != ind[0] && bins[i] != ind[1] && bins[i] != ind[2]) { match12[i] = -1; nmatches--; }
+    rot.cull([&](int i) { match12[i] = -1; nmatches--; });
     return nmatches;
 }

@@ -192,18 +192,6 @@ static int ensure_grid(orbm_matcher *m, OrbmGrid &g)
     return ORBX_OK;
 }
 
-static int ensure_query_staging(orbm_matcher *m, size_t nq)
-{
-    if (nq <= m->qf_elems) return ORBX_OK;
-    MHIPCHK(hipDeviceSynchronize());
-    (void)hipFree(m->d_qf); (void)hipFree(m->d_qi);
-    m->d_qf = nullptr; m->d_qi = nullptr; m->qf_elems = 0;
-    MHIPCHK(hipMalloc((void **)&m->d_qf, nq * 3 * sizeof(float)));
-    MHIPCHK(hipMalloc((void **)&m->d_qi, nq * 4 * sizeof(int32_t)));    // min_level, max_level, counts, offsets
-    m->qf_elems = nq;
-    return ORBX_OK;
-}
-
 // cv::undistortPoints(src, dst, K, distCoeffs, noArray(), K) of OpenCV 3.1.0 for one point (cvUndistortPoints: camera matrix
 // and coefficients converted to double, ITERS = 5, no tilt, R = I, P = K).  Called by Frame::UndistortKeyPoints (src/Frame.cc:421)
 // and Frame::ComputeImageBounds (:449).
@@ -263,8 +251,7 @@ extern "C" int orbm_image_bounds(int width, int height, float fx, float fy, floa
 int orbm_grid_build_into(orbm_matcher *m, OrbmGrid &g, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y,
                          float inv_w, float inv_h, float query_min_x, float query_min_y)
 {
-    int rc = ensure_grid(m, g);
-    if (rc != ORBX_OK) return rc;
+    MTRY(ensure_grid(m, g));
     g.min_x = assign_min_x; g.min_y = assign_min_y; g.inv_w = inv_w; g.inv_h = inv_h; g.qmin_x = query_min_x; g.qmin_y = query_min_y;
     g.n = n;
     hipStream_t s = m->stream;
@@ -273,10 +260,24 @@ int orbm_grid_build_into(orbm_matcher *m, OrbmGrid &g, const orbx_keypoint *kps_
     const size_t have = std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs) * 4;
     void *tmp = nullptr;
     if (need > have) { MHIPCHK(hipMalloc(&tmp, need)); d_kps = reinterpret_cast<orbx_keypoint *>(tmp); }
-    if (n > 0) { int rc_ = orbm_h2d(m, d_kps, kps_un, need, s); if (rc_ != ORBX_OK) return rc_; }
+    if (n > 0) MTRY(orbm_h2d(m, d_kps, kps_un, need, s));
     hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(G_THREADS), 0, s, g, d_kps);
     MHIPCHK(hipGetLastError());
     if (tmp) { MHIPCHK(hipStreamSynchronize(s)); (void)hipFree(tmp); }
+    return ORBX_OK;
+}
+
+// the body of orbm_grid_build / orbm_grid_build_kf: slot `grid` of the handle, synchronous
+static int grid_build(orbm_matcher *m, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y, float inv_w, float inv_h,
+                      float query_min_x, float query_min_y)
+{
+    MHIPCHK(hipSetDevice(m->device));
+    m->grid_ok = false;
+    MTRY(orbm_grow(m, 0, n, 0));
+    MTRY(orbm_arena_begin(m));
+    MTRY(orbm_grid_build_into(m, m->grid, kps_un, n, assign_min_x, assign_min_y, inv_w, inv_h, query_min_x, query_min_y));
+    MTRY(orbm_sync(m, m->stream));
+    m->grid_ok = true;
     return ORBX_OK;
 }
 
@@ -287,16 +288,8 @@ extern "C" int orbm_grid_build(orbm_matcher *m, const orbx_keypoint *kps_un, int
     if (n < 0) return mfail(ORBX_E_INVALID, "n=%d keypoints", n);
     if (n > 0 && !kps_un) return mfail(ORBX_E_INVALID, "NULL keypoints");
     if (!(max_x > min_x) || !(max_y > min_y)) return mfail(ORBX_E_INVALID, "empty image bounds");
-    MHIPCHK(hipSetDevice(m->device));
-    m->grid_ok = false;
-    { int rc_ = orbm_grow(m, 0, n, 0); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
-    int rc = orbm_grid_build_into(m, m->grid, kps_un, n, min_x, min_y, (float)ORBM_GRID_COLS / (max_x - min_x),     // src/Frame.cc:212
-                                  (float)ORBM_GRID_ROWS / (max_y - min_y), min_x, min_y);                        // :213
-    if (rc != ORBX_OK) return rc;
-    { int rc_ = orbm_sync(m, m->stream); if (rc_ != ORBX_OK) return rc_; }
-    m->grid_ok = true;
-    return ORBX_OK;
+    return grid_build(m, kps_un, n, min_x, min_y, (float)ORBM_GRID_COLS / (max_x - min_x),     // src/Frame.cc:212
+                      (float)ORBM_GRID_ROWS / (max_y - min_y), min_x, min_y);                  // :213
 }
 
 // number of keypoints in the handle's grid, -1 when there is none (never built, or dropped by a workspace growth)
@@ -313,27 +306,24 @@ extern "C" int orbm_grid_build_kf(orbm_matcher *m, const orbx_keypoint *kps_un, 
     if (n < 0) return mfail(ORBX_E_INVALID, "n=%d keypoints", n);
     if (n > 0 && !kps_un) return mfail(ORBX_E_INVALID, "NULL keypoints");
     if (!(inv_w > 0.f) || !(inv_h > 0.f)) return mfail(ORBX_E_INVALID, "grid cell sizes must be positive");
-    MHIPCHK(hipSetDevice(m->device));
-    m->grid_ok = false;
-    { int rc_ = orbm_grow(m, 0, n, 0); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
-    int rc = orbm_grid_build_into(m, m->grid, kps_un, n, assign_min_x, assign_min_y, inv_w, inv_h, query_min_x, query_min_y);
-    if (rc != ORBX_OK) return rc;
-    { int rc_ = orbm_sync(m, m->stream); if (rc_ != ORBX_OK) return rc_; }
-    m->grid_ok = true;
-    return ORBX_OK;
+    return grid_build(m, kps_un, n, assign_min_x, assign_min_y, inv_w, inv_h, query_min_x, query_min_y);
 }
 
-static int upload_windows(orbm_matcher *m, const float *x, const float *y, const float *r, const int32_t *mn,
-                          const int32_t *mx, int nq, hipStream_t s)
+// The window arrays of nq queries as parts of a call's input block, and the two passes of k_area_list over them.  The counts of
+// pass 0 land in d_out[0, nq) (nq <= max_q: the caller has grown the handle), which is free until the distances are queued.
+struct WindowParts {
+    int x, y, r, mn, mx;
+    WindowParts(InBlock &in, const float *qx, const float *qy, const float *qr, const int32_t *min_level, const int32_t *max_level, int nq)
+        : x(in.add(qx, (size_t)nq * 4)), y(in.add(qy, (size_t)nq * 4)), r(in.add(qr, (size_t)nq * 4)),
+          mn(in.add(min_level, (size_t)nq * 4)), mx(in.add(max_level, (size_t)nq * 4)) {}
+};
+template <int MODE>
+static int launch_area_list(orbm_matcher *m, const InBlock &in, const WindowParts &w, int nq, int32_t *d_counts, const int32_t *d_off,
+                            int32_t *d_list, hipStream_t s)
 {
-    int rc = ensure_query_staging(m, (size_t)nq);
-    if (rc != ORBX_OK) return rc;
-    { int rc_ = orbm_h2d(m, m->d_qf, x, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, m->d_qf + m->qf_elems, y, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, m->d_qf + 2 * m->qf_elems, r, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, m->d_qi, mn, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, m->d_qi + m->qf_elems, mx, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
+    hipLaunchKernelGGL(k_area_list<MODE>, dim3((nq + 3) / 4), dim3(M_THREADS), 0, s, m->grid, in.at<float>(w.x), in.at<float>(w.y),
+                       in.at<float>(w.r), in.at<int32_t>(w.mn), in.at<int32_t>(w.mx), nq, d_counts, d_off, d_list);
+    MHIPCHK(hipGetLastError());
     return ORBX_OK;
 }
 
@@ -348,31 +338,27 @@ extern "C" int orbm_features_in_area(orbm_matcher *m, const float *x, const floa
     if (nq == 0) return 0;
     if (!x || !y || !r || !min_level || !max_level) return mfail(ORBX_E_INVALID, "NULL window array");
     MHIPCHK(hipSetDevice(m->device));
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_grow(m, nq, 0, 0));
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    int rc = upload_windows(m, x, y, r, min_level, max_level, nq, s);
-    if (rc != ORBX_OK) return rc;
-    const size_t Q = m->qf_elems;
-    int32_t *d_cnt = m->d_qi + 2 * Q, *d_off = m->d_qi + 3 * Q;
-    const dim3 grid((nq + 3) / 4);
-    hipLaunchKernelGGL(k_area_list<0>, grid, dim3(M_THREADS), 0, s, m->grid, m->d_qf, m->d_qf + Q, m->d_qf + 2 * Q, m->d_qi, m->d_qi + Q,
-                       nq, d_cnt, (const int32_t *)nullptr, (int32_t *)nullptr);
-    MHIPCHK(hipGetLastError());
+    InBlock in(m);
+    const WindowParts w(in, x, y, r, min_level, max_level, nq);
+    const int poff = in.reserve((size_t)nq * 4);
+    MTRY(in.upload(s));
+    MTRY(launch_area_list<0>(m, in, w, nq, m->d_out, nullptr, nullptr, s));
     std::vector<int32_t> cnt(nq);
-    { int rc_ = orbm_d2h(m, cnt.data(), d_cnt, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_d2h(m, cnt.data(), m->d_out, (size_t)nq * 4, s));
+    MTRY(orbm_sync(m, s));
     for (int i = 0; i < nq; i++) cand_off[i + 1] = cand_off[i] + cnt[i];
     const int total = cand_off[nq];
     if (total > cap_idx) return mfail(ORBX_E_CAPACITY, "%d candidates, caller capacity %d", total, cap_idx);
     if (total == 0) return 0;
     if (!cand_idx) return mfail(ORBX_E_INVALID, "cand_idx is NULL");
-    if (total > m->max_pairs) { int rc_ = orbm_grow(m, 0, 0, total); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, d_off, cand_off, (size_t)nq * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    hipLaunchKernelGGL(k_area_list<1>, grid, dim3(M_THREADS), 0, s, m->grid, m->d_qf, m->d_qf + Q, m->d_qf + 2 * Q, m->d_qi, m->d_qi + Q,
-                       nq, (int32_t *)nullptr, d_off, m->d_idx);
-    MHIPCHK(hipGetLastError());
-    { int rc_ = orbm_d2h(m, cand_idx, m->d_idx, (size_t)total * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_grow(m, 0, 0, total));
+    MTRY(in.fill(poff, cand_off, s));
+    MTRY(launch_area_list<1>(m, in, w, nq, nullptr, in.at<int32_t>(poff), m->d_idx, s));
+    MTRY(orbm_d2h(m, cand_idx, m->d_idx, (size_t)total * 4, s));
+    MTRY(orbm_sync(m, s));
     return total;
 }
 
@@ -403,50 +389,24 @@ extern "C" int orbm_search_area_best2(orbm_matcher *m, const uint8_t *qdesc, con
     if (!m->grid_ok) return mfail(ORBX_E_INVALID, "orbm_grid_build has not been called");
     if (nq < 0) return mfail(ORBX_E_INVALID, "nq=%d", nq);
     if (nq == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, nq, 0, 0); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_grow(m, nq, 0, 0));
     if (!qdesc || !x || !y || !r || !min_level || !max_level || !best_idx || !best_d || !second_d || (m->grid.n > 0 && !train_desc))
         return mfail(ORBX_E_INVALID, "NULL buffer");
     MHIPCHK(hipSetDevice(m->device));
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    int rc;
     int32_t *o_bi = m->d_out, *o_bd = m->d_out + nq, *o_sd = m->d_out + 2 * (size_t)nq;
-    // usual path: every input of the call is staged in the pinned arena and goes up in one copy to its device mirror
-    const size_t mark = m->arena_used;
-    const size_t nb4 = (size_t)nq * 4;
-    const float *sx = (const float *)orbm_stage_in(m, x, nb4), *sy = (const float *)orbm_stage_in(m, y, nb4), *sr = (const float *)orbm_stage_in(m, r, nb4);
-    const int32_t *smn = (const int32_t *)orbm_stage_in(m, min_level, nb4), *smx = (const int32_t *)orbm_stage_in(m, max_level, nb4);
-    const uint8_t *sq = (const uint8_t *)orbm_stage_in(m, qdesc, (size_t)nq * 32);
-    const uint8_t *st = m->grid.n > 0 ? (const uint8_t *)orbm_stage_in(m, train_desc, (size_t)m->grid.n * 32) : m->d_t;
-    const uint8_t *ss = (skip && m->grid.n > 0) ? (const uint8_t *)orbm_stage_in(m, skip, (size_t)m->grid.n) : nullptr;
-    if (sx && sy && sr && smn && smx && sq && st && (ss || !(skip && m->grid.n > 0))) {
-        rc = orbm_flush_in(m, mark, s);
-        if (rc != ORBX_OK) return rc;
-        rc = orbm_search_area_best2_device(m, sq, sx, sy, sr, smn, smx, nq, st, ss, o_bi, o_bd, o_sd, s);
-        if (rc != ORBX_OK) return rc;
-    } else {     // first call / arena too small: per-array copies into the fixed buffers (the arena grows for the next call)
-        rc = upload_windows(m, x, y, r, min_level, max_level, nq, s);
-        if (rc != ORBX_OK) return rc;
-        const size_t Q = m->qf_elems;
-        { int rc_ = orbm_h2d(m, m->d_q, qdesc, (size_t)nq * 32, s); if (rc_ != ORBX_OK) return rc_; }
-        if (m->grid.n > 0) { int rc_ = orbm_h2d(m, m->d_t, train_desc, (size_t)m->grid.n * 32, s); if (rc_ != ORBX_OK) return rc_; }
-        const uint8_t *d_skip = nullptr;
-        if (skip && m->grid.n > 0) {
-            if (!m->d_skip) MHIPCHK(hipMalloc((void **)&m->d_skip, (size_t)m->max_t));
-            { int rc_ = orbm_h2d(m, m->d_skip, skip, (size_t)m->grid.n, s); if (rc_ != ORBX_OK) return rc_; }
-            d_skip = m->d_skip;
-        }
-        rc = orbm_search_area_best2_device(m, m->d_q, m->d_qf, m->d_qf + Q, m->d_qf + 2 * Q, m->d_qi, m->d_qi + Q, nq, m->d_t, d_skip,
-                                           o_bi, o_bd, o_sd, s);
-        if (rc != ORBX_OK) return rc;
-    }
-    {
-        void *const hosts[3] = {best_idx, best_d, second_d};
-        const size_t parts[3] = {nb4, nb4, nb4};
-        int rc_ = orbm_d2h_split(m, hosts, parts, 3, o_bi, s);
-        if (rc_ != ORBX_OK) return rc_;
-    }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
+    const size_t nb4 = (size_t)nq * 4, nt = (size_t)m->grid.n;
+    InBlock in(m);
+    const WindowParts w(in, x, y, r, min_level, max_level, nq);
+    const int pq = in.add(qdesc, (size_t)nq * 32), pt = in.add(train_desc, nt * 32), ps = in.add(skip, skip ? nt : 0);
+    MTRY(in.upload(s));
+    MTRY(orbm_search_area_best2_device(m, in.at<uint8_t>(pq), in.at<float>(w.x), in.at<float>(w.y), in.at<float>(w.r), in.at<int32_t>(w.mn),
+                                       in.at<int32_t>(w.mx), nq, nt > 0 ? in.at<uint8_t>(pt) : m->d_t, in.at<uint8_t>(ps), o_bi, o_bd, o_sd, s));
+    void *const hosts[3] = {best_idx, best_d, second_d};
+    const size_t parts[3] = {nb4, nb4, nb4};
+    MTRY(orbm_d2h_split(m, hosts, parts, 3, o_bi, s));
+    MTRY(orbm_sync(m, s));
     return ORBX_OK;
 }
 
@@ -454,70 +414,36 @@ extern "C" int orbm_search_area_best2(orbm_matcher *m, const uint8_t *qdesc, con
 // is sequential on the host (SearchForInitialization, SearchByProjection(Frame, Frame)): inputs go up in one copy, counts come
 // back, offsets go up, lists and distances come back -- two synchronisations.  (One pass into fixed per-window slots was
 // measured: the fullest windows need > 128 slots, and copying nq x slots back costs more than the second round trip.)
-// Falls back to the two public calls when the arena has no room yet (first call).
+// The caller has grown the handle to nq queries.  Returns the number of candidates.
 int orbm_area_pairs(orbm_matcher *m, const float *x, const float *y, const float *r, const int32_t *mn, const int32_t *mx, int nq,
-                      const uint8_t *qdesc, const uint8_t *train_desc, int n_train,
-                      std::vector<int32_t> &off, std::vector<int32_t> &idx, std::vector<int32_t> &dist)
+                    const uint8_t *qdesc, const uint8_t *train_desc, int n_train,
+                    std::vector<int32_t> &off, std::vector<int32_t> &idx, std::vector<int32_t> &dist)
 {
     off.assign((size_t)nq + 1, 0);
     MHIPCHK(hipSetDevice(m->device));
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = ensure_query_staging(m, (size_t)nq); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    const size_t nb4 = (size_t)nq * 4, mark = m->arena_used;
-    const float *sx = (const float *)orbm_stage_in(m, x, nb4), *sy = (const float *)orbm_stage_in(m, y, nb4), *sr = (const float *)orbm_stage_in(m, r, nb4);
-    const int32_t *smn = (const int32_t *)orbm_stage_in(m, mn, nb4), *smx = (const int32_t *)orbm_stage_in(m, mx, nb4);
-    const uint8_t *sq = (const uint8_t *)orbm_stage_in(m, qdesc, (size_t)nq * 32), *st = (const uint8_t *)orbm_stage_in(m, train_desc, (size_t)n_train * 32);
-    int32_t *soff = (int32_t *)orbm_stage_in(m, off.data(), ((size_t)nq + 1) * 4);      // place holder, filled after the counts are known
-    if (!(sx && sy && sr && smn && smx && sq && st && soff)) {
-        idx.assign((size_t)std::max<long long>(std::min<long long>(m->max_pairs, (long long)nq * n_train), 1), 0);
-        int total = orbm_features_in_area(m, x, y, r, mn, mx, nq, off.data(), idx.data(), (int)idx.size());
-        if (total == ORBX_E_CAPACITY) {       // more candidates than the handle was created for: every window can hold at most n_train
-            idx.assign((size_t)std::max<long long>(std::min<long long>((long long)nq * n_train, INT_MAX), 1), 0);
-            total = orbm_features_in_area(m, x, y, r, mn, mx, nq, off.data(), idx.data(), (int)idx.size());
-        }
-        if (total < 0) return total;
-        idx.resize((size_t)std::max(total, 1));
-        dist.assign((size_t)std::max(total, 1), 0);
-        if (total > 0) { int rc = orbm_distances(m, qdesc, nq, train_desc, n_train, off.data(), idx.data(), dist.data()); if (rc != ORBX_OK) return rc; }
-        return total;
-    }
-    { int rc_ = orbm_flush_in(m, mark, s); if (rc_ != ORBX_OK) return rc_; }
-    const size_t Q = m->qf_elems;
-    int32_t *d_cnt = m->d_qi + 2 * Q;
-    const dim3 grid((nq + 3) / 4);
-    hipLaunchKernelGGL(k_area_list<0>, grid, dim3(M_THREADS), 0, s, m->grid, sx, sy, sr, smn, smx, nq, d_cnt, (const int32_t *)nullptr, (int32_t *)nullptr);
-    MHIPCHK(hipGetLastError());
-    const int32_t *cnt = (const int32_t *)orbm_d2h_tmp(m, d_cnt, nb4, s);
-    std::vector<int32_t> cnt_plain;
-    if (!cnt) {           // no room left in the arena this call (it grows for the next one): a plain copy
-        cnt_plain.resize((size_t)nq);
-        MHIPCHK(hipMemcpyAsync(cnt_plain.data(), d_cnt, nb4, hipMemcpyDeviceToHost, s));
-        cnt = cnt_plain.data();
-    }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
+    InBlock in(m);
+    const WindowParts w(in, x, y, r, mn, mx, nq);
+    const int pq = in.add(qdesc, (size_t)nq * 32), pt = in.add(train_desc, (size_t)n_train * 32);
+    const int poff = in.reserve(((size_t)nq + 1) * 4);      // filled after the counts are known
+    MTRY(in.upload(s));
+    MTRY(launch_area_list<0>(m, in, w, nq, m->d_out, nullptr, nullptr, s));
+    std::vector<int32_t> cnt((size_t)nq);
+    MTRY(orbm_d2h(m, cnt.data(), m->d_out, (size_t)nq * 4, s));
+    MTRY(orbm_sync(m, s));
     for (int i = 0; i < nq; i++) off[i + 1] = off[i] + cnt[i];
     const int total = off[nq];
     idx.assign((size_t)std::max(total, 1), 0); dist.assign((size_t)std::max(total, 1), 0);
     if (total == 0) return 0;
-    if (total > m->max_pairs) { int rc_ = orbm_grow(m, 0, 0, total); if (rc_ != ORBX_OK) return rc_; }     // d_idx / d_out hold nothing yet
-    uint8_t *h_off = m->arena + ((uint8_t *)soff - m->d_arena);
-    memcpy(h_off, off.data(), ((size_t)nq + 1) * 4);
-    MHIPCHK(hipMemcpyAsync(soff, h_off, ((size_t)nq + 1) * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(k_area_list<1>, grid, dim3(M_THREADS), 0, s, m->grid, sx, sy, sr, smn, smx, nq, (int32_t *)nullptr, (const int32_t *)soff, m->d_idx);
+    MTRY(orbm_grow(m, 0, 0, total));                 // d_idx / d_out hold nothing yet
+    MTRY(in.fill(poff, off.data(), s));
+    MTRY(launch_area_list<1>(m, in, w, nq, nullptr, in.at<int32_t>(poff), m->d_idx, s));
+    orbm_launch_dist_csr(in.at<uint8_t>(pq), nq, in.at<uint8_t>(pt), in.at<int32_t>(poff), m->d_idx, total, m->d_out, s);
     MHIPCHK(hipGetLastError());
-    orbm_launch_dist_csr(sq, nq, st, soff, m->d_idx, total, m->d_out, s);
-    MHIPCHK(hipGetLastError());
-    const void *hi = orbm_d2h_tmp(m, m->d_idx, (size_t)total * 4, s), *hd = orbm_d2h_tmp(m, m->d_out, (size_t)total * 4, s);
-    if (!hi || !hd) {     // no room for the lists this call (the arena grows for the next one): plain copies
-        MHIPCHK(hipMemcpyAsync(idx.data(), m->d_idx, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-        MHIPCHK(hipMemcpyAsync(dist.data(), m->d_out, (size_t)total * 4, hipMemcpyDeviceToHost, s));
-        MHIPCHK(hipStreamSynchronize(s));
-        return total;
-    }
-    { int rc_ = orbm_sync(m, s); if (rc_ != ORBX_OK) return rc_; }
-    memcpy(idx.data(), hi, (size_t)total * 4);
-    memcpy(dist.data(), hd, (size_t)total * 4);
+    MTRY(orbm_d2h(m, idx.data(), m->d_idx, (size_t)total * 4, s));
+    MTRY(orbm_d2h(m, dist.data(), m->d_out, (size_t)total * 4, s));
+    MTRY(orbm_sync(m, s));
     return total;
 }
 
@@ -535,30 +461,19 @@ extern "C" int orbm_search_for_initialization(orbm_matcher *m, const orbx_keypoi
     if (n1 == 0 || n2 == 0) return ORBX_OK;
     if (!m->grid_ok || m->grid.n != n2) return mfail(ORBX_E_INVALID, "orbm_grid_build(frame 2) has not been called (grid holds %d keypoints, n2 = %d)", m->grid_ok ? m->grid.n : -1, n2);
     // the queries: keypoints of frame 1 on level 0 (:421-423), their windows and descriptors
-    std::vector<int> qi;
+    AreaQueries Q;
     for (int i = 0; i < n1; i++)
-        if (kps1[i].octave <= 0) qi.push_back(i);
-    const int nq = (int)qi.size();
+        if (kps1[i].octave <= 0) Q.add(i, prev_matched[2 * i], prev_matched[2 * i + 1], (float)window_size, kps1[i].octave, kps1[i].octave);
+    const int nq = Q.size();
     if (nq == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, nq, 0, 0); if (rc_ != ORBX_OK) return rc_; }
-    std::vector<float> x(nq), y(nq), r(nq, (float)window_size);
-    std::vector<int32_t> lv(nq), off, idx, dist;
-    std::vector<uint8_t> qd((size_t)nq * 32);
-    for (int k = 0; k < nq; k++) {
-        const int i = qi[k];
-        x[k] = prev_matched[2 * i]; y[k] = prev_matched[2 * i + 1]; lv[k] = kps1[i].octave;
-        memcpy(&qd[(size_t)k * 32], desc1 + (size_t)i * 32, 32);
-    }
-    const int total = orbm_area_pairs(m, x.data(), y.data(), r.data(), lv.data(), lv.data(), nq, qd.data(), desc2, n2, off, idx, dist);
-    if (total < 0) return total;
+    MTRY(Q.run(m, desc1, desc2, n2));
+    const std::vector<int32_t> &off = Q.off, &idx = Q.idx, &dist = Q.dist;
     // the sequential scan (:418-487)
     std::vector<int> matched_dist((size_t)n2, INT_MAX), matches21((size_t)n2, -1);
-    std::vector<std::pair<int, int>> rot;           // rotHist as (bin, i1) in push order
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    RotHist rot;                                     // tag = i1
     int nm = 0;
     for (int k = 0; k < nq; k++) {
-        const int i1 = qi[k];
+        const int i1 = Q.src[k];
         if (off[k + 1] == off[k]) continue;          // :427
         int bestDist = INT_MAX, bestDist2 = INT_MAX, bestIdx2 = -1;
         for (int c = off[k]; c < off[k + 1]; c++) {
@@ -573,25 +488,11 @@ extern "C" int orbm_search_for_initialization(orbm_matcher *m, const orbx_keypoi
             matches21[bestIdx2] = i1;
             matched_dist[bestIdx2] = bestDist;
             nm++;
-            if (check_orientation) {
-                float rot_ = kps1[i1].angle - kps2[bestIdx2].angle;
-                if (rot_ < 0.0) rot_ += 360.0f;
-                int bin = (int)roundf(rot_ * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-                if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");   // the reference asserts
-                rot.emplace_back(bin, i1);
-                hist[bin]++;
-            }
+            if (check_orientation) MTRY(rot.add(kps1[i1].angle, kps2[bestIdx2].angle, i1));
         }
     }
-    if (check_orientation) {                         // :489-510
-        int32_t ind[3];
-        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-        for (const auto &e : rot) {
-            if (e.first == ind[0] || e.first == ind[1] || e.first == ind[2]) continue;
-            if (matches12[e.second] >= 0) { matches12[e.second] = -1; nm--; }
-        }
-    }
+    if (check_orientation)                           // :489-510
+        rot.cull([&](int i1) { if (matches12[i1] >= 0) { matches12[i1] = -1; nm--; } });
     for (int i1 = 0; i1 < n1; i1++)                  // :513-516
         if (matches12[i1] >= 0) { prev_matched[2 * i1] = kps2[matches12[i1]].x; prev_matched[2 * i1 + 1] = kps2[matches12[i1]].y; }
     *nmatches = nm;
@@ -599,21 +500,6 @@ extern "C" int orbm_search_for_initialization(orbm_matcher *m, const orbx_keypoi
 }
 
 // ---- ORBmatcher::SearchByProjection(Frame&, const Frame&, th, bMono) (src/ORBmatcher.cc:1328-1470) ----
-// (R x + t)[row] as OpenCV 3.1.0 evaluates `R*x + t` on a 3x3 and a 3x1 float matrix: one cv::gemm(R, x, 1, t, 1, dst, 0) call, whose
-// small-matrix path (modules/core/src/matmul.cpp: flags == 0, 2 <= len <= 4) sums the three products in float, left to right, and
-// finishes with (float)(t0*alpha + c*beta) in double.  `-R.t()*t` materialises the transpose and takes the same path with alpha = -1.
-static inline float gemm_row(const float *T, int row, const float *x)
-{
-    const float t0 = T[4 * row] * x[0] + T[4 * row + 1] * x[1] + T[4 * row + 2] * x[2];
-    return (float)((double)t0 * 1.0 + (double)T[4 * row + 3] * 1.0);
-}
-static inline void camera_center(const float *T, float Ow[3])
-{
-    for (int k = 0; k < 3; k++) {
-        const float t0 = T[k] * T[3] + T[4 + k] * T[7] + T[8 + k] * T[11];
-        Ow[k] = (float)((double)t0 * -1.0 + 0.0 * 0.0);       // no C operand: c = zerof, beta = 0 (a zero sum comes out as +0)
-    }
-}
 extern "C" int orbm_search_by_projection_last(orbm_matcher *m, int n_last, const uint8_t *has_point, const float *xw, const uint8_t *mp_desc,
                                               const int32_t *mp_obs, const orbx_keypoint *kps_last, const float *Tcw, const float *Tlw,
                                               float fx, float fy, float cx, float cy, float mb, float mbf, const float bounds[4],
@@ -634,10 +520,8 @@ extern "C" int orbm_search_by_projection_last(orbm_matcher *m, int n_last, const
     const float tlc2 = gemm_row(Tlw, 2, twc);
     const bool forward = tlc2 > mb && !mono, backward = -tlc2 > mb && !mono;
     // projections (:1352-1394): one window per last-frame feature that survives the checks
-    struct Qr { int i; float u, invzc, radius; };
-    std::vector<Qr> qs;
-    std::vector<float> x, y, r;
-    std::vector<int32_t> mn, mx;
+    AreaQueries Q;
+    std::vector<float> invz;
     for (int i = 0; i < n_last; i++) {
         if (!has_point[i]) continue;
         const float *X = xw + 3 * (size_t)i;
@@ -650,61 +534,42 @@ extern "C" int orbm_search_by_projection_last(orbm_matcher *m, int n_last, const
         const int oct = kps_last[i].octave;
         if (oct < 0 || oct >= nlevels) return mfail(ORBX_E_INVALID, "last-frame keypoint %d on octave %d of %d", i, oct, nlevels);
         const float radius = th * scale_factors[oct];
-        qs.push_back({i, u, invzc, radius});
-        x.push_back(u); y.push_back(v); r.push_back(radius);
-        if (forward) { mn.push_back(oct); mx.push_back(-1); }
-        else if (backward) { mn.push_back(0); mx.push_back(oct); }
-        else { mn.push_back(oct - 1); mx.push_back(oct + 1); }
+        if (forward) Q.add(i, u, v, radius, oct, -1);
+        else if (backward) Q.add(i, u, v, radius, 0, oct);
+        else Q.add(i, u, v, radius, oct - 1, oct + 1);
+        invz.push_back(invzc);
     }
-    const int nq = (int)qs.size();
+    const int nq = Q.size();
     if (nq == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, nq, 0, 0); if (rc_ != ORBX_OK) return rc_; }
-    std::vector<int32_t> off, idx, dist;
-    std::vector<uint8_t> qd((size_t)nq * 32);
-    for (int k = 0; k < nq; k++) memcpy(&qd[(size_t)k * 32], mp_desc + (size_t)qs[k].i * 32, 32);
-    const int total = orbm_area_pairs(m, x.data(), y.data(), r.data(), mn.data(), mx.data(), nq, qd.data(), desc_cur, n_cur, off, idx, dist);
-    if (total < 0) return total;
+    MTRY(Q.run(m, mp_desc, desc_cur, n_cur));
+    const std::vector<int32_t> &off = Q.off, &idx = Q.idx, &dist = Q.dist;
     // the sequential scan (:1396-1444)
-    std::vector<std::pair<int, int>> rot;
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    RotHist rot;                                     // tag = the current frame's feature
     int nm = 0;
     for (int k = 0; k < nq; k++) {
         if (off[k + 1] == off[k]) continue;
-        const Qr &q = qs[k];
+        const int iLast = Q.src[k];
         int bestDist = 256, bestIdx2 = -1;
         for (int c = off[k]; c < off[k + 1]; c++) {
             const int i2 = idx[c];
             if (cur_obs[i2] > 0) continue;
             if (u_right && u_right[i2] > 0) {
-                const float ur = q.u - mbf * q.invzc;
+                const float ur = Q.x[k] - mbf * invz[k];
                 const float er = fabsf(ur - u_right[i2]);
-                if (er > q.radius) continue;
+                if (er > Q.r[k]) continue;
             }
             const int d = dist[c];
             if (d < bestDist) { bestDist = d; bestIdx2 = i2; }
         }
         if (bestDist <= ORBM_TH_HIGH) {
-            cur_obs[bestIdx2] = mp_obs[q.i];
-            cur_match[bestIdx2] = q.i;
+            cur_obs[bestIdx2] = mp_obs[iLast];
+            cur_match[bestIdx2] = iLast;
             nm++;
-            if (check_orientation) {
-                float rot_ = kps_last[q.i].angle - kps_cur[bestIdx2].angle;
-                if (rot_ < 0.0) rot_ += 360.0f;
-                int bin = (int)roundf(rot_ * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-                if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");
-                rot.emplace_back(bin, bestIdx2);
-                hist[bin]++;
-            }
+            if (check_orientation) MTRY(rot.add(kps_last[iLast].angle, kps_cur[bestIdx2].angle, bestIdx2));
         }
     }
-    if (check_orientation) {                         // :1447-1466
-        int32_t ind[3];
-        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-        for (const auto &e : rot)
-            if (e.first != ind[0] && e.first != ind[1] && e.first != ind[2]) { cur_obs[e.second] = -1; cur_match[e.second] = -1; nm--; }
-    }
+    if (check_orientation)                           // :1447-1466
+        rot.cull([&](int i2) { cur_obs[i2] = -1; cur_match[i2] = -1; nm--; });
     *nmatches = nm;
     return ORBX_OK;
 }
@@ -758,28 +623,19 @@ extern "C" int orbm_search_by_projection_kf(orbm_matcher *m, int n_mp, const uin
     for (int i = 0; i < n_cur; i++) cur_match[i] = -1;
     if (n_mp == 0 || n_cur == 0) return ORBX_OK;
     if (!m->grid_ok || m->grid.n != n_cur) return mfail(ORBX_E_INVALID, "orbm_grid_build(current frame) has not been called");
-    std::vector<int> qi;
-    std::vector<float> x, y, r;
-    std::vector<int32_t> mn, mx;
+    AreaQueries Q;
     for (int i = 0; i < n_mp; i++) {
         if (!use[i]) continue;
         const int lv = pred_level[i];
         if (lv < 0 || lv >= nlevels) return mfail(ORBX_E_INVALID, "MapPoint %d predicted on level %d of %d", i, lv, nlevels);
-        qi.push_back(i); x.push_back(proj_u[i]); y.push_back(proj_v[i]); r.push_back(th * scale_factors[lv]);   // :1526
-        mn.push_back(lv - 1); mx.push_back(lv + 1);                                                              // :1528
+        Q.add(i, proj_u[i], proj_v[i], th * scale_factors[lv], lv - 1, lv + 1);       // :1526, :1528
     }
-    const int nq = (int)qi.size();
+    const int nq = Q.size();
     if (nq == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, nq, 0, 0); if (rc_ != ORBX_OK) return rc_; }
-    std::vector<int32_t> off, idx, dist;
-    std::vector<uint8_t> qd((size_t)nq * 32);
-    for (int k = 0; k < nq; k++) memcpy(&qd[(size_t)k * 32], mp_desc + (size_t)qi[k] * 32, 32);
-    const int total = orbm_area_pairs(m, x.data(), y.data(), r.data(), mn.data(), mx.data(), nq, qd.data(), desc_cur, n_cur, off, idx, dist);
-    if (total < 0) return total;
+    MTRY(Q.run(m, mp_desc, desc_cur, n_cur));
+    const std::vector<int32_t> &off = Q.off, &idx = Q.idx, &dist = Q.dist;
     // the sequential scan (:1538-1575): an assignment blocks the slot for every later MapPoint
-    std::vector<std::pair<int, int>> rot;
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    RotHist rot;                                     // tag = the current frame's feature
     int nm = 0;
     for (int k = 0; k < nq; k++) {
         if (off[k + 1] == off[k]) continue;
@@ -792,25 +648,13 @@ extern "C" int orbm_search_by_projection_kf(orbm_matcher *m, int n_mp, const uin
         }
         if (bestDist <= orb_dist && bestIdx2 >= 0) {
             cur_has_point[bestIdx2] = 1;
-            cur_match[bestIdx2] = qi[k];
+            cur_match[bestIdx2] = Q.src[k];
             nm++;
-            if (check_orientation) {
-                float rot_ = kf_angle[qi[k]] - kps_cur[bestIdx2].angle;
-                if (rot_ < 0.0) rot_ += 360.0f;
-                int bin = (int)roundf(rot_ * factor);
-                if (bin == ORBM_HISTO_LENGTH) bin = 0;
-                if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");
-                rot.emplace_back(bin, bestIdx2);
-                hist[bin]++;
-            }
+            if (check_orientation) MTRY(rot.add(kf_angle[Q.src[k]], kps_cur[bestIdx2].angle, bestIdx2));
         }
     }
-    if (check_orientation) {                         // :1577-1596
-        int32_t ind[3];
-        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-        for (const auto &e : rot)
-            if (e.first != ind[0] && e.first != ind[1] && e.first != ind[2]) { cur_has_point[e.second] = 0; cur_match[e.second] = -1; nm--; }
-    }
+    if (check_orientation)                           // :1577-1596
+        rot.cull([&](int i2) { cur_has_point[i2] = 0; cur_match[i2] = -1; nm--; });
     *nmatches = nm;
     return ORBX_OK;
 }
@@ -832,37 +676,30 @@ extern "C" int orbm_search_by_projection_map(orbm_matcher *m, int n_mp, const ui
     if (n_mp == 0 || n_cur == 0) return ORBX_OK;
     if (!m->grid_ok || m->grid.n != n_cur) return mfail(ORBX_E_INVALID, "orbm_grid_build(frame) has not been called");
     const bool bFactor = th != 1.0;
-    std::vector<int> qi;
-    std::vector<float> x, y, r;
-    std::vector<int32_t> mn, mx;
+    AreaQueries Q;
     for (int i = 0; i < n_mp; i++) {
         if (!in_view[i]) continue;
         const int lv = pred_level[i];
         if (lv < 0 || lv >= nlevels) return mfail(ORBX_E_INVALID, "MapPoint %d predicted on level %d of %d", i, lv, nlevels);
         float rr = view_cos[i] > 0.998 ? 2.5f : 4.0f;         // RadiusByViewingCos
         if (bFactor) rr *= th;
-        qi.push_back(i); x.push_back(proj_x[i]); y.push_back(proj_y[i]); r.push_back(rr * scale_factors[lv]);
-        mn.push_back(lv - 1); mx.push_back(lv);
+        Q.add(i, proj_x[i], proj_y[i], rr * scale_factors[lv], lv - 1, lv);
     }
-    const int nq = (int)qi.size();
+    const int nq = Q.size();
     if (nq == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, nq, 0, 0); if (rc_ != ORBX_OK) return rc_; }
-    std::vector<int32_t> off, idx, dist;
-    std::vector<uint8_t> qd((size_t)nq * 32);
-    for (int k = 0; k < nq; k++) memcpy(&qd[(size_t)k * 32], mp_desc + (size_t)qi[k] * 32, 32);
-    const int total = orbm_area_pairs(m, x.data(), y.data(), r.data(), mn.data(), mx.data(), nq, qd.data(), desc_cur, n_cur, off, idx, dist);
-    if (total < 0) return total;
+    MTRY(Q.run(m, mp_desc, desc_cur, n_cur));
+    const std::vector<int32_t> &off = Q.off, &idx = Q.idx, &dist = Q.dist;
     int nm = 0;
     for (int k = 0; k < nq; k++) {                  // :73-122
         if (off[k + 1] == off[k]) continue;
-        const int iMP = qi[k];
+        const int iMP = Q.src[k];
         int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
         for (int c = off[k]; c < off[k + 1]; c++) {
             const int i2 = idx[c];
             if (cur_obs[i2] > 0) continue;
             if (u_right && u_right[i2] > 0) {
                 const float er = fabsf(proj_xr[iMP] - u_right[i2]);
-                if (er > r[k]) continue;
+                if (er > Q.r[k]) continue;
             }
             const int d = dist[c];
             if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestLevel2 = bestLevel; bestLevel = kps_cur[i2].octave; bestIdx = i2; }

@@ -1,8 +1,12 @@
-// orbm_internal.h -- shared by orbm.hip and orbm_grid.hip
+// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip and orbm_mappoint.hip
 #pragma once
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <cstring>
 #include <string>
+#include <utility>
+#include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/orbm.h"
 
@@ -13,6 +17,11 @@ int mfail(int code, const char *fmt, ...);
     do {                                                                                         \
         hipError_t e_ = (expr);                                                                  \
         if (e_ != hipSuccess) return mfail(ORBX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
+    } while (0)
+#define MTRY(expr)                            \
+    do {                                      \
+        int mtry_ = (expr);                   \
+        if (mtry_ != ORBX_OK) return mtry_;   \
     } while (0)
 
 __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
@@ -92,13 +101,10 @@ struct orbm_matcher {
     int dense_popcount = 0;                                          // ORBM_DENSE=popcount: the VALU kernel instead of the matrix cores (A/B record)
     OrbmGrid grid = {};  bool grid_ok = false;                       // N1: Frame grid of the last orbm_grid_build
     OrbmGrid grid2 = {}; bool grid2_ok = false;                      // second slot: orbm_search_by_sim3 searches two key frames
-    float *d_qf = nullptr; int32_t *d_qi = nullptr; uint8_t *d_skip = nullptr;   // window-query staging (lazy)
-    size_t qf_elems = 0;
-    uint8_t *h_pin = nullptr; size_t h_pin_bytes = 0;   // pinned staging of orbm_search_by_bow (lazy)
     // pinned bump arena for the host-buffer entry points: pageable hipMemcpyAsync is a staged, synchronous copy of tens of
     // microseconds each; through pinned memory the copies of one call queue up behind each other and cost one round trip
     uint8_t *arena = nullptr; size_t arena_cap = 0, arena_used = 0, arena_want = 0;
-    uint8_t *d_arena = nullptr;     // device mirror of the arena: inputs staged with orbm_stage_in() go up in ONE copy
+    uint8_t *d_arena = nullptr;     // device mirror of the arena: the inputs of a call (InBlock) go up in ONE copy
     struct Pend { void *dst; const void *src; size_t bytes; };
     Pend pend[8]; int npend = 0;
     uint8_t *d_dd = nullptr; size_t dd_bytes = 0;      // orbm_mappoint.hip: scratch of orbm_distinctive_descriptors (lazy, its own block)
@@ -110,16 +116,15 @@ void orbm_grid_free(OrbmGrid &g);
 // windows + candidate distances pass the host-scanned matchers share (against grid slot g: NULL = m->grid)
 int orbm_grid_build_into(orbm_matcher *m, OrbmGrid &g, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y,
                          float inv_w, float inv_h, float query_min_x, float query_min_y);
-#ifdef __cplusplus
-#include <vector>
 int orbm_area_pairs(orbm_matcher *m, const float *x, const float *y, const float *r, const int32_t *mn, const int32_t *mx, int nq,
                     const uint8_t *qdesc, const uint8_t *train_desc, int n_train,
                     std::vector<int32_t> &off, std::vector<int32_t> &idx, std::vector<int32_t> &dist);
-#endif
 int orbm_arena_begin(orbm_matcher *m);                                                    // start of a host-API call
 int orbm_h2d(orbm_matcher *m, void *dev, const void *host, size_t bytes, hipStream_t s);   // staged host -> device copy
 int orbm_d2h(orbm_matcher *m, void *host, const void *dev, size_t bytes, hipStream_t s);   // staged; lands in host at orbm_sync()
-int orbm_sync(orbm_matcher *m, hipStream_t s);
+// one device block -> up to four host arrays, one copy (parts[i] bytes each, consecutive in the block)
+int orbm_d2h_split(orbm_matcher *m, void *const *host, const size_t *parts, int nparts, const void *dev, hipStream_t s);
+int orbm_sync(orbm_matcher *m, hipStream_t s);                                            // synchronise + deliver the D2H copies
 // orbm_mfma.hip: dense best / second-best partials on the matrix cores (same partial format as k_best2_dense)
 int orbm_mfma_splits(int nq_cap, int nt_cap, int nbatch);
 int orbm_launch_dense_mfma(orbm_matcher *m, const uint8_t *d_q, const int32_t *d_nq, int nq_fixed, const uint8_t *d_t, const int32_t *d_nt,
@@ -128,12 +133,127 @@ int orbm_launch_dense_mfma(orbm_matcher *m, const uint8_t *d_q, const int32_t *d
 // k_dist_csr (orbm.hip) for callers in other files: dist[c] of every CSR candidate, off has nq + 1 entries
 void orbm_launch_dist_csr(const uint8_t *d_q, int nq, const uint8_t *d_t, const int32_t *d_off, const int32_t *d_idx, int total,
                           int32_t *d_dist, hipStream_t s);
-// Staged input: copies into the pinned arena and returns where it will be in the device mirror after orbm_flush_in()
-// (every hipMemcpyAsync costs ~7 us of host time, so the inputs of one call travel together).  NULL: no room this call.
-void *orbm_stage_in(orbm_matcher *m, const void *host, size_t bytes);
-int orbm_flush_in(orbm_matcher *m, size_t from, hipStream_t s);                            // uploads arena[from, used)
-// device -> pinned arena; returns where the bytes are after orbm_sync() (NULL: no room this call)
-void *orbm_d2h_tmp(orbm_matcher *m, const void *dev, size_t bytes, hipStream_t s);
-// one device block -> up to four host arrays, one copy (parts[i] bytes each, consecutive in the block)
-int orbm_d2h_split(orbm_matcher *m, void *const *host, const size_t *parts, int nparts, const void *dev, hipStream_t s);                                            // synchronise + deliver the D2H copies
 
+// -------------------------------------------------------------------------------------------------
+// host-only helpers
+// -------------------------------------------------------------------------------------------------
+// The host inputs of one call: list the parts, upload() sends them in ONE copy (every hipMemcpyAsync costs ~7 us of host time)
+// through the pinned arena to its device mirror.  Before the arena has grown (first call on a handle, or the first call larger
+// than any before it) the block lives in memory of its own, which goes with the InBlock.  Declare it before the kernels that
+// read it are queued and let it go out of scope after the call's orbm_sync(): the temporary is never freed under a running kernel.
+struct InBlock {
+    struct Part { const void *src; size_t bytes, off; };
+    orbm_matcher *m;
+    std::vector<Part> parts;
+    size_t total = 0;
+    uint8_t *host = nullptr, *dev = nullptr;    // the block after upload()
+    std::vector<uint8_t> tmp_host;
+    void *tmp_dev = nullptr;
+    explicit InBlock(orbm_matcher *m_) : m(m_) {}
+    InBlock(const InBlock &) = delete;
+    InBlock &operator=(const InBlock &) = delete;
+    ~InBlock() { if (tmp_dev) (void)hipFree(tmp_dev); }
+    int add(const void *src, size_t bytes)
+    {
+        parts.push_back({src, bytes, total});
+        total += (bytes + 63) & ~(size_t)63;
+        return (int)parts.size() - 1;
+    }
+    int reserve(size_t bytes) { return add(nullptr, bytes); }     // a part whose content comes later: fill()
+    int upload(hipStream_t s)
+    {
+        if (total == 0) return ORBX_OK;
+        m->arena_want += total;                          // when there is no room now, the next call has it
+        if (m->d_arena && m->arena_used + total <= m->arena_cap) {
+            host = m->arena + m->arena_used; dev = m->d_arena + m->arena_used;
+            m->arena_used += total;
+        } else {
+            tmp_host.resize(total);
+            MHIPCHK(hipMalloc(&tmp_dev, total));
+            host = tmp_host.data(); dev = (uint8_t *)tmp_dev;
+        }
+        for (const Part &p : parts)
+            if (p.src && p.bytes) memcpy(host + p.off, p.src, p.bytes);
+        MHIPCHK(hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, s));
+        if (tmp_dev) MHIPCHK(hipStreamSynchronize(s));   // pageable source
+        return ORBX_OK;
+    }
+    int fill(int part, const void *src, hipStream_t s)   // content of a reserved part, after upload(): one more copy
+    {
+        const Part &p = parts[part];
+        memcpy(host + p.off, src, p.bytes);
+        MHIPCHK(hipMemcpyAsync(dev + p.off, host + p.off, p.bytes, hipMemcpyHostToDevice, s));
+        return ORBX_OK;
+    }
+    template <class T> const T *at(int part) const { return parts[part].bytes ? reinterpret_cast<const T *>(dev + parts[part].off) : nullptr; }
+};
+
+// Rotation histogram of the matchers' orientation check (src/ORBmatcher.cc:236-246 and siblings) and the ComputeThreeMaxima cull
+// (:266-284).  The bin arithmetic is the reference's: float difference, comparison with a double zero, roundf, no contraction.
+struct RotHist {
+    int32_t hist[ORBM_HISTO_LENGTH] = {0};
+    std::vector<std::pair<int, int>> entries;           // rotHist as (bin, tag) in push order
+    int add(float angle_a, float angle_b, int tag)
+    {
+        const float factor = 1.0f / ORBM_HISTO_LENGTH;
+        float rot = angle_a - angle_b;
+        if (rot < 0.0) rot += 360.0f;
+        if (std::isnan(rot)) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");      // no int holds it
+        int bin = (int)roundf(rot * factor);
+        if (bin == ORBM_HISTO_LENGTH) bin = 0;
+        if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");   // the reference asserts
+        entries.emplace_back(bin, tag);
+        hist[bin]++;
+        return ORBX_OK;
+    }
+    template <class F> void cull(F drop)                // drop(tag) for every entry outside the three maxima, in push order
+    {
+        int32_t ind[3];
+        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
+        for (const auto &e : entries)
+            if (e.first != ind[0] && e.first != ind[1] && e.first != ind[2]) drop(e.second);
+    }
+};
+
+// The window queries of a matcher whose scan is sequential on the host: add() one per usable MapPoint / keypoint, run() gathers
+// their descriptors and fetches every window's candidates and distances (orbm_area_pairs): candidates of query k are
+// idx / dist[off[k] .. off[k + 1]).
+struct AreaQueries {
+    std::vector<int> src;                   // index of the query in the caller's arrays
+    std::vector<float> x, y, r;
+    std::vector<int32_t> mn, mx, off, idx, dist;
+    std::vector<uint8_t> desc;
+    void add(int src_index, float qx, float qy, float qr, int min_level, int max_level)
+    {
+        src.push_back(src_index); x.push_back(qx); y.push_back(qy); r.push_back(qr); mn.push_back(min_level); mx.push_back(max_level);
+    }
+    int size() const { return (int)src.size(); }
+    int run(orbm_matcher *m, const uint8_t *src_desc, const uint8_t *train_desc, int n_train)
+    {
+        const int nq = size();
+        MTRY(orbm_grow(m, nq, 0, 0));
+        desc.resize((size_t)nq * 32);
+        for (int k = 0; k < nq; k++) memcpy(&desc[(size_t)k * 32], src_desc + (size_t)src[k] * 32, 32);
+        const int total = orbm_area_pairs(m, x.data(), y.data(), r.data(), mn.data(), mx.data(), nq, desc.data(), train_desc, n_train, off, idx, dist);
+        return total < 0 ? total : ORBX_OK;
+    }
+};
+
+// cv::Mat algebra as OpenCV 3.1.0 evaluates it.  `R*x + t` on a 3x3 and a 3x1 float matrix is one cv::gemm(R, x, 1, t, 1, dst, 0)
+// call, whose small-matrix path (modules/core/src/matmul.cpp: flags == 0, 2 <= len <= 4) sums the three float products in float,
+// left to right, and finishes with (float)(t0*alpha + c*beta) in double.  `-A.t()*b` materialises the transpose and runs the same
+// path with alpha = -1 and no C operand: c = zerof, beta = 0 (a zero sum comes out as +0).
+static inline float gemm3(const float *a, int sa, const float *b, double alpha, float c, double beta)
+{
+    const float t0 = a[0] * b[0] + a[sa] * b[1] + a[2 * sa] * b[2];
+    return (float)((double)t0 * alpha + (double)c * beta);
+}
+static inline float gemm_row(const float *T, int row, const float *x)   // (R x + t)[row] of a row-major [R|t]
+{
+    return gemm3(T + 4 * row, 1, x, 1.0, T[4 * row + 3], 1.0);
+}
+static inline void camera_center(const float *T, float Ow[3])           // -Rcw^T tcw
+{
+    const float t[3] = {T[3], T[7], T[11]};
+    for (int k = 0; k < 3; k++) Ow[k] = gemm3(T + k, 4, t, -1.0, 0.f, 0.0);
+}

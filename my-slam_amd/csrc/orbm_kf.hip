@@ -25,19 +25,7 @@
 // -------------------------------------------------------------------------------------------------
 // host side: cv::Mat algebra as OpenCV 3.1.0 evaluates it
 // -------------------------------------------------------------------------------------------------
-// `R*x + t` on a 3x3 and a 3x1 float matrix is cv::gemm(R, x, 1, t, 1, dst, 0), whose small-matrix path (modules/core/src/matmul.cpp:
-// flags == 0, 2 <= len <= 4) sums the three float products in float, left to right, and finishes with (float)(t0*alpha + c*beta) in
-// double.  `-A.t()*b` materialises the transpose and runs the same path with alpha = -1.
-static inline float gemm3(const float *a, int sa, const float *b, double alpha, float c, double beta)
-{
-    const float t0 = a[0] * b[0] + a[sa] * b[1] + a[2 * sa] * b[2];
-    return (float)((double)t0 * alpha + (double)c * beta);
-}
-static inline void camera_center(const float *T, float Ow[3])           // -Rcw^T tcw
-{
-    const float t[3] = {T[3], T[7], T[11]};
-    for (int k = 0; k < 3; k++) Ow[k] = gemm3(T + k, 4, t, -1.0, 0.f, 0.0);
-}
+// (gemm3 / gemm_row / camera_center: orbm_internal.h)
 
 // Scw -> [Rcw|tcw] (row-major 4x4) and Ow: src/ORBmatcher.cc:299-303 and :986-990.
 //   scw = sqrt(sRcw.row(0).dot(sRcw.row(0)))   Mat::dot accumulates in double; the sqrt is a double one, stored in a float
@@ -82,7 +70,7 @@ extern "C" int orbm_project_points_kf(const float *Tcw, const float *Ow, float f
     if (Ow) memcpy(ow, Ow, sizeof ow); else camera_center(Tcw, ow);
     for (int i = 0; i < n; i++) {
         const float *X = xw + 3 * (size_t)i;
-        const float xc = gemm3(Tcw, 1, X, 1.0, Tcw[3], 1.0), yc = gemm3(Tcw + 4, 1, X, 1.0, Tcw[7], 1.0), zc = gemm3(Tcw + 8, 1, X, 1.0, Tcw[11], 1.0);
+        const float xc = gemm_row(Tcw, 0, X), yc = gemm_row(Tcw, 1, X), zc = gemm_row(Tcw, 2, X);
         const float iz = 1 / zc;
         const float x = xc * iz, y = yc * iz;
         u[i] = fx * x + cx; v[i] = fy * y + cy;
@@ -111,7 +99,7 @@ extern "C" int orbm_project_points_sim3(const float *TAw, const float *sR, const
     if (!TAw || !sR || !t || !boundsB || n < 0 || (n > 0 && (!xw || !u || !v || !dist3d || !ok))) return mfail(ORBX_E_INVALID, "bad argument");
     for (int i = 0; i < n; i++) {
         const float *X = xw + 3 * (size_t)i;
-        const float pA[3] = {gemm3(TAw, 1, X, 1.0, TAw[3], 1.0), gemm3(TAw + 4, 1, X, 1.0, TAw[7], 1.0), gemm3(TAw + 8, 1, X, 1.0, TAw[11], 1.0)};
+        const float pA[3] = {gemm_row(TAw, 0, X), gemm_row(TAw, 1, X), gemm_row(TAw, 2, X)};
         float pB[3];
         for (int r = 0; r < 3; r++) pB[r] = gemm3(sR + 3 * r, 1, pA, 1.0, t[r], 1.0);
         const float iz = (float)(1.0 / pB[2]);
@@ -255,55 +243,6 @@ __global__ __launch_bounds__(M_THREADS) void k_triangulation(const int4 *__restr
     if (lane == 0) match[q] = B == TRI_KEY_NONE ? -1 : idx2v[rec.y + (int)(0xFFFFFu - (B & 0xFFFFFu))];
 }
 
-// -------------------------------------------------------------------------------------------------
-// staging: the inputs of one call go up in one copy (pinned arena -> its device mirror), or through a temporary block on the first
-// call, before the arena has grown
-// -------------------------------------------------------------------------------------------------
-struct InBlock {
-    orbm_matcher *m;
-    std::vector<std::pair<const void *, size_t>> parts;
-    std::vector<size_t> offs;
-    size_t total = 0;
-    uint8_t *dev = nullptr;
-    void *tmp_dev = nullptr;
-    explicit InBlock(orbm_matcher *m_) : m(m_) {}
-    int add(const void *host, size_t bytes)
-    {
-        parts.emplace_back(host, bytes);
-        offs.push_back(total);
-        total += (bytes + 63) & ~(size_t)63;
-        return (int)parts.size() - 1;
-    }
-    int upload(hipStream_t s)
-    {
-        if (total == 0) return ORBX_OK;
-        const size_t mark = m->arena_used;
-        uint8_t *dst_dev = nullptr;
-        if (m->d_arena && m->arena_used + total <= m->arena_cap) {
-            uint8_t *h = m->arena + m->arena_used;
-            for (size_t i = 0; i < parts.size(); i++)
-                if (parts[i].second) memcpy(h + offs[i], parts[i].first, parts[i].second);
-            dst_dev = m->d_arena + m->arena_used;
-            m->arena_used += total; m->arena_want += total;
-            int rc = orbm_flush_in(m, mark, s);
-            if (rc != ORBX_OK) return rc;
-        } else {
-            m->arena_want += total;                      // the next call has room
-            std::vector<uint8_t> h(total);
-            for (size_t i = 0; i < parts.size(); i++)
-                if (parts[i].second) memcpy(h.data() + offs[i], parts[i].first, parts[i].second);
-            MHIPCHK(hipMalloc(&tmp_dev, total));
-            dst_dev = (uint8_t *)tmp_dev;
-            MHIPCHK(hipMemcpyAsync(dst_dev, h.data(), total, hipMemcpyHostToDevice, s));
-            MHIPCHK(hipStreamSynchronize(s));            // h goes out of scope
-        }
-        dev = dst_dev;
-        return ORBX_OK;
-    }
-    template <class T> const T *at(int part) const { return parts[part].second ? reinterpret_cast<const T *>(dev + offs[part]) : nullptr; }
-    void release() { if (tmp_dev) { (void)hipFree(tmp_dev); tmp_dev = nullptr; } }
-};
-
 // the compacted queries of one stateless window search, and its launch
 struct KfQueries {
     std::vector<int> src;                   // original MapPoint index
@@ -335,8 +274,7 @@ static int launch_search_kf(orbm_matcher *m, const OrbmGrid &g, const KfQueries 
     const int pl = in.add(Q.level.data(), (size_t)nq * 4), pd = in.add(Q.desc.data(), (size_t)nq * 32), pt = in.add(desc_kf, (size_t)n_kf * 32);
     const bool gated = u_right_kf != nullptr;
     const int pu = gated ? in.add(Q.ur.data(), (size_t)nq * 4) : -1, pk = gated ? in.add(u_right_kf, (size_t)n_kf * 4) : -1;
-    int rc = in.upload(s);
-    if (rc != ORBX_OK) return rc;
+    MTRY(in.upload(s));
     KfGate gate = {};
     gate.on = gated ? 1 : 0;
     if (gated) {
@@ -371,24 +309,18 @@ static int stateless_search(orbm_matcher *m, int n_mp, const uint8_t *use, const
     if (n_mp == 0 || n_kf == 0) return ORBX_OK;
     if (!m->grid_ok || m->grid.n != n_kf) return mfail(ORBX_E_INVALID, "orbm_grid_build_kf(key frame) has not been called");
     KfQueries Q;
-    int rc = Q.build(n_mp, use, proj_u, proj_v, proj_ur, pred_level, mp_desc, scale_factors, nlevels, th);
-    if (rc != ORBX_OK) return rc;
+    MTRY(Q.build(n_mp, use, proj_u, proj_v, proj_ur, pred_level, mp_desc, scale_factors, nlevels, th));
     const int nq = (int)Q.src.size();
     if (nq == 0) return ORBX_OK;
     MHIPCHK(hipSetDevice(m->device));
-    rc = orbm_grow(m, nq, 0, 0);
-    if (rc != ORBX_OK) return rc;
-    rc = orbm_arena_begin(m);
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_grow(m, nq, 0, 0));
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     InBlock in(m);
-    rc = launch_search_kf(m, m->grid, Q, desc_kf, n_kf, proj_ur ? u_right_kf : nullptr, inv_level_sigma2, nlevels, m->d_out, in, s);
-    if (rc != ORBX_OK) { in.release(); return rc; }
+    MTRY(launch_search_kf(m, m->grid, Q, desc_kf, n_kf, proj_ur ? u_right_kf : nullptr, inv_level_sigma2, nlevels, m->d_out, in, s));
     std::vector<int32_t> res((size_t)2 * nq);
-    rc = orbm_d2h(m, res.data(), m->d_out, (size_t)2 * nq * 4, s);
-    if (rc == ORBX_OK) rc = orbm_sync(m, s);
-    in.release();
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_d2h(m, res.data(), m->d_out, (size_t)2 * nq * 4, s));
+    MTRY(orbm_sync(m, s));
     int cnt = 0;
     for (int k = 0; k < nq; k++)
         if (res[k] >= 0 && res[(size_t)nq + k] <= max_dist) { best_idx[Q.src[k]] = res[k]; cnt++; }
@@ -404,8 +336,7 @@ extern "C" int orbm_fuse(orbm_matcher *m, int n_mp, const uint8_t *use, const fl
                          int nlevels, const orbx_keypoint *kps_kf, const float *u_right_kf, const uint8_t *desc_kf, int n_kf, float th,
                          int32_t *best_idx, int *nfused)
 {
-    int rc = check_kf_args(m, n_mp, use, proj_u, proj_v, pred_level, mp_desc, scale_factors, nlevels, kps_kf, desc_kf, n_kf);
-    if (rc != ORBX_OK) return rc;
+    MTRY(check_kf_args(m, n_mp, use, proj_u, proj_v, pred_level, mp_desc, scale_factors, nlevels, kps_kf, desc_kf, n_kf));
     if (!best_idx || !nfused || !inv_level_sigma2 || (n_mp > 0 && !proj_ur) || (n_kf > 0 && !u_right_kf)) return mfail(ORBX_E_INVALID, "bad argument");
     return stateless_search(m, n_mp, use, proj_u, proj_v, proj_ur, pred_level, mp_desc, scale_factors, inv_level_sigma2, nlevels, u_right_kf,
                             desc_kf, n_kf, th, ORBM_TH_LOW, best_idx, nfused);
@@ -415,8 +346,7 @@ extern "C" int orbm_fuse_sim3(orbm_matcher *m, int n_mp, const uint8_t *use, con
                               const int32_t *pred_level, const uint8_t *mp_desc, const float *scale_factors, int nlevels,
                               const orbx_keypoint *kps_kf, const uint8_t *desc_kf, int n_kf, float th, int32_t *best_idx, int *nfused)
 {
-    int rc = check_kf_args(m, n_mp, use, proj_u, proj_v, pred_level, mp_desc, scale_factors, nlevels, kps_kf, desc_kf, n_kf);
-    if (rc != ORBX_OK) return rc;
+    MTRY(check_kf_args(m, n_mp, use, proj_u, proj_v, pred_level, mp_desc, scale_factors, nlevels, kps_kf, desc_kf, n_kf));
     if (!best_idx || !nfused) return mfail(ORBX_E_INVALID, "bad argument");
     return stateless_search(m, n_mp, use, proj_u, proj_v, nullptr, pred_level, mp_desc, scale_factors, nullptr, nlevels, nullptr,
                             desc_kf, n_kf, th, ORBM_TH_LOW, best_idx, nfused);
@@ -427,33 +357,25 @@ extern "C" int orbm_search_by_projection_sim3(orbm_matcher *m, int n_mp, const u
                                               const orbx_keypoint *kps_kf, const uint8_t *desc_kf, int n_kf, int th,
                                               uint8_t *kf_matched, int32_t *kf_match, int *nmatches)
 {
-    int rc = check_kf_args(m, n_mp, use, proj_u, proj_v, pred_level, mp_desc, scale_factors, nlevels, kps_kf, desc_kf, n_kf);
-    if (rc != ORBX_OK) return rc;
+    MTRY(check_kf_args(m, n_mp, use, proj_u, proj_v, pred_level, mp_desc, scale_factors, nlevels, kps_kf, desc_kf, n_kf));
     if (!nmatches || (n_kf > 0 && (!kf_matched || !kf_match))) return mfail(ORBX_E_INVALID, "bad argument");
     *nmatches = 0;
     for (int i = 0; i < n_kf; i++) kf_match[i] = -1;
     if (n_mp == 0 || n_kf == 0) return ORBX_OK;
     if (!m->grid_ok || m->grid.n != n_kf) return mfail(ORBX_E_INVALID, "orbm_grid_build_kf(key frame) has not been called");
-    std::vector<int> qi;
-    std::vector<float> x, y, r;
-    std::vector<int32_t> mn, mx;
+    AreaQueries Q;
     for (int i = 0; i < n_mp; i++) {
         if (!use[i]) continue;
         const int lv = pred_level[i];
         if (lv < 0 || lv >= nlevels) return mfail(ORBX_E_INVALID, "MapPoint %d predicted on level %d of %d", i, lv, nlevels);
-        qi.push_back(i); x.push_back(proj_u[i]); y.push_back(proj_v[i]); r.push_back(th * scale_factors[lv]);     // :360
         // the octave test of :380 drops candidates without any other effect, so it rides in the window query: with (lv - 1, lv) the
         // level branch of GetFeaturesInArea's Frame twin is `octave < lv - 1 || octave > lv` for every lv >= 0
-        mn.push_back(lv - 1); mx.push_back(lv);
+        Q.add(i, proj_u[i], proj_v[i], th * scale_factors[lv], lv - 1, lv);          // :360
     }
-    const int nq = (int)qi.size();
+    const int nq = Q.size();
     if (nq == 0) return ORBX_OK;
-    { int rc_ = orbm_grow(m, nq, 0, 0); if (rc_ != ORBX_OK) return rc_; }
-    std::vector<int32_t> off, idx, dist;
-    std::vector<uint8_t> qd((size_t)nq * 32);
-    for (int k = 0; k < nq; k++) memcpy(&qd[(size_t)k * 32], mp_desc + (size_t)qi[k] * 32, 32);
-    const int total = orbm_area_pairs(m, x.data(), y.data(), r.data(), mn.data(), mx.data(), nq, qd.data(), desc_kf, n_kf, off, idx, dist);
-    if (total < 0) return total;
+    MTRY(Q.run(m, mp_desc, desc_kf, n_kf));
+    const std::vector<int32_t> &off = Q.off, &idx = Q.idx, &dist = Q.dist;
     int nm = 0;
     for (int k = 0; k < nq; k++) {                  // the sequential scan (:370-398): a match blocks its slot for every later MapPoint
         int bestDist = 256, bestIdx = -1;
@@ -463,7 +385,7 @@ extern "C" int orbm_search_by_projection_sim3(orbm_matcher *m, int n_mp, const u
             const int d = dist[c];
             if (d < bestDist) { bestDist = d; bestIdx = i2; }
         }
-        if (bestDist <= ORBM_TH_LOW) { kf_matched[bestIdx] = 1; kf_match[bestIdx] = qi[k]; nm++; }
+        if (bestDist <= ORBM_TH_LOW) { kf_matched[bestIdx] = 1; kf_match[bestIdx] = Q.src[k]; nm++; }
     }
     *nmatches = nm;
     return ORBX_OK;
@@ -479,10 +401,8 @@ extern "C" int orbm_search_by_sim3(orbm_matcher *m,
                                    const orbx_keypoint *kps2, const uint8_t *desc2, int n2, const orbm_kf_grid *grid2, const float *scale_factors2,
                                    int nlevels2, float th, int32_t *match12, int *nfound)
 {
-    int rc = check_kf_args(m, n_mp1, use1, proj_u1, proj_v1, pred_level1, mp_desc1, scale_factors2, nlevels2, kps2, desc2, n2);
-    if (rc != ORBX_OK) return rc;
-    rc = check_kf_args(m, n_mp2, use2, proj_u2, proj_v2, pred_level2, mp_desc2, scale_factors1, nlevels1, kps1, desc1, n1);
-    if (rc != ORBX_OK) return rc;
+    MTRY(check_kf_args(m, n_mp1, use1, proj_u1, proj_v1, pred_level1, mp_desc1, scale_factors2, nlevels2, kps2, desc2, n2));
+    MTRY(check_kf_args(m, n_mp2, use2, proj_u2, proj_v2, pred_level2, mp_desc2, scale_factors1, nlevels1, kps1, desc1, n1));
     if (!grid1 || !grid2 || !nfound || (n_mp1 > 0 && !match12)) return mfail(ORBX_E_INVALID, "bad argument");
     if (n_mp1 != n1 || n_mp2 != n2) return mfail(ORBX_E_INVALID, "one MapPoint slot per key-frame feature: n_mp1 = %d / n1 = %d, n_mp2 = %d / n2 = %d", n_mp1, n1, n_mp2, n2);
     *nfound = 0;
@@ -492,34 +412,26 @@ extern "C" int orbm_search_by_sim3(orbm_matcher *m,
     m->grid_ok = false; m->grid2_ok = false;
     if (n1 == 0 || n2 == 0) return ORBX_OK;
     KfQueries Q1, Q2;                                // Q1: MapPoints of key frame 1 searched in key frame 2 (:1148-1225); Q2: the reverse (:1228-1305)
-    rc = Q1.build(n_mp1, use1, proj_u1, proj_v1, nullptr, pred_level1, mp_desc1, scale_factors2, nlevels2, th);
-    if (rc != ORBX_OK) return rc;
-    rc = Q2.build(n_mp2, use2, proj_u2, proj_v2, nullptr, pred_level2, mp_desc2, scale_factors1, nlevels1, th);
-    if (rc != ORBX_OK) return rc;
+    MTRY(Q1.build(n_mp1, use1, proj_u1, proj_v1, nullptr, pred_level1, mp_desc1, scale_factors2, nlevels2, th));
+    MTRY(Q2.build(n_mp2, use2, proj_u2, proj_v2, nullptr, pred_level2, mp_desc2, scale_factors1, nlevels1, th));
     const int nq1 = (int)Q1.src.size(), nq2 = (int)Q2.src.size();
     if (nq1 == 0 || nq2 == 0) return ORBX_OK;       // a match needs both directions
     MHIPCHK(hipSetDevice(m->device));
-    rc = orbm_grow(m, 2 * std::max(nq1, nq2), std::max(n1, n2), 0);
-    if (rc != ORBX_OK) return rc;
-    rc = orbm_arena_begin(m);
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_grow(m, 2 * std::max(nq1, nq2), std::max(n1, n2), 0));
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     // both grids, then both searches, one synchronisation: key frame 1 -> slot `grid`, key frame 2 -> slot `grid2`
-    rc = orbm_grid_build_into(m, m->grid, kps1, n1, grid1->assign_min_x, grid1->assign_min_y, grid1->inv_w, grid1->inv_h, grid1->query_min_x, grid1->query_min_y);
-    if (rc != ORBX_OK) return rc;
-    rc = orbm_grid_build_into(m, m->grid2, kps2, n2, grid2->assign_min_x, grid2->assign_min_y, grid2->inv_w, grid2->inv_h, grid2->query_min_x, grid2->query_min_y);
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_grid_build_into(m, m->grid, kps1, n1, grid1->assign_min_x, grid1->assign_min_y, grid1->inv_w, grid1->inv_h, grid1->query_min_x, grid1->query_min_y));
+    MTRY(orbm_grid_build_into(m, m->grid2, kps2, n2, grid2->assign_min_x, grid2->assign_min_y, grid2->inv_w, grid2->inv_h, grid2->query_min_x, grid2->query_min_y));
     // the grid builder's keypoint staging in d_out is consumed by its kernel before the searches run (same stream), so d_out is free
     // again: the two searches share it
     InBlock in1(m), in2(m);
     int32_t *d_r1 = m->d_out, *d_r2 = m->d_out + 2 * (size_t)nq1;
-    rc = launch_search_kf(m, m->grid2, Q1, desc2, n2, nullptr, nullptr, nlevels2, d_r1, in1, s);
-    if (rc == ORBX_OK) rc = launch_search_kf(m, m->grid, Q2, desc1, n1, nullptr, nullptr, nlevels1, d_r2, in2, s);
+    MTRY(launch_search_kf(m, m->grid2, Q1, desc2, n2, nullptr, nullptr, nlevels2, d_r1, in1, s));
+    MTRY(launch_search_kf(m, m->grid, Q2, desc1, n1, nullptr, nullptr, nlevels1, d_r2, in2, s));
     std::vector<int32_t> res((size_t)2 * (nq1 + nq2));
-    if (rc == ORBX_OK) rc = orbm_d2h(m, res.data(), m->d_out, res.size() * 4, s);
-    if (rc == ORBX_OK) rc = orbm_sync(m, s);
-    in1.release(); in2.release();
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_d2h(m, res.data(), m->d_out, res.size() * 4, s));
+    MTRY(orbm_sync(m, s));
     m->grid_ok = true; m->grid2_ok = true;          // the handle's grid is key frame 1's now
     std::vector<int32_t> vnMatch1((size_t)n1, -1), vnMatch2((size_t)n2, -1);
     for (int k = 0; k < nq1; k++)
@@ -557,7 +469,7 @@ extern "C" int orbm_search_for_triangulation(orbm_matcher *m,
         return mfail(ORBX_E_INVALID, "NULL buffer");
     TriParams P;
     {   // epipole in the second image (:664-670)
-        const float C2x = gemm3(T2w, 1, Cw, 1.0, T2w[3], 1.0), C2y = gemm3(T2w + 4, 1, Cw, 1.0, T2w[7], 1.0), C2z = gemm3(T2w + 8, 1, Cw, 1.0, T2w[11], 1.0);
+        const float C2x = gemm_row(T2w, 0, Cw), C2y = gemm_row(T2w, 1, Cw), C2z = gemm_row(T2w, 2, Cw);
         const float invz = 1.0f / C2z;
         P.ex = fx2 * C2x * invz + cx2; P.ey = fy2 * C2y * invz + cy2;
     }
@@ -597,50 +509,30 @@ extern "C" int orbm_search_for_triangulation(orbm_matcher *m,
     for (int i = 0; i < n1; i++) { xy1[2 * (size_t)i] = kps1[i].x; xy1[2 * (size_t)i + 1] = kps1[i].y; }
     for (int i = 0; i < n2; i++) { xy2[2 * (size_t)i] = kps2[i].x; xy2[2 * (size_t)i + 1] = kps2[i].y; oct2[i] = kps2[i].octave; }
     MHIPCHK(hipSetDevice(m->device));
-    int rc = orbm_grow(m, nq, 0, 0);
-    if (rc != ORBX_OK) return rc;
-    rc = orbm_arena_begin(m);
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_grow(m, nq, 0, 0));
+    MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     InBlock in(m);
     const int pq = in.add(qs.data(), (size_t)nq * 16), pi = in.add(fv2_idx, (size_t)ni2 * 4), pd1 = in.add(desc1, (size_t)n1 * 32), pd2 = in.add(desc2, (size_t)n2 * 32);
     const int p1 = in.add(xy1.data(), (size_t)n1 * 8), p2 = in.add(xy2.data(), (size_t)n2 * 8), po = in.add(oct2.data(), (size_t)n2 * 4), pf = in.add(flags2.data(), (size_t)n2);
-    rc = in.upload(s);
-    if (rc != ORBX_OK) { in.release(); return rc; }
+    MTRY(in.upload(s));
     hipLaunchKernelGGL(k_triangulation, dim3((nq + 3) / 4), dim3(M_THREADS), 0, s, in.at<int4>(pq), nq, in.at<int32_t>(pi), in.at<uint8_t>(pd1),
                        in.at<uint8_t>(pd2), in.at<float2>(p1), in.at<float2>(p2), in.at<int32_t>(po), in.at<uint8_t>(pf), P, m->d_out);
     MHIPCHK(hipGetLastError());
     std::vector<int32_t> res((size_t)nq);
-    rc = orbm_d2h(m, res.data(), m->d_out, (size_t)nq * 4, s);
-    if (rc == ORBX_OK) rc = orbm_sync(m, s);
-    in.release();
-    if (rc != ORBX_OK) return rc;
+    MTRY(orbm_d2h(m, res.data(), m->d_out, (size_t)nq * 4, s));
+    MTRY(orbm_sync(m, s));
     // matches, rotation histogram and cull (:758-810) in visiting order
-    int32_t hist[ORBM_HISTO_LENGTH] = {0};
-    std::vector<std::pair<int, int>> rot;
-    const float factor = 1.0f / ORBM_HISTO_LENGTH;
+    RotHist rot;                                     // tag = idx1
     int nm = 0;
     for (int k = 0; k < nq; k++) {
         if (res[k] < 0) continue;
         const int idx1 = qs[k].x, idx2 = res[k];
         matches12[idx1] = idx2;
         nm++;
-        if (check_orientation) {
-            float r_ = kps1[idx1].angle - kps2[idx2].angle;
-            if (r_ < 0.0) r_ += 360.0f;
-            int bin = (int)roundf(r_ * factor);
-            if (bin == ORBM_HISTO_LENGTH) bin = 0;
-            if (bin < 0 || bin >= ORBM_HISTO_LENGTH) return mfail(ORBX_E_INVALID, "keypoint angle outside [0, 360)");     // the reference asserts
-            rot.emplace_back(bin, idx1);
-            hist[bin]++;
-        }
+        if (check_orientation) MTRY(rot.add(kps1[idx1].angle, kps2[idx2].angle, idx1));
     }
-    if (check_orientation) {
-        int32_t ind[3];
-        orbm_three_maxima(hist, ORBM_HISTO_LENGTH, ind);
-        for (const auto &e : rot)
-            if (e.first != ind[0] && e.first != ind[1] && e.first != ind[2]) { matches12[e.second] = -1; nm--; }
-    }
+    if (check_orientation) rot.cull([&](int idx1) { matches12[idx1] = -1; nm--; });
     *nmatches = nm;
     return ORBX_OK;
 }

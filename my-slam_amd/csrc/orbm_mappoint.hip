@@ -324,14 +324,14 @@ extern "C" int orbm_distinctive_descriptors(orbm_matcher *m, int n_points, const
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     DdScratch sc;
-    { int rc_ = dd_scratch(m, n_points, total_rows, s, &sc); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_arena_begin(m); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, sc.off, off, ((size_t)n_points + 1) * 4, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = orbm_h2d(m, sc.desc, desc, (size_t)total_rows * 32, s); if (rc_ != ORBX_OK) return rc_; }
-    { int rc_ = dd_launch(sc, n_points, sc.off, sc.desc, total_rows, max_run, sc.out, sc.out + n_points, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(dd_scratch(m, n_points, total_rows, s, &sc));
+    MTRY(orbm_arena_begin(m));
+    MTRY(orbm_h2d(m, sc.off, off, ((size_t)n_points + 1) * 4, s));
+    MTRY(orbm_h2d(m, sc.desc, desc, (size_t)total_rows * 32, s));
+    MTRY(dd_launch(sc, n_points, sc.off, sc.desc, total_rows, max_run, sc.out, sc.out + n_points, s));
     void *host[2] = {best, best_median};
     const size_t parts[2] = {(size_t)n_points * 4, (size_t)n_points * 4};
-    { int rc_ = orbm_d2h_split(m, host, parts, best_median ? 2 : 1, sc.out, s); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(orbm_d2h_split(m, host, parts, best_median ? 2 : 1, sc.out, s));
     return orbm_sync(m, s);
 }
 
@@ -349,6 +349,6 @@ extern "C" int orbm_distinctive_descriptors_device(orbm_matcher *m, int n_points
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;
     DdScratch sc;
-    { int rc_ = dd_scratch(m, n_points, -1, s, &sc); if (rc_ != ORBX_OK) return rc_; }
+    MTRY(dd_scratch(m, n_points, -1, s, &sc));
     return dd_launch(sc, n_points, d_off, d_desc, total_rows, max_run, d_best, d_best_median, s);
 }

@@ -81,6 +81,24 @@ def test_host_helpers_match_oracle(built):
     assert n1 == n2 and np.array_equal(m1, m2) and 0 < n1 < int((m >= 0).sum())
 
 
+@pytest.mark.parametrize("aq,at", [(float("nan"), 10.0), (10.0, float("nan")), (10.0, 400.0), (-400.0, 10.0)])
+def test_rot_filter_refuses_angles_off_the_histogram(built, aq, at):
+    """The reference asserts 0 <= bin < HISTO_LENGTH on the rotation difference (src/ORBmatcher.cc:242).  orbm_rot_filter makes the
+    same test on the same bin as every matcher entry point: a NaN angle, a train angle of 400 and a query angle of -400 (difference
+    -390 and -410 -> a negative bin) are refused with ORBX_E_INVALID instead of indexing the histogram with that bin.  Angles a little
+    outside [0, 360) whose difference still lands on the histogram stay defined, as in the reference."""
+    L = built.lib()
+    angle_q = np.array([20.0, aq, 30.0], np.float32)
+    angle_t = np.array([25.0, at], np.float32)
+    m = np.array([0, 1, -1], np.int32)
+    assert L.orbm_rot_filter(angle_q.ctypes.data, angle_t.ctypes.data, m.ctypes.data, 3) == built.ORBX_E_INVALID
+    assert built.ORBX_E_INVALID < 0
+    assert b"keypoint angle outside [0, 360)" in L.orbm_last_error()
+    ok_q = np.array([400.0, 370.0], np.float32); ok_t = np.array([10.0, -10.0], np.float32)      # differences 390 and 380: bin 13
+    m = np.array([0, 1], np.int32)
+    assert L.orbm_rot_filter(ok_q.ctypes.data, ok_t.ctypes.data, m.ctypes.data, 2) == 2 and list(m) == [0, 1]
+
+
 def test_null_and_bad_arguments_return_status(built):
     L = built.lib()
     assert L.orbx_create(None, 1000, 1.2, 8, 20, 7, 0, 640, 480, 1) == built.ORBX_E_INVALID

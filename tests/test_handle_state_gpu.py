@@ -325,6 +325,123 @@ def test_one_matcher_through_a_mixed_sequence(orbx, sc):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
+# (b') the host-input staging: a fresh handle stages the inputs of its first call in a block of the call's own, so does the first
+# call larger than any before it, and the calls after that go through the handle's pinned arena
+# ---------------------------------------------------------------------------------------------------------------------------------
+def _window_calls(m, orbx, sc, qstep, tstep):
+    """The entry points that upload window queries, on every qstep-th feature of key frame 1 (the queries) against every tstep-th
+    feature of key frame 2 (the train frame), each compared with the oracle.  Every call builds the grid it needs."""
+    sub = lambda a, st: np.ascontiguousarray(a[::st])
+    k0, d0, k1, d1 = sub(sc.k[0], qstep), sub(sc.d[0], qstep), sub(sc.k[1], tstep), sub(sc.d[1], tstep)
+    xw, nrm, mfm, mni, mxi = (sub(a[0], qstep) for a in (sc.xw, sc.normal, sc.mf_max, sc.min_inv, sc.max_inv))
+    n0, n1 = len(k0), len(k1)
+    rng = np.random.default_rng(7)
+    x = (k0["x"] - 4 + rng.uniform(-3, 3, n0)).astype(F32); y = (k0["y"] + rng.uniform(-3, 3, n0)).astype(F32)
+    r = (12.0 * sc.sf[k0["octave"]]).astype(F32)
+    mn = np.maximum(k0["octave"] - 1, -1).astype(np.int32); mx = (k0["octave"] + 1).astype(np.int32)
+    mn[::5] = -1; mx[::5] = -1
+
+    def frame_grid():
+        m.grid_build(k1, *FBOUNDS)
+        return O.FrameGrid(k1, *FBOUNDS)
+
+    def area():
+        fg = frame_grid()
+        off, idx = m.GetFeaturesInArea(x, y, r, mn, mx)
+        for i in range(0, n0, 3):
+            assert np.array_equal(idx[off[i]:off[i + 1]], fg.features_in_area(float(x[i]), float(y[i]), float(r[i]), int(mn[i]), int(mx[i]))), i
+        return int(off[-1])
+
+    def best2_area():
+        fg = frame_grid()
+        skip = (np.random.default_rng(2).random(n1) < 0.1).astype(np.uint8)
+        for sk in (None, skip):
+            got = m.search_area_best2(d0, x, y, r, mn, mx, d1, sk)
+            want = fg.search_area_best2(d0, x, y, r, mn, mx, d1, sk)
+            assert all(np.array_equal(p, q) for p, q in zip(got, want))
+        return int((got[0] >= 0).sum())
+
+    def init():
+        fg = frame_grid()
+        pa = np.ascontiguousarray(np.stack([k0["x"], k0["y"]], 1), F32); pb = pa.copy()
+        m12, nm = m.SearchForInitialization(k0, d0, k1, d1, pa, 100)
+        om12, onm = O.search_for_initialization(k0, d0, fg, d1, pb, 100, 0.9, True)
+        assert nm == onm and np.array_equal(m12, om12) and np.array_equal(pa, pb)
+        return nm
+
+    def proj_last():
+        fg = frame_grid()
+        has = (np.random.default_rng(3).random(n0) < 0.85).astype(np.uint8)
+        obs = np.random.default_rng(4).integers(0, 4, n0).astype(np.int32)
+        cur0 = np.full(n1, -1, np.int32); cur0[::11] = 1
+        ca, cb = cur0.copy(), cur0.copy()
+        args = (has, xw, d0, obs, k0, sc.T[1], sc.T[0], K, 0.54, 386.1448, FBOUNDS, sc.sf)
+        cm, nm = m.SearchByProjectionLast(*args, k1, d1, ca, 15.0, True)
+        ocm, onm = O.search_by_projection_last(*args, fg, d1, cb, 15.0, True, True)
+        assert nm == onm and np.array_equal(cm, ocm) and np.array_equal(ca, cb)
+        return nm
+
+    def proj_kf():
+        fg = frame_grid()
+        usable = (np.random.default_rng(5).random(n0) < 0.8).astype(np.uint8)
+        has0 = (np.random.default_rng(6).random(n1) < 0.15).astype(np.uint8)
+        ha, hb = has0.copy(), has0.copy()
+        u, v, iz, d3, inside = m.ProjectPoints(sc.T[1], K, FBOUNDS, xw)
+        lv = m.PredictScale(mfm, d3, sc.logsf, 8)
+        use = (usable.astype(bool) & inside.astype(bool) & ~(d3 < mni) & ~(d3 > mxi)).astype(np.uint8)
+        cm, nm = m.SearchByProjectionKF(use, u, v, lv, d0, k0["angle"], sc.sf, k1, d1, ha, 10.0, 100)
+        ocm, onm = O.search_by_projection_kf(usable, xw, mni, mxi, mfm, d0, k0["angle"], sc.T[1], K, FBOUNDS, sc.sf, sc.logsf, fg, d1, hb, 10.0,
+                                             100, True)
+        assert nm == onm and np.array_equal(cm, ocm) and np.array_equal(ha, hb)
+        return nm
+
+    def proj_map():
+        fg = frame_grid()
+        g = np.random.default_rng(8)
+        in_view = (g.random(n0) < 0.8).astype(np.uint8)
+        px = (k0["x"] - 4 + g.normal(0, 0.7, n0)).astype(F32); py = (k0["y"] + g.normal(0, 0.7, n0)).astype(F32)
+        lv = np.clip(k0["octave"] + g.integers(0, 2, n0), 0, 7).astype(np.int32)
+        vc = np.where(g.random(n0) < 0.5, 0.9985, 0.99).astype(F32)
+        obs = g.integers(1, 5, n0).astype(np.int32)
+        cur0 = np.full(n1, -1, np.int32); cur0[::9] = 2
+        ca, cb = cur0.copy(), cur0.copy()
+        cm, nm = m.SearchByProjectionMap(in_view, px, py, lv, vc, d0, obs, sc.sf, k1, d1, ca, 3.0)
+        ocm, onm = O.search_by_projection_map(in_view, px, py, lv, vc, d0, obs, sc.sf, fg, d1, cb, 3.0, 0.9)
+        assert nm == onm and np.array_equal(cm, ocm) and np.array_equal(ca, cb)
+        return nm
+
+    def proj_sim3():
+        m.grid_build_kf(k1, GRID)
+        kg = O.KeyFrameGrid(k1, GRID)
+        Scw = _sim3(1.0)
+        usable = (np.random.default_rng(44).random(n0) < 0.85).astype(np.uint8)
+        matched0 = (np.random.default_rng(45).random(n1) < 0.2).astype(np.uint8)
+        ma, mb = matched0.copy(), matched0.copy()
+        T, Ow = orbx.ORBmatcher.Sim3Decompose(Scw)
+        u, v, iz, d3, ok = orbx.ORBmatcher.ProjectPointsKF(T, K, BOUNDS, xw, nrm, Ow)
+        use = usable.astype(bool) & ok.astype(bool) & ~(d3 < mni) & ~(d3 > mxi)
+        lv = orbx.ORBmatcher.PredictScale(mfm, d3, sc.logsf, 8)
+        km, nm = m.SearchByProjectionSim3(use.astype(np.uint8), u, v, lv, d0, sc.sf, k1, d1, ma, 10)
+        okm, onm = O.search_by_projection_sim3(usable, xw, nrm, mni, mxi, mfm, d0, Scw, K, BOUNDS, sc.sf, sc.logsf, kg, d1, mb, 10)
+        assert nm == onm and np.array_equal(km, okm) and np.array_equal(ma, mb)
+        return nm
+
+    return dict(area=area, best2_area=best2_area, init=init, proj_last=proj_last, proj_kf=proj_kf, proj_map=proj_map, proj_sim3=proj_sim3)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("call", ["area", "best2_area", "init", "proj_last", "proj_kf", "proj_map", "proj_sim3"])
+def test_first_call_then_larger_calls_on_one_handle(orbx, sc, call):
+    """A thinned-out pair of frames first (a few KiB of inputs), then the whole frames twice: the full-size inputs are larger than
+    the arena the first call asked for, so the second call stages them in a block of its own again and the third is the first to
+    go through the arena.  All three against the oracle."""
+    m = orbx.ORBmatcher(0.9, True, max_queries=64, max_train=64, max_pairs=256)
+    _window_calls(m, orbx, sc, 30, 12)[call]()
+    for _ in range(2):
+        assert _window_calls(m, orbx, sc, 1, 1)[call]() > 50
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
 # (c) one extractor through shapes, options and errors
 # ---------------------------------------------------------------------------------------------------------------------------------
 _ORACLE = {}

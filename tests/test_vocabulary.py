@@ -166,9 +166,18 @@ def test_search_by_bow_equals_oracle(orbx, synth, tmp_path, nnratio, check_ori, 
     if with_valid:
         valid = (np.random.default_rng(1).random(len(d0)) < 0.7).astype(np.uint8)   # some key-frame features without a MapPoint
     m = orbx.ORBmatcher(nnratio, check_ori, max_queries=4096, max_train=4096, max_pairs=1 << 20)
-    mf, nm = m.SearchByBoW(k0, d0, fv0, k1, d1, fv1, valid)
-    omf, onm = O.search_by_bow(d0, k0["angle"], fv0, d1, k1["angle"], fv1, nnratio, check_ori, valid)
+    # the first call on the handle is a small one (its inputs are staged in a block of the call's own), the larger ones follow
+    ns = 200
+    _, fv0s = v.transform(d0[:ns], 2)
+    _, fv1s = v.transform(d1[:ns], 2)
+    vs = None if valid is None else valid[:ns]
+    mf, nm = m.SearchByBoW(k0[:ns], d0[:ns], fv0s, k1[:ns], d1[:ns], fv1s, vs)
+    omf, onm = O.search_by_bow(d0[:ns], k0["angle"][:ns], fv0s, d1[:ns], k1["angle"][:ns], fv1s, nnratio, check_ori, vs)
     assert nm == onm and np.array_equal(mf, omf)
+    for _ in range(2):
+        mf, nm = m.SearchByBoW(k0, d0, fv0, k1, d1, fv1, valid)
+        omf, onm = O.search_by_bow(d0, k0["angle"], fv0, d1, k1["angle"], fv1, nnratio, check_ori, valid)
+        assert nm == onm and np.array_equal(mf, omf)
     assert nm > 40 and nm == int((mf >= 0).sum())
     if with_valid:
         assert valid[mf[mf >= 0]].all()
