@@ -374,6 +374,81 @@ int orbm_distinctive_descriptors(orbm_matcher *m, int n_points, const int32_t *o
 int orbm_distinctive_descriptors_device(orbm_matcher *m, int n_points, const int32_t *d_off, const uint8_t *d_desc,
                                         int total_rows, int max_run, int32_t *d_best, int32_t *d_best_median, void *hip_stream);
 
+/*
+ * ---- LocalMapping::CreateNewMapPoints, the per-match loop (src/LocalMapping.cc:288-434) for all matches in one call ----
+ * For every pair of vMatchedIndices (:270) the reference checks the parallax of the two rays (:302-318), triangulates linearly
+ * (:324-339) or falls back to KeyFrame::UnprojectStereo (:342-348, src/KeyFrame.cc:615-631), and applies the gates: depth signs
+ * (:356-362), the chi-square reprojection tests in their mono and stereo forms (:365-415) and scale consistency (:418-433).  No
+ * match reads what another writes (:436-451 is the first write), so one lane takes one match.
+ *
+ * orbm_camera is what the loop reads of a key frame (:219-234, :272-284, :314-316, :365, :392, :428): Rcw = GetRotation() (row-major),
+ * tcw = GetTranslation(), Ow = GetCameraCenter(), the calibration, mb, mbf, mfScaleFactor and the per-level tables.  Key frame 1
+ * (mpCurrentKeyFrame) has one block; the second views are `ncams2` blocks, and every match names its view, so several neighbours'
+ * matches may share a call.  The reference's own caller goes one neighbour at a time (an accepted match changes the next
+ * neighbour's SearchForTriangulation): ncams2 = 1.  The per-feature arrays of the second views are concatenated, view v owning
+ * the features off2[v] .. off2[v+1]-1; off2 has ncams2 + 1 entries, off2[0] = 0.
+ *   kps_un = mvKeysUn (pt and octave are read), keys_xy = mvKeys[i].pt as 2 floats per feature (UnprojectStereo reads the raw
+ *   keys, not mvKeysUn), u_right = mvuRight, depth = mvDepth
+ *   matches[3*k .. 3*k+2] = idx1, idx2 (inside its view), view
+ *   status[k] = the line that decided match k (orbm_tri_status); x3d[3*k ..] = the new MapPoint's position for the accepted
+ *   statuses (<= ORBM_TRI_STEREO2), zeros otherwise.
+ * The reference's quirks are kept: `else if(bStereo2)` (:315: the second view's stereo angle is not looked at when the first is
+ * stereo), mpCurrentKeyFrame->mbf in the second view's stereo test (:408).  Arithmetic: the reference's float expressions
+ * operation by operation, except the 4x4 cv::SVD of :331, whose last bits depend on OpenCV's algorithm:
+ * here the right singular vector of the smallest singular value comes from a one-sided Jacobi in fp64 on the float matrix, and
+ * x3D = v[0:3] / v[3] is rounded to float once; the `== 0` test of :335 is made on v[3] rounded to float.
+ * ORBM_TRI_UNDEFINED: mvuRight >= 0 with mvDepth <= 0 reaching :344 / :348 -- UnprojectStereo returns an empty cv::Mat and :353
+ * reads it; the match is rejected.  ORBM_TRI_BAD_INDEX is only ever written by the device-pointer form (below).
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: negative counts, NULL buffers, nlevels outside
+ * [1, ORBX_MAX_LEVELS], off2 not monotone from 0, an index outside its key frame, a view outside [0, ncams2), a key point's
+ * octave outside its camera's levels); n == 0 is ORBX_OK and touches nothing, the handle included.  Every other call needs the
+ * GPU: a NULL handle fails with ORBX_E_HIP where there is no HIP device ("no CPU path") and with ORBX_E_INVALID where there is
+ * one.  The call runs on the handle's stream through its staging arena (one upload, one launch, one download) and grows the
+ * handle when n is larger than its workspace.
+ *
+ * orbm_triangulate_matches_device: the same on device pointers (the camera blocks and off2 included).  Nothing is uploaded,
+ * downloaded or synchronised; asynchronous on hip_stream (NULL = the handle's stream).
+ * The host cannot see the indices, so the kernel checks them: a match with an index, view or octave out of range gets
+ * ORBM_TRI_BAD_INDEX and reads nothing through it.
+ */
+typedef enum {
+    ORBM_TRI_SVD = 0,            /* accepted, x3D from the linear triangulation (:324-339) */
+    ORBM_TRI_STEREO1 = 1,        /* accepted, x3D = mpCurrentKeyFrame->UnprojectStereo(idx1) (:344) */
+    ORBM_TRI_STEREO2 = 2,        /* accepted, x3D = pKF2->UnprojectStereo(idx2) (:348) */
+    ORBM_TRI_LOW_PARALLAX = 3,   /* :351 */
+    ORBM_TRI_W_ZERO = 4,         /* :336 */
+    ORBM_TRI_BEHIND1 = 5,        /* :358 */
+    ORBM_TRI_BEHIND2 = 6,        /* :362 */
+    ORBM_TRI_REPROJ1 = 7,        /* :377 / :388 */
+    ORBM_TRI_REPROJ2 = 8,        /* :403 / :414 */
+    ORBM_TRI_ZERO_DIST = 9,      /* :425 */
+    ORBM_TRI_SCALE = 10,         /* :433 */
+    ORBM_TRI_UNDEFINED = 11,     /* undefined in the reference: UnprojectStereo of a feature with mvDepth <= 0 */
+    ORBM_TRI_BAD_INDEX = 12      /* device-pointer form only: index, view or octave out of range */
+} orbm_tri_status;
+typedef struct {
+    float Rcw[9];                               /* GetRotation(), row-major */
+    float tcw[3];                               /* GetTranslation() */
+    float Ow[3];                                /* GetCameraCenter() */
+    float fx, fy, cx, cy, invfx, invfy;
+    float mb, mbf;
+    float scale_factor;                         /* mfScaleFactor (:234; read of key frame 1 only) */
+    int32_t nlevels;
+    float scale_factors[ORBX_MAX_LEVELS];       /* mvScaleFactors */
+    float level_sigma2[ORBX_MAX_LEVELS];        /* mvLevelSigma2 */
+} orbm_camera;
+int orbm_triangulate_matches(orbm_matcher *m, const orbm_camera *cam1, const orbx_keypoint *kps_un1, const float *keys_xy1,
+                             const float *u_right1, const float *depth1, int n1,
+                             const orbm_camera *cams2, int ncams2, const int32_t *off2, const orbx_keypoint *kps_un2,
+                             const float *keys_xy2, const float *u_right2, const float *depth2,
+                             const int32_t *matches, int n, uint8_t *status, float *x3d);
+int orbm_triangulate_matches_device(orbm_matcher *m, const orbm_camera *d_cam1, const orbx_keypoint *d_kps_un1,
+                                    const float *d_keys_xy1, const float *d_u_right1, const float *d_depth1, int n1,
+                                    const orbm_camera *d_cams2, int ncams2, const int32_t *d_off2, const orbx_keypoint *d_kps_un2,
+                                    const float *d_keys_xy2, const float *d_u_right2, const float *d_depth2,
+                                    const int32_t *d_matches, int n, uint8_t *d_status, float *d_x3d, void *hip_stream);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

@@ -21,6 +21,12 @@ LIB_PATH = os.environ.get("ORBX_LIB") or os.path.join(PKG_DIR, "lib", "liborbx.s
 KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"),
                      ("response", "<f4"), ("octave", "<i4"), ("class_id", "<i4")])
 assert KP_DTYPE.itemsize == 28
+# orbm_camera (include/orbm.h): what CreateNewMapPoints' per-match loop reads of a key frame
+ORBX_MAX_LEVELS = 16
+CAM_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                      ("cy", "<f4"), ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("scale_factor", "<f4"),
+                      ("nlevels", "<i4"), ("scale_factors", "<f4", (ORBX_MAX_LEVELS,)), ("level_sigma2", "<f4", (ORBX_MAX_LEVELS,))])
+assert CAM_DTYPE.itemsize == 228
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
@@ -230,6 +236,9 @@ def _bind_matcher(L):
     L.orbm_distinctive_descriptors.argtypes = [vp, C.c_int, vp, vp, vp, vp]
     L.orbm_distinctive_descriptors_device.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp]
     L.orbm_distinctive_descriptors.restype = L.orbm_distinctive_descriptors_device.restype = C.c_int
+    L.orbm_triangulate_matches.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp]
+    L.orbm_triangulate_matches_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
+    L.orbm_triangulate_matches.restype = L.orbm_triangulate_matches_device.restype = C.c_int
     for name in ("orbm_reserve", "orbm_grid_build_kf", "orbm_sim3_decompose", "orbm_sim3_relative", "orbm_project_points_kf",
                  "orbm_project_points_sim3", "orbm_search_by_projection_sim3", "orbm_search_by_bow_kf", "orbm_search_for_triangulation",
                  "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_search_by_bow"):
@@ -522,6 +531,34 @@ class ORBmatcher:
     def distinctive_descriptors_device(self, n_points, d_off, d_desc, total_rows, max_run, d_best, d_best_median=None, stream=None):
         """The same on raw device pointers; nothing is synchronised.  total_rows = off[n_points], max_run >= the longest run."""
         _mchk(self.L.orbm_distinctive_descriptors_device(self.h, n_points, d_off, d_desc, total_rows, max_run, d_best, d_best_median, stream))
+
+    def triangulate_matches(self, cam1, kps_un1, keys_xy1, u_right1, depth1, cams2, off2, kps_un2, keys_xy2, u_right2, depth2, matches):
+        """The per-match loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:288-434) for all matches in one call.
+        cam1: one CAM_DTYPE record, cams2: one per second view; the second views' feature arrays are concatenated, view v owning
+        off2[v]:off2[v+1]; matches: int32 [n, 3] = idx1, idx2 inside its view, view.  Returns (status uint8 [n], x3d float32
+        [n, 3]): the orbm_tri_status of every match and the new point of the accepted ones (status <= 2)."""
+        cam1 = np.ascontiguousarray(cam1, CAM_DTYPE).reshape(1)
+        cams2 = np.ascontiguousarray(cams2, CAM_DTYPE).reshape(-1)
+        off2 = np.ascontiguousarray(off2, np.int32).reshape(-1)
+        k1, k2 = np.ascontiguousarray(kps_un1, KP_DTYPE), np.ascontiguousarray(kps_un2, KP_DTYPE)
+        x1, x2 = np.ascontiguousarray(keys_xy1, np.float32).reshape(-1, 2), np.ascontiguousarray(keys_xy2, np.float32).reshape(-1, 2)
+        u1, u2 = np.ascontiguousarray(u_right1, np.float32), np.ascontiguousarray(u_right2, np.float32)
+        d1, d2 = np.ascontiguousarray(depth1, np.float32), np.ascontiguousarray(depth2, np.float32)
+        matches = np.ascontiguousarray(matches, np.int32).reshape(-1, 3)
+        if len(off2) != len(cams2) + 1 or not (len(k1) == len(x1) == len(u1) == len(d1)) or not (len(k2) == len(x2) == len(u2) == len(d2)) \
+                or (len(off2) > 0 and int(off2[-1]) != len(k2)):
+            raise OrbxError(ORBX_E_INVALID, "array lengths disagree: %d views, off2 %s, %d / %d features" % (len(cams2), off2[-1:], len(k1), len(k2)))
+        n = len(matches)
+        status, x3d = np.full(n, 255, np.uint8), np.zeros((n, 3), np.float32)
+        _mchk(self.L.orbm_triangulate_matches(self.h, _p(cam1), _p(k1), _p(x1), _p(u1), _p(d1), len(k1), _p(cams2), len(cams2), _p(off2),
+                                              _p(k2), _p(x2), _p(u2), _p(d2), _p(matches), n, _p(status), _p(x3d)))
+        return status, x3d
+
+    def triangulate_matches_device(self, d_cam1, d_kps_un1, d_keys_xy1, d_u_right1, d_depth1, n1, d_cams2, ncams2, d_off2, d_kps_un2,
+                                   d_keys_xy2, d_u_right2, d_depth2, d_matches, n, d_status, d_x3d, stream=None):
+        """The same on raw device pointers; nothing is synchronised.  Out-of-range indices get status 12 (ORBM_TRI_BAD_INDEX)."""
+        _mchk(self.L.orbm_triangulate_matches_device(self.h, d_cam1, d_kps_un1, d_keys_xy1, d_u_right1, d_depth1, n1, d_cams2, ncams2, d_off2,
+                                                     d_kps_un2, d_keys_xy2, d_u_right2, d_depth2, d_matches, n, d_status, d_x3d, stream))
 
     def match_dense(self, q, kq, t, kt, th=None):
         """Dense SearchByBoW-style acceptance + rotation filter on host buffers (via best2)."""

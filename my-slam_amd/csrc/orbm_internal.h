@@ -1,4 +1,4 @@
-// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip and orbm_mappoint.hip
+// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip and orbm_triangulate.hip
 #pragma once
 #include <cmath>
 #include <cstdarg>
@@ -125,6 +125,8 @@ int orbm_d2h(orbm_matcher *m, void *host, const void *dev, size_t bytes, hipStre
 // one device block -> up to four host arrays, one copy (parts[i] bytes each, consecutive in the block)
 int orbm_d2h_split(orbm_matcher *m, void *const *host, const size_t *parts, int nparts, const void *dev, hipStream_t s);
 int orbm_sync(orbm_matcher *m, hipStream_t s);                                            // synchronise + deliver the D2H copies
+// orbm_mappoint.hip: the status of a NULL handle where device work is needed (ORBX_E_HIP without a device, else ORBX_E_INVALID)
+int orbm_no_handle();
 // orbm_mfma.hip: dense best / second-best partials on the matrix cores (same partial format as k_best2_dense)
 int orbm_mfma_splits(int nq_cap, int nt_cap, int nbatch);
 int orbm_launch_dense_mfma(orbm_matcher *m, const uint8_t *d_q, const int32_t *d_nq, int nq_fixed, const uint8_t *d_t, const int32_t *d_nt,

@@ -288,7 +288,7 @@ static int dd_launch(const DdScratch &sc, int n_points, const int32_t *d_off, co
 }
 
 // a NULL handle where device work is needed: without a device that is the library's "no CPU path" failure, with one a bad argument
-static int dd_no_handle()
+int orbm_no_handle()
 {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
@@ -320,7 +320,7 @@ extern "C" int orbm_distinctive_descriptors(orbm_matcher *m, int n_points, const
         }
         return ORBX_OK;
     }
-    if (!m) return dd_no_handle();
+    if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     DdScratch sc;
@@ -345,7 +345,7 @@ extern "C" int orbm_distinctive_descriptors_device(orbm_matcher *m, int n_points
     if (total_rows > (1 << 28)) return mfail(ORBX_E_CAPACITY, "request beyond 2^28 descriptors");
     if (!d_off || !d_best || (total_rows > 0 && !d_desc)) return mfail(ORBX_E_INVALID, "NULL buffer");
     if ((uintptr_t)d_desc & 15) return mfail(ORBX_E_INVALID, "d_desc must be 16-byte aligned");
-    if (!m) return dd_no_handle();
+    if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;
     DdScratch sc;

@@ -1,0 +1,344 @@
+// orbm_triangulate.hip -- the per-match loop of LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:288-434 of WChen09/My-SLAM)
+// for all matches of a call in one launch: orbm_triangulate_matches / orbm_triangulate_matches_device (include/orbm.h).
+//
+// One lane per match, wave64, one wave per workgroup (a few hundred to a few thousand matches: the waves spread over the CUs).
+// The camera blocks are read at wave-uniform addresses (scalar loads): key frame 1 has one block, and the lanes of a wave are
+// served one second view at a time (with one second view per call, the reference's own use, that is one pass).
+//
+// Arithmetic: the reference's float expressions, operation by operation, no contraction -- 3x3 * 3x1 products
+// as cv::gemm's small-matrix path (float sum left to right, then (float)(t0*alpha + c*beta) in double), Mat::dot and cv::norm
+// accumulated in double, `alpha*row - row` (:325-328) as cv::addWeighted's float kernel evaluates it in double, double constants
+// compared in double, cos / atan2 of :314 / :316 correctly rounded.  The 4x4 cv::SVD of :331 is NOT imitated: the right singular
+// vector of the smallest singular value comes from a one-sided (Hestenes) Jacobi in fp64 on the float matrix, at most
+// TRI_MAX_SWEEPS sweeps, + - * / sqrt only; x3D = v[0:3] / v[3] is rounded to float once.  tests/triangulation_oracle.py is the
+// same sequence of operations in numpy.
+//
+// The two 4x4 fp64 matrices of the Jacobi live in named registers (D4 columns, every access a compile-time member): a private
+// array indexed by a loop variable would go to scratch memory.
+#include "orbm_internal.h"
+#include "sincos_cr.h"
+
+#define TRI_THREADS 64
+#define TRI_MAX_SWEEPS 12
+// a column pair is left alone once |p.q| <= TRI_TOL |p| |q| (2^-50)
+#define TRI_TOL 8.8817841970012523e-16
+
+struct D4 { double a, b, c, d; };
+
+__device__ __forceinline__ double d4_dot(const D4 &p, const D4 &q) { return ((p.a * q.a + p.b * q.b) + p.c * q.c) + p.d * q.d; }
+
+// one Jacobi rotation of the column pair (p, q) of U, applied to V as well; false when the pair is already orthogonal
+__device__ __forceinline__ bool jacobi_pair(D4 &up, D4 &uq, D4 &vp, D4 &vq)
+{
+    const double alpha = d4_dot(up, up), beta = d4_dot(uq, uq), gamma = d4_dot(up, uq);
+    if (!(fabs(gamma) > TRI_TOL * sqrt(alpha * beta))) return false;
+    const double zeta = (beta - alpha) / (2.0 * gamma);
+    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+    D4 n;
+    n.a = c * up.a - s * uq.a; uq.a = s * up.a + c * uq.a; up.a = n.a;
+    n.b = c * up.b - s * uq.b; uq.b = s * up.b + c * uq.b; up.b = n.b;
+    n.c = c * up.c - s * uq.c; uq.c = s * up.c + c * uq.c; up.c = n.c;
+    n.d = c * up.d - s * uq.d; uq.d = s * up.d + c * uq.d; up.d = n.d;
+    n.a = c * vp.a - s * vq.a; vq.a = s * vp.a + c * vq.a; vp.a = n.a;
+    n.b = c * vp.b - s * vq.b; vq.b = s * vp.b + c * vq.b; vp.b = n.b;
+    n.c = c * vp.c - s * vq.c; vq.c = s * vp.c + c * vq.c; vp.c = n.c;
+    n.d = c * vp.d - s * vq.d; vq.d = s * vp.d + c * vq.d; vp.d = n.d;
+    return true;
+}
+
+// the right singular vector of the smallest singular value of the 4x4 matrix with columns u0..u3 (the first column of minimal
+// norm after the sweeps)
+__device__ __forceinline__ D4 smallest_right_singular_vector(D4 u0, D4 u1, D4 u2, D4 u3)
+{
+    D4 v0 = {1.0, 0.0, 0.0, 0.0}, v1 = {0.0, 1.0, 0.0, 0.0}, v2 = {0.0, 0.0, 1.0, 0.0}, v3 = {0.0, 0.0, 0.0, 1.0};
+    for (int sweep = 0; sweep < TRI_MAX_SWEEPS; sweep++) {
+        bool any = jacobi_pair(u0, u1, v0, v1);
+        any |= jacobi_pair(u0, u2, v0, v2);
+        any |= jacobi_pair(u0, u3, v0, v3);
+        any |= jacobi_pair(u1, u2, v1, v2);
+        any |= jacobi_pair(u1, u3, v1, v3);
+        any |= jacobi_pair(u2, u3, v2, v3);
+        if (!any) break;                // every further sweep would leave every pair alone as well
+    }
+    double best = d4_dot(u0, u0);
+    D4 v = v0;
+    const double s1 = d4_dot(u1, u1), s2 = d4_dot(u2, u2), s3 = d4_dot(u3, u3);
+    if (s1 < best) { best = s1; v = v1; }
+    if (s2 < best) { best = s2; v = v2; }
+    if (s3 < best) { best = s3; v = v3; }
+    return v;
+}
+
+// cv::gemm's small-matrix path, the float sum of one row (orbm_internal.h gemm3)
+__device__ __forceinline__ float tri_sum3(float a0, float a1, float a2, float b0, float b1, float b2)
+{
+    return __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
+}
+// Mat::dot / the squares of cv::norm: float products are exact in double, the sum is double
+__device__ __forceinline__ double tri_dot3(float a0, float a1, float a2, float b0, float b1, float b2)
+{
+    return ((double)a0 * (double)b0 + (double)a1 * (double)b1) + (double)a2 * (double)b2;
+}
+// one element of `alpha*rowA - rowB` (:325-328): MatOp_AddEx hands alpha != 1, beta = -1 to cv::addWeighted, whose 32f kernel works
+// in double and adds gamma = 0; alpha == 1 is cv::subtract in float
+__device__ __forceinline__ float tri_arow(float alpha, float a, float b)
+{
+    if (alpha == 1.0f) return __fsub_rn(a, b);
+    return (float)(((double)a * (double)alpha + (double)b * -1.0) + 0.0);
+}
+// cos(2*atan2(mb/2, depth)) of :314 / :316 with the float overloads, each function correctly rounded
+__device__ __forceinline__ float tri_cos_stereo(float mb, float depth)
+{
+    const float half = __fdiv_rn(mb, 2.0f);
+    const float at = (float)atan2((double)half, (double)depth);
+    const float ang = __fmul_rn(2.0f, at);
+    float cs, sn;
+    sincos_cr(fabsf(ang), &cs, &sn);    // |ang| <= 2 pi, cos is even
+    return cs;
+}
+
+struct TriView {                        // what :293-298 and UnprojectStereo read of one feature
+    float x, y, raw_x, raw_y, ur, depth;
+    int oct;
+};
+
+// KeyFrame::UnprojectStereo (src/KeyFrame.cc:615-631): false where the reference returns an empty matrix
+__device__ __forceinline__ bool tri_unproject(const orbm_camera *__restrict__ C, const TriView &f, float X[3])
+{
+    const float z = f.depth;
+    if (!(z > 0)) return false;
+    const float x = __fmul_rn(__fmul_rn(__fsub_rn(f.raw_x, C->cx), z), C->invfx);
+    const float y = __fmul_rn(__fmul_rn(__fsub_rn(f.raw_y, C->cy), z), C->invfy);
+    // Twc.rowRange(0,3).colRange(0,3) = Rcw^T, Twc.rowRange(0,3).col(3) = Ow (src/KeyFrame.cc:66-70)
+    X[0] = (float)((double)tri_sum3(C->Rcw[0], C->Rcw[3], C->Rcw[6], x, y, z) + (double)C->Ow[0]);
+    X[1] = (float)((double)tri_sum3(C->Rcw[1], C->Rcw[4], C->Rcw[7], x, y, z) + (double)C->Ow[1]);
+    X[2] = (float)((double)tri_sum3(C->Rcw[2], C->Rcw[5], C->Rcw[8], x, y, z) + (double)C->Ow[2]);
+    return true;
+}
+
+// the reprojection test of one view (:365-389 / :392-415); mbf is mpCurrentKeyFrame's in both (:382, :408)
+__device__ __forceinline__ bool tri_reprojection_fails(const orbm_camera *__restrict__ C, const TriView &f, bool stereo, float mbf,
+                                                       const float X[3], float z)
+{
+    const float sigma2 = C->level_sigma2[f.oct];
+    const float xc = (float)(tri_dot3(C->Rcw[0], C->Rcw[1], C->Rcw[2], X[0], X[1], X[2]) + (double)C->tcw[0]);
+    const float yc = (float)(tri_dot3(C->Rcw[3], C->Rcw[4], C->Rcw[5], X[0], X[1], X[2]) + (double)C->tcw[1]);
+    const float invz = (float)(1.0 / (double)z);
+    const float u = __fadd_rn(__fmul_rn(__fmul_rn(C->fx, xc), invz), C->cx);
+    const float v = __fadd_rn(__fmul_rn(__fmul_rn(C->fy, yc), invz), C->cy);
+    const float ex = __fsub_rn(u, f.x), ey = __fsub_rn(v, f.y);
+    const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+    if (!stereo) return (double)e2 > 5.991 * (double)sigma2;
+    const float u_r = __fsub_rn(u, __fmul_rn(mbf, invz));
+    const float er = __fsub_rn(u_r, f.ur);
+    return (double)__fadd_rn(e2, __fmul_rn(er, er)) > 7.8 * (double)sigma2;
+}
+
+__device__ __forceinline__ int tri_one(const orbm_camera *__restrict__ C1, const orbm_camera *__restrict__ C2, const TriView &f1,
+                                       const TriView &f2, float X[3])
+{
+    const bool st1 = f1.ur >= 0, st2 = f2.ur >= 0;                                              // :295, :299
+    // Check parallax between rays :302-307
+    const float xn1x = __fmul_rn(__fsub_rn(f1.x, C1->cx), C1->invfx), xn1y = __fmul_rn(__fsub_rn(f1.y, C1->cy), C1->invfy);
+    const float xn2x = __fmul_rn(__fsub_rn(f2.x, C2->cx), C2->invfx), xn2y = __fmul_rn(__fsub_rn(f2.y, C2->cy), C2->invfy);
+    const float r1x = tri_sum3(C1->Rcw[0], C1->Rcw[3], C1->Rcw[6], xn1x, xn1y, 1.0f);
+    const float r1y = tri_sum3(C1->Rcw[1], C1->Rcw[4], C1->Rcw[7], xn1x, xn1y, 1.0f);
+    const float r1z = tri_sum3(C1->Rcw[2], C1->Rcw[5], C1->Rcw[8], xn1x, xn1y, 1.0f);
+    const float r2x = tri_sum3(C2->Rcw[0], C2->Rcw[3], C2->Rcw[6], xn2x, xn2y, 1.0f);
+    const float r2y = tri_sum3(C2->Rcw[1], C2->Rcw[4], C2->Rcw[7], xn2x, xn2y, 1.0f);
+    const float r2z = tri_sum3(C2->Rcw[2], C2->Rcw[5], C2->Rcw[8], xn2x, xn2y, 1.0f);
+    const double n1 = sqrt(tri_dot3(r1x, r1y, r1z, r1x, r1y, r1z)), n2 = sqrt(tri_dot3(r2x, r2y, r2z, r2x, r2y, r2z));
+    const float cos_rays = (float)(tri_dot3(r1x, r1y, r1z, r2x, r2y, r2z) / (n1 * n2));
+    float cos_st1 = __fadd_rn(cos_rays, 1.0f), cos_st2 = cos_st1;                               // :309-311
+    if (st1) cos_st1 = tri_cos_stereo(C1->mb, f1.depth);                                        // :313-316
+    else if (st2) cos_st2 = tri_cos_stereo(C2->mb, f2.depth);
+    const float cos_st = cos_st2 < cos_st1 ? cos_st2 : cos_st1;                                 // std::min :318
+    int accepted;
+    if (cos_rays < cos_st && cos_rays > 0 && (st1 || st2 || (double)cos_rays < 0.9998)) {       // :321
+        // Linear Triangulation Method :324-328; column j of A = element j of the four rows
+        const D4 u0 = {(double)tri_arow(xn1x, C1->Rcw[6], C1->Rcw[0]), (double)tri_arow(xn1y, C1->Rcw[6], C1->Rcw[3]),
+                       (double)tri_arow(xn2x, C2->Rcw[6], C2->Rcw[0]), (double)tri_arow(xn2y, C2->Rcw[6], C2->Rcw[3])};
+        const D4 u1 = {(double)tri_arow(xn1x, C1->Rcw[7], C1->Rcw[1]), (double)tri_arow(xn1y, C1->Rcw[7], C1->Rcw[4]),
+                       (double)tri_arow(xn2x, C2->Rcw[7], C2->Rcw[1]), (double)tri_arow(xn2y, C2->Rcw[7], C2->Rcw[4])};
+        const D4 u2 = {(double)tri_arow(xn1x, C1->Rcw[8], C1->Rcw[2]), (double)tri_arow(xn1y, C1->Rcw[8], C1->Rcw[5]),
+                       (double)tri_arow(xn2x, C2->Rcw[8], C2->Rcw[2]), (double)tri_arow(xn2y, C2->Rcw[8], C2->Rcw[5])};
+        const D4 u3 = {(double)tri_arow(xn1x, C1->tcw[2], C1->tcw[0]), (double)tri_arow(xn1y, C1->tcw[2], C1->tcw[1]),
+                       (double)tri_arow(xn2x, C2->tcw[2], C2->tcw[0]), (double)tri_arow(xn2y, C2->tcw[2], C2->tcw[1])};
+        const D4 v = smallest_right_singular_vector(u0, u1, u2, u3);                            // in place of :331-333
+        if ((float)v.d == 0) return ORBM_TRI_W_ZERO;                                            // :335
+        X[0] = (float)(v.a / v.d); X[1] = (float)(v.b / v.d); X[2] = (float)(v.c / v.d);        // :339
+        accepted = ORBM_TRI_SVD;
+    } else if (st1 && cos_st1 < cos_st2) {                                                      // :342
+        if (!tri_unproject(C1, f1, X)) return ORBM_TRI_UNDEFINED;
+        accepted = ORBM_TRI_STEREO1;
+    } else if (st2 && cos_st2 < cos_st1) {                                                      // :346
+        if (!tri_unproject(C2, f2, X)) return ORBM_TRI_UNDEFINED;
+        accepted = ORBM_TRI_STEREO2;
+    } else
+        return ORBM_TRI_LOW_PARALLAX;                                                           // :351
+    // Check triangulation in front of cameras :356-362
+    const float z1 = (float)(tri_dot3(C1->Rcw[6], C1->Rcw[7], C1->Rcw[8], X[0], X[1], X[2]) + (double)C1->tcw[2]);
+    if (z1 <= 0) return ORBM_TRI_BEHIND1;
+    const float z2 = (float)(tri_dot3(C2->Rcw[6], C2->Rcw[7], C2->Rcw[8], X[0], X[1], X[2]) + (double)C2->tcw[2]);
+    if (z2 <= 0) return ORBM_TRI_BEHIND2;
+    if (tri_reprojection_fails(C1, f1, st1, C1->mbf, X, z1)) return ORBM_TRI_REPROJ1;           // :365-389
+    if (tri_reprojection_fails(C2, f2, st2, C1->mbf, X, z2)) return ORBM_TRI_REPROJ2;           // :392-415
+    // Check scale consistency :418-433
+    const float a0 = __fsub_rn(X[0], C1->Ow[0]), a1 = __fsub_rn(X[1], C1->Ow[1]), a2 = __fsub_rn(X[2], C1->Ow[2]);
+    const float b0 = __fsub_rn(X[0], C2->Ow[0]), b1 = __fsub_rn(X[1], C2->Ow[1]), b2 = __fsub_rn(X[2], C2->Ow[2]);
+    const float dist1 = (float)sqrt(tri_dot3(a0, a1, a2, a0, a1, a2)), dist2 = (float)sqrt(tri_dot3(b0, b1, b2, b0, b1, b2));
+    if (dist1 == 0 || dist2 == 0) return ORBM_TRI_ZERO_DIST;
+    const float ratio_dist = __fdiv_rn(dist2, dist1);
+    const float ratio_octave = __fdiv_rn(C1->scale_factors[f1.oct], C2->scale_factors[f2.oct]);
+    const float ratio_factor = __fmul_rn(1.5f, C1->scale_factor);                               // :234
+    if (__fmul_rn(ratio_dist, ratio_factor) < ratio_octave || ratio_dist > __fmul_rn(ratio_octave, ratio_factor)) return ORBM_TRI_SCALE;
+    return accepted;
+}
+
+__device__ __forceinline__ TriView tri_load(const orbx_keypoint *__restrict__ kps, const float2 *__restrict__ keys,
+                                            const float *__restrict__ ur, const float *__restrict__ depth, long long i)
+{
+    TriView f;
+    f.x = kps[i].x; f.y = kps[i].y; f.oct = kps[i].octave;
+    const float2 raw = keys[i];
+    f.raw_x = raw.x; f.raw_y = raw.y; f.ur = ur[i]; f.depth = depth[i];
+    return f;
+}
+
+__global__ __launch_bounds__(TRI_THREADS) void k_triangulate(
+    const orbm_camera *__restrict__ cam1, const orbx_keypoint *__restrict__ kps1, const float2 *__restrict__ keys1,
+    const float *__restrict__ ur1, const float *__restrict__ depth1, int n1,
+    const orbm_camera *__restrict__ cams2, int ncams2, const int32_t *__restrict__ off2, const orbx_keypoint *__restrict__ kps2,
+    const float2 *__restrict__ keys2, const float *__restrict__ ur2, const float *__restrict__ depth2,
+    const int32_t *__restrict__ matches, int n, uint8_t *__restrict__ status, float *__restrict__ x3d)
+{
+    const int k = blockIdx.x * TRI_THREADS + threadIdx.x;
+    int idx1 = 0, idx2 = 0;
+    uint32_t view = 0xFFFFFFFFu;                    // 0xFFFFFFFF: nothing (left) to do in this lane
+    int st = ORBM_TRI_BAD_INDEX;
+    float X[3] = {0.f, 0.f, 0.f};
+    TriView f1 = {};
+    if (k < n) {
+        idx1 = matches[3 * (long long)k]; idx2 = matches[3 * (long long)k + 1];
+        const int v = matches[3 * (long long)k + 2];
+        if (v >= 0 && v < ncams2 && idx1 >= 0 && idx1 < n1 && idx2 >= 0) {
+            f1 = tri_load(kps1, keys1, ur1, depth1, idx1);
+            if (f1.oct >= 0 && f1.oct < min(cam1->nlevels, ORBX_MAX_LEVELS)) view = (uint32_t)v;
+        }
+    }
+    // the second views of this wave, one at a time, so that the camera block's address is wave-uniform; a pass retires every lane
+    // of its view, so there are at most 64
+    for (int pass = 0; pass < 64; pass++) {
+        const uint32_t vmin = wave_min_u32(view);
+        if (vmin == 0xFFFFFFFFu) break;
+        if (view == vmin) {
+            // every active lane holds vmin here; taken through readfirstlane the index is a scalar for the compiler as well (inside
+            // this branch it puts the lane's own `view` in vmin's place, and the camera block's address would become a vector)
+            const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
+            view = 0xFFFFFFFFu;
+            const orbm_camera *__restrict__ cam2 = cams2 + v;
+            const int base = off2[v], count = off2[v + 1] - base;
+            if (idx2 < count) {
+                const TriView f2 = tri_load(kps2, keys2, ur2, depth2, (long long)base + idx2);
+                if (f2.oct >= 0 && f2.oct < min(cam2->nlevels, ORBX_MAX_LEVELS)) st = tri_one(cam1, cam2, f1, f2, X);
+            }
+        }
+    }
+    if (k < n) {
+        const bool ok = st <= ORBM_TRI_STEREO2;
+        status[k] = (uint8_t)st;
+        x3d[3 * (long long)k] = ok ? X[0] : 0.f; x3d[3 * (long long)k + 1] = ok ? X[1] : 0.f; x3d[3 * (long long)k + 2] = ok ? X[2] : 0.f;
+    }
+}
+
+static void tri_launch(const orbm_camera *cam1, const orbx_keypoint *kps1, const float *keys1, const float *ur1, const float *depth1, int n1,
+                       const orbm_camera *cams2, int ncams2, const int32_t *off2, const orbx_keypoint *kps2, const float *keys2,
+                       const float *ur2, const float *depth2, const int32_t *matches, int n, uint8_t *status, float *x3d, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_triangulate, dim3((n + TRI_THREADS - 1) / TRI_THREADS), dim3(TRI_THREADS), 0, s, cam1, kps1,
+                       reinterpret_cast<const float2 *>(keys1), ur1, depth1, n1, cams2, ncams2, off2, kps2,
+                       reinterpret_cast<const float2 *>(keys2), ur2, depth2, matches, n, status, x3d);
+}
+
+static int tri_check_counts(int n1, int ncams2, int n)
+{
+    if (n < 0 || n1 < 0 || ncams2 < 0) return mfail(ORBX_E_INVALID, "n=%d n1=%d ncams2=%d", n, n1, ncams2);
+    if (n > (1 << 28)) return mfail(ORBX_E_CAPACITY, "request beyond 2^28 matches");
+    return ORBX_OK;
+}
+
+extern "C" int orbm_triangulate_matches(orbm_matcher *m, const orbm_camera *cam1, const orbx_keypoint *kps_un1, const float *keys_xy1,
+                                        const float *u_right1, const float *depth1, int n1,
+                                        const orbm_camera *cams2, int ncams2, const int32_t *off2, const orbx_keypoint *kps_un2,
+                                        const float *keys_xy2, const float *u_right2, const float *depth2,
+                                        const int32_t *matches, int n, uint8_t *status, float *x3d)
+{
+    MTRY(tri_check_counts(n1, ncams2, n));
+    if (n == 0) return ORBX_OK;
+    if (!cam1 || !cams2 || !off2 || !kps_un1 || !keys_xy1 || !u_right1 || !depth1 || !kps_un2 || !keys_xy2 || !u_right2 || !depth2 ||
+        !matches || !status || !x3d)
+        return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (ncams2 < 1) return mfail(ORBX_E_INVALID, "ncams2=%d with n=%d matches", ncams2, n);
+    if (cam1->nlevels < 1 || cam1->nlevels > ORBX_MAX_LEVELS) return mfail(ORBX_E_INVALID, "key frame 1 has nlevels=%d", cam1->nlevels);
+    if (off2[0] != 0) return mfail(ORBX_E_INVALID, "off2[0] must be 0");
+    for (int v = 0; v < ncams2; v++) {
+        if (off2[v + 1] < off2[v]) return mfail(ORBX_E_INVALID, "off2 not monotone at %d", v);
+        if (cams2[v].nlevels < 1 || cams2[v].nlevels > ORBX_MAX_LEVELS) return mfail(ORBX_E_INVALID, "second view %d has nlevels=%d", v, cams2[v].nlevels);
+    }
+    const int n2 = off2[ncams2];
+    for (int k = 0; k < n; k++) {
+        const int idx1 = matches[3 * (size_t)k], idx2 = matches[3 * (size_t)k + 1], v = matches[3 * (size_t)k + 2];
+        if (v < 0 || v >= ncams2) return mfail(ORBX_E_INVALID, "match %d: view %d outside [0,%d)", k, v, ncams2);
+        if (idx1 < 0 || idx1 >= n1) return mfail(ORBX_E_INVALID, "match %d: feature index %d outside [0,%d)", k, idx1, n1);
+        if (idx2 < 0 || idx2 >= off2[v + 1] - off2[v]) return mfail(ORBX_E_INVALID, "match %d: feature index %d outside [0,%d)", k, idx2, off2[v + 1] - off2[v]);
+        const int o1 = kps_un1[idx1].octave, o2 = kps_un2[(size_t)off2[v] + idx2].octave;
+        if (o1 < 0 || o1 >= cam1->nlevels) return mfail(ORBX_E_INVALID, "match %d: octave %d of %d levels", k, o1, cam1->nlevels);
+        if (o2 < 0 || o2 >= cams2[v].nlevels) return mfail(ORBX_E_INVALID, "match %d: octave %d of %d levels", k, o2, cams2[v].nlevels);
+    }
+    if (!m) return orbm_no_handle();
+    MHIPCHK(hipSetDevice(m->device));
+    MTRY(orbm_grow(m, ((long long)4 * n + 2) / 3, 0, 0));          // d_out holds 3 * max_q ints: x3d (3 n floats), then status (n bytes)
+    MTRY(orbm_arena_begin(m));
+    hipStream_t s = m->stream;
+    InBlock in(m);
+    const int pc1 = in.add(cam1, sizeof(orbm_camera)), pc2 = in.add(cams2, (size_t)ncams2 * sizeof(orbm_camera)), po = in.add(off2, ((size_t)ncams2 + 1) * 4);
+    const int pk1 = in.add(kps_un1, (size_t)n1 * sizeof(orbx_keypoint)), px1 = in.add(keys_xy1, (size_t)n1 * 8), pu1 = in.add(u_right1, (size_t)n1 * 4), pd1 = in.add(depth1, (size_t)n1 * 4);
+    const int pk2 = in.add(kps_un2, (size_t)n2 * sizeof(orbx_keypoint)), px2 = in.add(keys_xy2, (size_t)n2 * 8), pu2 = in.add(u_right2, (size_t)n2 * 4), pd2 = in.add(depth2, (size_t)n2 * 4);
+    const int pm = in.add(matches, (size_t)n * 12);
+    MTRY(in.upload(s));
+    float *d_x3d = reinterpret_cast<float *>(m->d_out);
+    uint8_t *d_status = reinterpret_cast<uint8_t *>(m->d_out + 3 * (size_t)n);
+    tri_launch(in.at<orbm_camera>(pc1), in.at<orbx_keypoint>(pk1), in.at<float>(px1), in.at<float>(pu1), in.at<float>(pd1), n1,
+               in.at<orbm_camera>(pc2), ncams2, in.at<int32_t>(po), in.at<orbx_keypoint>(pk2), in.at<float>(px2), in.at<float>(pu2), in.at<float>(pd2),
+               in.at<int32_t>(pm), n, d_status, d_x3d, s);
+    MHIPCHK(hipGetLastError());
+    void *host[2] = {x3d, status};
+    const size_t parts[2] = {(size_t)n * 12, (size_t)n};
+    MTRY(orbm_d2h_split(m, host, parts, 2, m->d_out, s));
+    return orbm_sync(m, s);
+}
+
+extern "C" int orbm_triangulate_matches_device(orbm_matcher *m, const orbm_camera *d_cam1, const orbx_keypoint *d_kps_un1,
+                                               const float *d_keys_xy1, const float *d_u_right1, const float *d_depth1, int n1,
+                                               const orbm_camera *d_cams2, int ncams2, const int32_t *d_off2, const orbx_keypoint *d_kps_un2,
+                                               const float *d_keys_xy2, const float *d_u_right2, const float *d_depth2,
+                                               const int32_t *d_matches, int n, uint8_t *d_status, float *d_x3d, void *hip_stream)
+{
+    MTRY(tri_check_counts(n1, ncams2, n));
+    if (n == 0) return ORBX_OK;
+    if (!d_cam1 || !d_cams2 || !d_off2 || !d_kps_un1 || !d_keys_xy1 || !d_u_right1 || !d_depth1 || !d_kps_un2 || !d_keys_xy2 || !d_u_right2 ||
+        !d_depth2 || !d_matches || !d_status || !d_x3d)
+        return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (ncams2 < 1) return mfail(ORBX_E_INVALID, "ncams2=%d with n=%d matches", ncams2, n);
+    if (((uintptr_t)d_keys_xy1 | (uintptr_t)d_keys_xy2) & 7) return mfail(ORBX_E_INVALID, "d_keys_xy must be 8-byte aligned");
+    if (((uintptr_t)d_cam1 | (uintptr_t)d_cams2 | (uintptr_t)d_kps_un1 | (uintptr_t)d_kps_un2 | (uintptr_t)d_matches | (uintptr_t)d_off2) & 3)
+        return mfail(ORBX_E_INVALID, "device arrays must be 4-byte aligned");
+    if (!m) return orbm_no_handle();
+    MHIPCHK(hipSetDevice(m->device));
+    hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;
+    tri_launch(d_cam1, d_kps_un1, d_keys_xy1, d_u_right1, d_depth1, n1, d_cams2, ncams2, d_off2, d_kps_un2, d_keys_xy2, d_u_right2, d_depth2,
+               d_matches, n, d_status, d_x3d, s);
+    MHIPCHK(hipGetLastError());
+    return ORBX_OK;
+}

@@ -1,4 +1,4 @@
-// orbm_pool.h -- the thread-local pool of GPU matcher handles behind the adapters (ORBmatcher.h, MapPointDescriptors.h).
+// orbm_pool.h -- the thread-local pool of GPU matcher handles behind the adapters (ORBmatcher.h, MapPointDescriptors.h, NewMapPoints.h).
 // The reference builds a matcher on the stack at every call site, so a handle (device buffers + a stream) and its marshalling
 // buffers are taken from the pool and go back to it; handles are not re-entrant, threads never share one.
 #pragma once
@@ -15,7 +15,7 @@ struct Scratch {                                 // marshalling buffers: they st
     std::vector<float> f0_, f1_, f2_, f3_, f4_, f5_, f6_, g0_, g1_, g2_, g3_;
     std::vector<uint8_t> v8_, w8_, desc2_;
     std::vector<int32_t> i0_, i1_, i2_, j0_, j1_, j2_, obs_, match_;
-    std::vector<orbx_keypoint> kp_;
+    std::vector<orbx_keypoint> kp_, kp2_;
 };
 struct PooledHandle {
     orbm_matcher *m = nullptr; Scratch *s = nullptr;
