@@ -449,6 +449,88 @@ int orbm_triangulate_matches_device(orbm_matcher *m, const orbm_camera *d_cam1, 
                                     const float *d_keys_xy2, const float *d_u_right2, const float *d_depth2,
                                     const int32_t *d_matches, int n, uint8_t *d_status, float *d_x3d, void *hip_stream);
 
+/*
+ * ---- Frame::isInFrustum for all local MapPoints of a frame, and Tracking::SearchLocalPoints in one call ----
+ * Tracking::SearchLocalPoints (src/Tracking.cc:1174-1187) calls Frame::isInFrustum (src/Frame.cc:269-325) once per local
+ * MapPoint: camera coordinates (:277), the depth sign (:283), the projection against the image bounds (:287-294), the distance
+ * against the scale-invariance region (:297-303, MapPoint::GetMin / MaxDistanceInvariance src/MapPoint.cc:373-383), the viewing
+ * angle (:306-311) and MapPoint::PredictScale (:314, src/MapPoint.cc:402-417).  No MapPoint reads what another writes, so one lane
+ * takes one MapPoint.
+ *
+ * orbm_frame_view is what the loop reads of the frame: Rcw = mRcw (row-major), tcw = mtcw, Ow = mOw (src/Frame.cc:261-266), the
+ * calibration, mbf, bounds = mnMinX, mnMaxX, mnMinY, mnMaxY, log_scale_factor = mfLogScaleFactor, nlevels = mnScaleLevels and
+ * scale_factors = mvScaleFactors (read by orbm_search_local_points only).
+ *   per MapPoint i:  skip[i] = (pMP->mnLastFrameSeen == mCurrentFrame.mnId || pMP->isBad()) (src/Tracking.cc:1177-1180);
+ *                    xw = GetWorldPos(), normal = GetNormal() (3 floats each); mf_max / mf_min = the raw members mfMaxDistance /
+ *                    mfMinDistance -- the 1.2f and 0.8f of the two getters are applied here, and PredictScale divides the raw
+ *                    mfMaxDistance;  viewing_cos_limit = the second argument of isInFrustum as a float (0.5 at :1182)
+ *   status[i]   = the line that decided the point (orbm_frustum_status); mbTrackInView = (status[i] == ORBM_FRUSTUM_IN_VIEW)
+ *   proj_x, proj_y, proj_xr, pred_level, view_cos = mTrackProjX, mTrackProjY, mTrackProjXR, mnTrackScaleLevel, mTrackViewCos
+ *                 (:318-322) of the points in view, zeros for every other point
+ *   *n_to_match = the points in view (nToMatch, :1185); the caller calls IncreaseVisible() on them (:1184)
+ * Arithmetic: the reference's float expressions operation by operation: Pc through cv::gemm's small-matrix
+ * path, invz = 1.0f/PcZ in float, cv::norm and Mat::dot accumulated in double, viewCos = the double dot product divided by
+ * (double)dist and rounded to float once, PredictScale as float division, logf, float division, ceil.  logf is the correctly
+ * rounded fp32 logarithm (orbm_predict_scale keeps the host's logf; the two differ only where the quotient is within rounding
+ * of an integer).  The reference's quirks are kept: PcZ == +-0 passes :283 (invz is then infinite), a NaN u or v passes both
+ * bounds tests, a NaN viewCos passes :310.  ORBM_FRUSTUM_UNDEFINED: the `int nScale = ceil(...)` of src/MapPoint.cc:410 converts
+ * a value that is not finite or lies outside int (mfMaxDistance <= 0, a zero or NaN distance, log_scale_factor == 0), which is
+ * undefined in C++; the point is rejected.
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: a negative count, NULL buffers, nlevels outside
+ * [1, ORBX_MAX_LEVELS], u_right without mbf in orbm_search_local_points); n == 0 is ORBX_OK and touches nothing, the handle
+ * included.  Every other call needs the GPU: a NULL handle fails with ORBX_E_HIP where there is no HIP device ("no CPU path") and
+ * with ORBX_E_INVALID where there is one.  orbm_frustum runs on the handle's stream through its staging arena (one upload, one
+ * launch, one download) and grows the handle when n is larger than its workspace; the grid in the handle is not touched.
+ *
+ * orbm_frustum_device: the same on device pointers, the view block included (4-byte aligned).  Nothing is uploaded, downloaded
+ * or synchronised, hence no count either; asynchronous on hip_stream (NULL = the handle's stream).
+ *
+ * orbm_search_local_points is src/Tracking.cc:1174-1199 in one call: the frustum test of every local MapPoint followed by
+ * ORBmatcher::SearchByProjection(F, vpMapPoints, th) (src/ORBmatcher.cc:45-125) on the points in view, when there is one (:1189).
+ * The frustum arguments and outputs are orbm_frustum's; mp_desc, mp_obs, the frame side, th, nnratio, cur_obs, cur_match and
+ * nmatches are orbm_search_by_projection_map's (scale_factors and nlevels come from the view; the current frame's grid must be
+ * in the handle when n_cur > 0).  The projection does not return to the host between the two halves: the frustum kernel also
+ * writes each point's window (RadiusByViewingCos :127-133 compared in double, times th when th != 1, times
+ * mvScaleFactors[level]; levels [level-1, level]; an empty window for a point not in view) where the window pass reads it.  The
+ * frustum outputs come back with the window counts and the candidates with their distances in a second round trip, so the call
+ * synchronises twice, as orbm_search_by_projection_map does; the scan runs on the host in MapPoint order.
+ */
+typedef enum {
+    ORBM_FRUSTUM_IN_VIEW = 0,    /* isInFrustum returned true (:324) */
+    ORBM_FRUSTUM_SKIPPED = 1,    /* the caller's skip[i]: isInFrustum was not called (src/Tracking.cc:1177-1180) */
+    ORBM_FRUSTUM_BEHIND = 2,     /* :283 */
+    ORBM_FRUSTUM_OUT_X = 3,      /* :291 */
+    ORBM_FRUSTUM_OUT_Y = 4,      /* :293 */
+    ORBM_FRUSTUM_DISTANCE = 5,   /* :302 */
+    ORBM_FRUSTUM_VIEW_COS = 6,   /* :310 */
+    ORBM_FRUSTUM_UNDEFINED = 7   /* undefined in the reference: the int conversion of src/MapPoint.cc:410 */
+} orbm_frustum_status;
+typedef struct {
+    float Rcw[9];                               /* mRcw, row-major */
+    float tcw[3];                               /* mtcw */
+    float Ow[3];                                /* mOw */
+    float fx, fy, cx, cy;
+    float mbf;
+    float bounds[4];                            /* mnMinX, mnMaxX, mnMinY, mnMaxY */
+    float log_scale_factor;                     /* mfLogScaleFactor */
+    int32_t nlevels;                            /* mnScaleLevels */
+    float scale_factors[ORBX_MAX_LEVELS];       /* mvScaleFactors */
+} orbm_frame_view;
+int orbm_frustum(orbm_matcher *m, const orbm_frame_view *view, int n, const uint8_t *skip, const float *xw, const float *normal,
+                 const float *mf_max, const float *mf_min, float viewing_cos_limit, uint8_t *status, float *proj_x, float *proj_y,
+                 float *proj_xr, int32_t *pred_level, float *view_cos, int *n_to_match);
+int orbm_frustum_device(orbm_matcher *m, const orbm_frame_view *d_view, int n, const uint8_t *d_skip, const float *d_xw,
+                        const float *d_normal, const float *d_mf_max, const float *d_mf_min, float viewing_cos_limit,
+                        uint8_t *d_status, float *d_proj_x, float *d_proj_y, float *d_proj_xr, int32_t *d_pred_level,
+                        float *d_view_cos, void *hip_stream);
+int orbm_search_local_points(orbm_matcher *m, const orbm_frame_view *view, int n, const uint8_t *skip, const float *xw,
+                             const float *normal, const float *mf_max, const float *mf_min, float viewing_cos_limit,
+                             const uint8_t *mp_desc, const int32_t *mp_obs, const orbx_keypoint *kps_cur, const uint8_t *desc_cur,
+                             const float *u_right, int n_cur, float th, float nnratio,
+                             uint8_t *status, float *proj_x, float *proj_y, float *proj_xr, int32_t *pred_level, float *view_cos,
+                             int *n_to_match, int32_t *cur_obs, int32_t *cur_match, int *nmatches);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

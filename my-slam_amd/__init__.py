@@ -27,6 +27,11 @@ CAM_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", 
                       ("cy", "<f4"), ("invfx", "<f4"), ("invfy", "<f4"), ("mb", "<f4"), ("mbf", "<f4"), ("scale_factor", "<f4"),
                       ("nlevels", "<i4"), ("scale_factors", "<f4", (ORBX_MAX_LEVELS,)), ("level_sigma2", "<f4", (ORBX_MAX_LEVELS,))])
 assert CAM_DTYPE.itemsize == 228
+# orbm_frame_view (include/orbm.h): what Frame::isInFrustum reads of the frame
+VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                       ("cy", "<f4"), ("mbf", "<f4"), ("bounds", "<f4", (4,)), ("log_scale_factor", "<f4"), ("nlevels", "<i4"),
+                       ("scale_factors", "<f4", (ORBX_MAX_LEVELS,))])
+assert VIEW_DTYPE.itemsize == 168
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
@@ -239,6 +244,11 @@ def _bind_matcher(L):
     L.orbm_triangulate_matches.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp]
     L.orbm_triangulate_matches_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbm_triangulate_matches.restype = L.orbm_triangulate_matches_device.restype = C.c_int
+    L.orbm_frustum.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_frustum_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_search_local_points.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_float,
+                                           vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_frustum.restype = L.orbm_frustum_device.restype = L.orbm_search_local_points.restype = C.c_int
     for name in ("orbm_reserve", "orbm_grid_build_kf", "orbm_sim3_decompose", "orbm_sim3_relative", "orbm_project_points_kf",
                  "orbm_project_points_sim3", "orbm_search_by_projection_sim3", "orbm_search_by_bow_kf", "orbm_search_for_triangulation",
                  "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_search_by_bow"):
@@ -559,6 +569,55 @@ class ORBmatcher:
         """The same on raw device pointers; nothing is synchronised.  Out-of-range indices get status 12 (ORBM_TRI_BAD_INDEX)."""
         _mchk(self.L.orbm_triangulate_matches_device(self.h, d_cam1, d_kps_un1, d_keys_xy1, d_u_right1, d_depth1, n1, d_cams2, ncams2, d_off2,
                                                      d_kps_un2, d_keys_xy2, d_u_right2, d_depth2, d_matches, n, d_status, d_x3d, stream))
+
+    @staticmethod
+    def _frustum_inputs(view, skip, xw, normal, mf_max, mf_min):
+        view = np.ascontiguousarray(view, VIEW_DTYPE).reshape(1)
+        skip = np.ascontiguousarray(skip, np.uint8).reshape(-1)
+        xw, normal = np.ascontiguousarray(xw, np.float32).reshape(-1, 3), np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        mf_max, mf_min = np.ascontiguousarray(mf_max, np.float32).reshape(-1), np.ascontiguousarray(mf_min, np.float32).reshape(-1)
+        n = len(skip)
+        if not (len(xw) == len(normal) == len(mf_max) == len(mf_min) == n):
+            raise OrbxError(ORBX_E_INVALID, "array lengths disagree: %d / %d / %d / %d / %d" % (n, len(xw), len(normal), len(mf_max), len(mf_min)))
+        out = (np.full(n, 255, np.uint8), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.int32),
+               np.zeros(n, np.float32))
+        return (view, skip, xw, normal, mf_max, mf_min), out, n
+
+    def frustum(self, view, skip, xw, normal, mf_max, mf_min, viewing_cos_limit=0.5):
+        """Frame::isInFrustum (src/Frame.cc:269-325) for the local MapPoints of Tracking::SearchLocalPoints (src/Tracking.cc:1174-1187)
+        in one call.  view: one VIEW_DTYPE record; skip[i] = mnLastFrameSeen == mnId or isBad(); mf_max / mf_min: the raw
+        mfMaxDistance / mfMinDistance.  Returns (status uint8, proj_x, proj_y, proj_xr float32, pred_level int32, view_cos float32,
+        n_to_match): the orbm_frustum_status of every point and the mTrack* values of the ones in view (status 0)."""
+        a, out, n = self._frustum_inputs(view, skip, xw, normal, mf_max, mf_min)
+        nt = C.c_int(0)
+        _mchk(self.L.orbm_frustum(self.h, _p(a[0]), n, _p(a[1]), _p(a[2]), _p(a[3]), _p(a[4]), _p(a[5]), C.c_float(viewing_cos_limit),
+                                  *[_p(o) for o in out], C.byref(nt)))
+        return out + (nt.value,)
+
+    def frustum_device(self, d_view, n, d_skip, d_xw, d_normal, d_mf_max, d_mf_min, viewing_cos_limit, d_status, d_proj_x, d_proj_y,
+                       d_proj_xr, d_pred_level, d_view_cos, stream=None):
+        """The same on raw device pointers (the view block included); nothing is synchronised and nothing is counted."""
+        _mchk(self.L.orbm_frustum_device(self.h, d_view, n, d_skip, d_xw, d_normal, d_mf_max, d_mf_min, C.c_float(viewing_cos_limit),
+                                         d_status, d_proj_x, d_proj_y, d_proj_xr, d_pred_level, d_view_cos, stream))
+
+    def search_local_points(self, view, skip, xw, normal, mf_max, mf_min, mp_desc, mp_obs, kps_cur, desc_cur, cur_obs, th,
+                            u_right=None, viewing_cos_limit=0.5):
+        """Tracking::SearchLocalPoints (src/Tracking.cc:1174-1199) in one call: frustum() followed by SearchByProjectionMap() on the
+        points in view, the projection staying on the device in between.  The frame's grid must be in the handle (grid_build);
+        cur_obs (int32) is updated in place.  Returns frustum()'s tuple + (cur_match, nmatches)."""
+        a, out, n = self._frustum_inputs(view, skip, xw, normal, mf_max, mf_min)
+        mp_desc = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32); mp_obs = np.ascontiguousarray(mp_obs, np.int32).reshape(-1)
+        kps_cur = np.ascontiguousarray(kps_cur, KP_DTYPE); desc_cur = np.ascontiguousarray(desc_cur, np.uint8).reshape(-1, 32)
+        ur = None if u_right is None else np.ascontiguousarray(u_right, np.float32)
+        if len(mp_desc) != n or len(mp_obs) != n or len(desc_cur) != len(kps_cur) or (ur is not None and len(ur) != len(kps_cur)):
+            raise OrbxError(ORBX_E_INVALID, "array lengths disagree: %d MapPoints, %d key points" % (n, len(kps_cur)))
+        assert cur_obs.dtype == np.int32 and cur_obs.flags["C_CONTIGUOUS"] and len(cur_obs) == len(kps_cur)
+        cm = np.full(len(kps_cur), -1, np.int32)
+        nt, nm = C.c_int(0), C.c_int(0)
+        _mchk(self.L.orbm_search_local_points(self.h, _p(a[0]), n, _p(a[1]), _p(a[2]), _p(a[3]), _p(a[4]), _p(a[5]), C.c_float(viewing_cos_limit),
+                                              _p(mp_desc), _p(mp_obs), _p(kps_cur), _p(desc_cur), _p(ur), len(kps_cur), C.c_float(th),
+                                              C.c_float(self.mfNNratio), *[_p(o) for o in out], C.byref(nt), _p(cur_obs), _p(cm), C.byref(nm)))
+        return out + (nt.value, cm, nm.value)
 
     def match_dense(self, q, kq, t, kt, th=None):
         """Dense SearchByBoW-style acceptance + rotation filter on host buffers (via best2)."""

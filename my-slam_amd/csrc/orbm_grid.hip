@@ -316,6 +316,9 @@ struct WindowParts {
     WindowParts(InBlock &in, const float *qx, const float *qy, const float *qr, const int32_t *min_level, const int32_t *max_level, int nq)
         : x(in.add(qx, (size_t)nq * 4)), y(in.add(qy, (size_t)nq * 4)), r(in.add(qr, (size_t)nq * 4)),
           mn(in.add(min_level, (size_t)nq * 4)), mx(in.add(max_level, (size_t)nq * 4)) {}
+    WindowParts(InBlock &in, int nq)            // room only: a kernel writes the windows
+        : x(in.reserve((size_t)nq * 4)), y(in.reserve((size_t)nq * 4)), r(in.reserve((size_t)nq * 4)), mn(in.reserve((size_t)nq * 4)),
+          mx(in.reserve((size_t)nq * 4)) {}
 };
 template <int MODE>
 static int launch_area_list(orbm_matcher *m, const InBlock &in, const WindowParts &w, int nq, int32_t *d_counts, const int32_t *d_off,
@@ -659,6 +662,39 @@ extern "C" int orbm_search_by_projection_kf(orbm_matcher *m, int n_mp, const uin
     return ORBX_OK;
 }
 
+// The scan of ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:73-122) over the windows'
+// candidates and distances: query k belongs to MapPoint src[k], has radius r[k] and the candidates idx / dist[off[k] .. off[k + 1]).
+// Returns the number of assignments.
+static int map_scan(int nq, const int *src, const float *r, const int32_t *off, const int32_t *idx, const int32_t *dist, const float *proj_xr,
+                    const float *u_right, const orbx_keypoint *kps_cur, const int32_t *mp_obs, float nnratio, int32_t *cur_obs,
+                    int32_t *cur_match)
+{
+    int nm = 0;
+    for (int k = 0; k < nq; k++) {
+        if (off[k + 1] == off[k]) continue;
+        const int iMP = src[k];
+        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
+        for (int c = off[k]; c < off[k + 1]; c++) {
+            const int i2 = idx[c];
+            if (cur_obs[i2] > 0) continue;
+            if (u_right && u_right[i2] > 0) {
+                const float er = fabsf(proj_xr[iMP] - u_right[i2]);
+                if (er > r[k]) continue;
+            }
+            const int d = dist[c];
+            if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestLevel2 = bestLevel; bestLevel = kps_cur[i2].octave; bestIdx = i2; }
+            else if (d < bestDist2) { bestLevel2 = kps_cur[i2].octave; bestDist2 = d; }
+        }
+        if (bestDist <= ORBM_TH_HIGH) {
+            if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
+            cur_obs[bestIdx] = mp_obs[iMP];
+            cur_match[bestIdx] = iMP;
+            nm++;
+        }
+    }
+    return nm;
+}
+
 // ---- ORBmatcher::SearchByProjection(Frame&, const vector<MapPoint*>&, th) (src/ORBmatcher.cc:45-125) ----
 extern "C" int orbm_search_by_projection_map(orbm_matcher *m, int n_mp, const uint8_t *in_view, const float *proj_x, const float *proj_y,
                                              const float *proj_xr, const int32_t *pred_level, const float *view_cos, const uint8_t *mp_desc,
@@ -688,30 +724,91 @@ extern "C" int orbm_search_by_projection_map(orbm_matcher *m, int n_mp, const ui
     const int nq = Q.size();
     if (nq == 0) return ORBX_OK;
     MTRY(Q.run(m, mp_desc, desc_cur, n_cur));
-    const std::vector<int32_t> &off = Q.off, &idx = Q.idx, &dist = Q.dist;
-    int nm = 0;
-    for (int k = 0; k < nq; k++) {                  // :73-122
-        if (off[k + 1] == off[k]) continue;
-        const int iMP = Q.src[k];
-        int bestDist = 256, bestLevel = -1, bestDist2 = 256, bestLevel2 = -1, bestIdx = -1;
-        for (int c = off[k]; c < off[k + 1]; c++) {
-            const int i2 = idx[c];
-            if (cur_obs[i2] > 0) continue;
-            if (u_right && u_right[i2] > 0) {
-                const float er = fabsf(proj_xr[iMP] - u_right[i2]);
-                if (er > Q.r[k]) continue;
-            }
-            const int d = dist[c];
-            if (d < bestDist) { bestDist2 = bestDist; bestDist = d; bestLevel2 = bestLevel; bestLevel = kps_cur[i2].octave; bestIdx = i2; }
-            else if (d < bestDist2) { bestLevel2 = kps_cur[i2].octave; bestDist2 = d; }
-        }
-        if (bestDist <= ORBM_TH_HIGH) {
-            if (bestLevel == bestLevel2 && (float)bestDist > nnratio * (float)bestDist2) continue;
-            cur_obs[bestIdx] = mp_obs[iMP];
-            cur_match[bestIdx] = iMP;
-            nm++;
-        }
+    *nmatches = map_scan(nq, Q.src.data(), Q.r.data(), Q.off.data(), Q.idx.data(), Q.dist.data(), proj_xr, u_right, kps_cur, mp_obs, nnratio,
+                         cur_obs, cur_match);
+    return ORBX_OK;
+}
+
+// ---- Tracking::SearchLocalPoints (src/Tracking.cc:1174-1199): Frame::isInFrustum for every local MapPoint, then the search above
+// on the points in view.  k_frustum (orbm_frustum.hip) writes one window per MapPoint into the call's device block, the count pass
+// reads them there, and the frustum outputs come back with the counts.  The host then knows the points in view: their descriptors,
+// the offsets of all windows (for the list pass) and of the windows in view (for the distances; the candidates of the empty windows
+// in between take no room, so both describe the same list) go up in one copy, lists and distances come back. ----
+extern "C" int orbm_search_local_points(orbm_matcher *m, const orbm_frame_view *view, int n, const uint8_t *skip, const float *xw,
+                                        const float *normal, const float *mf_max, const float *mf_min, float viewing_cos_limit,
+                                        const uint8_t *mp_desc, const int32_t *mp_obs, const orbx_keypoint *kps_cur, const uint8_t *desc_cur,
+                                        const float *u_right, int n_cur, float th, float nnratio,
+                                        uint8_t *status, float *proj_x, float *proj_y, float *proj_xr, int32_t *pred_level, float *view_cos,
+                                        int *n_to_match, int32_t *cur_obs, int32_t *cur_match, int *nmatches)
+{
+    if (n < 0 || n_cur < 0) return mfail(ORBX_E_INVALID, "n=%d MapPoints, n_cur=%d keypoints", n, n_cur);
+    if (n > (1 << 27)) return mfail(ORBX_E_CAPACITY, "request beyond 2^27 MapPoints");
+    if (n == 0) return ORBX_OK;                     // nothing to project, nToMatch = 0: no search (:1189)
+    MTRY(orbm_frustum_check(view, skip, xw, normal, mf_max, mf_min, status, proj_x, proj_y, proj_xr, pred_level, view_cos, n_to_match));
+    if (!mp_desc || !mp_obs || !nmatches || (n_cur > 0 && (!kps_cur || !desc_cur || !cur_obs || !cur_match))) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (u_right && !(view->mbf > 0.f)) return mfail(ORBX_E_INVALID, "u_right given, but the frame has mbf=%g", (double)view->mbf);
+    if (!m) return orbm_no_handle();
+    if (n_cur > 0 && (!m->grid_ok || m->grid.n != n_cur)) return mfail(ORBX_E_INVALID, "orbm_grid_build(frame) has not been called");
+    *nmatches = 0;
+    for (int i = 0; i < n_cur; i++) cur_match[i] = -1;
+    if (n_cur == 0)                                 // a frame without keypoints: every window is empty
+        return orbm_frustum(m, view, n, skip, xw, normal, mf_max, mf_min, viewing_cos_limit, status, proj_x, proj_y, proj_xr, pred_level, view_cos, n_to_match);
+    MHIPCHK(hipSetDevice(m->device));
+    const size_t N = (size_t)n;
+    MTRY(orbm_grow(m, (25ll * n) / 12 + 2, 0, 0));  // d_out: the counts and five arrays of n words, then the n status bytes
+    MTRY(orbm_arena_begin(m));
+    hipStream_t s = m->stream;
+    InBlock in(m);
+    const int pv = in.add(view, sizeof(orbm_frame_view)), ps = in.add(skip, N), px = in.add(xw, N * 12), pn = in.add(normal, N * 12),
+              pa = in.add(mf_max, N * 4), pi = in.add(mf_min, N * 4), pt = in.add(desc_cur, (size_t)n_cur * 32);
+    in.device_only_from_here();
+    const WindowParts w(in, n);
+    const size_t off_bytes = ((N + 1) * 4 + 63) & ~(size_t)63;
+    const int p2 = in.reserve(2 * off_bytes + N * 32);      // second trip: off of all windows, off of those in view, their descriptors
+    MTRY(in.upload(s));
+    int32_t *d_counts = m->d_out;
+    float *o = reinterpret_cast<float *>(m->d_out + N);
+    uint8_t *d_status = reinterpret_cast<uint8_t *>(m->d_out + 6 * N);
+    const FrustumWindows fw = {th, in.dev_at<float>(w.x), in.dev_at<float>(w.y), in.dev_at<float>(w.r), in.dev_at<int32_t>(w.mn), in.dev_at<int32_t>(w.mx)};
+    orbm_frustum_launch(in.at<orbm_frame_view>(pv), n, in.at<uint8_t>(ps), in.at<float>(px), in.at<float>(pn), in.at<float>(pa),
+                        in.at<float>(pi), viewing_cos_limit, d_status, o, o + N, o + 2 * N, m->d_out + 4 * N, o + 4 * N, &fw, s);
+    MHIPCHK(hipGetLastError());
+    MTRY(launch_area_list<0>(m, in, w, n, d_counts, nullptr, nullptr, s));
+    std::vector<int32_t> cnt(N);
+    void *host[7] = {cnt.data(), proj_x, proj_y, proj_xr, pred_level, view_cos, status};
+    const size_t parts[7] = {N * 4, N * 4, N * 4, N * 4, N * 4, N * 4, N};
+    MTRY(orbm_d2h_split(m, host, parts, 7, m->d_out, s));
+    MTRY(orbm_sync(m, s));
+    // the points in view: their windows, in MapPoint order
+    int32_t *off_all = reinterpret_cast<int32_t *>(in.host_at(p2)), *off_view = reinterpret_cast<int32_t *>(in.host_at(p2) + off_bytes);
+    uint8_t *desc_view = in.host_at(p2) + 2 * off_bytes;
+    std::vector<int> src;
+    std::vector<float> radius;
+    const bool bFactor = th != 1.0;                 // src/ORBmatcher.cc:49
+    off_all[0] = 0; off_view[0] = 0;
+    for (int i = 0; i < n; i++) {
+        off_all[i + 1] = off_all[i] + cnt[i];
+        if (status[i] != ORBM_FRUSTUM_IN_VIEW) continue;
+        float r = view_cos[i] > 0.998 ? 2.5f : 4.0f;   // RadiusByViewingCos, as k_frustum computed it
+        if (bFactor) r *= th;
+        radius.push_back(r * view->scale_factors[pred_level[i]]);
+        memcpy(desc_view + 32 * src.size(), mp_desc + 32 * (size_t)i, 32);
+        src.push_back(i);
+        off_view[src.size()] = off_all[i + 1];
     }
-    *nmatches = nm;
+    const int nq = (int)src.size(), total = off_all[n];
+    *n_to_match = nq;                               // nToMatch, :1185
+    if (nq == 0 || total == 0) return ORBX_OK;      // :1189, or no keypoint in any window
+    MTRY(orbm_grow(m, 0, 0, total));                // d_idx / d_out hold nothing any more
+    MTRY(in.send(p2, 2 * off_bytes + (size_t)nq * 32, s));
+    const int32_t *d_off_all = in.dev_at<int32_t>(p2), *d_off_view = reinterpret_cast<const int32_t *>(in.dev_at<uint8_t>(p2) + off_bytes);
+    MTRY(launch_area_list<1>(m, in, w, n, nullptr, d_off_all, m->d_idx, s));
+    orbm_launch_dist_csr(in.dev_at<uint8_t>(p2) + 2 * off_bytes, nq, in.at<uint8_t>(pt), d_off_view, m->d_idx, total, m->d_out, s);
+    MHIPCHK(hipGetLastError());
+    std::vector<int32_t> idx((size_t)total), dist((size_t)total);
+    MTRY(orbm_d2h(m, idx.data(), m->d_idx, (size_t)total * 4, s));
+    MTRY(orbm_d2h(m, dist.data(), m->d_out, (size_t)total * 4, s));
+    MTRY(orbm_sync(m, s));
+    *nmatches = map_scan(nq, src.data(), radius.data(), off_view, idx.data(), dist.data(), proj_xr, u_right, kps_cur, mp_obs, nnratio, cur_obs, cur_match);
     return ORBX_OK;
 }

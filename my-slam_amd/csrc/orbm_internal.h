@@ -1,5 +1,6 @@
-// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip and orbm_triangulate.hip
+// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip and orbm_frustum.hip
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -122,7 +123,7 @@ int orbm_area_pairs(orbm_matcher *m, const float *x, const float *y, const float
 int orbm_arena_begin(orbm_matcher *m);                                                    // start of a host-API call
 int orbm_h2d(orbm_matcher *m, void *dev, const void *host, size_t bytes, hipStream_t s);   // staged host -> device copy
 int orbm_d2h(orbm_matcher *m, void *host, const void *dev, size_t bytes, hipStream_t s);   // staged; lands in host at orbm_sync()
-// one device block -> up to four host arrays, one copy (parts[i] bytes each, consecutive in the block)
+// one device block -> several host arrays (the pending list holds eight), one copy (parts[i] bytes each, consecutive in the block)
 int orbm_d2h_split(orbm_matcher *m, void *const *host, const size_t *parts, int nparts, const void *dev, hipStream_t s);
 int orbm_sync(orbm_matcher *m, hipStream_t s);                                            // synchronise + deliver the D2H copies
 // orbm_mappoint.hip: the status of a NULL handle where device work is needed (ORBX_E_HIP without a device, else ORBX_E_INVALID)
@@ -132,6 +133,16 @@ int orbm_mfma_splits(int nq_cap, int nt_cap, int nbatch);
 int orbm_launch_dense_mfma(orbm_matcher *m, const uint8_t *d_q, const int32_t *d_nq, int nq_fixed, const uint8_t *d_t, const int32_t *d_nt,
                            int nt_fixed, long long qstride, long long tstride, int cap_q, int cap_t, int nbatch, int out_stride, int S,
                            uint2 *part, hipStream_t s);
+// orbm_frustum.hip: k_frustum on device pointers.  w != NULL: also each point's SearchByProjection window (radius from the viewing
+// cosine, th and the level's scale factor; levels [level-1, level]; r < 0 for a point not in view) for k_area_list
+struct FrustumWindows { float th; float *x, *y, *r; int32_t *min_level, *max_level; };
+void orbm_frustum_launch(const orbm_frame_view *d_view, int n, const uint8_t *d_skip, const float *d_xw, const float *d_normal,
+                         const float *d_mf_max, const float *d_mf_min, float cos_limit, uint8_t *d_status, float *d_proj_x,
+                         float *d_proj_y, float *d_proj_xr, int32_t *d_pred_level, float *d_view_cos, const FrustumWindows *w,
+                         hipStream_t s);
+int orbm_frustum_check(const orbm_frame_view *view, const uint8_t *skip, const float *xw, const float *normal, const float *mf_max,
+                       const float *mf_min, const uint8_t *status, const float *proj_x, const float *proj_y, const float *proj_xr,
+                       const int32_t *pred_level, const float *view_cos, const int *n_to_match);
 // k_dist_csr (orbm.hip) for callers in other files: dist[c] of every CSR candidate, off has nq + 1 entries
 void orbm_launch_dist_csr(const uint8_t *d_q, int nq, const uint8_t *d_t, const int32_t *d_off, const int32_t *d_idx, int total,
                           int32_t *d_dist, hipStream_t s);
@@ -147,7 +158,7 @@ struct InBlock {
     struct Part { const void *src; size_t bytes, off; };
     orbm_matcher *m;
     std::vector<Part> parts;
-    size_t total = 0;
+    size_t total = 0, sent = (size_t)-1;       // sent: the bytes upload() copies (everything unless device_only_from_here())
     uint8_t *host = nullptr, *dev = nullptr;    // the block after upload()
     std::vector<uint8_t> tmp_host;
     void *tmp_dev = nullptr;
@@ -162,6 +173,8 @@ struct InBlock {
         return (int)parts.size() - 1;
     }
     int reserve(size_t bytes) { return add(nullptr, bytes); }     // a part whose content comes later: fill()
+    void device_only_from_here() { if (sent == (size_t)-1) sent = total; }   // the parts reserved after this are written by kernels:
+                                                                             // room in the block, not part of the copy
     int upload(hipStream_t s)
     {
         if (total == 0) return ORBX_OK;
@@ -176,7 +189,7 @@ struct InBlock {
         }
         for (const Part &p : parts)
             if (p.src && p.bytes) memcpy(host + p.off, p.src, p.bytes);
-        MHIPCHK(hipMemcpyAsync(dev, host, total, hipMemcpyHostToDevice, s));
+        if (std::min(sent, total)) MHIPCHK(hipMemcpyAsync(dev, host, std::min(sent, total), hipMemcpyHostToDevice, s));
         if (tmp_dev) MHIPCHK(hipStreamSynchronize(s));   // pageable source
         return ORBX_OK;
     }
@@ -187,6 +200,14 @@ struct InBlock {
         MHIPCHK(hipMemcpyAsync(dev + p.off, host + p.off, p.bytes, hipMemcpyHostToDevice, s));
         return ORBX_OK;
     }
+    // a reserved part the caller composes in place after upload(): host_at() is its host side, send() copies its first bytes
+    uint8_t *host_at(int part) const { return host + parts[part].off; }
+    int send(int part, size_t bytes, hipStream_t s)
+    {
+        if (bytes) MHIPCHK(hipMemcpyAsync(dev + parts[part].off, host + parts[part].off, bytes, hipMemcpyHostToDevice, s));
+        return ORBX_OK;
+    }
+    template <class T> T *dev_at(int part) const { return reinterpret_cast<T *>(dev + parts[part].off); }
     template <class T> const T *at(int part) const { return parts[part].bytes ? reinterpret_cast<const T *>(dev + parts[part].off) : nullptr; }
 };
 
