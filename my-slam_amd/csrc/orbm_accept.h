@@ -1,4 +1,4 @@
-// orbm_accept.h -- the matcher's second half, shared by k_accept_rot (orbm.hip) and the fused tail of k_best2_mfma (orbm_mfma.hip):
+// orbm_accept.h -- the matcher's second half, the device code of k_accept_rot (orbm.hip):
 // merge of the train-range partials, acceptance (src/ORBmatcher.cc:228-232), rotation histogram (:236-246), ComputeThreeMaxima and
 // the cull (:266-284).
 #ifndef ORBM_ACCEPT_H

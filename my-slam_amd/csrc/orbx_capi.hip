@@ -1,25 +1,25 @@
-// orbx_capi.hip -- host side of liborbx.so: constructor tables, shape planning, workspace, C ABI.
-// The arithmetic here restates the reference constructor and OpenCV's resize planning on the host
-// (citations: src/ORBextractor.cc of WChen09/My-SLAM); all pixel work is in the per-stage kernel files (orbx_pyramid/fast/octree/describe.hip).
-#include <cfloat>
+// orbx_capi.hip -- host side of liborbx.so: the handle, its workspace and the C ABI.  Shapes are planned in orbx_plan.hip (host arithmetic,
+// no handle) and committed here; all pixel work is in the per-stage kernel files (orbx_pyramid/fast/octree/describe.hip).
 #include <chrono>
 #include <cstdarg>
 #include <algorithm>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <atomic>
-#include <condition_variable>
-#include <functional>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "orbx_internal.h"
-
+#include "orbx_plan.h"
 #include "stage_pool.h"
+
+// A/B switches of orbx_extract_batch, read once per process
+static bool batch_equal_chunks() { static const bool on = getenv("ORBX_BATCH_EQUAL") != nullptr; return on; }   // A/B switch
+static int batch_streams() { static const int n = [] { const char *e = getenv("ORBX_BATCH_STREAMS"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : v > 3 ? 3 : v; }(); return n; }   // compute streams the chunks rotate over
+static bool batch_trace() { static const bool on = getenv("ORBX_BATCH_TRACE") != nullptr; return on; }      // host-side time split of a call, to stderr
+static bool batch_pinned_ok() { static const bool on = [] { const char *e = getenv("ORBX_BATCH_PINNED"); return !e || atoi(e) != 0; }(); return on; }   // page-locked caller memory is uploaded where it lies (0 keeps the staging copy: A/B switch)
 
 static thread_local std::string g_err;
 static int fail(int code, const char *fmt, ...)
@@ -41,19 +41,9 @@ static int fail(int code, const char *fmt, ...)
 extern "C" const char *orbx_last_error(void) { return g_err.c_str(); }
 extern "C" const char *orbx_version(void) { return "orbx 0.1 (gfx950)"; }
 
-static inline int cv_round(double v) { return (int)lrint(v); }   // cvRound: half to even
-static inline int cv_floor(double v) { int i = (int)v; return i - (v < i); }
-static inline int cv_ceil(double v) { int i = (int)v; return i + (v > i); }
-static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 #define ORBX_MAX_SUB 4
-struct orbx_extractor {
-    int nfeatures = 0; float scale_factor = 0; int nlevels = 0, ini_th = 0, min_th = 0, device = 0;
-    int max_w = 0, max_h = 0, max_batch = 0;
-    float scale[ORBX_MAX_LEVELS], inv_scale[ORBX_MAX_LEVELS], sigma2[ORBX_MAX_LEVELS], inv_sigma2[ORBX_MAX_LEVELS];
-    int quota[ORBX_MAX_LEVELS];
-    int umax[16]; int gauss_k[7];
-    int blur_mode = 0;
+struct orbx_extractor : PlanParams {   // the constructor's arguments and tables, the A/B switches and the table capacities are what the planner reads
+    int device = 0, max_w = 0, max_h = 0, max_batch = 0;
     bool need_clear = true;
     hipStream_t stream = nullptr;
     hipStream_t aux[ORBX_MAX_SUB - 1] = {}; hipEvent_t ev_fork = nullptr, ev_join[ORBX_MAX_SUB - 1] = {}; int nsub = 1; int overlap_pyr = 0;
@@ -62,20 +52,16 @@ struct orbx_extractor {
     const uint8_t *last_input = nullptr; int last_in_stride = 0; long long last_in_frame = 0;
     uint8_t *h_pyr = nullptr; size_t h_pyr_bytes = 0;      // page-locked staging of orbx_download_pyramid (lazy)
     const uint8_t *pin_ptr = nullptr; int pin_n = 0; size_t pin_stride = 0, pin_bytes = 0; bool pin_is = false;   // last is_pinned_host() answer
-    OrbxPlan plan; OrbxWork work; ResizeTab tabs[ORBX_MAX_LEVELS]; int area2[ORBX_MAX_LEVELS];
-    // several pyramid levels per launch (k_resize_fused): one plan per band height (16 rows for batches, 8 for a few frames)
-    struct FusePlan { bool ok = false; int a = 0, b = 0, nbands = 0, buf0 = 0, lds = 0, bh = 0; size_t off = 0; } fuse[2];
-    int4 *d_bands = nullptr; size_t bands_cap = 0; int fuse_on = 1; int oct_fast = 1; int oct_cap_max = 0;
-    // upper pyramid levels in one launch, one wave per 2-D tile (k_resize_tiles): levels tile.a + 1 .. nlevels - 1
-    struct TilePlan { bool ok = false; int a = 0, b = 0, ntx = 0, nty = 0, lds = 0; int lds_off[ORBX_FUSE_MAX] = {}, tab_off[ORBX_FUSE_MAX] = {}; size_t offx = 0, offy = 0; } tile;
-    int4 *d_tiles = nullptr; size_t tiles_cap = 0; int tile_a = 0, tile_w = 32, tile_h = 32, tile_min_frames = 8;   // off by default: measured slower than the launches it replaces
-    size_t oct_lds = 0;
+    // the plan of cur_w x cur_h, committed by ensure_plan(): all of it or none (level 0's source and blur_mode follow the call)
+    OrbxPlan plan; ResizeTab tabs[ORBX_MAX_LEVELS]; int resize_mode[ORBX_MAX_LEVELS]; FusePlan fuse[2]; TilePlan tile;
+    OrbxWork work;
+    int4 *d_bands = nullptr, *d_tiles = nullptr; int oct_cap_max = 0; size_t oct_lds = 0;
     // allocations (sized for the max shape)
     OrbxPlan max_plan; size_t pyr_bytes = 0; size_t pyr_level_off[ORBX_MAX_LEVELS];
     uint8_t *d_input = nullptr; int in_stride = 0; size_t in_frame = 0;
     uint8_t *d_pyr = nullptr;
-    int *d_tab_i = nullptr; short2 *d_tab_s = nullptr; size_t tab_elems = 0;
-    uint32_t *d_cells = nullptr; int cells_cap = 0;   // per-cell (level, row, column) table of the current plan
+    int *d_tab_i = nullptr; short2 *d_tab_s = nullptr;
+    uint32_t *d_cells = nullptr;   // per-cell (level, row, column) table of the current plan
     orbx_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_status = nullptr;
     uint8_t *h_in = nullptr;
     orbx_keypoint *h_kps = nullptr; uint8_t *h_desc = nullptr; int32_t *h_counts = nullptr, *h_status = nullptr;
@@ -93,152 +79,6 @@ struct orbx_extractor {
     hipEvent_t evr[ORBX_PROF_RING][5] = {}; long long ring_calls = 0;
 };
 
-// ---- A1: ORBextractor::ORBextractor tables (:412-472) ----
-static void build_tables(orbx_extractor *h)
-{
-    const int L = h->nlevels;
-    h->scale[0] = 1.0f; h->sigma2[0] = 1.0f;
-    for (int i = 1; i < L; i++) {
-        h->scale[i] = h->scale[i - 1] * h->scale_factor;
-        h->sigma2[i] = h->scale[i] * h->scale[i];
-    }
-    for (int i = 0; i < L; i++) {
-        h->inv_scale[i] = 1.0f / h->scale[i];
-        h->inv_sigma2[i] = 1.0f / h->sigma2[i];
-    }
-    float factor = 1.0f / h->scale_factor;
-    float nDesired = h->nfeatures * (1 - factor) / (1 - (float)pow((double)factor, (double)L));
-    int sum = 0;
-    for (int level = 0; level < L - 1; level++) {
-        h->quota[level] = cv_round(nDesired);
-        sum += h->quota[level];
-        nDesired *= factor;
-    }
-    h->quota[L - 1] = std::max(h->nfeatures - sum, 0);
-
-    int v, v0, vmax = cv_floor(ORBX_HALF_PATCH * sqrtf(2.f) / 2 + 1);
-    int vmin = cv_ceil(ORBX_HALF_PATCH * sqrtf(2.f) / 2);
-    const double hp2 = ORBX_HALF_PATCH * ORBX_HALF_PATCH;
-    for (v = 0; v <= vmax; ++v) h->umax[v] = cv_round(sqrt(hp2 - v * v));
-    for (v = ORBX_HALF_PATCH, v0 = 0; v >= vmin; --v) {
-        while (h->umax[v0] == h->umax[v0 + 1]) ++v0;
-        h->umax[v] = v0;
-        ++v0;
-    }
-    // OpenCV getGaussianKernel(7, 2, CV_32F) -> x256 fixed point (cv::GaussianBlur u8 path)
-    float cf[7]; double s = 0;
-    for (int i = 0; i < 7; i++) { double x = i - 3.0; cf[i] = (float)exp(-0.5 / 4.0 * x * x); s += cf[i]; }
-    s = 1. / s;
-    for (int i = 0; i < 7; i++) { cf[i] = (float)(cf[i] * s); h->gauss_k[i] = cv_round((double)cf[i] * 256.0); }
-}
-
-// ---- shape planning: level sizes (:1113-1114), cell grid (:775-789), quadtree roots (:545-547) ----
-static int make_plan(const orbx_extractor *h, int W, int H, OrbxPlan *P, std::string *why)
-{
-    memset(P, 0, sizeof(*P));
-    P->nlevels = h->nlevels; P->ini_th = h->ini_th; P->min_th = h->min_th; P->blur_mode = h->blur_mode;
-    long long cand_off = 0, list_off = 0, arena_off = 0;
-    int cells = 0;
-    for (int l = 0; l < h->nlevels; l++) {
-        OrbxLevel &L = P->lv[l];
-        L.w = cv_round((float)W * h->inv_scale[l]);
-        L.h = cv_round((float)H * h->inv_scale[l]);
-        if (L.w < 1 || L.h < 1 || L.w > 65535 || L.h > 65535) { *why = "level size out of range"; return ORBX_E_SHAPE; }
-        L.maxBX = L.w - ORBX_MINB; L.maxBY = L.h - ORBX_MINB;
-        const float width = (float)(L.maxBX - ORBX_MINB), height = (float)(L.maxBY - ORBX_MINB);
-        L.nCols = width > 0 ? (int)(width / 30.f) : 0;
-        L.nRows = height > 0 ? (int)(height / 30.f) : 0;
-        if (L.nCols <= 0 || L.nRows <= 0) { L.nCols = L.nRows = 0; L.wCell = L.hCell = 1; }   // no cell => no keypoint
-        else { L.wCell = (int)ceilf(width / L.nCols); L.hCell = (int)ceilf(height / L.nRows); }
-        L.rcpW = L.wCell > 1 ? (uint32_t)((1ull << 32) / (unsigned)L.wCell + 1) : 0u;
-        L.rcpH = L.hCell > 1 ? (uint32_t)((1ull << 32) / (unsigned)L.hCell + 1) : 0u;
-        L.cell_begin = cells;
-        cells += L.nCols * L.nRows;
-        L.quota = h->quota[l];
-        L.nIni = 0; L.hX = 1.f;
-        if (L.nCols > 0) {
-            L.nIni = (int)roundf(width / (float)(L.maxBY - ORBX_MINB));
-            if (L.nIni <= 0) { *why = "portrait level (quadtree root count 0): undefined in the reference"; return ORBX_E_SHAPE; }
-            L.hX = width / L.nIni;
-        }
-        // Candidate capacity = the most NMS survivors a level can have, so that no image overflows it (the reference has no
-        // such limit): survivors are strict 8-neighbour maxima inside a cell's zone (cv::FAST nonmax, per cell :811-817), no
-        // two of them are adjacent, so a zw x zh zone holds at most ceil(zw/2) * ceil(zh/2); the zones of a level's cells tile
-        // [19, w-19) x [19, h-19), hence sum <= ceil((w-38+nCols)/2) * ceil((h-38+nRows)/2) (monotone in w and h, so a
-        // smaller frame always fits the workspace planned for the handle's maximum).  The quadtree packs a candidate index
-        // into 20 bits: only a level beyond ~4.1 M pixels can still report ORBX_E_CAND_OVERFLOW.
-        const long long zw_all = std::max(L.w - 2 * ORBX_EDGE, 0), zh_all = std::max(L.h - 2 * ORBX_EDGE, 0);
-        const long long zone = zw_all * zh_all;
-        const long long nmax = ((zw_all + L.nCols + 1) / 2) * ((zh_all + L.nRows + 1) / 2);
-        L.cand_cap = L.nCols > 0 ? (int)std::min<long long>(nmax + 64, (1 << 20) - 1) : 0;
-        if (L.nCols > 0 && zone / 8 + 256 >= 100000) P->oct_big = 1;   // 1080p-class level: the quadtree runs 1024-thread workgroups
-        // quadtree fast-forward depth (k_octree): 4 levels of the tree from one key histogram, 5 for 1080p-class levels; fewer when
-        // many roots (a wide level) would make the tables large.  ORBX_OCT_FAST=0 turns it off (A/B measurements).
-        L.fastD = 0;
-        if (L.nCols > 0 && h->oct_fast) {
-            int d = (zone / 8 + 256 >= 100000) ? 5 : 4;
-            while (d > 0 && (long long)L.nIni * (((1ll << (2 * (d + 1))) - 1) / 3) > 2800) d--;
-            L.fastD = d;
-            P->oct_ft = std::max(P->oct_ft, (int)(L.nIni * (((1ll << (2 * (d + 1))) - 1) / 3)));
-            // per-coordinate path tables of the fast-forward (k_octree): one u16 per column and per row of the level's box
-            if (d > 0) P->oct_map = std::max(P->oct_map, (int)align_up((size_t)std::max(L.maxBX - ORBX_MINB, 1), 8) + (int)align_up((size_t)std::max(L.maxBY - ORBX_MINB, 1), 8));
-        }
-        L.cand_off = cand_off; cand_off += (L.cand_cap + 15) / 16 * 16;
-        L.list_cap = L.nCols > 0 ? (std::max(L.quota + 3, 4 * L.nIni) + 1 + 3) / 4 * 4 : 0;
-        L.list_off = list_off; list_off += L.list_cap;
-        L.arena_cap = L.nCols > 0 ? 24 * L.list_cap + 256 : 0;
-        L.arena_off = arena_off; arena_off += L.arena_cap;
-        L.scale = h->scale[l];
-        L.kp_size = (float)(int)(31 * h->scale[l]);   // :839,:848
-    }
-    P->ncells = cells;
-    P->cand_frame = cand_off; P->list_frame = list_off; P->arena_frame = arena_off;
-    P->out_cap = (int)list_off;
-    return ORBX_OK;
-}
-
-// cv::resize INTER_LINEAR planning for one level pair (OpenCV 3.1.0 imgwarp.cpp)
-static void plan_resize(int sw, int sh, int dw, int dh, int *xofs, short2 *alpha, int *yofs, short2 *beta, int *mode)
-{
-    const double inv_x = (double)dw / sw, inv_y = (double)dh / sh;
-    const double scale_x = 1. / inv_x, scale_y = 1. / inv_y;
-    const int isx = cv_round(scale_x), isy = cv_round(scale_y);
-    const bool area2 = fabs(scale_x - isx) < DBL_EPSILON && fabs(scale_y - isy) < DBL_EPSILON && isx == 2 && isy == 2;
-    auto sat = [](float v) { int i = cv_round(v); return (short)(i < -32768 ? -32768 : i > 32767 ? 32767 : i); };
-    for (int dx = 0; dx < dw; dx++) {
-        float fx = (float)((dx + 0.5) * scale_x - 0.5);
-        int sx = cv_floor(fx);
-        fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
-        if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        xofs[dx] = sx;
-        alpha[dx] = make_short2(sat((1.f - fx) * 2048), sat(fx * 2048));
-    }
-    for (int dy = 0; dy < dh; dy++) {
-        float fy = (float)((dy + 0.5) * scale_y - 0.5);
-        int sy = cv_floor(fy);
-        fy -= sy;
-        yofs[dy] = sy;
-        beta[dy] = make_short2(sat((1.f - fy) * 2048), sat(fy * 2048));
-    }
-    // the 4x4 kernel moves 8 source bytes per 4 destination columns: needs xofs[x+3]+1 - xofs[x] <= 7
-    int span = 0;
-    for (int dx = 0; dx + 3 < dw; dx += 4) span = std::max(span, xofs[dx + 3] + 1 - xofs[dx]);
-    *mode = area2 ? RESIZE_AREA2 : (span <= 7 && sw >= 12 ? RESIZE_FAST : RESIZE_GENERIC);
-    // the shared-row kernel (k_resize_linear_4x4s / k_resize_tiles): rows y4 .. y4+3 of every block of four destination rows
-    // start r or r + 1 source rows below the block's first one (true for scale factors up to 4/3) and nothing reflects at the top
-    if (*mode == RESIZE_FAST) {
-        static const bool on = [] { const char *e = getenv("ORBX_RESIZE6"); return !e || atoi(e) != 0; }();   // A/B switch
-        bool six = on && sh >= 2;
-        for (int y4 = 0; y4 < dh && six; y4++) {                 // any first row: k_resize_tiles starts its blocks where a tile's region starts
-            six = yofs[y4] >= 0;
-            for (int r = 1; r < 4 && y4 + r < dh; r++) { const int o = yofs[y4 + r] - yofs[y4]; six = six && (o == r || o == r + 1); }
-        }
-        for (int dx = 0; dx + 3 < dw && six; dx++) six = xofs[dx + 3] + 1 - xofs[dx] <= 7;     // and any first column (the 8-byte window)
-        if (six) *mode = RESIZE_FAST6;
-    }
-}
-
 // Stream captures against the rest of the process.  A capture is begun in RELAXED mode (this library issues nothing unsafe inside one,
 // and other threads' calls must not be judged against it), and the phases in which a handle uses synchronous runtime calls -- creation,
 // destruction, the table upload of a shape change -- exclude every capture of this library through one process-wide lock: on this runtime
@@ -249,6 +89,34 @@ static std::recursive_mutex &capture_mutex()
 {
     static std::recursive_mutex m;
     return m;
+}
+// Capture what `body` enqueues on s (body returns false if it failed) into an instantiated graph; null if the capture could not begin,
+// the body failed or the capture was invalidated.  capture_mutex() is held for the capture; a capture that began is always ended and its
+// hipGraph_t destroyed; a failure leaves no sticky error behind.  Nothing has run then: the caller runs the work plainly.
+template <class Body> static hipGraphExec_t capture_graph(hipStream_t s, Body body)
+{
+    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
+    hipGraphExec_t exec = nullptr;
+    if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
+        const bool ok = body();
+        hipGraph_t g = nullptr;
+        if (hipStreamEndCapture(s, &g) != hipSuccess || !ok || !g || hipGraphInstantiate(&exec, g, nullptr, nullptr, 0) != hipSuccess) exec = nullptr;
+        if (g) (void)hipGraphDestroy(g);
+    }
+    if (!exec) (void)hipGetLastError();
+    return exec;
+}
+// the switches read at every create (tests and A/B runs set them between two handles of one process)
+static void read_create_switches(orbx_extractor *h)
+{
+    if (const char *e = getenv("ORBX_OCT_FAST")) h->oct_fast = atoi(e);
+    // ORBX_PYRAMID_TILES = "a[,tile width[,tile height[,min frames]]]": levels a + 1 .. last in one launch (0 = off = default).
+    // Bit-exact, and at 64 x 640x480 slower than the per-level launches (levels 3..7: 40 us against 27; without any store 30): the
+    // tiles' halos make it compute 1.8x the pixels, two waves per SIMD are all the 1920 tiles give.  Kept as an A/B switch.
+    if (const char *e = getenv("ORBX_PYRAMID_TILES")) { int a = 2, tw = 32, th = 32, mf = 8; const int n = sscanf(e, "%d,%d,%d,%d", &a, &tw, &th, &mf); if (n >= 1) h->tile_a = a; if (n >= 2) h->tile_w = tw; if (n >= 3) h->tile_h = th; if (n >= 4) h->tile_min_frames = mf; }
+    if (h->tile_w < 8 || h->tile_w > 128 || (h->tile_w & 3) || h->tile_h < 8 || h->tile_h > 128 || (h->tile_h & 3)) h->tile_a = 0;
+    if (const char *e = getenv("ORBX_PYRAMID_FUSE")) h->fuse_on = atoi(e);
+    if (const char *e = getenv("ORBX_OVERLAP_PYRAMID")) h->overlap_pyr = atoi(e) != 0;   // A/B switch for ORBX_OPT_OVERLAP_PYRAMID
 }
 static void free_all(orbx_extractor *h)
 {
@@ -291,27 +159,29 @@ extern "C" int orbx_create(orbx_extractor **out, int nfeatures, float scale_fact
     if (device < 0 || device >= ndev) return fail(ORBX_E_INVALID, "device %d of %d", device, ndev);
     HIPCHK(hipSetDevice(device));
 
-    orbx_extractor *h = new orbx_extractor();
+    struct FreeAll { void operator()(orbx_extractor *p) const { free_all(p); } };
+    std::unique_ptr<orbx_extractor, FreeAll> owner(new orbx_extractor());   // every failure exit below frees what was built so far
+    orbx_extractor *h = owner.get();
     h->nfeatures = nfeatures; h->scale_factor = scale_factor; h->nlevels = nlevels;
     h->ini_th = std::min(std::max(ini_th, 0), 255); h->min_th = std::min(std::max(min_th, 0), 255);
     h->device = device; h->max_w = max_width; h->max_h = max_height; h->max_batch = max_batch;
     memset(&h->work, 0, sizeof(h->work));
-    { const char *e = getenv("ORBX_OCT_FAST"); if (e) h->oct_fast = atoi(e); }
-    build_tables(h);
+    read_create_switches(h);
+    orbx_build_tables(h);
 
     std::string why;
-    int rc = make_plan(h, max_width, max_height, &h->max_plan, &why);
-    if (rc != ORBX_OK) { delete h; return fail(rc, "max shape %dx%d: %s", max_width, max_height, why.c_str()); }
+    int rc = orbx_make_plan(*h, max_width, max_height, &h->max_plan, &why);
+    if (rc != ORBX_OK) return fail(rc, "max shape %dx%d: %s", max_width, max_height, why.c_str());
     int max_list = 0;
     for (int l = 0; l < nlevels; l++) max_list = std::max(max_list, h->max_plan.lv[l].list_cap);
     h->oct_cap_max = std::max(max_list, 8);
     h->oct_lds = orbx_octree_lds_bytes(h->oct_cap_max, 0, 0);
-    if (h->oct_lds > 150 * 1024) { delete h; return fail(ORBX_E_INVALID, "nfeatures=%d needs %zu B of LDS for the quadtree (max 153600)", nfeatures, h->oct_lds); }
+    if (h->oct_lds > 150 * 1024) return fail(ORBX_E_INVALID, "nfeatures=%d needs %zu B of LDS for the quadtree (max 153600)", nfeatures, h->oct_lds);
 
 #define ALLOC(ptr, bytes)                                                                       \
     do {                                                                                        \
         hipError_t e_ = hipMalloc((void **)&(ptr), std::max<size_t>((bytes), 256));             \
-        if (e_ != hipSuccess) { free_all(h); return fail(ORBX_E_HIP, "hipMalloc(%s, %zu): %s", #ptr, (size_t)(bytes), hipGetErrorString(e_)); } \
+        if (e_ != hipSuccess) return fail(ORBX_E_HIP, "hipMalloc(%s, %zu): %s", #ptr, (size_t)(bytes), hipGetErrorString(e_)); \
     } while (0)
     const size_t B = (size_t)max_batch;
     h->in_stride = (int)align_up(max_width, 64);
@@ -332,15 +202,6 @@ extern "C" int orbx_create(orbx_extractor **out, int nfeatures, float scale_fact
     ALLOC(h->d_bands, h->bands_cap * sizeof(int4));
     h->tiles_cap = 8192;
     ALLOC(h->d_tiles, h->tiles_cap * sizeof(int4));
-    {   // ORBX_PYRAMID_TILES = "a[,tile width[,tile height[,min frames]]]": levels a + 1 .. last in one launch (0 = off = default).
-        // Bit-exact, and at 64 x 640x480 slower than the per-level launches (levels 3..7: 40 us against 27; without any store 30): the
-        // tiles' halos make it compute 1.8x the pixels, two waves per SIMD are all the 1920 tiles give.  Kept as an A/B switch.
-        const char *e = getenv("ORBX_PYRAMID_TILES");
-        if (e) { int a = 2, tw = 32, th = 32, mf = 8; const int n = sscanf(e, "%d,%d,%d,%d", &a, &tw, &th, &mf); if (n >= 1) h->tile_a = a; if (n >= 2) h->tile_w = tw; if (n >= 3) h->tile_h = th; if (n >= 4) h->tile_min_frames = mf; }
-        if (h->tile_w < 8 || h->tile_w > 128 || (h->tile_w & 3) || h->tile_h < 8 || h->tile_h > 128 || (h->tile_h & 3)) h->tile_a = 0;
-    }
-    { const char *e = getenv("ORBX_PYRAMID_FUSE"); if (e) h->fuse_on = atoi(e); }
-    { const char *e = getenv("ORBX_OVERLAP_PYRAMID"); if (e) h->overlap_pyr = atoi(e) != 0; }   // A/B switch for ORBX_OPT_OVERLAP_PYRAMID
     h->cells_cap = h->max_plan.ncells + 64 * nlevels;   // a smaller frame never has more cells; slack for rounding
     ALLOC(h->d_cells, (size_t)h->cells_cap * sizeof(uint32_t));
     const OrbxPlan &M = h->max_plan;
@@ -361,22 +222,20 @@ extern "C" int orbx_create(orbx_extractor **out, int nfeatures, float scale_fact
     ALLOC(h->d_out, h->out_bytes);
 #undef ALLOC
     if (hipHostMalloc((void **)&h->h_in, B * h->in_frame + 256) != hipSuccess ||
-        hipHostMalloc((void **)&h->h_out, h->out_bytes) != hipSuccess) {
-        free_all(h);
+        hipHostMalloc((void **)&h->h_out, h->out_bytes) != hipSuccess)
         return fail(ORBX_E_HIP, "hipHostMalloc failed");
-    }
     h->d_counts = reinterpret_cast<int32_t *>(h->d_out); h->d_status = h->d_counts + B;
     h->d_kps = reinterpret_cast<orbx_keypoint *>(h->d_out + h->out_hdr); h->d_desc = h->d_out + h->out_hdr + h->out_kps_bytes;
     h->h_counts = reinterpret_cast<int32_t *>(h->h_out); h->h_status = h->h_counts + B;
     h->h_kps = reinterpret_cast<orbx_keypoint *>(h->h_out + h->out_hdr); h->h_desc = h->h_out + h->out_hdr + h->out_kps_bytes;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { free_all(h); return fail(ORBX_E_HIP, "hipStreamCreate failed"); }
-    for (auto &e : h->ev) if (hipEventCreate(&e) != hipSuccess) { free_all(h); return fail(ORBX_E_HIP, "hipEventCreate failed"); }
-    for (auto &a : h->aux) if (hipStreamCreateWithFlags(&a, hipStreamNonBlocking) != hipSuccess) { free_all(h); return fail(ORBX_E_HIP, "hipStreamCreate failed"); }
-    for (auto &e : h->ev_join) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) { free_all(h); return fail(ORBX_E_HIP, "hipEventCreate failed"); }
-    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) { free_all(h); return fail(ORBX_E_HIP, "hipEventCreate failed"); }
-    if (orbx_upload_constants(h->umax, h->gauss_k) != 0) { free_all(h); return fail(ORBX_E_HIP, "constant upload failed"); }
-    if (orbx_selftest_fp16() != 0) { free_all(h); return fail(ORBX_E_HIP, "fp16 subnormal self-test failed: the FAST score tree needs fp16 subnormals enabled on this device"); }
-    *out = h;
+    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(ORBX_E_HIP, "hipStreamCreate failed");
+    for (auto &e : h->ev) if (hipEventCreate(&e) != hipSuccess) return fail(ORBX_E_HIP, "hipEventCreate failed");
+    for (auto &a : h->aux) if (hipStreamCreateWithFlags(&a, hipStreamNonBlocking) != hipSuccess) return fail(ORBX_E_HIP, "hipStreamCreate failed");
+    for (auto &e : h->ev_join) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(ORBX_E_HIP, "hipEventCreate failed");
+    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) return fail(ORBX_E_HIP, "hipEventCreate failed");
+    if (orbx_upload_constants(h->umax, h->gauss_k) != 0) return fail(ORBX_E_HIP, "constant upload failed");
+    if (orbx_selftest_fp16() != 0) return fail(ORBX_E_HIP, "fp16 subnormal self-test failed: the FAST score tree needs fp16 subnormals enabled on this device");
+    *out = owner.release();
     return ORBX_OK;
 }
 
@@ -442,185 +301,114 @@ extern "C" int orbx_last_stage_ms(orbx_extractor *h, float ms[4])
     return ORBX_OK;
 }
 
-// One axis of the tile plan of k_resize_tiles.  n[l] = extent of level l, ofs[l] = level l's source-offset table (level-l coordinate ->
-// level l-1 coordinate, monotone), T = tile extent at level b.  out[i * (b - a + 1) + (l - a)] = (own0, own1, comp0, comp1) of tile i at
-// level l: the owned ranges of a level are cut at the images of the level-b tile boundaries , so they partition the level; the computed range is the hull of the owned range
-// and the bilinear footprint of what the tile computes one level down, lengthened to a multiple of 4 (the kernel works in 4x4 blocks
-// counted from the range's first pixel).  align_own (the x axis): the computed range starts a multiple of 4 before the owned one, so
-// that a block is owned from its first column on or not at all (the range may then start at -1 .. -3: the kernel's table slices repeat column 0).
-static int plan_tile_axis(int a, int b, int T, const int *n, const int *const *ofs, bool align_own, std::vector<int4> &out, int *max_comp)
-{
-    const int nt = (n[b] + T - 1) / T, nl = b - a + 1;
-    T = std::min(T, (((n[b] + nt - 1) / nt) + 3) & ~3);       // equal tiles: the kernel ends with its largest tile, and a sliver of a tile carries a full halo
-    out.assign((size_t)nt * nl, make_int4(0, 0, 0, 0));
-    std::vector<std::vector<int>> B((size_t)nl, std::vector<int>((size_t)nt + 1, 0));
-    for (int i = 0; i <= nt; i++) B[(size_t)(b - a)][(size_t)i] = std::min(i * T, n[b]);
-    for (int l = b - 1; l >= a; l--)
-        for (int i = 0; i <= nt; i++) {
-            int v = 0;
-            if (i == nt) v = n[l];
-            else if (i > 0) {
-                const int d = B[(size_t)(l + 1 - a)][(size_t)i];
-                if (d >= n[l + 1]) v = n[l];
-                else v = std::min(std::max(ofs[l + 1][d], 0), n[l] - 1);
-                v = std::max(v, B[(size_t)(l - a)][(size_t)i - 1]);
-            }
-            B[(size_t)(l - a)][(size_t)i] = v;
-        }
-    for (int l = a; l <= b; l++) max_comp[l] = 0;
-    for (int i = 0; i < nt; i++) {
-        int c0 = B[(size_t)(b - a)][(size_t)i], c1 = c0 + ((B[(size_t)(b - a)][(size_t)i + 1] - c0 + 3) & ~3);
-        out[(size_t)i * nl + (size_t)(b - a)] = make_int4(B[(size_t)(b - a)][(size_t)i], B[(size_t)(b - a)][(size_t)i + 1], c0, c1);
-        max_comp[b] = std::max(max_comp[b], c1 - c0);
-        for (int l = b - 1; l >= a; l--) {
-            const int v1 = std::min(c1, n[l + 1]);                     // valid coordinates of the computed range one level down
-            if (v1 <= c0) return -1;
-            const int need0 = std::min(std::max(ofs[l + 1][std::max(c0, 0)], 0), n[l] - 1);
-            const int need1 = std::min(std::max(ofs[l + 1][v1 - 1], 0) + 1, n[l] - 1) + 1;
-            const int o0 = B[(size_t)(l - a)][(size_t)i], o1 = B[(size_t)(l - a)][(size_t)i + 1];
-            c0 = o0 < o1 ? std::min(o0, need0) : need0;
-            if (align_own && o0 < o1) c0 = o0 - ((o0 - c0 + 3) & ~3);                // the owned part starts on a block boundary (c0 may be -1 .. -3)
-            c1 = c0 + (((o0 < o1 ? std::max(o1, need1) : need1) - c0 + 3) & ~3);     // whole 4x4 blocks from the range's first pixel on
-            out[(size_t)i * nl + (size_t)(l - a)] = make_int4(o0, o1, c0, c1);
-            max_comp[l] = std::max(max_comp[l], c1 - c0);
-        }
-    }
-    return nt;
-}
-
-// (re)plan for a frame shape; buffers stay those sized at create
+// (re)plan for a frame shape; buffers stay those sized at create.  Plan, upload, commit: the handle is written only after the last
+// step that can fail, so a refused shape leaves it planned for the shape it had.  A copy that fails may have left a device table
+// half rewritten, which no plan describes: the one write on that path drops the current shape, so the next call plans and uploads again.
 static int ensure_plan(orbx_extractor *h, int W, int H)
 {
     if (W == h->cur_w && H == h->cur_h) return ORBX_OK;
     if (W > h->max_w || H > h->max_h) return fail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", W, H, h->max_w, h->max_h);
-    OrbxPlan P;
+    ShapePlan S;
     std::string why;
-    int rc = make_plan(h, W, H, &P, &why);
+    const int rc = orbx_plan_shape(*h, h->max_plan, W, H, &S, &why);
     if (rc != ORBX_OK) return fail(rc, "frame %dx%d: %s", W, H, why.c_str());
-    const OrbxPlan &M = h->max_plan;
-    // keep the allocation layout of the max plan (offsets/capacities) so every shape fits
-    for (int l = 0; l < h->nlevels; l++) {
-        OrbxLevel &L = P.lv[l];
-        const OrbxLevel &X = M.lv[l];
-        if (L.cand_cap > X.cand_cap || L.list_cap > X.list_cap || L.arena_cap > X.arena_cap || L.w > X.w || L.h > X.h)
-            return fail(ORBX_E_SHAPE, "frame %dx%d level %d does not fit the workspace planned for %dx%d", W, H, l, h->max_w, h->max_h);
-        L.cand_off = X.cand_off; L.list_off = X.list_off; L.arena_off = X.arena_off;
-        if (L.nCols > 0) { L.cand_cap = X.cand_cap; L.arena_cap = X.arena_cap; }
+    {   // a shape change rewrites tables that kernels of an earlier call may still be reading -- on the handle's stream, its aux
+        // streams or a caller's stream (orbx_extract_batch_device): wait for the device, not only for h->stream (shape changes are rare)
+        std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
+        HIPCHK(hipDeviceSynchronize());
+        hipError_t e = hipSuccess;
+        auto up = [&e](void *dst, const void *src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
+        up(h->d_bands, S.bands.data(), S.bands.size() * sizeof(int4));
+        up(h->d_tiles, S.tiles.data(), S.tiles.size() * sizeof(int4));
+        up(h->d_cells, S.cells.data(), (size_t)S.plan.ncells * sizeof(uint32_t));
+        up(h->d_tab_i, S.tab_i.data(), S.tab_used * sizeof(int));
+        up(h->d_tab_s, S.tab_s.data(), S.tab_used * sizeof(short2));
+        if (e != hipSuccess) { h->cur_w = h->cur_h = 0; return fail(ORBX_E_HIP, "table upload for %dx%d: %s", W, H, hipGetErrorString(e)); }
     }
-    P.cand_frame = M.cand_frame; P.list_frame = M.list_frame; P.arena_frame = M.arena_frame; P.out_cap = M.out_cap;
-
-    std::vector<int> ti(h->tab_elems ? h->tab_elems : 1);
-    std::vector<short2> ts(h->tab_elems ? h->tab_elems : 1);
-    size_t e = 0;
-    size_t yofs_at[ORBX_MAX_LEVELS] = {}, xofs_at[ORBX_MAX_LEVELS] = {};
+    // commit: the plan with the device addresses filled in
+    h->plan = S.plan;
+    h->plan.cell_tab = h->d_cells;
     for (int l = 1; l < h->nlevels; l++) {
-        OrbxLevel &L = P.lv[l];
-        L.stride = (int)align_up(L.w, 64);
-        L.frame_stride = (long long)align_up((size_t)L.stride * L.h, 256);
-        L.base = h->d_pyr + h->pyr_level_off[l];
-        const OrbxLevel &S = P.lv[l - 1];
-        const size_t ex = align_up((size_t)L.w + 4, 4), ey = align_up((size_t)L.h + 4, 4);
-        plan_resize(S.w, S.h, L.w, L.h, &ti[e], &ts[e], &ti[e + ex], &ts[e + ex], &h->area2[l]);
-        for (size_t dy = (size_t)L.h; dy < ey; dy++) { ti[e + ex + dy] = ti[e + ex + L.h - 1]; ts[e + ex + dy] = ts[e + ex + L.h - 1]; }   // k_resize_linear_4x4 reads rows in fours
-        yofs_at[l] = e + ex; xofs_at[l] = e;
-        h->tabs[l].xofs = h->d_tab_i + e; h->tabs[l].alpha = h->d_tab_s + e;
-        h->tabs[l].yofs = h->d_tab_i + e + ex; h->tabs[l].beta = h->d_tab_s + e + ex;
-        e += ex + ey;
+        h->plan.lv[l].base = h->d_pyr + h->pyr_level_off[l];
+        h->tabs[l].xofs = h->d_tab_i + S.xofs_at[l]; h->tabs[l].alpha = h->d_tab_s + S.xofs_at[l];
+        h->tabs[l].yofs = h->d_tab_i + S.yofs_at[l]; h->tabs[l].beta = h->d_tab_s + S.yofs_at[l];
+        h->resize_mode[l] = S.resize_mode[l];
     }
-    if (P.ncells > h->cells_cap) return fail(ORBX_E_SHAPE, "frame %dx%d has more FAST cells than the workspace planned for %dx%d", W, H, h->max_w, h->max_h);
-    std::vector<uint32_t> cells((size_t)std::max(P.ncells, 1));
-    for (int l = 0; l < h->nlevels; l++) {
-        const OrbxLevel &L = P.lv[l];
-        if (L.nRows >= 4096 || L.nCols >= 4096) return fail(ORBX_E_SHAPE, "level %d has too many FAST cells", l);
-        for (int i = 0; i < L.nRows; i++)
-            for (int j = 0; j < L.nCols; j++) cells[(size_t)L.cell_begin + (size_t)i * L.nCols + j] = (uint32_t)l | ((uint32_t)i << 4) | ((uint32_t)j << 16);
-    }
-    // ---- fused upper levels: row-band ownership / footprint tables (k_resize_fused) ----
-    std::vector<int4> bands;
-    for (int v = 0; v < 2; v++) {
-        orbx_extractor::FusePlan &F = h->fuse[v];
-        F = orbx_extractor::FusePlan();
-        F.bh = v == 0 ? 16 : 8;
-        const int b = h->nlevels - 1;
-        for (int a = 1; h->fuse_on && b - a >= 2 && b < ORBX_FUSE_MAX; a++) {
-            bool fast = true;
-            for (int l = a + 1; l <= b; l++) fast = fast && resize_is_fast(h->area2[l]) && (P.lv[l].w + 3) / 4 <= 512;
-            if (!fast) continue;
-            const int nl = b - a + 1, nb = (P.lv[b].h + F.bh - 1) / F.bh;
-            std::vector<int4> t((size_t)nb * nl);
-            int need_rows[ORBX_MAX_LEVELS] = {};
-            for (int j = 0; j < nb; j++) {
-                int o0 = j * F.bh, o1 = std::min((j + 1) * F.bh, P.lv[b].h), n0 = o0, n1 = o1;
-                t[(size_t)j * nl + (b - a)] = make_int4(o0, o1, n0, n1);
-                need_rows[b] = std::max(need_rows[b], n1 - n0);
-                for (int l = b - 1; l >= a; l--) {
-                    const int *yo = &ti[yofs_at[l + 1]];
-                    const int hl = P.lv[l].h, hu = P.lv[l + 1].h;
-                    auto cl = [&](int v2) { return std::min(std::max(v2, 0), hl - 1); };
-                    const int p0 = o0 == 0 ? 0 : cl(yo[o0]), p1 = o1 == hu ? hl : cl(yo[o1]);
-                    const int q0 = std::min(cl(yo[n0]), p0), q1 = std::max(cl(yo[n1 - 1] + 1) + 1, p1);
-                    o0 = p0; o1 = p1; n0 = q0; n1 = q1;
-                    t[(size_t)j * nl + (l - a)] = make_int4(o0, o1, n0, n1);
-                    need_rows[l] = std::max(need_rows[l], n1 - n0);
-                }
-            }
-            int buf[2] = {0, 0};
-            for (int l = a + 1; l < b; l++) {
-                const int pitch = (int)align_up((size_t)P.lv[l].w + 12, 16);
-                buf[(l - a) & 1] = std::max(buf[(l - a) & 1], need_rows[l] * pitch);
-            }
-            int ysum = 0;
-            for (int l = a + 1; l <= b; l++) ysum += need_rows[l];
-            if (buf[0] + buf[1] > 64 * 1024 || ysum > ORBX_FUSE_YTAB) continue;      // too much for LDS from this level on: start the fusion one level up
-            if (bands.size() + t.size() > h->bands_cap) break;
-            F.ok = true; F.a = a; F.b = b; F.nbands = nb; F.buf0 = (int)align_up((size_t)buf[0], 16); F.lds = F.buf0 + (int)align_up((size_t)buf[1], 16) + 16;
-            F.off = bands.size();
-            bands.insert(bands.end(), t.begin(), t.end());
-            break;
-        }
-    }
-    // ---- fused upper levels, one wave per 2-D tile (k_resize_tiles) ----
-    std::vector<int4> tiles;
-    h->tile = orbx_extractor::TilePlan();
-    {
-        orbx_extractor::TilePlan &T = h->tile;
-        const int b = h->nlevels - 1, a = h->tile_a;
-        bool ok = a >= 1 && b - a >= 2 && b < ORBX_FUSE_MAX;
-        for (int l = a + 1; l <= b && ok; l++) ok = h->area2[l] == RESIZE_FAST6;
-        if (ok) {
-            int nw[ORBX_MAX_LEVELS], nh[ORBX_MAX_LEVELS], mcx[ORBX_MAX_LEVELS], mcy[ORBX_MAX_LEVELS];
-            const int *ox[ORBX_MAX_LEVELS] = {}, *oy[ORBX_MAX_LEVELS] = {};
-            for (int l = a; l <= b; l++) { nw[l] = P.lv[l].w; nh[l] = P.lv[l].h; if (l > a) { ox[l] = &ti[xofs_at[l]]; oy[l] = &ti[yofs_at[l]]; } }
-            std::vector<int4> tx, ty;
-            const int ntx = plan_tile_axis(a, b, h->tile_w, nw, ox, true, tx, mcx), nty = plan_tile_axis(a, b, h->tile_h, nh, oy, false, ty, mcy);
-            ok = ntx >= 1 && nty >= 1 && ntx <= 64 && ntx * nty < 4096 && tx.size() + ty.size() <= h->tiles_cap;
-            int off = 0;
-            for (int l = a + 1; l <= b && ok; l++) {                             // every fused level has its own region in the wave's LDS
-                ok = mcx[l] / 4 <= 64 && (mcx[l] / 4) * mcy[l] < 4096;           // the lane -> block / lane -> dword division table of the kernel
-                T.lds_off[l] = off;
-                off += (int)align_up((size_t)mcy[l] * mcx[l] + ORBX_TILE_SLACK, 16);
-            }
-            for (int l = a + 1; l <= b && ok; l++) { T.tab_off[l] = off; off += 8 * (mcx[l] + mcy[l]); }    // the tile's table slices (mcx, mcy: multiples of 4)
-            if (ok && off <= 60 * 1024) {
-                T.ok = true; T.a = a; T.b = b; T.ntx = ntx; T.nty = nty; T.lds = off;
-                T.offx = 0; T.offy = tx.size();
-                tiles = tx; tiles.insert(tiles.end(), ty.begin(), ty.end());
-            }
-        }
-    }
-    P.cell_tab = h->d_cells;
-    // a shape change rewrites tables that kernels of an earlier call may still be reading -- on the handle's stream, its aux
-    // streams or a caller's stream (orbx_extract_batch_device): wait for the device, not only for h->stream (shape changes are rare)
-    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
-    HIPCHK(hipDeviceSynchronize());
-    if (!bands.empty()) HIPCHK(hipMemcpy(h->d_bands, bands.data(), bands.size() * sizeof(int4), hipMemcpyHostToDevice));
-    if (!tiles.empty()) HIPCHK(hipMemcpy(h->d_tiles, tiles.data(), tiles.size() * sizeof(int4), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_cells, cells.data(), (size_t)P.ncells * sizeof(uint32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_tab_i, ti.data(), e * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->d_tab_s, ts.data(), e * sizeof(short2), hipMemcpyHostToDevice));
-    h->plan = P;
+    h->fuse[0] = S.fuse[0]; h->fuse[1] = S.fuse[1]; h->tile = S.tile;
     h->cur_w = W; h->cur_h = H;
     return ORBX_OK;
+}
+
+// what FuseLevel and TileLevel share
+template <class U> static void fill_level(U &u, const OrbxLevel &L, const ResizeTab &tab)
+{
+    u.base = L.base; u.w = L.w; u.h = L.h; u.stride = L.stride; u.frame = L.frame_stride; u.tab = tab;
+}
+// levels 1 .. last of nf frames, one launch per level
+static void launch_levels(const orbx_extractor *h, const OrbxPlan &P, int last, int nf, const uint8_t *src_end, hipStream_t s)
+{
+    for (int l = 1; l <= last; l++) orbx_launch_resize(P.lv[l - 1], P.lv[l], h->tabs[l], h->resize_mode[l], nf, l == 1 ? src_end : nullptr, s);
+}
+// build levels 1 .. L-1 of the nf frames of one sub-batch (P: its view of the plan) on stream s
+static void enqueue_pyramid(const orbx_extractor *h, const OrbxPlan &P, int nf, const uint8_t *src_end, hipStream_t s)
+{
+    // The upper levels in one launch -- for a FEW frames only.  The resize arithmetic is ~22 vector instructions per pixel
+    // and the per-level kernels of a large batch are bound by that, not by their launches (rocprofv3 + SQ_INSTS_VALU:
+    // 47 % VALU-busy over the six upper levels at 64 x 640 x 480); the fused kernel recomputes the band overlaps
+    // (+25 % pixels) and measured 70 us against 57 for the chain there.  With one frame the launches dominate and
+    // fusing wins (28.6 -> 24.6 us at 640 x 480).  ORBX_PYRAMID_FUSE=2 forces it for A/B measurements.
+    const FusePlan *F = nullptr;
+    const FusePlan *cand = h->fuse[1].ok ? &h->fuse[1] : (h->fuse[0].ok ? &h->fuse[0] : nullptr);
+    if (h->fuse_on == 2 && h->fuse[0].ok && (long long)h->fuse[0].nbands * nf >= 384) cand = &h->fuse[0];
+    if (cand && (h->fuse_on == 2 || (long long)nf * P.lv[cand->a + 1].w * P.lv[cand->a + 1].h <= 1200000)) F = cand;
+    // many frames: the upper levels as one wave per 2-D tile (k_resize_tiles); it takes precedence over the band kernel
+    const bool use_tiles = h->tile.ok && h->fuse_on != 2 && nf >= h->tile_min_frames;
+    if (use_tiles) F = nullptr;
+    launch_levels(h, P, use_tiles ? h->tile.a : (F ? F->a : h->nlevels - 1), nf, src_end, s);
+    if (use_tiles) {
+        TileArgs A;
+        memset(&A, 0, sizeof(A));
+        A.a = h->tile.a; A.b = h->tile.b; A.ntx = h->tile.ntx; A.nty = h->tile.nty;
+        for (int l = 0; l < ORBX_FUSE_MAX; l++) { A.lds_off[l] = h->tile.lds_off[l]; A.tab_off[l] = h->tile.tab_off[l]; }
+        A.xr = h->d_tiles + h->tile.offx; A.yr = h->d_tiles + h->tile.offy;
+        for (int l = A.a; l <= A.b; l++) fill_level(A.lv[l], P.lv[l], h->tabs[l]);
+        orbx_launch_resize_tiles(A, nf, (size_t)h->tile.lds, s);
+    }
+    if (F) {
+        FuseArgs A;
+        memset(&A, 0, sizeof(A));
+        A.a = F->a; A.b = F->b; A.bands = h->d_bands + F->off; A.nbands = F->nbands; A.buf0_bytes = F->buf0;
+        for (int l = F->a; l <= F->b; l++) {
+            FuseLevel &U = A.lv[l];
+            fill_level(U, P.lv[l], h->tabs[l]);
+            U.nbx = (U.w + 3) / 4;
+            U.rcp_nbx = U.nbx > 1 ? (uint32_t)((1ull << 32) / (unsigned)U.nbx + 1) : 0u;
+            U.pitch = (int)align_up((size_t)U.w + 12, 16);
+        }
+        orbx_launch_resize_fused(A, nf, (size_t)F->lds, s);
+    }
+}
+
+// Sub-batches on separate streams: the quadtree and the small pyramid levels are latency-bound (few, long workgroups), so one
+// half-batch's latency-bound kernels run beside the other half's VALU-bound ones.  Frames are independent, so a sub-batch is
+// only a pointer offset: frames [f0, f0 + nf) of the call, its stream, its views of the plan and of the workspace.
+struct SubBatch { int f0, nf; hipStream_t s; OrbxPlan plan; OrbxWork work; };
+static void make_sub_batches(const orbx_extractor *h, int nframes, int nsub, int work_frame0, hipStream_t s, SubBatch *sb)
+{
+    const OrbxPlan &P = h->plan;
+    for (int i = 0; i < nsub; i++) {
+        SubBatch &B = sb[i];
+        B.f0 = (int)((long long)nframes * i / nsub); B.nf = (int)((long long)nframes * (i + 1) / nsub) - B.f0;
+        B.s = i == 0 ? s : h->aux[i - 1];
+        B.plan = P;
+        B.work = h->work;
+        const long long o = (long long)work_frame0 + B.f0;
+        B.plan.lv[0].base = P.lv[0].base + (long long)B.f0 * P.lv[0].frame_stride;      // d_images is this call's first frame already
+        for (int l = 1; l < h->nlevels; l++) B.plan.lv[l].base = P.lv[l].base + o * P.lv[l].frame_stride;
+        B.work.cand += o * P.cand_frame; B.work.owner += o * P.cand_frame; B.work.arena += o * P.arena_frame;
+        B.work.sel += o * P.list_frame; B.work.nk += o * h->nlevels; B.work.ncand += o * h->nlevels; B.work.errflags += o;
+        B.work.cand_count += o * h->nlevels * ORBX_CNT_STRIDE;
+    }
 }
 
 // enqueue the whole pipeline for `nframes` frames already resident in HBM
@@ -632,9 +420,7 @@ static int enqueue(orbx_extractor *h, const uint8_t *d_images, int nframes, int 
     if (rc != ORBX_OK) return rc;
     OrbxPlan &P = h->plan;
     P.blur_mode = h->blur_mode;
-    P.lv[0].base = const_cast<uint8_t *>(d_images);
-    P.lv[0].stride = row_stride;
-    P.lv[0].frame_stride = frame_stride;
+    P.lv[0].base = const_cast<uint8_t *>(d_images); P.lv[0].stride = row_stride; P.lv[0].frame_stride = frame_stride;
     h->last_input = d_images; h->last_in_stride = row_stride; h->last_in_frame = frame_stride; h->last_batch = nframes;
 
     const bool prof = h->profiling == 1;          // mode 1 times one call in isolation; mode 2 only drops events into the stream
@@ -649,29 +435,12 @@ static int enqueue(orbx_extractor *h, const uint8_t *d_images, int nframes, int 
     if (d_images < h->d_input || d_images >= h->d_input + (size_t)h->max_batch * h->in_frame)   // the handle's own input block has slack
         src_end = d_images + (long long)(nframes - 1) * frame_stride + (long long)(H - 1) * row_stride + W;
 
-    // Sub-batches on separate streams: the quadtree and the small pyramid levels are latency-bound
-    // (few, long workgroups), so one half-batch's latency-bound kernels run beside the other half's
-    // VALU-bound ones.  Frames are independent, so a sub-batch is only a pointer offset.
-    int nsub = (h->profiling != 0 || nframes < 16) ? 1 : std::min(h->nsub, ORBX_MAX_SUB);
-    hipStream_t st[ORBX_MAX_SUB];
-    OrbxPlan sp[ORBX_MAX_SUB];
-    OrbxWork sw[ORBX_MAX_SUB];
-    int f0[ORBX_MAX_SUB + 1];
-    for (int i = 0; i <= nsub; i++) f0[i] = (int)((long long)nframes * i / nsub);
-    for (int i = 0; i < nsub; i++) {
-        st[i] = i == 0 ? s : h->aux[i - 1];
-        sp[i] = P;
-        sw[i] = h->work;
-        const long long o = (long long)work_frame0 + f0[i];
-        sp[i].lv[0].base = P.lv[0].base + (long long)f0[i] * P.lv[0].frame_stride;      // d_images is this call's first frame already
-        for (int l = 1; l < h->nlevels; l++) sp[i].lv[l].base = P.lv[l].base + o * P.lv[l].frame_stride;
-        sw[i].cand += o * P.cand_frame; sw[i].owner += o * P.cand_frame; sw[i].arena += o * P.arena_frame;
-        sw[i].sel += o * P.list_frame; sw[i].nk += o * h->nlevels; sw[i].ncand += o * h->nlevels; sw[i].errflags += o;
-        sw[i].cand_count += o * h->nlevels * ORBX_CNT_STRIDE;
-    }
+    const int nsub = (h->profiling != 0 || nframes < 16) ? 1 : std::min(h->nsub, ORBX_MAX_SUB);
+    SubBatch sb[ORBX_MAX_SUB];
+    make_sub_batches(h, nframes, nsub, work_frame0, s, sb);
     if (nsub > 1) {
         HIPCHK(hipEventRecord(h->ev_fork, s));
-        for (int i = 1; i < nsub; i++) HIPCHK(hipStreamWaitEvent(st[i], h->ev_fork, 0));
+        for (int i = 1; i < nsub; i++) HIPCHK(hipStreamWaitEvent(sb[i].s, h->ev_fork, 0));
     }
     if (pe) HIPCHK(hipEventRecord(pe[0], s));
     // FAST on level 0 needs only the input, so with one sub-batch the resize chain (seven small, latency-bound
@@ -681,77 +450,34 @@ static int enqueue(orbx_extractor *h, const uint8_t *d_images, int nframes, int 
         hipStream_t sa = h->aux[ORBX_MAX_SUB - 2];
         HIPCHK(hipEventRecord(h->ev_fork, s));
         HIPCHK(hipStreamWaitEvent(sa, h->ev_fork, 0));
-        for (int l = 1; l < h->nlevels; l++)
-            orbx_launch_resize(sp[0].lv[l - 1], sp[0].lv[l], h->tabs[l], h->area2[l], nframes, l == 1 ? src_end : nullptr, sa);
+        launch_levels(h, sb[0].plan, h->nlevels - 1, nframes, src_end, sa);
         HIPCHK(hipEventRecord(h->ev_join[ORBX_MAX_SUB - 2], sa));
-        orbx_launch_fast(sp[0], sw[0], nframes, 0, P.lv[1].cell_begin, s);
+        orbx_launch_fast(sb[0].plan, sb[0].work, nframes, 0, P.lv[1].cell_begin, s);
         HIPCHK(hipStreamWaitEvent(s, h->ev_join[ORBX_MAX_SUB - 2], 0));
-        orbx_launch_fast(sp[0], sw[0], nframes, P.lv[1].cell_begin, P.ncells, s);
+        orbx_launch_fast(sb[0].plan, sb[0].work, nframes, P.lv[1].cell_begin, P.ncells, s);
     } else {
-        for (int i = 0; i < nsub; i++) {
-            const int nf = f0[i + 1] - f0[i];
-            // The upper levels in one launch -- for a FEW frames only.  The resize arithmetic is ~22 vector instructions per pixel
-            // and the per-level kernels of a large batch are bound by that, not by their launches (rocprofv3 + SQ_INSTS_VALU:
-            // 47 % VALU-busy over the six upper levels at 64 x 640 x 480); the fused kernel recomputes the band overlaps
-            // (+25 % pixels) and measured 70 us against 57 for the chain there.  With one frame the launches dominate and
-            // fusing wins (28.6 -> 24.6 us at 640 x 480).  ORBX_PYRAMID_FUSE=2 forces it for A/B measurements.
-            const orbx_extractor::FusePlan *F = nullptr;
-            const orbx_extractor::FusePlan *cand = h->fuse[1].ok ? &h->fuse[1] : (h->fuse[0].ok ? &h->fuse[0] : nullptr);
-            if (h->fuse_on == 2 && h->fuse[0].ok && (long long)h->fuse[0].nbands * nf >= 384) cand = &h->fuse[0];
-            if (cand && (h->fuse_on == 2 || (long long)nf * sp[i].lv[cand->a + 1].w * sp[i].lv[cand->a + 1].h <= 1200000)) F = cand;
-            // many frames: the upper levels as one wave per 2-D tile (k_resize_tiles); it takes precedence over the band kernel
-            const bool use_tiles = h->tile.ok && h->fuse_on != 2 && nf >= h->tile_min_frames;
-            if (use_tiles) F = nullptr;
-            const int last_single = use_tiles ? h->tile.a : (F ? F->a : h->nlevels - 1);
-            for (int l = 1; l <= last_single; l++)
-                orbx_launch_resize(sp[i].lv[l - 1], sp[i].lv[l], h->tabs[l], h->area2[l], nf, l == 1 ? src_end : nullptr, st[i]);
-            if (use_tiles) {
-                TileArgs A;
-                memset(&A, 0, sizeof(A));
-                A.a = h->tile.a; A.b = h->tile.b; A.ntx = h->tile.ntx; A.nty = h->tile.nty;
-                for (int l = 0; l < ORBX_FUSE_MAX; l++) { A.lds_off[l] = h->tile.lds_off[l]; A.tab_off[l] = h->tile.tab_off[l]; }
-                A.xr = h->d_tiles + h->tile.offx; A.yr = h->d_tiles + h->tile.offy;
-                for (int l = A.a; l <= A.b; l++) {
-                    const OrbxLevel &L = sp[i].lv[l];
-                    TileLevel &U = A.lv[l];
-                    U.base = L.base; U.w = L.w; U.h = L.h; U.stride = L.stride; U.frame = L.frame_stride; U.tab = h->tabs[l];
-                }
-                orbx_launch_resize_tiles(A, nf, (size_t)h->tile.lds, st[i]);
-            }
-            if (F) {
-                FuseArgs A;
-                memset(&A, 0, sizeof(A));
-                A.a = F->a; A.b = F->b; A.bands = h->d_bands + F->off; A.nbands = F->nbands; A.buf0_bytes = F->buf0;
-                for (int l = F->a; l <= F->b; l++) {
-                    const OrbxLevel &L = sp[i].lv[l];
-                    FuseLevel &U = A.lv[l];
-                    U.base = L.base; U.w = L.w; U.h = L.h; U.stride = L.stride; U.frame = L.frame_stride; U.tab = h->tabs[l];
-                    U.nbx = (L.w + 3) / 4;
-                    U.rcp_nbx = U.nbx > 1 ? (uint32_t)((1ull << 32) / (unsigned)U.nbx + 1) : 0u;
-                    U.pitch = (int)align_up((size_t)L.w + 12, 16);
-                }
-                orbx_launch_resize_fused(A, nf, (size_t)F->lds, st[i]);
-            }
-        }
+        for (int i = 0; i < nsub; i++) enqueue_pyramid(h, sb[i].plan, sb[i].nf, src_end, sb[i].s);
         if (pe) HIPCHK(hipEventRecord(pe[1], s));
-        for (int i = 0; i < nsub; i++) orbx_launch_fast(sp[i], sw[i], f0[i + 1] - f0[i], 0, P.ncells, st[i]);
+        for (int i = 0; i < nsub; i++) orbx_launch_fast(sb[i].plan, sb[i].work, sb[i].nf, 0, P.ncells, sb[i].s);
     }
     if (pe) HIPCHK(hipEventRecord(pe[2], s));
-    {   // dynamic LDS of the launch: the list arrays for the handle's largest list + this shape's fast-forward tables
-        size_t lds = orbx_octree_lds_bytes(h->oct_cap_max, P.oct_ft, P.oct_map);
-        if (lds > 150 * 1024) {              // no room for the tables beside very long lists: plain passes
-            for (int i = 0; i < nsub; i++) { sp[i].oct_ft = 0; sp[i].oct_map = 0; for (int l = 0; l < h->nlevels; l++) sp[i].lv[l].fastD = 0; }
-            lds = orbx_octree_lds_bytes(h->oct_cap_max, 0, 0);
-        }
-        for (int i = 0; i < nsub; i++) { sp[i].oct_cap_max = h->oct_cap_max; orbx_launch_octree(sp[i], sw[i], f0[i + 1] - f0[i], lds, st[i]); }
+    // dynamic LDS of the quadtree launch: the list arrays for the handle's largest list + this shape's fast-forward tables
+    size_t lds = orbx_octree_lds_bytes(h->oct_cap_max, P.oct_ft, P.oct_map);
+    const bool plain = lds > 150 * 1024;         // no room for the tables beside very long lists: plain passes
+    if (plain) lds = orbx_octree_lds_bytes(h->oct_cap_max, 0, 0);
+    for (int i = 0; i < nsub; i++) {
+        OrbxPlan &Q = sb[i].plan;
+        if (plain) { Q.oct_ft = 0; Q.oct_map = 0; for (int l = 0; l < h->nlevels; l++) Q.lv[l].fastD = 0; }
+        Q.oct_cap_max = h->oct_cap_max;
+        orbx_launch_octree(Q, sb[i].work, sb[i].nf, lds, sb[i].s);
     }
     if (pe) HIPCHK(hipEventRecord(pe[3], s));
     for (int i = 0; i < nsub; i++)
-        orbx_launch_describe(sp[i], sw[i], f0[i + 1] - f0[i], d_kps + (long long)f0[i] * P.out_cap,
-                             d_desc + (long long)f0[i] * P.out_cap * 32, d_counts + f0[i], d_status + f0[i], st[i]);
+        orbx_launch_describe(sb[i].plan, sb[i].work, sb[i].nf, d_kps + (long long)sb[i].f0 * P.out_cap,
+                             d_desc + (long long)sb[i].f0 * P.out_cap * 32, d_counts + sb[i].f0, d_status + sb[i].f0, sb[i].s);
     if (pe) HIPCHK(hipEventRecord(pe[4], s));
     for (int i = 1; i < nsub; i++) {
-        HIPCHK(hipEventRecord(h->ev_join[i - 1], st[i]));
+        HIPCHK(hipEventRecord(h->ev_join[i - 1], sb[i].s));
         HIPCHK(hipStreamWaitEvent(s, h->ev_join[i - 1], 0));
     }
     HIPCHK(hipGetLastError());
@@ -844,6 +570,24 @@ static void stage_frames(orbx_extractor *h, const uint8_t *images, int k0, int k
     else for (int u = 0; u < n; u++) unit(u);
 }
 
+static const char *device_status_text(int st)
+{
+    return st == ORBX_E_CAND_OVERFLOW ? "FAST candidate buffer overflow" : st == ORBX_E_TREE_OVERFLOW ? "quadtree arena overflow" : "capacity";
+}
+// the staging outputs of the first nframes frames, device to pinned host: the whole block in one copy when it is full
+static int download_outputs(orbx_extractor *h, int nframes, hipStream_t s)
+{
+    if (nframes == h->max_batch) {
+        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_bytes, hipMemcpyDeviceToHost, s));
+    } else {
+        const size_t n = (size_t)h->max_plan.out_cap * nframes;
+        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_hdr, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h->h_kps, h->d_kps, sizeof(orbx_keypoint) * n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h->h_desc, h->d_desc, 32 * n, hipMemcpyDeviceToHost, s));
+    }
+    return ORBX_OK;
+}
+
 // hand frames [k0, k1) over to the caller; hc / hs / hk / hd = counts, status, keypoints, descriptors of frame k0 in pinned memory
 static int deliver_batch(orbx_extractor *h, int k0, int k1, orbx_keypoint *keypoints, uint8_t *descriptors, int cap, int *counts,
                          const int32_t *hc, const int32_t *hs, const orbx_keypoint *hk, const uint8_t *hd)
@@ -851,10 +595,7 @@ static int deliver_batch(orbx_extractor *h, int k0, int k1, orbx_keypoint *keypo
     const int ocap = h->max_plan.out_cap;
     for (int k = k0; k < k1; k++) {
         const int st = hs[k - k0];
-        if (st != ORBX_OK)
-            return fail(st, "frame %d: device status %d (%s)", k, st,
-                        st == ORBX_E_CAND_OVERFLOW ? "FAST candidate buffer overflow" :
-                        st == ORBX_E_TREE_OVERFLOW ? "quadtree arena overflow" : "capacity");
+        if (st != ORBX_OK) return fail(st, "frame %d: device status %d (%s)", k, st, device_status_text(st));
         if (hc[k - k0] > cap) return fail(ORBX_E_CAPACITY, "frame %d produced %d keypoints, caller capacity %d (use orbx_capacity())", k, hc[k - k0], cap);
     }
     auto unit = [&](int u) {
@@ -874,20 +615,13 @@ static int extract_batch_simple(orbx_extractor *h, const uint8_t *images, int nf
                                 size_t frame_stride, orbx_keypoint *keypoints, uint8_t *descriptors, int cap, int *counts)
 {
     hipStream_t s = h->stream;
-    const int ocap = h->max_plan.out_cap;
     stage_frames(h, images, 0, nframes, width, height, row_stride, frame_stride);
     HIPCHK(hipMemcpyAsync(h->d_input, h->h_in, (size_t)(nframes - 1) * h->in_frame + (size_t)h->in_stride * height,
                           hipMemcpyHostToDevice, s));
     int rc = enqueue(h, h->d_input, nframes, width, height, h->in_stride, (long long)h->in_frame, h->d_kps, h->d_desc,
                      h->d_counts, h->d_status, s);
+    if (rc == ORBX_OK) rc = download_outputs(h, nframes, s);
     if (rc != ORBX_OK) return rc;
-    if (nframes == h->max_batch) {
-        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_bytes, hipMemcpyDeviceToHost, s));
-    } else {
-        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_hdr, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h->h_kps, h->d_kps, sizeof(orbx_keypoint) * (size_t)ocap * nframes, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h->h_desc, h->d_desc, (size_t)32 * ocap * nframes, hipMemcpyDeviceToHost, s));
-    }
     HIPCHK(hipStreamSynchronize(s));
     rc = finish_profile(h);
     if (rc != ORBX_OK) return rc;
@@ -953,8 +687,7 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
     // chunk boundaries: a half-size first chunk (the pipeline starts sooner) and a half-size last one (the tail that nothing hides
     // is shorter) around full-size ones
     std::vector<int> cut(1, 0);
-    static const bool equal_chunks = getenv("ORBX_BATCH_EQUAL") != nullptr;   // A/B switch
-    if (nframes >= 3 * chunk && chunk >= 2 && !equal_chunks) {
+    if (nframes >= 3 * chunk && chunk >= 2 && !batch_equal_chunks()) {
         cut.push_back(chunk / 2);
         while (nframes - cut.back() > chunk + chunk / 2) cut.push_back(cut.back() + chunk);
         if (nframes - cut.back() > chunk / 2) cut.push_back(nframes - chunk / 2);
@@ -974,32 +707,26 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
         if (off > h->out_bytes) return fail(ORBX_E_INVALID, "internal: chunk output blocks exceed the staging block");
     }
     hipStream_t st[3] = {h->stream, h->aux[0], h->aux[2]};
-    static const int nst = [] { const char *e = getenv("ORBX_BATCH_STREAMS"); const int v = e ? atoi(e) : 3; return v < 1 ? 1 : v > 3 ? 3 : v; }();   // compute streams the chunks rotate over
+    const int nst = batch_streams();
     const bool have_graphs = !h->bg_off && h->bg_w == width && h->bg_h == height && h->bg_n == nframes && h->bg_chunk == chunk && (int)h->bgraph.size() == nch;
     if (!have_graphs && !h->bg_off) {                       // (re)build the per-chunk graphs for this shape
         for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
         h->bgraph.assign(nch, nullptr);
         bool ok = true;
-        std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
+        std::lock_guard<std::recursive_mutex> lk_(capture_mutex());   // once around all chunk captures (capture_graph() takes it again: recursive)
         for (int c = 0; c < nch && ok; c++) {
             hipStream_t s = st[c % nst];
-            ok = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
-            if (!ok) break;
-            const int rc = enqueue_chunk(h, c, cut[c], cut[c + 1], width, height, s);
-            hipGraph_t g = nullptr;
-            const hipError_t e = hipStreamEndCapture(s, &g);
-            ok = rc == ORBX_OK && e == hipSuccess && g && hipGraphInstantiate(&h->bgraph[c], g, nullptr, nullptr, 0) == hipSuccess;
-            if (g) (void)hipGraphDestroy(g);
+            h->bgraph[c] = capture_graph(s, [&] { return enqueue_chunk(h, c, cut[c], cut[c + 1], width, height, s) == ORBX_OK; });
+            ok = h->bgraph[c] != nullptr;
         }
         if (ok) { h->bg_w = width; h->bg_h = height; h->bg_n = nframes; h->bg_chunk = chunk; }
         else {
-            (void)hipGetLastError();
             for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
             h->bgraph.clear(); h->bg_off = true; h->bg_w = h->bg_h = h->bg_n = 0;
         }
     }
     const bool graphs = !h->bg_off && (int)h->bgraph.size() == nch;
-    static const bool trace = getenv("ORBX_BATCH_TRACE") != nullptr;      // host-side time split of a call, to stderr
+    const bool trace = batch_trace();
     auto now = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     // uploads go back to back on a stream of their own (on a chunk's compute stream the upload of chunk c + 2 would wait for
     // chunk c's kernels and downloads); each chunk's kernels wait for its own upload only
@@ -1009,8 +736,7 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
         HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming)); h->ev_up.push_back(a);
         HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableTiming)); h->ev_done.push_back(b);
     }
-    // page-locked caller memory is uploaded where it lies (ORBX_BATCH_PINNED=0 keeps the staging copy: A/B switch)
-    static const bool pinned_ok = [] { const char *e = getenv("ORBX_BATCH_PINNED"); return !e || atoi(e) != 0; }();
+    const bool pinned_ok = batch_pinned_ok();
     // the answer for one buffer is remembered (a capture pipeline hands over the same page-locked block again and again; should it
     // have been unregistered meanwhile, the copies below are still correct -- the runtime stages them -- only slower)
     const size_t frame_bytes = (size_t)(height - 1) * row_stride + width;
@@ -1060,6 +786,13 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
     return rcd;
 }
 
+// one staged frame: upload, then the pipeline
+static int upload_and_enqueue_one(orbx_extractor *h, int w, int hgt, hipStream_t s)
+{
+    HIPCHK(hipMemcpyAsync(h->d_input, h->h_in, (size_t)h->in_stride * hgt, hipMemcpyHostToDevice, s));
+    return enqueue(h, h->d_input, 1, w, hgt, h->in_stride, (long long)h->in_frame, h->d_kps, h->d_desc, h->d_counts, h->d_status, s);
+}
+
 extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int width, int height, int stride)
 {
     if (!h) return fail(ORBX_E_INVALID, "NULL handle");
@@ -1075,52 +808,26 @@ extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int w
     // Same shape as the last call, nothing to clear, no profiling: the upload, the kernels and the download are one HIP graph
     // (captured on the second call of a shape, replayed from then on); every pointer in it belongs to the handle.
     const bool graphable = !h->graph_off && h->profiling == 0 && h->max_batch == 1 && !h->need_clear && width == h->cur_w && height == h->cur_h;
-    if (graphable && h->graph_exec && h->graph_w == width && h->graph_h == height) {
-        HIPCHK(hipGraphLaunch(h->graph_exec, s));
-        h->inflight = 1; h->inflight_frames = 1;
-        return ORBX_OK;
-    }
-    bool capturing = false;
-    std::unique_lock<std::recursive_mutex> caplk(capture_mutex(), std::defer_lock);   // see capture_mutex()
-    if (graphable && h->graph_seen_w == width && h->graph_seen_h == height) {
-        if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-        caplk.lock();
-        capturing = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess;
-        if (!capturing) { (void)hipGetLastError(); caplk.unlock(); if (++h->graph_fails >= 3) h->graph_off = true; }
-    }
-    h->graph_seen_w = width; h->graph_seen_h = height;
-    int rc = ORBX_OK;
-    hipError_t e1 = hipMemcpyAsync(h->d_input, h->h_in, (size_t)h->in_stride * height, hipMemcpyHostToDevice, s);
-    if (e1 == hipSuccess) rc = enqueue(h, h->d_input, 1, width, height, h->in_stride, (long long)h->in_frame, h->d_kps, h->d_desc, h->d_counts, h->d_status, s);
-    if (capturing) {
-        hipError_t e2 = (e1 == hipSuccess && rc == ORBX_OK) ? hipMemcpyAsync(h->h_out, h->d_out, h->out_bytes, hipMemcpyDeviceToHost, s) : hipErrorUnknown;
-        hipGraph_t g = nullptr;
-        hipError_t e3 = hipStreamEndCapture(s, &g);
-        if (e2 == hipSuccess && e3 == hipSuccess && g && hipGraphInstantiate(&h->graph_exec, g, nullptr, nullptr, 0) == hipSuccess) {
-            h->graph_w = width; h->graph_h = height;
-        } else {
-            // a capture that failed or was invalidated (another thread's synchronous call) is not an error of this call: nothing has
-            // run yet, the call runs plainly below; the capture is tried again on a later call, three times at most
-            h->graph_exec = nullptr; (void)hipGetLastError();
-            if (++h->graph_fails >= 3) h->graph_off = true; else h->graph_seen_w = h->graph_seen_h = 0;
+    auto have_graph = [&] { return graphable && h->graph_exec && h->graph_w == width && h->graph_h == height; };
+    if (!have_graph()) {
+        const bool second = graphable && h->graph_seen_w == width && h->graph_seen_h == height;
+        h->graph_seen_w = width; h->graph_seen_h = height;
+        if (second) {
+            if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+            h->graph_exec = capture_graph(s, [&] { return upload_and_enqueue_one(h, width, height, s) == ORBX_OK && download_outputs(h, 1, s) == ORBX_OK; });
+            // a capture that failed or was invalidated (another thread's synchronous call) is not an error of this call; the capture
+            // is tried again on a later call, three times at most
+            if (h->graph_exec) { h->graph_w = width; h->graph_h = height; }
+            else if (++h->graph_fails >= 3) h->graph_off = true;
+            else h->graph_seen_w = h->graph_seen_h = 0;
         }
-        if (g) (void)hipGraphDestroy(g);
-        caplk.unlock();
-        // nothing ran during the capture: run this call now, through the graph or (if that failed) plainly
-        if (h->graph_exec) { HIPCHK(hipGraphLaunch(h->graph_exec, s)); h->inflight = 1; h->inflight_frames = 1; return ORBX_OK; }
-        e1 = hipMemcpyAsync(h->d_input, h->h_in, (size_t)h->in_stride * height, hipMemcpyHostToDevice, s);
-        rc = ORBX_OK;
-        if (e1 == hipSuccess) rc = enqueue(h, h->d_input, 1, width, height, h->in_stride, (long long)h->in_frame, h->d_kps, h->d_desc, h->d_counts, h->d_status, s);
     }
-    if (e1 != hipSuccess) return fail(ORBX_E_HIP, "hipMemcpyAsync: %s", hipGetErrorString(e1));
-    if (rc != ORBX_OK) return rc;
-    const int ocap = h->max_plan.out_cap;
-    if (h->max_batch == 1) {
-        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_bytes, hipMemcpyDeviceToHost, s));
-    } else {
-        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_hdr, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h->h_kps, h->d_kps, sizeof(orbx_keypoint) * (size_t)ocap, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(h->h_desc, h->d_desc, (size_t)32 * ocap, hipMemcpyDeviceToHost, s));
+    // nothing ran during a capture: run this call now, through the graph or (without one) plainly
+    if (have_graph()) HIPCHK(hipGraphLaunch(h->graph_exec, s));
+    else {
+        int rc = upload_and_enqueue_one(h, width, height, s);
+        if (rc == ORBX_OK) rc = download_outputs(h, 1, s);
+        if (rc != ORBX_OK) return rc;
     }
     h->inflight = 1; h->inflight_frames = 1;
     return ORBX_OK;
@@ -1138,10 +845,7 @@ extern "C" int orbx_extract_end(orbx_extractor *h, orbx_keypoint *keypoints, uin
     HIPCHK(hipStreamSynchronize(h->stream));
     int rc = finish_profile(h);
     if (rc != ORBX_OK) return rc;
-    if (h->h_status[0] != ORBX_OK)
-        return fail(h->h_status[0], "device status %d (%s)", h->h_status[0],
-                    h->h_status[0] == ORBX_E_CAND_OVERFLOW ? "FAST candidate buffer overflow" :
-                    h->h_status[0] == ORBX_E_TREE_OVERFLOW ? "quadtree arena overflow" : "capacity");
+    if (h->h_status[0] != ORBX_OK) return fail(h->h_status[0], "device status %d (%s)", h->h_status[0], device_status_text(h->h_status[0]));
     const int cnt = h->h_counts[0];
     if (cnt > cap) return fail(ORBX_E_CAPACITY, "%d keypoints, caller capacity %d (use orbx_capacity())", cnt, cap);
     memcpy(keypoints, h->h_kps, sizeof(orbx_keypoint) * cnt);
@@ -1221,43 +925,18 @@ static inline int reflect101_host(int p, int len)
     return p;
 }
 
-extern "C" int orbx_download_level(orbx_extractor *h, int frame, int level, uint8_t *dst, int dst_stride, int border)
-{
-    if (!h || !dst || level < 0 || level >= h->nlevels || h->cur_w == 0 || frame < 0 || frame >= h->last_batch || border < 0)
-        return fail(ORBX_E_INVALID, "bad download_level argument");
-    HIPCHK(hipSetDevice(h->device));
-    OrbxLevel L = h->plan.lv[level];
-    if (level == 0) { L.base = const_cast<uint8_t *>(h->last_input); L.stride = h->last_in_stride; L.frame_stride = h->last_in_frame; }
-    if (dst_stride < L.w + 2 * border) return fail(ORBX_E_INVALID, "dst_stride too small");
-    HIPCHK(hipDeviceSynchronize());   // the last call may have run on a caller stream and the aux streams
-    uint8_t *interior = dst + (size_t)border * dst_stride + border;
-    HIPCHK(hipMemcpy2D(interior, dst_stride, L.base + (size_t)frame * L.frame_stride, L.stride, L.w, L.h, hipMemcpyDeviceToHost));
-    if (border > 0) {   // copyMakeBorder(..., BORDER_REFLECT_101), :1127-1133
-        for (int y = -border; y < L.h + border; y++) {
-            const uint8_t *srow = interior + (ptrdiff_t)reflect101_host(y, L.h) * dst_stride;
-            uint8_t *drow = interior + (ptrdiff_t)y * dst_stride;
-            if (y < 0 || y >= L.h) memcpy(drow, srow, (size_t)L.w);
-            for (int x = 1; x <= border; x++) {
-                drow[-x] = srow[reflect101_host(-x, L.w)];
-                drow[L.w - 1 + x] = srow[reflect101_host(L.w - 1 + x, L.w)];
-            }
-        }
-    }
-    return ORBX_OK;
-}
-
-// Every level of frame `frame` of the last call in one go: one asynchronous copy per level into a page-locked staging block, ONE
-// synchronisation, then the rows are laid out in the caller's buffers and the reflect-101 border is rebuilt on the host
+// Levels [l0, l1) of frame `frame` of the last call into dst[l - l0]: one asynchronous copy per level into a page-locked staging block,
+// ONE synchronisation, then the rows are laid out in the caller's buffers and the reflect-101 border is rebuilt on the host
 // (src/ORBextractor.cc:1115-1133).  This is what keeps ORBextractor::mvImagePyramid valid after every operator() in the adapter.
-extern "C" int orbx_download_pyramid(orbx_extractor *h, int frame, uint8_t *const *dst, const int *dst_stride, int border)
+static int download_levels(orbx_extractor *h, int frame, int l0, int l1, uint8_t *const *dst, const int *dst_stride, int border)
 {
-    if (!h || !dst || !dst_stride || h->cur_w == 0 || frame < 0 || frame >= h->last_batch || border < 0)
-        return fail(ORBX_E_INVALID, "bad download_pyramid argument");
+    if (!dst || !dst_stride || l0 < 0 || l1 > h->nlevels || h->cur_w == 0 || frame < 0 || frame >= h->last_batch || border < 0)
+        return fail(ORBX_E_INVALID, "bad pyramid download argument");
     HIPCHK(hipSetDevice(h->device));
     size_t need = 0, off[ORBX_MAX_LEVELS];
-    for (int l = 0; l < h->nlevels; l++) {
+    for (int l = l0; l < l1; l++) {
         const OrbxLevel &L = h->plan.lv[l];
-        if (!dst[l] || dst_stride[l] < L.w + 2 * border) return fail(ORBX_E_INVALID, "level %d: NULL buffer or dst_stride too small", l);
+        if (!dst[l - l0] || dst_stride[l - l0] < L.w + 2 * border) return fail(ORBX_E_INVALID, "level %d: NULL buffer or dst_stride too small", l);
         off[l] = need;
         need += ((size_t)L.w * L.h + 255) & ~(size_t)255;
     }
@@ -1267,16 +946,16 @@ extern "C" int orbx_download_pyramid(orbx_extractor *h, int frame, uint8_t *cons
         h->h_pyr_bytes = need + need / 4;
     }
     HIPCHK(hipDeviceSynchronize());   // the last call may have run on a caller stream and the aux streams
-    for (int l = 0; l < h->nlevels; l++) {
+    for (int l = l0; l < l1; l++) {
         OrbxLevel L = h->plan.lv[l];
         if (l == 0) { L.base = const_cast<uint8_t *>(h->last_input); L.stride = h->last_in_stride; L.frame_stride = h->last_in_frame; }
         HIPCHK(hipMemcpy2DAsync(h->h_pyr + off[l], (size_t)L.w, L.base + (size_t)frame * L.frame_stride, L.stride, L.w, L.h, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
-    for (int l = 0; l < h->nlevels; l++) {
+    for (int l = l0; l < l1; l++) {
         const OrbxLevel &L = h->plan.lv[l];
-        const int ds = dst_stride[l];
-        uint8_t *interior = dst[l] + (size_t)border * ds + border;
+        const int ds = dst_stride[l - l0];
+        uint8_t *interior = dst[l - l0] + (size_t)border * ds + border;
         for (int y = 0; y < L.h; y++) memcpy(interior + (size_t)y * ds, h->h_pyr + off[l] + (size_t)y * L.w, (size_t)L.w);
         if (border > 0) {             // copyMakeBorder(..., BORDER_REFLECT_101), :1127-1133
             for (int y = 0; y < L.h; y++) {
@@ -1290,6 +969,16 @@ extern "C" int orbx_download_pyramid(orbx_extractor *h, int frame, uint8_t *cons
         }
     }
     return ORBX_OK;
+}
+extern "C" int orbx_download_level(orbx_extractor *h, int frame, int level, uint8_t *dst, int dst_stride, int border)
+{
+    if (!h || level < 0 || level >= h->nlevels) return fail(ORBX_E_INVALID, "bad download_level argument");
+    return download_levels(h, frame, level, level + 1, &dst, &dst_stride, border);
+}
+extern "C" int orbx_download_pyramid(orbx_extractor *h, int frame, uint8_t *const *dst, const int *dst_stride, int border)
+{
+    if (!h) return fail(ORBX_E_INVALID, "bad download_pyramid argument");
+    return download_levels(h, frame, 0, h->nlevels, dst, dst_stride, border);
 }
 
 extern "C" int orbx_download_candidates(orbx_extractor *h, int frame, int level, int32_t *xyr, int cap)

@@ -1,4 +1,4 @@
-// orbx_internal.h -- shared between the host-side planner (orbx_capi.hip) and the gfx950 kernels.
+// orbx_internal.h -- shared between the host side (the planner orbx_plan.hip, the handle and C ABI orbx_capi.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -19,6 +19,7 @@
 
 #ifndef OCT_THREADS
 #define OCT_THREADS 512
+#endif
 
 #ifdef __HIPCC__
 // base + number of set bits of mask below this lane: v_mbcnt_lo + v_mbcnt_hi (two instructions, base folded in)
@@ -64,7 +65,6 @@ __device__ __forceinline__ int orbx_lane_prev(int v) { return __builtin_amdgcn_u
 #define ORBX_TRACE_FLUSH(SYM) do { } while (0)
 #endif
 
-#endif
 #define OCT_ID_MASK 0x3FFFFFFFu
 
 #define DESC_R 18             // rotated rBRIEF sample radius (max |p| = 18.38)

@@ -521,3 +521,45 @@ def test_batch_extractor_through_chunk_graphs(orbx, synth):
     batch(4, 1, t26); batch(4, 1, t26)
     ex.set_blur_rounding(0)
     batch(4, 0, t26)
+
+
+@pytest.mark.gpu
+def test_shape_refused_by_the_planner_then_the_old_shape(orbx, synth):
+    """640x481 above is refused before planning; 120x400 is refused inside it (level 0's box is 88 wide and 368 high, the quadtree
+    root count rounds to 0).  The handle must stay planned for 322x241: its tables, its resize modes, its graph."""
+    ex = orbx.ORBextractor(1000, max_width=640, max_height=480)
+    seed = iter(range(500, 600))
+    img = lambda w, h: synth.texture(next(seed), w, h)
+    for _ in range(3):                                          # plain, capture, replay
+        a = img(322, 241); _same(ex(a), a, 0)
+    _err(orbx, orbx.ORBX_E_SHAPE, ex, img(120, 400))
+    for _ in range(2):
+        a = img(322, 241); _same(ex(a), a, 0)
+    a = img(640, 480); _same(ex(a), a, 0)
+
+
+@pytest.mark.gpu
+def test_batch_extractor_across_a_shape_change(orbx, synth):
+    """The repeat of each shape replays the chunk graphs captured by the call before it; a shape change rewrites the tables while
+    chunk graphs of the other shape exist."""
+    ex = orbx.ORBextractor(1000, max_width=640, max_height=480, max_batch=4)
+    ex.set_batch_chunk(2)
+    seed = iter(range(600, 700))
+    for w, h in ((322, 241), (322, 241), (640, 480), (640, 480), (322, 241), (322, 241)):
+        imgs = np.stack([synth.texture(next(seed), w, h) for _ in range(4)])
+        for got, a in zip(ex.extract_batch(imgs), imgs):
+            _same(got, a, 0)
+
+
+@pytest.mark.gpu
+def test_tile_switch_across_a_shape_change(orbx, synth, monkeypatch):
+    """ORBX_PYRAMID_TILES on one handle through 640x480, 322x241, 640x480: a tile plan left over from the other shape would show
+    in the upper pyramid levels."""
+    monkeypatch.setenv("ORBX_PYRAMID_TILES", "2,32,32,1")
+    ex = orbx.ORBextractor(1000, max_width=640, max_height=480)
+    opyr = O.Extractor(1000)
+    for i, (w, h) in enumerate(((640, 480), (322, 241), (640, 480))):
+        a = synth.texture(700 + i, w, h)
+        ex(a)
+        for l, (got, want) in enumerate(zip(ex.image_pyramid(), opyr.pyramid(a))):
+            assert np.array_equal(got, want), "call %d (%dx%d): level %d differs" % (i, w, h, l)
