@@ -61,6 +61,17 @@ enum {
 };
 
 /*
+ * Pixel format of the frames a handle is given.  The reference's callers convert every camera frame to grey on the host before the
+ * extractor sees it (cvtColor in Tracking::GrabImage*, src/Tracking.cc:172-199, 212-227, 242-257); a handle set to a colour format
+ * takes the frame as the camera delivers it and converts it on the GPU, with OpenCV 3.1.0's portable 8-bit RGB2Gray arithmetic:
+ * grey = (4899 R + 9617 G + 1868 B + 8192) >> 14, alpha ignored.  The format is a property of the handle: EVERY entry point that
+ * takes frames (orbx_extract, orbx_extract_begin, orbx_extract_batch, orbx_extract_batch_multi, orbx_extract_batch_device) reads
+ * them in it.  width and height stay in pixels, row_stride and frame_stride in bytes, and row_stride >= width * channels.  For a
+ * colour handle, level 0 of the pyramid is the handle's own grey plane on every route.
+ */
+typedef enum { ORBX_FMT_GRAY8 = 0, ORBX_FMT_BGR8 = 1, ORBX_FMT_RGB8 = 2, ORBX_FMT_BGRA8 = 3, ORBX_FMT_RGBA8 = 4 } orbx_format;
+
+/*
  * ORBextractor::ORBextractor (include/ORBextractor.h:51).  `device` is the HIP device ordinal;
  * max_width/max_height/max_batch size the workspace (pyramids, candidate and tree buffers) once.
  */
@@ -69,6 +80,13 @@ int orbx_create(orbx_extractor **out, int nfeatures, float scale_factor, int nle
                 int max_width, int max_height, int max_batch);
 void orbx_destroy(orbx_extractor *h);
 int orbx_set_option(orbx_extractor *h, int option, int value);
+/* The handle's input format (an orbx_format; default ORBX_FMT_GRAY8).  ORBX_E_INVALID for a NULL handle, an unknown value, or while
+ * an orbx_extract_begin call is in flight; setting the current value does nothing.  The colour buffers (device, and page-locked
+ * staging for the host entry points; sized from max_width, max_height, max_batch) are allocated by the first colour call that needs
+ * them, not here and not in orbx_create: if that fails the call returns ORBX_E_HIP and the handle stays usable in grey.
+ * orbx_extract_batch_multi needs the same format on all its handles (else ORBX_E_INVALID). */
+int orbx_set_input_format(orbx_extractor *h, int format);
+int orbx_get_input_format(const orbx_extractor *h);   /* < 0: NULL handle */
 
 /* include/ORBextractor.h:63-83 getters.  Arrays must hold nlevels floats. */
 int orbx_get_levels(const orbx_extractor *h);
@@ -90,8 +108,8 @@ int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int width, int h
 int orbx_extract_end(orbx_extractor *h, orbx_keypoint *keypoints, uint8_t *descriptors, int cap, int *n);
 
 /*
- * ORBextractor::operator() (include/ORBextractor.h:59).  Host image (CV_8UC1, `stride` bytes per
- * row), host outputs with room for `cap` >= orbx_capacity() entries; *n receives the count.
+ * ORBextractor::operator() (include/ORBextractor.h:59).  Host image (CV_8UC1, or the handle's colour
+ * format; `stride` bytes per row), host outputs with room for `cap` >= orbx_capacity() entries; *n receives the count.
  * An empty image (NULL / w<=0 / h<=0) is the reference's silent return: ORBX_OK with *n = 0.
  * Keypoint order and descriptor rows follow the reference: level 0..L-1, quadtree list order inside.
  */
@@ -118,7 +136,9 @@ int orbx_extract_batch_multi(orbx_extractor *const *handles, int nhandles, const
  * Device-resident batch: all pointers are HIP device pointers on the handle's device; the work is
  * enqueued on `hip_stream` (a hipStream_t, NULL = the handle's own stream) and NOT synchronised.
  * d_status[nframes] receives an orbx_status per frame.  The input must stay valid until the stream
- * has drained (level 0 of the pyramid is the input itself).
+ * has drained (level 0 of the pyramid is the input itself).  A colour handle reads d_images in the conversion kernel only: level 0
+ * is then the handle's own grey plane, and row_stride (of the colour rows) is what must stay below 8 MiB, one colour frame below 2 GiB
+ * (else ORBX_E_SHAPE).
  */
 int orbx_extract_batch_device(orbx_extractor *h, const uint8_t *d_images, int nframes, int width,
                               int height, int row_stride, size_t frame_stride,
@@ -158,7 +178,8 @@ int orbx_stage_ms_ring(orbx_extractor *h, float *ms, int max_calls);
  * orbx_extract_begin/end, and FRAME 0 of orbx_extract_batch / orbx_extract_batch_device.  Levels >= 1 are frame 0's
  * slot of the handle's own pyramid; level 0 is read where that call read frame 0: the handle's upload buffer for the
  * host entry points, but the CALLER's device buffer for orbx_extract_batch_device, which must therefore hold the same
- * bytes until this call returns.  Both handles need the same nlevels (else ORBX_E_INVALID) and the same level sizes
+ * bytes until this call returns.  For a handle with a colour input format, level 0 is the handle's own grey plane on every route,
+ * orbx_extract_batch_device included: nothing of the caller's is read after the extraction.  Both handles need the same nlevels (else ORBX_E_INVALID) and the same level sizes
  * (else ORBX_E_SHAPE); nr >= 2^22 returns ORBX_E_CAPACITY before anything is allocated or launched.
  */
 int orbx_stereo_matches(orbx_extractor *left, orbx_extractor *right,

@@ -39,6 +39,9 @@ ORBX_OPT_BLUR_ROUNDING = 1
 ORBX_OPT_SUBBATCHES = 2
 ORBX_OPT_OVERLAP_PYRAMID = 3
 ORBX_OPT_BATCH_CHUNK = 4
+# orbx_format (include/orbx.h): what a handle's frames hold; colour frames are converted to grey on the GPU
+ORBX_FMT_GRAY8, ORBX_FMT_BGR8, ORBX_FMT_RGB8, ORBX_FMT_BGRA8, ORBX_FMT_RGBA8 = 0, 1, 2, 3, 4
+_FMT_CHANNELS = {ORBX_FMT_GRAY8: 1, ORBX_FMT_BGR8: 3, ORBX_FMT_RGB8: 3, ORBX_FMT_BGRA8: 4, ORBX_FMT_RGBA8: 4}
 
 
 class OrbxError(RuntimeError):
@@ -77,6 +80,10 @@ def lib():
     L.orbx_destroy.restype = None
     L.orbx_set_option.argtypes = [vp, C.c_int, C.c_int]
     L.orbx_get_levels.argtypes = [vp]
+    L.orbx_set_input_format.argtypes = [vp, C.c_int]
+    L.orbx_set_input_format.restype = C.c_int
+    L.orbx_get_input_format.argtypes = [vp]
+    L.orbx_get_input_format.restype = C.c_int
     L.orbx_get_scale_factor.argtypes = [vp]
     L.orbx_get_scale_factor.restype = C.c_float
     L.orbx_get_tables.argtypes = [vp, vp, vp, vp, vp]
@@ -331,6 +338,23 @@ class ORBextractor:
     def set_overlap_pyramid(self, on):
         _chk(self.L.orbx_set_option(self.h, ORBX_OPT_OVERLAP_PYRAMID, int(on)))
 
+    def set_input_format(self, fmt):
+        """ORBX_FMT_GRAY8 (default) or a colour format: every extraction entry point then takes (..., H, W, 3|4) uint8 frames."""
+        _chk(self.L.orbx_set_input_format(self.h, int(fmt)))
+
+    @property
+    def input_format(self):
+        return self.L.orbx_get_input_format(self.h)
+
+    def _check_frames(self, a, batch):
+        """The array's shape against the handle's format: (H, W) grey or (H, W, cn) colour, one more leading axis for a batch."""
+        cn = _FMT_CHANNELS[self.input_format]
+        want = (2 if cn == 1 else 3) + (1 if batch else 0)
+        if a.dtype != np.uint8 or a.ndim != want or (cn > 1 and a.shape[-1] != cn):
+            raise OrbxError(ORBX_E_INVALID, "input format %d takes uint8 arrays of shape (%sH, W%s), got %s %s"
+                            % (self.input_format, "B, " if batch else "", ", %d" % cn if cn > 1 else "", a.dtype, a.shape))
+        return cn
+
     def set_profiling(self, on):
         _chk(self.L.orbx_set_profiling(self.h, int(on)))
 
@@ -350,10 +374,15 @@ class ORBextractor:
         """operator()(image, mask, keypoints, descriptors) -> (keypoints[KP_DTYPE], descriptors[n,32])."""
         if image is None or image.size == 0:
             return np.zeros(0, KP_DTYPE), np.zeros((0, 32), np.uint8)
-        assert image.dtype == np.uint8 and image.ndim == 2   # assert(image.type() == CV_8UC1), :1052
-        if image.strides[1] != 1:
-            image = np.ascontiguousarray(image)
-        H, W = image.shape
+        if self.input_format != ORBX_FMT_GRAY8 or image.ndim != 2:
+            cn = self._check_frames(image, False)
+            if image.strides[1] != cn or image.strides[2] != 1:
+                image = np.ascontiguousarray(image)
+        else:
+            assert image.dtype == np.uint8 and image.ndim == 2   # assert(image.type() == CV_8UC1), :1052
+            if image.strides[1] != 1:
+                image = np.ascontiguousarray(image)
+        H, W = image.shape[:2]
         kps = np.zeros(self.cap, KP_DTYPE)
         desc = np.zeros((self.cap, 32), np.uint8)
         n = C.c_int()
@@ -365,7 +394,11 @@ class ORBextractor:
         if image is None or image.size == 0:
             _chk(self.L.orbx_extract_begin(self.h, None, 0, 0, 0))
             return
-        assert image.dtype == np.uint8 and image.ndim == 2 and image.strides[1] == 1
+        if self.input_format != ORBX_FMT_GRAY8 or image.ndim != 2:
+            cn = self._check_frames(image, False)
+            assert image.strides[1] == cn and image.strides[2] == 1
+        else:
+            assert image.dtype == np.uint8 and image.ndim == 2 and image.strides[1] == 1
         _chk(self.L.orbx_extract_begin(self.h, image.ctypes.data_as(C.c_void_p), image.shape[1], image.shape[0], image.strides[0]))
 
     def extract_end(self):
@@ -378,7 +411,9 @@ class ORBextractor:
 
     def extract_batch(self, images):
         images = np.ascontiguousarray(images, dtype=np.uint8)
-        B, H, W = images.shape
+        if self.input_format != ORBX_FMT_GRAY8 or images.ndim != 3:
+            self._check_frames(images, True)
+        B, H, W = images.shape[:3]
         kps = np.zeros((B, self.cap), KP_DTYPE)
         desc = np.zeros((B, self.cap, 32), np.uint8)
         counts = np.zeros(B, np.int32)
@@ -393,9 +428,14 @@ class ORBextractor:
         batch size overwrites them in place, so copy what must survive it; rows at and beyond counts[f] are stale data of
         earlier calls."""
         images = np.asarray(images, dtype=np.uint8)
-        if images.strides[2] != 1 or images.strides[1] < images.shape[2] or images.strides[0] < images.strides[1] * (images.shape[1] - 1) + images.shape[2]:
+        if self.input_format != ORBX_FMT_GRAY8 or images.ndim != 3:
+            cn = self._check_frames(images, True)
+            if images.strides[3] != 1 or images.strides[2] != cn or images.strides[1] < images.shape[2] * cn or \
+                    images.strides[0] < images.strides[1] * (images.shape[1] - 1) + images.shape[2] * cn:
+                images = np.ascontiguousarray(images)
+        elif images.strides[2] != 1 or images.strides[1] < images.shape[2] or images.strides[0] < images.strides[1] * (images.shape[1] - 1) + images.shape[2]:
             images = np.ascontiguousarray(images)
-        B, H, W = images.shape
+        B, H, W = images.shape[:3]
         if getattr(self, "_raw", None) is None or self._raw[0].shape[0] != B:
             self._raw = (np.zeros((B, self.cap), KP_DTYPE), np.zeros((B, self.cap, 32), np.uint8), np.zeros(B, np.int32))
         kps, desc, counts = self._raw
@@ -447,7 +487,9 @@ def extract_batch_multi(extractors, images):
     """orbx_extract_batch_multi: one batch of host frames sharded over several ORBextractor handles (one per GPU; one host thread
     each).  Returns (kps [B, cap], desc [B, cap, 32], counts [B]) like ORBextractor.extract_batch_raw."""
     images = np.ascontiguousarray(images, dtype=np.uint8)
-    B, H, W = images.shape
+    if extractors[0].input_format != ORBX_FMT_GRAY8 or images.ndim != 3:
+        extractors[0]._check_frames(images, True)
+    B, H, W = images.shape[:3]
     cap = max(e.cap for e in extractors)
     kps = np.zeros((B, cap), KP_DTYPE); desc = np.zeros((B, cap, 32), np.uint8); counts = np.zeros(B, np.int32)
     hs = (C.c_void_p * len(extractors))(*[e.h for e in extractors])

@@ -64,12 +64,15 @@ struct orbx_extractor : PlanParams {   // the constructor's arguments and tables
     uint32_t *d_cells = nullptr;   // per-cell (level, row, column) table of the current plan
     orbx_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_status = nullptr;
     uint8_t *h_in = nullptr;
+    // input format (orbx_set_input_format).  A colour frame is converted into d_input by one kernel ahead of the pyramid; the host entry
+    // points stage and upload it through h_color / d_color (allocated by the first colour call; pitches follow the call's width)
+    int fmt = ORBX_FMT_GRAY8; uint8_t *d_color = nullptr, *h_color = nullptr;
     orbx_keypoint *h_kps = nullptr; uint8_t *h_desc = nullptr; int32_t *h_counts = nullptr, *h_status = nullptr;
     uint8_t *d_out = nullptr, *h_out = nullptr; size_t out_hdr = 0, out_kps_bytes = 0, out_bytes = 0;   // the block the eight pointers above point into
     std::vector<size_t> chunk_off;   // orbx_extract_batch: byte offset of every chunk's own [counts | status | keypoints | descriptors] block in d_out / h_out
     int inflight = 0, inflight_frames = 0;      // orbx_extract_begin / orbx_extract_end
     // orbx_extract_begin replays one HIP graph per shape (upload, ~10 kernels, download) instead of ~12 launches
-    hipGraphExec_t graph_exec = nullptr; int graph_w = 0, graph_h = 0, graph_seen_w = 0, graph_seen_h = 0; bool graph_off = false; int graph_fails = 0;
+    hipGraphExec_t graph_exec = nullptr; int graph_fmt = 0; int graph_w = 0, graph_h = 0, graph_seen_w = 0, graph_seen_h = 0; bool graph_off = false; int graph_fails = 0;
     // orbx_extract_batch in chunks: staging threads, two streams, one HIP graph per chunk (kernels + download) per shape
     StagePool *pool = nullptr; int batch_chunk = 16;
     std::vector<hipGraphExec_t> bgraph; int bg_w = 0, bg_h = 0, bg_n = 0, bg_chunk = 0; bool bg_off = false;
@@ -127,7 +130,7 @@ static void free_all(orbx_extractor *h)
     hipFree(h->d_input); hipFree(h->d_pyr); hipFree(h->d_tab_i); hipFree(h->d_tab_s); hipFree(h->d_cells); hipFree(h->d_bands); hipFree(h->d_tiles);
     hipFree(h->work.cand); hipFree(h->work.cand_count); hipFree(h->work.owner); hipFree(h->work.arena);
     hipFree(h->work.sel); hipFree(h->work.nk); hipFree(h->work.ncand); hipFree(h->work.errflags);
-    hipFree(h->d_out);
+    hipFree(h->d_out); hipFree(h->d_color); (void)hipHostFree(h->h_color);
     hipHostFree(h->h_in); hipHostFree(h->h_out);
     if (h->graph_exec) hipGraphExecDestroy(h->graph_exec);
     for (auto &g : h->bgraph) if (g) hipGraphExecDestroy(g);
@@ -253,6 +256,53 @@ extern "C" int orbx_set_option(orbx_extractor *h, int option, int value)
     if (option == ORBX_OPT_OVERLAP_PYRAMID && (value == 0 || value == 1)) { h->overlap_pyr = value; return ORBX_OK; }
     return fail(ORBX_E_INVALID, "unknown option %d=%d", option, value);
 }
+static void drop_graphs(orbx_extractor *h)
+{
+    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
+    h->graph_w = h->graph_h = h->graph_seen_w = h->graph_seen_h = 0;
+    for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
+    h->bgraph.clear(); h->bg_w = h->bg_h = h->bg_n = 0;
+}
+extern "C" int orbx_set_input_format(orbx_extractor *h, int format)
+{
+    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
+    if (format < ORBX_FMT_GRAY8 || format > ORBX_FMT_RGBA8) return fail(ORBX_E_INVALID, "unknown input format %d", format);
+    if (h->inflight) return fail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle");
+    if (format == h->fmt) return ORBX_OK;
+    drop_graphs(h);   // the captured graphs hold the upload and (for colour) the conversion of the format they were captured in
+    h->fmt = format;
+    return ORBX_OK;
+}
+extern "C" int orbx_get_input_format(const orbx_extractor *h) { return h ? h->fmt : fail(ORBX_E_INVALID, "NULL handle"); }
+
+// Colour input.  The host entry points stage a colour frame with a pitch of its own row bytes rounded up to 64 (so every staged row is
+// aligned for the kernel's wide loads, and a BGR upload is 3x the grey one, not 4x); both blocks are sized for 4 channels at the
+// handle's maximum shape, which every smaller frame and every 3-channel frame fits.
+struct ColorSrc { const uint8_t *base; int stride; long long frame; };
+static int color_pitch(int W, int cn) { return (int)align_up((size_t)W * cn, 64); }
+static size_t color_frame(int W, int H, int cn) { return align_up((size_t)color_pitch(W, cn) * H, 256); }
+static int ensure_color(orbx_extractor *h)
+{
+    if (h->d_color && h->h_color) return ORBX_OK;
+    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());   // allocation is a synchronous runtime call
+    const size_t bytes = (size_t)h->max_batch * color_frame(h->max_w, h->max_h, 4) + 256;
+    hipError_t e = hipMalloc((void **)&h->d_color, bytes);
+    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_color, bytes);
+    if (e != hipSuccess) {
+        (void)hipFree(h->d_color); h->d_color = nullptr;
+        (void)hipGetLastError();
+        return fail(ORBX_E_HIP, "colour input buffers (%zu bytes, device and page-locked): %s", bytes, hipGetErrorString(e));
+    }
+    return ORBX_OK;
+}
+// one colour frame must be below 2 GiB and its row stride below 8 MiB (the conversion kernel's 32-bit offsets inside a frame)
+static int check_color_limits(int width, int height, int row_stride)
+{
+    if (row_stride >= (1 << 23) || (long long)height * row_stride >= (1ll << 31))
+        return fail(ORBX_E_SHAPE, "colour frame %dx%d with row stride %d: one frame must be below 2 GiB, the stride below 8 MiB", width, height, row_stride);
+    return ORBX_OK;
+}
+
 extern "C" int orbx_get_levels(const orbx_extractor *h) { return h ? h->nlevels : 0; }
 extern "C" float orbx_get_scale_factor(const orbx_extractor *h) { return h ? h->scale_factor : 0.f; }
 extern "C" int orbx_get_tables(const orbx_extractor *h, float *sf, float *isf, float *s2, float *is2)
@@ -414,7 +464,8 @@ static void make_sub_batches(const orbx_extractor *h, int nframes, int nsub, int
 // enqueue the whole pipeline for `nframes` frames already resident in HBM
 static int enqueue(orbx_extractor *h, const uint8_t *d_images, int nframes, int W, int H, int row_stride,
                    long long frame_stride, orbx_keypoint *d_kps, uint8_t *d_desc, int32_t *d_counts,
-                   int32_t *d_status, hipStream_t s, int work_frame0 = 0)   // work_frame0: first frame slot of the workspace / pyramid
+                   int32_t *d_status, hipStream_t s, int work_frame0 = 0,   // work_frame0: first frame slot of the workspace / pyramid
+                   const ColorSrc *cs = nullptr)   // colour: d_images is the handle's grey block, filled from *cs ahead of the pyramid
 {
     int rc = ensure_plan(h, W, H);
     if (rc != ORBX_OK) return rc;
@@ -438,11 +489,15 @@ static int enqueue(orbx_extractor *h, const uint8_t *d_images, int nframes, int 
     const int nsub = (h->profiling != 0 || nframes < 16) ? 1 : std::min(h->nsub, ORBX_MAX_SUB);
     SubBatch sb[ORBX_MAX_SUB];
     make_sub_batches(h, nframes, nsub, work_frame0, s, sb);
+    if (cs) {   // the conversion is part of stage [0]; it runs on s ahead of the fork, so every sub-batch sees its grey frames
+        if (pe) HIPCHK(hipEventRecord(pe[0], s));
+        orbx_launch_color(cs->base, cs->stride, cs->frame, const_cast<uint8_t *>(d_images), row_stride, frame_stride, W, H, nframes, h->fmt, s);
+    }
     if (nsub > 1) {
         HIPCHK(hipEventRecord(h->ev_fork, s));
         for (int i = 1; i < nsub; i++) HIPCHK(hipStreamWaitEvent(sb[i].s, h->ev_fork, 0));
     }
-    if (pe) HIPCHK(hipEventRecord(pe[0], s));
+    if (pe && !cs) HIPCHK(hipEventRecord(pe[0], s));
     // FAST on level 0 needs only the input, so with one sub-batch the resize chain (seven small, latency-bound
     // launches) runs on a side stream underneath it; the remaining levels' cells wait for the chain.
     const bool overlap = h->profiling == 0 && nsub == 1 && h->overlap_pyr && h->nlevels > 1 && P.lv[1].cell_begin > 0;
@@ -503,14 +558,20 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *h, const uint8_t *d_ima
     if (h->inflight) return fail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle (its workspace would be overwritten)");
     if (!d_images || !d_keypoints || !d_descriptors || !d_counts || !d_status) return fail(ORBX_E_INVALID, "NULL device pointer");
     if (nframes < 1 || nframes > h->max_batch) return fail(ORBX_E_INVALID, "nframes=%d (max_batch=%d)", nframes, h->max_batch);
-    if (width < 1 || height < 1 || row_stride < width) return fail(ORBX_E_INVALID, "bad frame geometry %dx%d stride %d", width, height, row_stride);
+    const int cn = orbx_format_channels(h->fmt);
+    if (width < 1 || height < 1 || row_stride / cn < width) return fail(ORBX_E_INVALID, "bad frame geometry %dx%d stride %d (%d channel%s)", width, height, row_stride, cn, cn > 1 ? "s" : "");
     // the kernels index one frame with 31-bit byte offsets and 24-bit row strides
     if (row_stride >= (1 << 23) || (long long)height * row_stride >= (1ll << 31))
         return fail(ORBX_E_SHAPE, "frame %dx%d with row stride %d: one frame must be below 2 GiB, the stride below 8 MiB", width, height, row_stride);
     if (cap != h->max_plan.out_cap) return fail(ORBX_E_CAPACITY, "device outputs must be laid out with cap == orbx_capacity() == %d (got %d)", h->max_plan.out_cap, cap);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
-    int rc = enqueue(h, d_images, nframes, width, height, row_stride, (long long)frame_stride, d_keypoints,
+    int rc;
+    if (cn > 1) {   // the caller's buffer is read by the conversion only; level 0 is the handle's grey block
+        const ColorSrc cs = {d_images, row_stride, (long long)frame_stride};
+        rc = enqueue(h, h->d_input, nframes, width, height, h->in_stride, (long long)h->in_frame, d_keypoints, d_descriptors, d_counts, d_status, s, 0, &cs);
+    } else
+        rc = enqueue(h, d_images, nframes, width, height, row_stride, (long long)frame_stride, d_keypoints,
                      d_descriptors, d_counts, d_status, s);
     if (rc != ORBX_OK) return rc;
     if (h->profiling == 1) return finish_profile(h);
@@ -541,29 +602,38 @@ static bool is_pinned_host(const uint8_t *images, int nframes, size_t frame_stri
 }
 
 // upload frames [k0, k1) straight from the caller's page-locked buffer into the handle's input block (rows are re-pitched by the copy)
-static int upload_pinned(orbx_extractor *h, const uint8_t *images, int k0, int k1, int width, int height, int row_stride, size_t frame_stride, hipStream_t s)
+// (d_dst, dst_stride, dst_frame: that block and its pitches; row_bytes = width * channels)
+static int upload_pinned(uint8_t *d_dst, size_t dst_stride, size_t dst_frame, const uint8_t *images, int k0, int k1, size_t row_bytes, int height, int row_stride, size_t frame_stride, hipStream_t s)
 {
-    const bool tall = frame_stride == (size_t)row_stride * height && h->in_frame == (size_t)h->in_stride * height;   // the chunk is one tall image
+    const bool tall = frame_stride == (size_t)row_stride * height && dst_frame == dst_stride * height;   // the chunk is one tall image
     if (tall) {
-        HIPCHK(hipMemcpy2DAsync(h->d_input + (size_t)k0 * h->in_frame, (size_t)h->in_stride, images + (size_t)k0 * frame_stride, (size_t)row_stride,
-                                (size_t)width, (size_t)height * (k1 - k0), hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemcpy2DAsync(d_dst + (size_t)k0 * dst_frame, dst_stride, images + (size_t)k0 * frame_stride, (size_t)row_stride,
+                                row_bytes, (size_t)height * (k1 - k0), hipMemcpyHostToDevice, s));
     } else {
         for (int k = k0; k < k1; k++)
-            HIPCHK(hipMemcpy2DAsync(h->d_input + (size_t)k * h->in_frame, (size_t)h->in_stride, images + (size_t)k * frame_stride, (size_t)row_stride,
-                                    (size_t)width, (size_t)height, hipMemcpyHostToDevice, s));
+            HIPCHK(hipMemcpy2DAsync(d_dst + (size_t)k * dst_frame, dst_stride, images + (size_t)k * frame_stride, (size_t)row_stride,
+                                    row_bytes, (size_t)height, hipMemcpyHostToDevice, s));
     }
     return ORBX_OK;
 }
+// where the host entry points stage and upload a call's frames: the grey input block, or the colour block with the call's own pitches
+struct StageGeom { uint8_t *h_base, *d_base; size_t stride, frame, row_bytes; };
+static StageGeom stage_geom(const orbx_extractor *h, int width, int height)
+{
+    const int cn = orbx_format_channels(h->fmt);
+    if (cn == 1) return {h->h_in, h->d_input, (size_t)h->in_stride, h->in_frame, (size_t)width};
+    return {h->h_color, h->d_color, (size_t)color_pitch(width, cn), color_frame(width, height, cn), (size_t)width * cn};
+}
 
-static void stage_frames(orbx_extractor *h, const uint8_t *images, int k0, int k1, int width, int height, int row_stride, size_t frame_stride)
+static void stage_frames(orbx_extractor *h, const StageGeom &G, const uint8_t *images, int k0, int k1, int height, int row_stride, size_t frame_stride)
 {
     const int RB = 64, nblk = (height + RB - 1) / RB;
     auto unit = [&](int u) {
         const int k = k0 + u / nblk, y0 = (u % nblk) * RB, y1 = std::min(height, y0 + RB);
-        uint8_t *dst = h->h_in + (size_t)k * h->in_frame;
+        uint8_t *dst = G.h_base + (size_t)k * G.frame;
         const uint8_t *src = images + (size_t)k * frame_stride;
-        if (row_stride == h->in_stride) memcpy(dst + (size_t)y0 * row_stride, src + (size_t)y0 * row_stride, (size_t)row_stride * (y1 - y0 - 1) + width);
-        else for (int y = y0; y < y1; y++) memcpy(dst + (size_t)y * h->in_stride, src + (size_t)y * row_stride, (size_t)width);
+        if ((size_t)row_stride == G.stride) memcpy(dst + (size_t)y0 * row_stride, src + (size_t)y0 * row_stride, (size_t)row_stride * (y1 - y0 - 1) + G.row_bytes);
+        else for (int y = y0; y < y1; y++) memcpy(dst + (size_t)y * G.stride, src + (size_t)y * row_stride, G.row_bytes);
     };
     const int n = (k1 - k0) * nblk;
     if (h->pool) h->pool->parallel_for(n, unit);
@@ -609,17 +679,25 @@ static int deliver_batch(orbx_extractor *h, int k0, int k1, orbx_keypoint *keypo
     return ORBX_OK;
 }
 
+// the pipeline for frames [k0, k0 + nf) of the handle's staged-and-uploaded block (grey: the input block itself; colour: converted into it)
+static int enqueue_staged(orbx_extractor *h, const StageGeom &G, int k0, int nf, int width, int height, orbx_keypoint *d_kps, uint8_t *d_desc,
+                          int32_t *d_counts, int32_t *d_status, hipStream_t s)
+{
+    const ColorSrc cs = {G.d_base + (size_t)k0 * G.frame, (int)G.stride, (long long)G.frame};
+    return enqueue(h, h->d_input + (size_t)k0 * h->in_frame, nf, width, height, h->in_stride, (long long)h->in_frame, d_kps, d_desc, d_counts, d_status, s, k0,
+                   h->fmt == ORBX_FMT_GRAY8 ? nullptr : &cs);
+}
+
 // The whole batch in one piece: upload, kernels, download, strictly one after the other (first call of a shape, profiling,
 // small batches).
 static int extract_batch_simple(orbx_extractor *h, const uint8_t *images, int nframes, int width, int height, int row_stride,
                                 size_t frame_stride, orbx_keypoint *keypoints, uint8_t *descriptors, int cap, int *counts)
 {
     hipStream_t s = h->stream;
-    stage_frames(h, images, 0, nframes, width, height, row_stride, frame_stride);
-    HIPCHK(hipMemcpyAsync(h->d_input, h->h_in, (size_t)(nframes - 1) * h->in_frame + (size_t)h->in_stride * height,
-                          hipMemcpyHostToDevice, s));
-    int rc = enqueue(h, h->d_input, nframes, width, height, h->in_stride, (long long)h->in_frame, h->d_kps, h->d_desc,
-                     h->d_counts, h->d_status, s);
+    const StageGeom G = stage_geom(h, width, height);
+    stage_frames(h, G, images, 0, nframes, height, row_stride, frame_stride);
+    HIPCHK(hipMemcpyAsync(G.d_base, G.h_base, (size_t)(nframes - 1) * G.frame + G.stride * height, hipMemcpyHostToDevice, s));
+    int rc = enqueue_staged(h, G, 0, nframes, width, height, h->d_kps, h->d_desc, h->d_counts, h->d_status, s);
     if (rc == ORBX_OK) rc = download_outputs(h, nframes, s);
     if (rc != ORBX_OK) return rc;
     HIPCHK(hipStreamSynchronize(s));
@@ -650,8 +728,7 @@ static int enqueue_chunk(orbx_extractor *h, int c, int k0, int k1, int width, in
 {
     const int nf = k1 - k0;
     const ChunkBlock D = chunk_block(h, h->d_out, c, nf);
-    int rc = enqueue(h, h->d_input + (size_t)k0 * h->in_frame, nf, width, height, h->in_stride, (long long)h->in_frame,
-                     D.kps, D.desc, D.counts, D.status, s, k0);
+    int rc = enqueue_staged(h, stage_geom(h, width, height), k0, nf, width, height, D.kps, D.desc, D.counts, D.status, s);
     if (rc != ORBX_OK) return rc;
     HIPCHK(hipMemcpyAsync(h->h_out + h->chunk_off[c], h->d_out + h->chunk_off[c], D.bytes, hipMemcpyDeviceToHost, s));
     return ORBX_OK;
@@ -668,9 +745,11 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
     if (!images || width <= 0 || height <= 0 || nframes <= 0) return ORBX_OK;   // :1048 empty image: silent return
     if (!keypoints || !descriptors) return fail(ORBX_E_INVALID, "NULL output buffer");
     if (nframes > h->max_batch) return fail(ORBX_E_INVALID, "nframes=%d (max_batch=%d)", nframes, h->max_batch);
-    if (row_stride < width) return fail(ORBX_E_INVALID, "row_stride %d < width %d", row_stride, width);
+    const int cn = orbx_format_channels(h->fmt);
+    if (row_stride / cn < width) return fail(ORBX_E_INVALID, "row_stride %d < width %d x %d channel%s", row_stride, width, cn, cn > 1 ? "s" : "");
     if (width > h->max_w || height > h->max_h) return fail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", width, height, h->max_w, h->max_h);
     HIPCHK(hipSetDevice(h->device));
+    if (cn > 1) { int rcc = check_color_limits(width, height, color_pitch(width, cn)); if (rcc == ORBX_OK) rcc = ensure_color(h); if (rcc != ORBX_OK) return rcc; }
     if (!h->pool && nframes >= 8) {                         // staging threads: up to 6, leaving cores to the caller
         const unsigned hc = (unsigned)StagePool::usable_cpus();       // affinity mask and cgroup quota, not the machine's core count
         h->pool = new StagePool((int)std::min<unsigned>(6u, hc > 2 ? hc / 2 - 1 : 0u));
@@ -739,7 +818,8 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
     const bool pinned_ok = batch_pinned_ok();
     // the answer for one buffer is remembered (a capture pipeline hands over the same page-locked block again and again; should it
     // have been unregistered meanwhile, the copies below are still correct -- the runtime stages them -- only slower)
-    const size_t frame_bytes = (size_t)(height - 1) * row_stride + width;
+    const size_t frame_bytes = (size_t)(height - 1) * row_stride + (size_t)width * cn;
+    const StageGeom G = stage_geom(h, width, height);
     if (pinned_ok && !(h->pin_ptr == images && h->pin_n == nframes && h->pin_stride == frame_stride && h->pin_bytes == frame_bytes)) {
         h->pin_ptr = images; h->pin_n = nframes; h->pin_stride = frame_stride; h->pin_bytes = frame_bytes;
         h->pin_is = is_pinned_host(images, nframes, frame_stride, frame_bytes);
@@ -751,12 +831,12 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
         const int k0 = cut[c], k1 = cut[c + 1];
         hipStream_t s = st[c % nst];
         const double ta = trace ? now() : 0;
-        if (!pinned_in) stage_frames(h, images, k0, k1, width, height, row_stride, frame_stride);
+        if (!pinned_in) stage_frames(h, G, images, k0, k1, height, row_stride, frame_stride);
         const double tb = trace ? now() : 0;
-        if (pinned_in) { int rcu = upload_pinned(h, images, k0, k1, width, height, row_stride, frame_stride, up); if (rcu != ORBX_OK) return rcu; }
+        if (pinned_in) { int rcu = upload_pinned(G.d_base, G.stride, G.frame, images, k0, k1, G.row_bytes, height, row_stride, frame_stride, up); if (rcu != ORBX_OK) return rcu; }
         else
-            HIPCHK(hipMemcpyAsync(h->d_input + (size_t)k0 * h->in_frame, h->h_in + (size_t)k0 * h->in_frame,
-                                  (size_t)(k1 - k0 - 1) * h->in_frame + (size_t)h->in_stride * height, hipMemcpyHostToDevice, up));
+            HIPCHK(hipMemcpyAsync(G.d_base + (size_t)k0 * G.frame, G.h_base + (size_t)k0 * G.frame,
+                                  (size_t)(k1 - k0 - 1) * G.frame + G.stride * height, hipMemcpyHostToDevice, up));
         HIPCHK(hipEventRecord(h->ev_up[c], up));
         HIPCHK(hipStreamWaitEvent(s, h->ev_up[c], 0));
         if (graphs) HIPCHK(hipGraphLaunch(h->bgraph[c], s));
@@ -789,8 +869,9 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
 // one staged frame: upload, then the pipeline
 static int upload_and_enqueue_one(orbx_extractor *h, int w, int hgt, hipStream_t s)
 {
-    HIPCHK(hipMemcpyAsync(h->d_input, h->h_in, (size_t)h->in_stride * hgt, hipMemcpyHostToDevice, s));
-    return enqueue(h, h->d_input, 1, w, hgt, h->in_stride, (long long)h->in_frame, h->d_kps, h->d_desc, h->d_counts, h->d_status, s);
+    const StageGeom G = stage_geom(h, w, hgt);
+    HIPCHK(hipMemcpyAsync(G.d_base, G.h_base, G.stride * hgt, hipMemcpyHostToDevice, s));
+    return enqueue_staged(h, G, 0, 1, w, hgt, h->d_kps, h->d_desc, h->d_counts, h->d_status, s);
 }
 
 extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int width, int height, int stride)
@@ -799,16 +880,23 @@ extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int w
     if (h->inflight) return fail(ORBX_E_INVALID, "orbx_extract_begin: a call is already in flight on this handle");
     h->inflight_frames = 0;
     if (!image || width <= 0 || height <= 0) { h->inflight = 1; return ORBX_OK; }     // :1048 empty image
-    if (stride < width) return fail(ORBX_E_INVALID, "row_stride %d < width %d", stride, width);
+    const int cn = orbx_format_channels(h->fmt);
+    if (stride / cn < width) return fail(ORBX_E_INVALID, "row_stride %d < width %d x %d channel%s", stride, width, cn, cn > 1 ? "s" : "");
     if (width > h->max_w || height > h->max_h) return fail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", width, height, h->max_w, h->max_h);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
-    if (stride == h->in_stride) memcpy(h->h_in, image, (size_t)stride * height);
+    if (cn > 1) {
+        int rcc = check_color_limits(width, height, color_pitch(width, cn));
+        if (rcc == ORBX_OK) rcc = ensure_color(h);
+        if (rcc != ORBX_OK) return rcc;
+        const StageGeom G = stage_geom(h, width, height);
+        for (int y = 0; y < height; y++) memcpy(G.h_base + (size_t)y * G.stride, image + (size_t)y * stride, G.row_bytes);
+    } else if (stride == h->in_stride) memcpy(h->h_in, image, (size_t)stride * height);
     else for (int y = 0; y < height; y++) memcpy(h->h_in + (size_t)y * h->in_stride, image + (size_t)y * stride, (size_t)width);
     // Same shape as the last call, nothing to clear, no profiling: the upload, the kernels and the download are one HIP graph
     // (captured on the second call of a shape, replayed from then on); every pointer in it belongs to the handle.
     const bool graphable = !h->graph_off && h->profiling == 0 && h->max_batch == 1 && !h->need_clear && width == h->cur_w && height == h->cur_h;
-    auto have_graph = [&] { return graphable && h->graph_exec && h->graph_w == width && h->graph_h == height; };
+    auto have_graph = [&] { return graphable && h->graph_exec && h->graph_w == width && h->graph_h == height && h->graph_fmt == h->fmt; };
     if (!have_graph()) {
         const bool second = graphable && h->graph_seen_w == width && h->graph_seen_h == height;
         h->graph_seen_w = width; h->graph_seen_h = height;
@@ -817,7 +905,7 @@ extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int w
             h->graph_exec = capture_graph(s, [&] { return upload_and_enqueue_one(h, width, height, s) == ORBX_OK && download_outputs(h, 1, s) == ORBX_OK; });
             // a capture that failed or was invalidated (another thread's synchronous call) is not an error of this call; the capture
             // is tried again on a later call, three times at most
-            if (h->graph_exec) { h->graph_w = width; h->graph_h = height; }
+            if (h->graph_exec) { h->graph_w = width; h->graph_h = height; h->graph_fmt = h->fmt; }
             else if (++h->graph_fails >= 3) h->graph_off = true;
             else h->graph_seen_w = h->graph_seen_h = 0;
         }
@@ -894,6 +982,8 @@ extern "C" int orbx_extract_batch_multi(orbx_extractor *const *handles, int nhan
         for (int j = 0; j < i; j++)
             if (handles[j] == handles[i]) return fail(ORBX_E_INVALID, "handle %d is handle %d again: a handle is not re-entrant", i, j);
     }
+    for (int i = 1; i < nhandles; i++)
+        if (handles[i]->fmt != handles[0]->fmt) return fail(ORBX_E_INVALID, "handle %d has input format %d, handle 0 has %d: one batch has one format", i, handles[i]->fmt, handles[0]->fmt);
     if (!counts) return fail(ORBX_E_INVALID, "counts is NULL");
     for (int k = 0; k < std::max(nframes, 0); k++) counts[k] = 0;
     if (!images || width <= 0 || height <= 0 || nframes <= 0) return ORBX_OK;

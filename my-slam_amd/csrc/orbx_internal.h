@@ -156,6 +156,11 @@ static inline bool resize_is_fast(int mode) { return mode == RESIZE_FAST || mode
 // src_end != NULL: the source is caller-owned memory; one past its last valid byte (fast path guard)
 void orbx_launch_resize(const OrbxLevel &src, const OrbxLevel &dst, const ResizeTab &tab, int mode,
                         int nframes, const uint8_t *src_end, hipStream_t s);
+// orbx_color.hip: nframes colour frames (format = ORBX_FMT_BGR8 .. ORBX_FMT_RGBA8; src_stride / src_frame in bytes, any alignment) into a grey
+// plane whose rows are 4-aligned and whose pitch covers W rounded up to 4 (the handle's input block).  One frame below 2 GiB, src_stride below 8 MiB.
+static inline int orbx_format_channels(int format) { return format == ORBX_FMT_GRAY8 ? 1 : (format == ORBX_FMT_BGR8 || format == ORBX_FMT_RGB8) ? 3 : 4; }
+void orbx_launch_color(const uint8_t *src, int src_stride, long long src_frame, uint8_t *dst, int dst_stride, long long dst_frame,
+                       int W, int H, int nframes, int format, hipStream_t s);
 // cells [cell_lo, cell_hi) of the per-frame cell list (level 0 comes first)
 void orbx_launch_fast(const OrbxPlan &plan, const OrbxWork &wk, int nframes, int cell_lo, int cell_hi, hipStream_t s);
 void orbx_launch_octree(const OrbxPlan &plan, const OrbxWork &wk, int nframes, size_t lds_bytes,

@@ -14,6 +14,8 @@
 //     after the extraction in one synchronisation (orbx_download_pyramid).  A caller that never reads it on the
 //     host (monocular tracking; stereo through orbx_stereo_matches, which reads the levels on the device)
 //     switches the download off with SetHostPyramid(false) and may still call FetchImagePyramid() on demand.
+//   * ExtractColor(image, bRGB, keypoints, descriptors) takes the camera's CV_8UC3 / CV_8UC4 frame and converts it on the GPU: it
+//     replaces the cvtColor block at the top of Tracking::GrabImage* (src/Tracking.cc:174-199, 244-257).  operator() is unchanged.
 //   * The handle is sized for the largest image seen so far (it starts at 1920x1080 and grows on demand).
 //   * Failures of the GPU layer, and an image that is not CV_8UC1 (the reference asserts, :1052), produce an
 //     empty result, the reference's only failure mode (src/ORBextractor.cc:1048-1049); the text is in LastError().
@@ -58,10 +60,32 @@ public:
         if (image.type() != CV_8UC1) { err_ = "image is not CV_8UC1"; _descriptors.release(); return; }   // :1052 assert
         if (!fits(image.cols, image.rows)) { _descriptors.release(); return; }
         int n = 0;
+        if (!format(ORBX_FMT_GRAY8)) { _descriptors.release(); return; }
         const int rc = orbx_extract(h_, image.data, image.cols, image.rows, (int)image.step, kp_.data(), desc_.data(), cap_, &n);
         if (rc != ORBX_OK) { err_ = orbx_last_error(); _descriptors.release(); return; }
         fill(n, _keypoints, _descriptors);
         if (hostPyramid_) FetchImagePyramid();                           // ComputePyramid's side effect, :1055
+    }
+
+    // The camera's frame as Tracking::GrabImage* receives it (src/Tracking.cc:172-199): CV_8UC3 or CV_8UC4 in RGB(A) order when bRGB
+    // (Tracking::mbRGB), else BGR(A); the cvtColor of those lines runs on the GPU ahead of the pyramid (OpenCV 3.1.0's portable
+    // RGB2Gray arithmetic) and mvImagePyramid[0] is the grey image.  CV_8UC1 passes through unchanged.  Failures give the same
+    // empty result as operator().
+    void ExtractColor(cv::InputArray _image, bool bRGB, std::vector<cv::KeyPoint> &_keypoints, cv::OutputArray _descriptors)
+    {
+        _keypoints.clear();
+        if (_image.empty()) { _descriptors.release(); return; }
+        cv::Mat image = _image.getMat();
+        const int t = image.type();
+        if (t != CV_8UC1 && t != CV_8UC3 && t != CV_8UC4) { err_ = "image is not CV_8UC1, CV_8UC3 or CV_8UC4"; _descriptors.release(); return; }
+        if (!fits(image.cols, image.rows)) { _descriptors.release(); return; }
+        const int fmt = t == CV_8UC1 ? ORBX_FMT_GRAY8 : t == CV_8UC3 ? (bRGB ? ORBX_FMT_RGB8 : ORBX_FMT_BGR8) : (bRGB ? ORBX_FMT_RGBA8 : ORBX_FMT_BGRA8);
+        if (!format(fmt)) { _descriptors.release(); return; }
+        int n = 0;
+        const int rc = orbx_extract(h_, image.data, image.cols, image.rows, (int)image.step, kp_.data(), desc_.data(), cap_, &n);
+        if (rc != ORBX_OK) { err_ = orbx_last_error(); _descriptors.release(); return; }
+        fill(n, _keypoints, _descriptors);
+        if (hostPyramid_) FetchImagePyramid();
     }
 
     // operator() in two halves (orbx_extract_begin / orbx_extract_end): Begin returns as soon as the image is staged and the
@@ -71,7 +95,7 @@ public:
         cv::Mat image = _image.getMat();
         if (!image.empty() && image.type() != CV_8UC1) { err_ = "image is not CV_8UC1"; return false; }
         if (!image.empty() && !fits(image.cols, image.rows)) return false;
-        if (!h_) return false;
+        if (!h_ || !format(ORBX_FMT_GRAY8)) return false;
         const int rc = image.empty() ? orbx_extract_begin(h_, nullptr, 0, 0, 0)
                                      : orbx_extract_begin(h_, image.data, image.cols, image.rows, (int)image.step);
         if (rc != ORBX_OK) err_ = orbx_last_error();
@@ -129,7 +153,7 @@ protected:
             h_ = nullptr;
             return false;
         }
-        maxW_ = maxW; maxH_ = maxH;
+        maxW_ = maxW; maxH_ = maxH; fmt_ = ORBX_FMT_GRAY8;
         mvScaleFactor.resize(nlevels_); mvInvScaleFactor.resize(nlevels_);
         mvLevelSigma2.resize(nlevels_); mvInvLevelSigma2.resize(nlevels_);
         orbx_get_tables(h_, mvScaleFactor.data(), mvInvScaleFactor.data(), mvLevelSigma2.data(), mvInvLevelSigma2.data());
@@ -142,6 +166,13 @@ protected:
     {
         if (h_ && w <= maxW_ && h <= maxH_) return true;
         return open(w > maxW_ ? w : maxW_, h > maxH_ ? h : maxH_);
+    }
+    bool format(int fmt)   // the handle's input format, set only when it differs from the last call's
+    {
+        if (fmt == fmt_) return true;
+        if (orbx_set_input_format(h_, fmt) != ORBX_OK) { err_ = orbx_last_error(); return false; }
+        fmt_ = fmt;
+        return true;
     }
     void fill(int n, std::vector<cv::KeyPoint> &_keypoints, cv::OutputArray _descriptors)
     {
@@ -159,7 +190,7 @@ protected:
     }
 
     orbx_extractor *h_ = nullptr;
-    int nfeatures_, nlevels_, iniTh_, minTh_, device_, cap_ = 0, maxW_ = 0, maxH_ = 0;
+    int nfeatures_, nlevels_, iniTh_, minTh_, device_, cap_ = 0, maxW_ = 0, maxH_ = 0, fmt_ = ORBX_FMT_GRAY8;
     float scaleFactor_;
     std::vector<orbx_keypoint> kp_;
     std::vector<unsigned char> desc_;

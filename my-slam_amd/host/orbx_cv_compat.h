@@ -5,7 +5,7 @@
 // compiled and exercised by this repo's own tests THROUGH THE SAME CODE PATH a maintainer compiles against
 // OpenCV: the adapters are written against OpenCV's API (InputArray::getMat(), OutputArray::create(),
 // unqualified CV_8U ...), and this header models exactly those calls:
-//   CV_8U / CV_8UC1 / CV_32F / CV_32FC1 are macros with OpenCV's values (core/hal/interface.h);
+//   CV_8U / CV_8UC1 / CV_8UC3 / CV_8UC4 / CV_32F / CV_32FC1 are macros with OpenCV's values (core/hal/interface.h);
 //   cv::InputArray = const cv::_InputArray &, cv::OutputArray = const cv::_OutputArray & (core/mat.hpp:...),
 //   both constructible from a cv::Mat as in `extractor(im, cv::Mat(), keys, descriptors)` (src/Frame.cc:250).
 #pragma once
@@ -20,6 +20,8 @@
 #define CV_CN_SHIFT 3
 #define CV_MAKETYPE(depth, cn) ((depth) + (((cn) - 1) << CV_CN_SHIFT))
 #define CV_8UC1 CV_MAKETYPE(CV_8U, 1)
+#define CV_8UC3 CV_MAKETYPE(CV_8U, 3)
+#define CV_8UC4 CV_MAKETYPE(CV_8U, 4)
 #define CV_32FC1 CV_MAKETYPE(CV_32F, 1)
 #endif
 
@@ -30,7 +32,7 @@ struct KeyPoint {                      // field order of cv::KeyPoint (28 bytes)
     Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1;
 };
 
-class Mat {                            // single-channel CV_8U / CV_32F, two dimensions
+class Mat {                            // CV_8U / CV_32F with 1..4 interleaved channels, two dimensions
 public:
     int rows = 0, cols = 0; size_t step = 0; uint8_t *data = nullptr;
     Mat() {}
@@ -45,6 +47,7 @@ public:
     void release() { store_.reset(); data = nullptr; rows = cols = 0; step = 0; }
     bool empty() const { return data == nullptr || rows == 0 || cols == 0; }
     int type() const { return type_; }
+    int channels() const { return (type_ >> CV_CN_SHIFT) + 1; }
     size_t elemSize() const { return esz(type_); }
     bool isContinuous() const { return step == (size_t)cols * esz(type_) || rows <= 1; }
     template <class T> T *ptr(int r = 0) { return (T *)(data + (size_t)r * step); }
@@ -60,7 +63,7 @@ public:
         return m;
     }
 private:
-    static size_t esz(int type) { return (type & 7) == CV_32F ? 4 : 1; }
+    static size_t esz(int type) { return (size_t)((type & 7) == CV_32F ? 4 : 1) * ((type >> CV_CN_SHIFT) + 1); }
     std::shared_ptr<uint8_t> store_;
     int type_ = CV_8UC1;
 };
