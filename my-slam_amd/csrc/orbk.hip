@@ -12,33 +12,13 @@
 #include <unordered_set>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-#include "../../include/orbk.h"
+#include "orbk_internal.h"
 #include "../../include/orbv.h"
-
-static thread_local std::string g_kerr;
-static int kfail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_kerr = buf;
-    return code;
-}
-extern "C" const char *orbk_last_error(void) { return g_kerr.c_str(); }
-#define KHIP(expr)                                                                               \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return kfail(ORBX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
 
 #define K_THREADS 256
 #define K_LDS_QUERY 8192          // query word ids staged in LDS up to this length (32 KiB); longer queries search global memory
 #define K_MAX_BLOCKS 2048         // the waves of a launch stride over the slots: the query is staged once per block, not per slot
 
-struct KSlotDev { long long off; int32_t len; int32_t pad; };   // len 0: erased (or an empty BowVector)
 struct KRecDev { int32_t slot, words, first, pad; double score; };
 
 // lower bound of w in the ascending q[0, n); -1 if absent
@@ -120,43 +100,8 @@ __global__ __launch_bounds__(K_THREADS) void k_kfdb_compact(const int32_t *__res
     }
 }
 
-namespace {
-struct KState {                   // KeyFrame::mnLoopQuery .. mRelocScore; scores read 0.0f before their first write (orbk.h)
-    uint64_t loop_q = 0, reloc_q = 0;
-    int loop_w = 0, reloc_w = 0;
-    float loop_s = 0.0f, reloc_s = 0.0f;
-};
-struct KSlot { uint64_t id; long long off; int len; bool live; KState *st; };
-struct KPending {
-    bool active = false;
-    uint64_t qid = 0;
-    int min_common = 0;
-    float min_score = 0.0f;
-    std::vector<uint64_t> ids;
-    std::vector<float> si;
-};
 struct KRec { int slot, words, first; double score; };
-}  // namespace
 
-struct orbk_database {
-    int device = 0, nwords = 0;
-    mutable std::mutex mu;
-    std::unordered_map<uint64_t, KState> state;        // by id: outlives membership (erase, clear, re-add)
-    std::unordered_map<uint64_t, int> slot_of;         // live ids
-    std::vector<KSlot> slots;                          // add order; erased slots stay until the next compaction
-    long long tail = 0, live_entries = 0;
-    int nlive = 0;
-    KPending pending[2];
-    // device arena
-    int32_t *d_ids = nullptr; double *d_vals = nullptr; KSlotDev *d_slots = nullptr;
-    long long cap_entries = 0; int cap_slots = 0;
-    // per-query I/O: [query ids | query vals | counter | records], one copy in and one copy out
-    uint8_t *d_io = nullptr, *h_io = nullptr; size_t cap_io = 0;
-    int rec_hint = 0;                                  // records copied back with the counter (grows with the last count)
-    hipStream_t stream = nullptr;
-};
-
-static size_t align16(size_t b) { return (b + 15) & ~(size_t)15; }
 static size_t query_bytes(int n) { return align16((size_t)n * 4) + align16((size_t)n * 8); }
 
 static int check_bow(const orbk_database *db, const int32_t *ids, const double *vals, int n)
@@ -170,75 +115,11 @@ static int check_bow(const orbk_database *db, const int32_t *ids, const double *
     return ORBX_OK;
 }
 
-static int ensure_io(orbk_database *db, size_t bytes)
+hipError_t orbk_launch_compact(const int32_t *src_ids, const double *src_vals, int32_t *dst_ids, double *dst_vals,
+                               const long long *d_plan, int nplan, hipStream_t s)
 {
-    if (bytes <= db->cap_io) return ORBX_OK;
-    KHIP(hipStreamSynchronize(db->stream));
-    (void)hipFree(db->d_io); (void)hipHostFree(db->h_io);
-    db->d_io = nullptr; db->h_io = nullptr; db->cap_io = 0;
-    const size_t cap = align16(bytes + bytes / 2);
-    KHIP(hipMalloc((void **)&db->d_io, cap));
-    KHIP(hipHostMalloc((void **)&db->h_io, cap, hipHostMallocDefault));
-    db->cap_io = cap;
-    return ORBX_OK;
-}
-
-// Make room for one more slot of n entries: drop erased slots and, if still short, move to larger buffers.  The slot order
-// (the add order) is kept.
-static int make_room(orbk_database *db, int n)
-{
-    if ((int)db->slots.size() < db->cap_slots && db->tail + n <= db->cap_entries) return ORBX_OK;
-    const long long need_e = db->live_entries + n;
-    const int need_s = db->nlive + 1;
-    const long long new_ce = std::max(db->cap_entries, 2 * need_e);
-    const int new_cs = std::max(db->cap_slots, 2 * need_s);
-    int32_t *n_ids = nullptr; double *n_vals = nullptr; KSlotDev *n_slots = nullptr;
-    KHIP(hipStreamSynchronize(db->stream));
-    KHIP(hipMalloc((void **)&n_ids, (size_t)new_ce * 4));
-    if (hipMalloc((void **)&n_vals, (size_t)new_ce * 8) != hipSuccess || hipMalloc((void **)&n_slots, (size_t)new_cs * sizeof(KSlotDev)) != hipSuccess) {
-        (void)hipFree(n_ids); (void)hipFree(n_vals);
-        return kfail(ORBX_E_HIP, "keyframe arena of %lld entries / %d slots: out of device memory", new_ce, new_cs);
-    }
-    std::vector<long long> plan;
-    std::vector<KSlotDev> table;
-    std::vector<KSlot> kept;
-    long long off = 0;
-    for (const KSlot &s : db->slots) {
-        if (!s.live) continue;
-        if (s.len > 0) { plan.push_back(s.off); plan.push_back(off); plan.push_back(s.len); }
-        KSlot t = s; t.off = off;
-        table.push_back(KSlotDev{off, s.len, 0});
-        kept.push_back(t);
-        off += s.len;
-    }
-    const int nplan = (int)(plan.size() / 3);
-    long long *d_plan = nullptr;
-    int rc = ORBX_OK;
-    if (nplan > 0) {
-        if (hipMalloc((void **)&d_plan, plan.size() * 8) != hipSuccess ||
-            hipMemcpy(d_plan, plan.data(), plan.size() * 8, hipMemcpyHostToDevice) != hipSuccess) rc = ORBX_E_HIP;
-        if (rc == ORBX_OK) {
-            hipLaunchKernelGGL(k_kfdb_compact, dim3((nplan + 3) / 4), dim3(K_THREADS), 0, db->stream, db->d_ids, db->d_vals, n_ids, n_vals,
-                               d_plan, nplan);
-            if (hipGetLastError() != hipSuccess) rc = ORBX_E_HIP;
-        }
-    }
-    if (rc == ORBX_OK && !table.empty() &&
-        hipMemcpyAsync(n_slots, table.data(), table.size() * sizeof(KSlotDev), hipMemcpyHostToDevice, db->stream) != hipSuccess) rc = ORBX_E_HIP;
-    if (rc == ORBX_OK && hipStreamSynchronize(db->stream) != hipSuccess) rc = ORBX_E_HIP;
-    (void)hipFree(d_plan);
-    if (rc != ORBX_OK) {
-        (void)hipFree(n_ids); (void)hipFree(n_vals); (void)hipFree(n_slots);
-        return kfail(ORBX_E_HIP, "keyframe arena compaction failed");
-    }
-    (void)hipFree(db->d_ids); (void)hipFree(db->d_vals); (void)hipFree(db->d_slots);
-    db->d_ids = n_ids; db->d_vals = n_vals; db->d_slots = n_slots;
-    db->cap_entries = new_ce; db->cap_slots = new_cs;
-    db->slots.swap(kept);
-    db->tail = off;
-    db->slot_of.clear();
-    for (int i = 0; i < (int)db->slots.size(); i++) db->slot_of[db->slots[i].id] = i;
-    return ORBX_OK;
+    hipLaunchKernelGGL(k_kfdb_compact, dim3((nplan + 3) / 4), dim3(K_THREADS), 0, s, src_ids, src_vals, dst_ids, dst_vals, d_plan, nplan);
+    return hipGetLastError();
 }
 
 // The scoring pass: one record per live slot sharing a word with the query, in no particular order.
@@ -248,13 +129,13 @@ static int run_score(orbk_database *db, const int32_t *ids, const double *vals, 
     if (n == 0 || db->nlive == 0) return ORBX_OK;
     const int nslots = (int)db->slots.size();
     const size_t qb = query_bytes(n);
-    int rc = ensure_io(db, qb + 16 + (size_t)nslots * sizeof(KRecDev));
+    int rc = orbk_ensure_io(db, qb + 16 + (size_t)nslots * sizeof(KRecDev));
     if (rc != ORBX_OK) return rc;
     std::memcpy(db->h_io, ids, (size_t)n * 4);
     std::memcpy(db->h_io + align16((size_t)n * 4), vals, (size_t)n * 8);
     std::memset(db->h_io + qb, 0, 16);
     KHIP(hipMemcpyAsync(db->d_io, db->h_io, qb + 16, hipMemcpyHostToDevice, db->stream));
-    const int32_t *d_q = reinterpret_cast<const int32_t *>(db->d_io);
+    const int32_t *d_q = reinterpret_cast<const int32_t *>(db->d_io.get());
     const double *d_qv = reinterpret_cast<const double *>(db->d_io + align16((size_t)n * 4));
     int32_t *d_cnt = reinterpret_cast<int32_t *>(db->d_io + qb);
     KRecDev *d_rec = reinterpret_cast<KRecDev *>(db->d_io + qb + 16);
@@ -285,44 +166,6 @@ static int run_score(orbk_database *db, const int32_t *ids, const double *vals, 
     return ORBX_OK;
 }
 
-extern "C" void orbk_destroy(orbk_database *db)
-{
-    if (!db) return;
-    (void)hipSetDevice(db->device);
-    if (db->stream) (void)hipStreamSynchronize(db->stream);
-    (void)hipFree(db->d_ids); (void)hipFree(db->d_vals); (void)hipFree(db->d_slots); (void)hipFree(db->d_io);
-    (void)hipHostFree(db->h_io);
-    if (db->stream) (void)hipStreamDestroy(db->stream);
-    delete db;
-}
-
-extern "C" int orbk_create(orbk_database **out, int device, int nwords, int scoring, int max_keyframes, int max_entries)
-{
-    if (!out) return kfail(ORBX_E_INVALID, "NULL argument");
-    *out = nullptr;
-    if (nwords <= 0) return kfail(ORBX_E_INVALID, "nwords = %d", nwords);
-    if (scoring != ORBV_L1_NORM) return kfail(ORBX_E_INVALID, "scoring type %d: the keyframe database scores with L1 only", scoring);
-    if (max_keyframes < 0 || max_entries < 0) return kfail(ORBX_E_INVALID, "negative capacity");
-    int ndev = 0;
-    const hipError_t e = hipGetDeviceCount(&ndev);
-    if (e != hipSuccess || ndev <= 0) return kfail(ORBX_E_HIP, "no HIP device: liborbx has no CPU path (%s)", hipGetErrorString(e));
-    if (device < 0 || device >= ndev) return kfail(ORBX_E_INVALID, "device %d of %d", device, ndev);
-    KHIP(hipSetDevice(device));
-    orbk_database *db = new orbk_database();
-    db->device = device; db->nwords = nwords;
-    db->cap_slots = std::max(max_keyframes, 4);
-    db->cap_entries = std::max<long long>(max_entries, 256);
-    if (hipStreamCreateWithFlags(&db->stream, hipStreamNonBlocking) != hipSuccess ||
-        hipMalloc((void **)&db->d_ids, (size_t)db->cap_entries * 4) != hipSuccess ||
-        hipMalloc((void **)&db->d_vals, (size_t)db->cap_entries * 8) != hipSuccess ||
-        hipMalloc((void **)&db->d_slots, (size_t)db->cap_slots * sizeof(KSlotDev)) != hipSuccess) {
-        orbk_destroy(db);
-        return kfail(ORBX_E_HIP, "keyframe database allocation failed");
-    }
-    *out = db;
-    return ORBX_OK;
-}
-
 extern "C" int orbk_add(orbk_database *db, uint64_t id, const int32_t *word_ids, const double *values, int n)
 {
     if (!db) return kfail(ORBX_E_INVALID, "NULL handle");
@@ -331,8 +174,8 @@ extern "C" int orbk_add(orbk_database *db, uint64_t id, const int32_t *word_ids,
     if (rc != ORBX_OK) return rc;
     if (db->slot_of.count(id)) return kfail(ORBX_E_INVALID, "keyframe %llu is already in the database", (unsigned long long)id);
     KHIP(hipSetDevice(db->device));
-    if ((rc = make_room(db, n)) != ORBX_OK) return rc;
-    if ((rc = ensure_io(db, align16((size_t)n * 4) + (size_t)n * 8 + sizeof(KSlotDev))) != ORBX_OK) return rc;
+    if ((rc = orbk_make_room(db, n)) != ORBX_OK) return rc;
+    if ((rc = orbk_ensure_io(db, align16((size_t)n * 4) + (size_t)n * 8 + sizeof(KSlotDev))) != ORBX_OK) return rc;
     const int s = (int)db->slots.size();
     const long long off = db->tail;
     const KSlotDev sd{off, n, 0};

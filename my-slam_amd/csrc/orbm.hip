@@ -15,39 +15,12 @@
 #include "orbm_internal.h"
 #include "orbm_accept.h"
 
-static thread_local std::string g_merr;
-int mfail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_merr = buf;
-    return code;
-}
-extern "C" const char *orbm_last_error(void) { return g_merr.c_str(); }
-
-// ---- pinned staging arena (see orbm_internal.h) ----
-int orbm_arena_begin(orbm_matcher *m)
-{
-    if (m->arena_want > m->arena_cap) {          // grow between calls only: nothing is in flight here
-        MHIPCHK(hipStreamSynchronize(m->stream));
-        (void)hipHostFree(m->arena); m->arena = nullptr; m->arena_cap = 0;
-        const size_t cap = m->arena_want + m->arena_want / 2 + (64u << 10);
-        MHIPCHK(hipHostMalloc((void **)&m->arena, cap, hipHostMallocDefault));
-        (void)hipFree(m->d_arena); m->d_arena = nullptr;
-        if (hipMalloc((void **)&m->d_arena, cap) != hipSuccess) { m->d_arena = nullptr; (void)hipGetLastError(); }
-        m->arena_cap = cap;
-    }
-    m->arena_used = 0; m->arena_want = 0; m->npend = 0;
-    return ORBX_OK;
-}
+// ---- pinned staging arena (see orbm_internal.h; orbm_arena_begin is in orbm_workspace.cc) ----
 static void *arena_take(orbm_matcher *m, size_t bytes)
 {
     const size_t a = (bytes + 63) & ~(size_t)63;
     m->arena_want += a;
-    if (m->arena_used + a > m->arena_cap) return nullptr;     // this call falls back to a pageable copy; the next one has room
+    if (m->arena_used + a > m->arena_cap()) return nullptr;     // this call falls back to a pageable copy; the next one has room
     void *p = m->arena + m->arena_used;
     m->arena_used += a;
     return p;
@@ -278,97 +251,12 @@ extern "C" int orbm_distance(const uint8_t a[32], const uint8_t b[32])
     return dist;
 }
 
-extern "C" void orbm_destroy(orbm_matcher *m)
-{
-    if (!m) return;
-    (void)hipSetDevice(m->device);
-    (void)hipFree(m->d_q); (void)hipFree(m->d_t); (void)hipFree(m->d_off); (void)hipFree(m->d_idx);
-    (void)hipFree(m->d_out); (void)hipFree(m->d_part);
-    orbm_grid_free(m->grid); orbm_grid_free(m->grid2);
-    if (m->stream) (void)hipStreamDestroy(m->stream);
-    (void)hipHostFree(m->arena); (void)hipFree(m->d_arena);
-    (void)hipFree(m->d_dd);
-    delete m;
-}
-
-extern "C" int orbm_create(orbm_matcher **out, int device, int max_queries, int max_train, int max_pairs)
-{
-    if (!out) return mfail(ORBX_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (max_queries < 1 || max_train < 1 || max_pairs < 0) return mfail(ORBX_E_INVALID, "bad sizes");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return mfail(ORBX_E_HIP, "no HIP device: liborbx has no CPU path");
-    if (device < 0 || device >= ndev) return mfail(ORBX_E_INVALID, "device %d of %d", device, ndev);
-    MHIPCHK(hipSetDevice(device));
-    orbm_matcher *m = new orbm_matcher();
-    m->device = device; m->max_q = max_queries; m->max_t = max_train; m->max_pairs = max_pairs;
-    { const char *e = getenv("ORBM_DENSE"); m->dense_popcount = e && !strcmp(e, "popcount"); }
-    const size_t outn = std::max<size_t>((size_t)3 * max_queries, (size_t)max_pairs);
-    if (hipMalloc((void **)&m->d_q, (size_t)max_queries * 32) != hipSuccess ||
-        hipMalloc((void **)&m->d_t, (size_t)max_train * 32) != hipSuccess ||
-        hipMalloc((void **)&m->d_off, ((size_t)max_queries + 1) * 4) != hipSuccess ||
-        hipMalloc((void **)&m->d_idx, std::max<size_t>((size_t)max_pairs, 1) * 4) != hipSuccess ||
-        hipMalloc((void **)&m->d_out, outn * 4) != hipSuccess ||
-        hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking) != hipSuccess) {
-        orbm_destroy(m);
-        return mfail(ORBX_E_HIP, "matcher workspace allocation failed");
-    }
-    *out = m;
-    return ORBX_OK;
-}
-
-void orbm_grid_free(OrbmGrid &g)
-{
-    (void)hipFree(g.kx); (void)hipFree(g.ky); (void)hipFree(g.koct); (void)hipFree(g.cell_start); (void)hipFree(g.items); (void)hipFree(g.cell_of);
-    g.kx = g.ky = nullptr; g.koct = g.cell_start = g.items = g.cell_of = nullptr;
-}
-
-// Grows the workspace (never shrinks it).  The reference's matcher has no size limit (it works on std::vectors), so every entry
-// point that finds its inputs larger than the handle grows the handle instead of refusing; a caller that knows its sizes calls this
-// once up front and no call allocates.  Growing max_train drops the Frame grid in the handle (orbm_grid_build again).
-extern "C" int orbm_reserve(orbm_matcher *m, int max_queries, int max_train, int max_pairs)
-{
-    if (!m) return mfail(ORBX_E_INVALID, "NULL handle");
-    const int nq = std::max(m->max_q, max_queries), nt = std::max(m->max_t, max_train), np = std::max(m->max_pairs, max_pairs);
-    if (nq == m->max_q && nt == m->max_t && np == m->max_pairs) return ORBX_OK;
-    MHIPCHK(hipSetDevice(m->device));
-    MHIPCHK(hipStreamSynchronize(m->stream));
-    if (nq > m->max_q) {
-        (void)hipFree(m->d_q); (void)hipFree(m->d_off); m->d_q = nullptr; m->d_off = nullptr;
-        MHIPCHK(hipMalloc((void **)&m->d_q, (size_t)nq * 32));
-        MHIPCHK(hipMalloc((void **)&m->d_off, ((size_t)nq + 1) * 4));
-    }
-    if (nt > m->max_t) {
-        (void)hipFree(m->d_t); m->d_t = nullptr;
-        MHIPCHK(hipMalloc((void **)&m->d_t, (size_t)nt * 32));
-        orbm_grid_free(m->grid); orbm_grid_free(m->grid2); m->grid_ok = false; m->grid2_ok = false;     // sized by max_train
-    }
-    if (np > m->max_pairs) {
-        (void)hipFree(m->d_idx); m->d_idx = nullptr;
-        MHIPCHK(hipMalloc((void **)&m->d_idx, std::max<size_t>((size_t)np, 1) * 4));
-    }
-    const size_t out_old = std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs), out_new = std::max<size_t>((size_t)3 * nq, (size_t)np);
-    if (out_new > out_old) {
-        (void)hipFree(m->d_out); m->d_out = nullptr;
-        MHIPCHK(hipMalloc((void **)&m->d_out, out_new * 4));
-    }
-    m->max_q = nq; m->max_t = nt; m->max_pairs = np;
-    return ORBX_OK;
-}
-int orbm_grow(orbm_matcher *m, long long need_q, long long need_t, long long need_pairs)
-{
-    if (need_q > (1ll << 28) || need_t > (1ll << 28) || need_pairs > (1ll << 30)) return mfail(ORBX_E_CAPACITY, "request beyond 2^28 descriptors / 2^30 pairs");
-    auto up = [](long long need, int have) { return need > have ? (int)std::min<long long>(need + need / 2, 1ll << 30) : have; };
-    return orbm_reserve(m, up(need_q, m->max_q), up(need_t, m->max_t), up(need_pairs, m->max_pairs));
-}
-
-static int check_csr(const int32_t *off, const int32_t *idx, int nq, int nt, int max_pairs, int *total)
+static int check_csr(const int32_t *off, const int32_t *idx, int nq, int nt, int *total)
 {
     if (off[0] != 0) return mfail(ORBX_E_INVALID, "cand_off[0] must be 0");
     for (int i = 0; i < nq; i++)
         if (off[i + 1] < off[i]) return mfail(ORBX_E_INVALID, "cand_off not monotone at %d", i);
     *total = off[nq];
-    (void)max_pairs;
     if (*total > 0 && !idx) return mfail(ORBX_E_INVALID, "cand_idx is NULL");
     for (int c = 0; c < *total; c++)
         if (idx[c] < 0 || idx[c] >= nt) return mfail(ORBX_E_INVALID, "cand_idx[%d]=%d outside [0,%d)", c, idx[c], nt);
@@ -387,23 +275,6 @@ static int pick_splits(int nq_cap, int nbatch, int nt_hint)
     while (S > 1 && nt_hint / S < 16) S--;       // keep >= 16 train descriptors per split
     return S;
 }
-static int ensure_partials(orbm_matcher *m, size_t need, hipStream_t s = nullptr)
-{
-    if (need <= m->part_elems) return ORBX_OK;
-    {   // growing means synchronise + free + allocate: not inside a stream capture (warm the handle up with the same arguments first)
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive)
-            return mfail(ORBX_E_INVALID, "the matcher's partial buffer must grow (%zu -> %zu pairs) while the stream is being captured: run the call once outside the capture", m->part_elems, need);
-        (void)hipGetLastError();
-    }
-    MHIPCHK(hipDeviceSynchronize());
-    (void)hipFree(m->d_part);
-    m->d_part = nullptr; m->part_elems = 0;
-    MHIPCHK(hipMalloc((void **)&m->d_part, need * sizeof(uint2)));
-    m->part_elems = need;
-    return ORBX_OK;
-}
-
 extern "C" int orbm_best2(orbm_matcher *m, const uint8_t *q, int nq, const uint8_t *t, int nt,
                           const int32_t *cand_off, const int32_t *cand_idx,
                           int32_t *best_idx, int32_t *best_d, int32_t *second_d)
@@ -421,13 +292,13 @@ extern "C" int orbm_best2(orbm_matcher *m, const uint8_t *q, int nq, const uint8
     int32_t *o_bi = m->d_out, *o_bd = m->d_out + nq, *o_sd = m->d_out + 2 * (size_t)nq;
     if (cand_off) {
         int total = 0;
-        MTRY(check_csr(cand_off, cand_idx, nq, nt, m->max_pairs, &total));
+        MTRY(check_csr(cand_off, cand_idx, nq, nt, &total));
         MTRY(orbm_h2d(m, m->d_off, cand_off, ((size_t)nq + 1) * 4, s));
         if (total > 0) MTRY(orbm_h2d(m, m->d_idx, cand_idx, (size_t)total * 4, s));
         hipLaunchKernelGGL(k_best2_csr, dim3((nq + 3) / 4), dim3(M_THREADS), 0, s, m->d_q, nq, m->d_t, m->d_off, m->d_idx, o_bi, o_bd, o_sd);
     } else {
         const int S = m->dense_popcount ? pick_splits(nq, 1, nt) : orbm_mfma_splits(nq, nt, 1);
-        int rc = ensure_partials(m, (size_t)S * nq);
+        int rc = orbm_ensure_partials(m, (size_t)S * nq);
         if (rc != ORBX_OK) return rc;
         if (m->dense_popcount)
             hipLaunchKernelGGL(k_best2_dense, dim3((nq + M_THREADS - 1) / M_THREADS, 1, S), dim3(M_THREADS), 0, s,
@@ -460,7 +331,7 @@ extern "C" int orbm_distances(orbm_matcher *m, const uint8_t *q, int nq, const u
     long long total;
     if (cand_off) {
         int tot = 0;
-        MTRY(check_csr(cand_off, cand_idx, nq, nt, m->max_pairs, &tot));
+        MTRY(check_csr(cand_off, cand_idx, nq, nt, &tot));
         total = tot;
         if (total == 0) return ORBX_OK;
         MTRY(orbm_h2d(m, m->d_off, cand_off, ((size_t)nq + 1) * 4, s));
@@ -469,8 +340,8 @@ extern "C" int orbm_distances(orbm_matcher *m, const uint8_t *q, int nq, const u
                            m->d_q, nq, m->d_t, m->d_off, m->d_idx, (int)total, m->d_out);
     } else {
         total = (long long)nq * nt;
-        if (total > (long long)std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs))
-            return mfail(ORBX_E_CAPACITY, "dense distances need %lld ints, matcher sized for %d pairs", total, m->max_pairs);
+        if (total > (long long)m->d_out.count())
+            return mfail(ORBX_E_CAPACITY, "dense distances need %lld ints, matcher sized for %d pairs", total, m->max_pairs());
         hipLaunchKernelGGL(k_dist_dense, dim3((unsigned)((total + M_THREADS - 1) / M_THREADS)), dim3(M_THREADS), 0, s,
                            m->d_q, nq, m->d_t, nt, m->d_out);
     }
@@ -484,7 +355,7 @@ static int launch_dense_batch(orbm_matcher *m, const uint8_t *d_q, const int32_t
                               const int32_t *d_nt, int cap, int nbatch, hipStream_t s, int *S_out)
 {
     const int S = m->dense_popcount ? pick_splits(cap, nbatch, cap) : orbm_mfma_splits(cap, cap, nbatch);
-    int rc = ensure_partials(m, (size_t)(S + 1) * nbatch * cap, s);     // + one slot per query for k_merge_keys
+    int rc = orbm_ensure_partials(m, (size_t)(S + 1) * nbatch * cap, s);     // + one slot per query for k_merge_keys
     if (rc != ORBX_OK) return rc;
     if (m->dense_popcount)
         hipLaunchKernelGGL(k_best2_dense, dim3((cap + M_THREADS - 1) / M_THREADS, nbatch, S), dim3(M_THREADS), 0, s,
@@ -684,7 +555,7 @@ static int search_by_bow_device(orbm_matcher *m,
         if (fv_kf_idx[c] < 0 || fv_kf_idx[c] >= n_kf) return mfail(ORBX_E_INVALID, "key-frame feature index %d outside [0,%d)", fv_kf_idx[c], n_kf);
     for (int c = 0; c < nfi; c++)
         if (fv_f_idx[c] < 0 || fv_f_idx[c] >= n_f) return mfail(ORBX_E_INVALID, "frame feature index %d outside [0,%d)", fv_f_idx[c], n_f);
-    if ((size_t)n_f > std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs)) return 1;     // the match table lives in d_out
+    if ((size_t)n_f > m->d_out.count()) return 1;     // the match table lives in d_out
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = m->stream;
     MTRY(orbm_arena_begin(m));

@@ -139,7 +139,7 @@ extern "C" int orbm_frustum(orbm_matcher *m, const orbm_frame_view *view, int n,
     const int pv = in.add(view, sizeof(orbm_frame_view)), ps = in.add(skip, (size_t)n), px = in.add(xw, (size_t)n * 12),
               pn = in.add(normal, (size_t)n * 12), pa = in.add(mf_max, (size_t)n * 4), pi = in.add(mf_min, (size_t)n * 4);
     MTRY(in.upload(s));
-    float *o = reinterpret_cast<float *>(m->d_out);
+    float *o = reinterpret_cast<float *>(m->d_out.get());
     const size_t N = (size_t)n;
     uint8_t *d_status = reinterpret_cast<uint8_t *>(m->d_out + 5 * N);
     orbm_frustum_launch(in.at<orbm_frame_view>(pv), n, in.at<uint8_t>(ps), in.at<float>(px), in.at<float>(pn), in.at<float>(pa),

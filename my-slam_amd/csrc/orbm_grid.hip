@@ -179,19 +179,6 @@ __global__ __launch_bounds__(M_THREADS) void k_search_area(OrbmGrid g, const uin
 // -------------------------------------------------------------------------------------------------
 // C ABI
 // -------------------------------------------------------------------------------------------------
-static int ensure_grid(orbm_matcher *m, OrbmGrid &g)
-{
-    if (g.cell_start) return ORBX_OK;
-    const size_t n = (size_t)m->max_t;
-    MHIPCHK(hipMalloc((void **)&g.kx, n * 4));
-    MHIPCHK(hipMalloc((void **)&g.ky, n * 4));
-    MHIPCHK(hipMalloc((void **)&g.koct, n * 4));
-    MHIPCHK(hipMalloc((void **)&g.items, n * 4));
-    MHIPCHK(hipMalloc((void **)&g.cell_of, n * 4));
-    MHIPCHK(hipMalloc((void **)&g.cell_start, (ORBM_GRID_CELLS + 1) * 4));
-    return ORBX_OK;
-}
-
 // cv::undistortPoints(src, dst, K, distCoeffs, noArray(), K) of OpenCV 3.1.0 for one point (cvUndistortPoints: camera matrix
 // and coefficients converted to double, ITERS = 5, no tilt, R = I, P = K).  Called by Frame::UndistortKeyPoints (src/Frame.cc:421)
 // and Frame::ComputeImageBounds (:449).
@@ -248,22 +235,22 @@ extern "C" int orbm_image_bounds(int width, int height, float fx, float fy, floa
 
 // Builds a grid slot.  The keypoints are staged in the pinned arena of the current call (the caller has run orbm_arena_begin) and
 // go to the handle's d_out (a temporary block when that is too small); the kernel is queued on the handle's stream.
-int orbm_grid_build_into(orbm_matcher *m, OrbmGrid &g, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y,
+int orbm_grid_build_into(orbm_matcher *m, int slot, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y,
                          float inv_w, float inv_h, float query_min_x, float query_min_y)
 {
-    MTRY(ensure_grid(m, g));
+    MTRY(orbm_grid_ensure(m, slot));
+    OrbmGrid &g = slot ? m->grid2 : m->grid;
     g.min_x = assign_min_x; g.min_y = assign_min_y; g.inv_w = inv_w; g.inv_h = inv_h; g.qmin_x = query_min_x; g.qmin_y = query_min_y;
     g.n = n;
     hipStream_t s = m->stream;
-    orbx_keypoint *d_kps = reinterpret_cast<orbx_keypoint *>(m->d_out);
+    orbx_keypoint *d_kps = reinterpret_cast<orbx_keypoint *>(m->d_out.get());
     const size_t need = (size_t)n * sizeof(orbx_keypoint);
-    const size_t have = std::max<size_t>((size_t)3 * m->max_q, (size_t)m->max_pairs) * 4;
-    void *tmp = nullptr;
-    if (need > have) { MHIPCHK(hipMalloc(&tmp, need)); d_kps = reinterpret_cast<orbx_keypoint *>(tmp); }
+    DevBuf<orbx_keypoint> tmp;                 // freed on every return path; on success after the synchronisation below
+    if (need > m->d_out.bytes()) { MTRY(tmp.grow(need, mfail, "grid keypoint staging")); d_kps = tmp; }
     if (n > 0) MTRY(orbm_h2d(m, d_kps, kps_un, need, s));
     hipLaunchKernelGGL(k_grid_build, dim3(1), dim3(G_THREADS), 0, s, g, d_kps);
     MHIPCHK(hipGetLastError());
-    if (tmp) { MHIPCHK(hipStreamSynchronize(s)); (void)hipFree(tmp); }
+    if (tmp) MHIPCHK(hipStreamSynchronize(s));
     return ORBX_OK;
 }
 
@@ -275,7 +262,7 @@ static int grid_build(orbm_matcher *m, const orbx_keypoint *kps_un, int n, float
     m->grid_ok = false;
     MTRY(orbm_grow(m, 0, n, 0));
     MTRY(orbm_arena_begin(m));
-    MTRY(orbm_grid_build_into(m, m->grid, kps_un, n, assign_min_x, assign_min_y, inv_w, inv_h, query_min_x, query_min_y));
+    MTRY(orbm_grid_build_into(m, 0, kps_un, n, assign_min_x, assign_min_y, inv_w, inv_h, query_min_x, query_min_y));
     MTRY(orbm_sync(m, m->stream));
     m->grid_ok = true;
     return ORBX_OK;

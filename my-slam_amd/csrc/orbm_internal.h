@@ -10,6 +10,7 @@
 #include <vector>
 #include <hip/hip_runtime.h>
 #include "../../include/orbm.h"
+#include "dev_buf.h"
 
 #define M_THREADS 256
 
@@ -25,6 +26,7 @@ int mfail(int code, const char *fmt, ...);
         if (mtry_ != ORBX_OK) return mtry_;   \
     } while (0)
 
+#ifdef __HIPCC__
 __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, const uint4 &b0, const uint4 &b1)
 {
     int d = __popc(a0.x ^ b0.x);
@@ -37,6 +39,7 @@ __device__ __forceinline__ int hamming256(const uint4 &a0, const uint4 &a1, cons
     d += __popc(a1.w ^ b1.w);
     return d;
 }
+#endif
 
 #define ORBM_GRID_COLS 64   // FRAME_GRID_COLS, include/Frame.h:38
 #define ORBM_GRID_ROWS 48   // FRAME_GRID_ROWS, include/Frame.h:37
@@ -94,28 +97,39 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
 #endif
 
 struct orbm_matcher {
-    int device = 0, max_q = 0, max_t = 0, max_pairs = 0;
+    int device = 0;
     hipStream_t stream = nullptr;
-    uint8_t *d_q = nullptr, *d_t = nullptr;
-    int32_t *d_off = nullptr, *d_idx = nullptr, *d_out = nullptr;   // d_out: max(3*max_q, max_pairs) ints
-    uint2 *d_part = nullptr; size_t part_elems = 0;                  // train-split partials (lazy)
+    DevBuf<uint8_t> d_q, d_t;
+    DevBuf<int32_t> d_off, d_idx, d_out;                             // d_out: max(3*max_q, max_pairs) ints
+    DevBuf<uint2> d_part;                                            // train-split partials (lazy)
     int dense_popcount = 0;                                          // ORBM_DENSE=popcount: the VALU kernel instead of the matrix cores (A/B record)
-    OrbmGrid grid = {};  bool grid_ok = false;                       // N1: Frame grid of the last orbm_grid_build
-    OrbmGrid grid2 = {}; bool grid2_ok = false;                      // second slot: orbm_search_by_sim3 searches two key frames
+    // N1: Frame grid of the last orbm_grid_build, and a second slot: orbm_search_by_sim3 searches two key frames.  A slot's six
+    // arrays are one block of max_t keypoints (grid_mem[slot]): all of them or none.  grid_ok: the slot has been built
+    OrbmGrid grid = {};  bool grid_ok = false;
+    OrbmGrid grid2 = {}; bool grid2_ok = false;
+    DevBuf<uint8_t> grid_mem[2];
     // pinned bump arena for the host-buffer entry points: pageable hipMemcpyAsync is a staged, synchronous copy of tens of
     // microseconds each; through pinned memory the copies of one call queue up behind each other and cost one round trip
-    uint8_t *arena = nullptr; size_t arena_cap = 0, arena_used = 0, arena_want = 0;
-    uint8_t *d_arena = nullptr;     // device mirror of the arena: the inputs of a call (InBlock) go up in ONE copy
+    PinBuf<uint8_t> arena; size_t arena_used = 0, arena_want = 0;
+    DevBuf<uint8_t> d_arena;        // device mirror of the arena: the inputs of a call (InBlock) go up in ONE copy
     struct Pend { void *dst; const void *src; size_t bytes; };
     Pend pend[8]; int npend = 0;
-    uint8_t *d_dd = nullptr; size_t dd_bytes = 0;      // orbm_mappoint.hip: scratch of orbm_distinctive_descriptors (lazy, its own block)
+    DevBuf<uint8_t> d_dd;           // orbm_mappoint.hip: scratch of orbm_distinctive_descriptors (lazy, its own block)
+    // the capacities the handle advertises are what its buffers hold
+    int max_q() const { return (int)std::min(std::min(d_q.bytes() / 32, (d_off.count() ? d_off.count() - 1 : 0)), d_out.count() / 3); }
+    int max_t() const { return (int)(d_t.bytes() / 32); }
+    int max_pairs() const { return (int)std::min(d_idx.count(), d_out.count()); }
+    size_t arena_cap() const { return std::min(arena.bytes(), d_arena.bytes()); }
 };
-// workspace growth (orbm.hip): the reference's matcher has no size limit, so entry points grow the handle instead of refusing
+// orbm_workspace.cc (host-only): workspace growth.  The reference's matcher has no size limit, so entry points grow the handle
+// instead of refusing.  A failed growth leaves the buffer empty and the capacity 0: the next call grows again.
 int orbm_grow(orbm_matcher *m, long long need_q, long long need_t, long long need_pairs);
-void orbm_grid_free(OrbmGrid &g);
+int orbm_grid_ensure(orbm_matcher *m, int slot);       // the slot's arrays, sized by max_t (dropped when max_t grows)
+int orbm_ensure_partials(orbm_matcher *m, size_t need, hipStream_t s = nullptr);          // d_part of `need` pairs
+int orbm_ensure_dd(orbm_matcher *m, size_t need, hipStream_t s);                            // d_dd of `need` bytes
 // orbm_grid.hip: builds a grid slot (asynchronous on the handle's stream unless it had to allocate a staging block), and the
-// windows + candidate distances pass the host-scanned matchers share (against grid slot g: NULL = m->grid)
-int orbm_grid_build_into(orbm_matcher *m, OrbmGrid &g, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y,
+// windows + candidate distances pass the host-scanned matchers share (against grid slot g: NULL = m->grid); slot 0 = m->grid, 1 = m->grid2
+int orbm_grid_build_into(orbm_matcher *m, int slot, const orbx_keypoint *kps_un, int n, float assign_min_x, float assign_min_y,
                          float inv_w, float inv_h, float query_min_x, float query_min_y);
 int orbm_area_pairs(orbm_matcher *m, const float *x, const float *y, const float *r, const int32_t *mn, const int32_t *mx, int nq,
                     const uint8_t *qdesc, const uint8_t *train_desc, int n_train,
@@ -179,7 +193,7 @@ struct InBlock {
     {
         if (total == 0) return ORBX_OK;
         m->arena_want += total;                          // when there is no room now, the next call has it
-        if (m->d_arena && m->arena_used + total <= m->arena_cap) {
+        if (m->arena_used + total <= m->arena_cap()) {
             host = m->arena + m->arena_used; dev = m->d_arena + m->arena_used;
             m->arena_used += total;
         } else {

@@ -421,8 +421,8 @@ extern "C" int orbm_search_by_sim3(orbm_matcher *m,
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     // both grids, then both searches, one synchronisation: key frame 1 -> slot `grid`, key frame 2 -> slot `grid2`
-    MTRY(orbm_grid_build_into(m, m->grid, kps1, n1, grid1->assign_min_x, grid1->assign_min_y, grid1->inv_w, grid1->inv_h, grid1->query_min_x, grid1->query_min_y));
-    MTRY(orbm_grid_build_into(m, m->grid2, kps2, n2, grid2->assign_min_x, grid2->assign_min_y, grid2->inv_w, grid2->inv_h, grid2->query_min_x, grid2->query_min_y));
+    MTRY(orbm_grid_build_into(m, 0, kps1, n1, grid1->assign_min_x, grid1->assign_min_y, grid1->inv_w, grid1->inv_h, grid1->query_min_x, grid1->query_min_y));
+    MTRY(orbm_grid_build_into(m, 1, kps2, n2, grid2->assign_min_x, grid2->assign_min_y, grid2->inv_w, grid2->inv_h, grid2->query_min_x, grid2->query_min_y));
     // the grid builder's keypoint staging in d_out is consumed by its kernel before the searches run (same stream), so d_out is free
     // again: the two searches share it
     InBlock in1(m), in2(m);

@@ -240,18 +240,7 @@ static int dd_scratch(orbm_matcher *m, int n_points, long long host_rows, hipStr
     if (host_rows >= 0) {
         o_off = o_out + dd_align(2 * np * 4); o_desc = o_off + dd_align((np + 1) * 4); need = o_desc + dd_align((size_t)host_rows * 32);
     }
-    if (need > m->dd_bytes) {
-        hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-        if (s && hipStreamIsCapturing(s, &st) == hipSuccess && st == hipStreamCaptureStatusActive)
-            return mfail(ORBX_E_INVALID, "the matcher's MapPoint scratch must grow (%zu -> %zu bytes) while the stream is being captured: run the call once outside the capture", m->dd_bytes, need);
-        (void)hipGetLastError();
-        MHIPCHK(hipStreamSynchronize(m->stream));
-        if (s && s != m->stream) MHIPCHK(hipStreamSynchronize(s));
-        (void)hipFree(m->d_dd); m->d_dd = nullptr; m->dd_bytes = 0;
-        const size_t cap = need + need / 2;
-        MHIPCHK(hipMalloc((void **)&m->d_dd, cap));
-        m->dd_bytes = cap;
-    }
+    MTRY(orbm_ensure_dd(m, need, s));
     uint8_t *b = m->d_dd;
     sc->cnt = (int32_t *)b;
     sc->key = (unsigned long long *)(b + o_key);

@@ -307,7 +307,7 @@ extern "C" int orbm_triangulate_matches(orbm_matcher *m, const orbm_camera *cam1
     const int pk2 = in.add(kps_un2, (size_t)n2 * sizeof(orbx_keypoint)), px2 = in.add(keys_xy2, (size_t)n2 * 8), pu2 = in.add(u_right2, (size_t)n2 * 4), pd2 = in.add(depth2, (size_t)n2 * 4);
     const int pm = in.add(matches, (size_t)n * 12);
     MTRY(in.upload(s));
-    float *d_x3d = reinterpret_cast<float *>(m->d_out);
+    float *d_x3d = reinterpret_cast<float *>(m->d_out.get());
     uint8_t *d_status = reinterpret_cast<uint8_t *>(m->d_out + 3 * (size_t)n);
     tri_launch(in.at<orbm_camera>(pc1), in.at<orbx_keypoint>(pk1), in.at<float>(px1), in.at<float>(pu1), in.at<float>(pd1), n1,
                in.at<orbm_camera>(pc2), ncams2, in.at<int32_t>(po), in.at<orbx_keypoint>(pk2), in.at<float>(px2), in.at<float>(pu2), in.at<float>(pd2),

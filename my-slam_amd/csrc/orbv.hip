@@ -12,42 +12,7 @@
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime.h>
-#include "../../include/orbv.h"
-
-static thread_local std::string g_verr;
-static int vfail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_verr = buf;
-    return code;
-}
-extern "C" const char *orbv_last_error(void) { return g_verr.c_str(); }
-#define VHIP(expr)                                                                               \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return vfail(ORBX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-struct orbv_vocabulary {
-    int k = 0, L = 0, scoring = 0, weighting = 0, device = 0;
-    std::vector<int32_t> parent, child_off, child_ids, word_of;   // per node (child lists in push order)
-    std::vector<uint8_t> desc;                                   // nnodes x 32
-    std::vector<double> weight;
-    int nwords = 0;
-    // device copies
-    int32_t *d_child_off = nullptr, *d_child_ids = nullptr, *d_word_of = nullptr;
-    uint8_t *d_desc = nullptr;
-    double *d_weight = nullptr;
-    // staging
-    uint8_t *d_feat = nullptr; int32_t *d_out_i = nullptr; double *d_out_w = nullptr; size_t cap_feat = 0;
-    hipStream_t stream = nullptr;
-    uint8_t *h_pin = nullptr;      // pinned: [cap_feat * 32] features in, [cap_feat * 16] results out
-};
+#include "orbv_internal.h"
 
 // greedy descent (TemplatedVocabulary.h:1218-1259): one WAVE per feature.  At every node the lanes take one child each
 // (all k descriptors are fetched in one memory round trip instead of k dependent ones), the wave's minimum of
@@ -89,17 +54,6 @@ __global__ __launch_bounds__(256) void k_voc_transform(const int32_t *__restrict
         node_id[i] = nid;
         weight[i] = nweight[final_id];
     }
-}
-
-extern "C" void orbv_destroy(orbv_vocabulary *v)
-{
-    if (!v) return;
-    (void)hipSetDevice(v->device);
-    (void)hipFree(v->d_child_off); (void)hipFree(v->d_child_ids); (void)hipFree(v->d_word_of); (void)hipFree(v->d_desc);
-    (void)hipFree(v->d_weight); (void)hipFree(v->d_feat); (void)hipFree(v->d_out_i); (void)hipFree(v->d_out_w);
-    (void)hipHostFree(v->h_pin);
-    if (v->stream) (void)hipStreamDestroy(v->stream);
-    delete v;
 }
 
 extern "C" int orbv_load_text(orbv_vocabulary **out, const char *path, int device)
@@ -152,7 +106,7 @@ extern "C" int orbv_load_text(orbv_vocabulary **out, const char *path, int devic
 #define VALLOC(dst, src)                                                                                       \
     do {                                                                                                       \
         const size_t b_ = (src).size() * sizeof((src)[0]);                                                     \
-        if (hipMalloc((void **)&(dst), b_ ? b_ : 256) != hipSuccess ||                                         \
+        if ((dst).grow(b_ ? b_ : 256, vfail, #dst) != ORBX_OK ||                                               \
             (b_ && hipMemcpy((dst), (src).data(), b_, hipMemcpyHostToDevice) != hipSuccess)) {                 \
             orbv_destroy(v); return vfail(ORBX_E_HIP, "vocabulary upload failed");                             \
         }                                                                                                      \
@@ -182,23 +136,14 @@ extern "C" int orbv_transform_features(orbv_vocabulary *v, const uint8_t *desc, 
     if (!desc || !word_id || !node_id || !weight) return vfail(ORBX_E_INVALID, "NULL buffer");
     VHIP(hipSetDevice(v->device));
     if (!v->stream) VHIP(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
-    if ((size_t)n > v->cap_feat) {
-        VHIP(hipStreamSynchronize(v->stream));
-        (void)hipFree(v->d_feat); (void)hipFree(v->d_out_i); (void)hipFree(v->d_out_w); (void)hipHostFree(v->h_pin);
-        v->d_feat = nullptr; v->d_out_i = nullptr; v->d_out_w = nullptr; v->h_pin = nullptr; v->cap_feat = 0;
-        const size_t cap = (size_t)n + (size_t)n / 4 + 64;
-        VHIP(hipMalloc((void **)&v->d_feat, cap * 32));
-        VHIP(hipMalloc((void **)&v->d_out_i, cap * 16));      // [cap] word | [cap] node | [cap] weight (double): one block, one copy back
-        VHIP(hipHostMalloc((void **)&v->h_pin, cap * 48, hipHostMallocDefault));
-        v->cap_feat = cap;
-    }
+    VTRY(orbv_ensure_feat(v, (size_t)n));
     // pinned staging + one stream: one copy in, one kernel, one copy out, one synchronisation
-    const size_t cap = v->cap_feat;
+    const size_t cap = v->cap_feat();
     std::memcpy(v->h_pin, desc, (size_t)n * 32);
     VHIP(hipMemcpyAsync(v->d_feat, v->h_pin, (size_t)n * 32, hipMemcpyHostToDevice, v->stream));
     const int nid_level = v->L - levelsup;      // <= 0: nid stays 0 (the root), :1228-1229
     int32_t *d_word = v->d_out_i, *d_node = v->d_out_i + cap;
-    double *d_w = reinterpret_cast<double *>(v->d_out_i + 2 * cap);
+    double *d_w = reinterpret_cast<double *>(v->d_out_i.get() + 2 * cap);
     hipLaunchKernelGGL(k_voc_transform, dim3((n + 3) / 4), dim3(256), 0, v->stream, v->d_child_off, v->d_child_ids, v->d_desc, v->d_word_of,
                        v->d_weight, v->d_feat, n, nid_level, d_word, d_node, d_w);
     VHIP(hipGetLastError());

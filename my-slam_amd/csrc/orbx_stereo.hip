@@ -141,8 +141,12 @@ __global__ __launch_bounds__(256) void k_stereo(StereoLevels lv, const orbx_keyp
 }
 
 #include <mutex>
-struct StereoScratch { void *p = nullptr; size_t bytes = 0; std::mutex mu; };
-static StereoScratch g_scr[16];   // per device; a call holds the device's scratch lock (stereo pairs are matched one at a time per device)
+#include "dev_buf.h"
+// per device; a call holds the device's scratch lock (stereo pairs are matched one at a time per device).  Never destroyed: the
+// HIP runtime may be gone when static destructors run
+struct StereoScratch { DevBuf<uint8_t> mem; std::mutex mu; };
+static StereoScratch *const g_scr = new StereoScratch[16];
+static int stereo_fail(int code, const char *, ...) { return code; }     // this entry point reports status codes only
 
 // host-side description of a handle's pyramid (orbx_capi.hip)
 int orbx_internal_levels(orbx_extractor *h, const uint8_t **base, int *w, int *hh, int *stride, float *scale, float *inv_scale, int *nlevels, int *device);
@@ -173,12 +177,8 @@ extern "C" int orbx_stereo_matches(orbx_extractor *left, orbx_extractor *right,
     const size_t need = al(bk) + al(bd) + al(brk) + al(brd) + 3 * al(bo) + 256;
     StereoScratch &sc = g_scr[devL & 15];
     std::lock_guard<std::mutex> lock(sc.mu);
-    if (need > sc.bytes) {
-        (void)hipFree(sc.p); sc.p = nullptr; sc.bytes = 0;
-        if (hipMalloc(&sc.p, need) != hipSuccess) return ORBX_E_HIP;
-        sc.bytes = need;
-    }
-    uint8_t *p = (uint8_t *)sc.p;
+    if (sc.mem.grow(need, stereo_fail, "stereo scratch") != ORBX_OK) return ORBX_E_HIP;
+    uint8_t *p = sc.mem;
     orbx_keypoint *d_kl = (orbx_keypoint *)p; p += al(bk);
     uint8_t *d_dl = p; p += al(bd);
     orbx_keypoint *d_kr = (orbx_keypoint *)p; p += al(brk);
