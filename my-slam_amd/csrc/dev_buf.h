@@ -1,7 +1,8 @@
-// dev_buf.h -- host-only.  The one owning buffer type of the matcher-side handles (orbm_matcher and its grid slots,
-// orbv_vocabulary, orbk_database, the stereo scratch): a device block (DevBuf) or a page-locked host block (PinBuf) whose pointer
-// and byte capacity change only together.  A handle's advertised capacities are derived from its buffers, so no call can run on a
-// block smaller than the handle claims.
+// dev_buf.h -- host-only.  The owning types of every handle (orbx_extractor, orbm_matcher and its grid slots, orbv_vocabulary,
+// orbk_database, the stereo scratch): a device block (DevBuf) or a page-locked host block (PinBuf) whose pointer and byte capacity
+// change only together, and move-only owners of a stream, an event and an instantiated graph (DevStream, DevEvent, DevGraphExec).
+// A handle's advertised capacities are derived from its buffers, so no call can run on a block smaller than the handle claims, and a
+// handle's destructor is its members' destructors: nothing is freed from a hand-written list.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -52,3 +53,48 @@ public:
     }
 };
 template <class T> using PinBuf = DevBuf<T, true>;
+
+// A stream, an event or an instantiated graph with one owner: empty by default, destroyed by reset() and by the destructor.
+template <class H, hipError_t (*kDestroy)(H)>
+class DevHandle {
+protected:
+    H h_ = nullptr;
+public:
+    DevHandle() = default;
+    explicit DevHandle(H h) : h_(h) {}
+    DevHandle(const DevHandle &) = delete;
+    DevHandle &operator=(const DevHandle &) = delete;
+    DevHandle(DevHandle &&o) noexcept : h_(o.h_) { o.h_ = nullptr; }
+    DevHandle &operator=(DevHandle &&o) noexcept
+    {
+        if (this != &o) { reset(); h_ = o.h_; o.h_ = nullptr; }
+        return *this;
+    }
+    ~DevHandle() { reset(); }
+    void reset()
+    {
+        if (h_) (void)kDestroy(h_);
+        h_ = nullptr;
+    }
+    H get() const { return h_; }
+    operator H() const { return h_; }
+protected:
+    // what create() of the owners below shares: on failure the owner is empty and the call returns ORBX_E_HIP through `fail`
+    template <class Create> int create_with(Create create, dev_fail_fn fail, const char *what)
+    {
+        reset();
+        const hipError_t e = create(&h_);
+        if (e == hipSuccess) return ORBX_OK;
+        h_ = nullptr;
+        (void)hipGetLastError();
+        return fail(ORBX_E_HIP, "%s: %s", what, hipGetErrorString(e));
+    }
+};
+struct DevStream : DevHandle<hipStream_t, hipStreamDestroy> {
+    int create(dev_fail_fn fail, const char *what) { return create_with([](hipStream_t *s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); }, fail, what); }
+};
+struct DevEvent : DevHandle<hipEvent_t, hipEventDestroy> {
+    int create(unsigned flags, dev_fail_fn fail, const char *what) { return create_with([flags](hipEvent_t *e) { return hipEventCreateWithFlags(e, flags); }, fail, what); }
+};
+// a graph is instantiated from a capture, which may fail without being an error: the owner takes what the capture gave (or nothing)
+struct DevGraphExec : DevHandle<hipGraphExec_t, hipGraphExecDestroy> { using DevHandle::DevHandle; };

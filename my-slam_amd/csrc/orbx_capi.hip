@@ -1,19 +1,15 @@
-// orbx_capi.hip -- host side of liborbx.so: the handle, its workspace and the C ABI.  Shapes are planned in orbx_plan.hip (host arithmetic,
-// no handle) and committed here; all pixel work is in the per-stage kernel files (orbx_pyramid/fast/octree/describe.hip).
+// orbx_capi.hip -- host side of liborbx.so: the per-call path of the extractor and its C ABI.  The handle is declared in orbx_handle.h; its
+// life and its lazy resources are in orbx_workspace.cc, shapes are planned in orbx_plan.cc (host arithmetic, no handle) and committed here;
+// all pixel work is in the per-stage kernel files (orbx_pyramid/fast/octree/describe.hip).
 #include <chrono>
-#include <cstdarg>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
 #include <string>
 #include <thread>
-#include <vector>
 
-#include "orbx_plan.h"
-#include "stage_pool.h"
+#include "orbx_handle.h"
 
 // A/B switches of orbx_extract_batch, read once per process
 static bool batch_equal_chunks() { static const bool on = getenv("ORBX_BATCH_EQUAL") != nullptr; return on; }   // A/B switch
@@ -21,84 +17,14 @@ static int batch_streams() { static const int n = [] { const char *e = getenv("O
 static bool batch_trace() { static const bool on = getenv("ORBX_BATCH_TRACE") != nullptr; return on; }      // host-side time split of a call, to stderr
 static bool batch_pinned_ok() { static const bool on = [] { const char *e = getenv("ORBX_BATCH_PINNED"); return !e || atoi(e) != 0; }(); return on; }   // page-locked caller memory is uploaded where it lies (0 keeps the staging copy: A/B switch)
 
-static thread_local std::string g_err;
-static int fail(int code, const char *fmt, ...)
-{
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    g_err = buf;
-    return code;
-}
-#define HIPCHK(expr)                                                                            \
-    do {                                                                                        \
-        hipError_t e_ = (expr);                                                                 \
-        if (e_ != hipSuccess) return fail(ORBX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
-
-extern "C" const char *orbx_last_error(void) { return g_err.c_str(); }
 extern "C" const char *orbx_version(void) { return "orbx 0.1 (gfx950)"; }
 
-#define ORBX_MAX_SUB 4
-struct orbx_extractor : PlanParams {   // the constructor's arguments and tables, the A/B switches and the table capacities are what the planner reads
-    int device = 0, max_w = 0, max_h = 0, max_batch = 0;
-    bool need_clear = true;
-    hipStream_t stream = nullptr;
-    hipStream_t aux[ORBX_MAX_SUB - 1] = {}; hipEvent_t ev_fork = nullptr, ev_join[ORBX_MAX_SUB - 1] = {}; int nsub = 1; int overlap_pyr = 0;
-    // current plan
-    int cur_w = 0, cur_h = 0; int last_batch = 0;
-    const uint8_t *last_input = nullptr; int last_in_stride = 0; long long last_in_frame = 0;
-    uint8_t *h_pyr = nullptr; size_t h_pyr_bytes = 0;      // page-locked staging of orbx_download_pyramid (lazy)
-    const uint8_t *pin_ptr = nullptr; int pin_n = 0; size_t pin_stride = 0, pin_bytes = 0; bool pin_is = false;   // last is_pinned_host() answer
-    // the plan of cur_w x cur_h, committed by ensure_plan(): all of it or none (level 0's source and blur_mode follow the call)
-    OrbxPlan plan; ResizeTab tabs[ORBX_MAX_LEVELS]; int resize_mode[ORBX_MAX_LEVELS]; FusePlan fuse[2]; TilePlan tile;
-    OrbxWork work;
-    int4 *d_bands = nullptr, *d_tiles = nullptr; int oct_cap_max = 0; size_t oct_lds = 0;
-    // allocations (sized for the max shape)
-    OrbxPlan max_plan; size_t pyr_bytes = 0; size_t pyr_level_off[ORBX_MAX_LEVELS];
-    uint8_t *d_input = nullptr; int in_stride = 0; size_t in_frame = 0;
-    uint8_t *d_pyr = nullptr;
-    int *d_tab_i = nullptr; short2 *d_tab_s = nullptr;
-    uint32_t *d_cells = nullptr;   // per-cell (level, row, column) table of the current plan
-    orbx_keypoint *d_kps = nullptr; uint8_t *d_desc = nullptr; int32_t *d_counts = nullptr, *d_status = nullptr;
-    uint8_t *h_in = nullptr;
-    // input format (orbx_set_input_format).  A colour frame is converted into d_input by one kernel ahead of the pyramid; the host entry
-    // points stage and upload it through h_color / d_color (allocated by the first colour call; pitches follow the call's width)
-    int fmt = ORBX_FMT_GRAY8; uint8_t *d_color = nullptr, *h_color = nullptr;
-    orbx_keypoint *h_kps = nullptr; uint8_t *h_desc = nullptr; int32_t *h_counts = nullptr, *h_status = nullptr;
-    uint8_t *d_out = nullptr, *h_out = nullptr; size_t out_hdr = 0, out_kps_bytes = 0, out_bytes = 0;   // the block the eight pointers above point into
-    std::vector<size_t> chunk_off;   // orbx_extract_batch: byte offset of every chunk's own [counts | status | keypoints | descriptors] block in d_out / h_out
-    int inflight = 0, inflight_frames = 0;      // orbx_extract_begin / orbx_extract_end
-    // orbx_extract_begin replays one HIP graph per shape (upload, ~10 kernels, download) instead of ~12 launches
-    hipGraphExec_t graph_exec = nullptr; int graph_fmt = 0; int graph_w = 0, graph_h = 0, graph_seen_w = 0, graph_seen_h = 0; bool graph_off = false; int graph_fails = 0;
-    // orbx_extract_batch in chunks: staging threads, two streams, one HIP graph per chunk (kernels + download) per shape
-    StagePool *pool = nullptr; int batch_chunk = 16;
-    std::vector<hipGraphExec_t> bgraph; int bg_w = 0, bg_h = 0, bg_n = 0, bg_chunk = 0; bool bg_off = false;
-    std::vector<hipEvent_t> ev_up, ev_done;
-    int profiling = 0; hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; float stage_ms[4] = {0, 0, 0, 0};
-    // profiling == 2: the stage events of the last ORBX_PROF_RING calls are recorded and never waited for by the library
-    hipEvent_t evr[ORBX_PROF_RING][5] = {}; long long ring_calls = 0;
-};
-
-// Stream captures against the rest of the process.  A capture is begun in RELAXED mode (this library issues nothing unsafe inside one,
-// and other threads' calls must not be judged against it), and the phases in which a handle uses synchronous runtime calls -- creation,
-// destruction, the table upload of a shape change -- exclude every capture of this library through one process-wide lock: on this runtime
-// a synchronous copy in one thread has been seen to fail, and to invalidate the capture of ANOTHER thread's handle, even in thread-local
-// mode (tests/test_threads_gpu.py, once in a dozen runs).  A capture that is invalidated all the same is not an error: the call runs
-// plainly and the capture is tried again on a later call (three times at most).
-static std::recursive_mutex &capture_mutex()
-{
-    static std::recursive_mutex m;
-    return m;
-}
 // Capture what `body` enqueues on s (body returns false if it failed) into an instantiated graph; null if the capture could not begin,
-// the body failed or the capture was invalidated.  capture_mutex() is held for the capture; a capture that began is always ended and its
+// the body failed or the capture was invalidated.  orbx_capture_mutex() is held for the capture; a capture that began is always ended and its
 // hipGraph_t destroyed; a failure leaves no sticky error behind.  Nothing has run then: the caller runs the work plainly.
-template <class Body> static hipGraphExec_t capture_graph(hipStream_t s, Body body)
+template <class Body> static DevGraphExec capture_graph(hipStream_t s, Body body)
 {
-    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
+    std::lock_guard<std::recursive_mutex> lk_(orbx_capture_mutex());
     hipGraphExec_t exec = nullptr;
     if (hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed) == hipSuccess) {
         const bool ok = body();
@@ -107,199 +33,44 @@ template <class Body> static hipGraphExec_t capture_graph(hipStream_t s, Body bo
         if (g) (void)hipGraphDestroy(g);
     }
     if (!exec) (void)hipGetLastError();
-    return exec;
+    return DevGraphExec(exec);
 }
-// the switches read at every create (tests and A/B runs set them between two handles of one process)
-static void read_create_switches(orbx_extractor *h)
-{
-    if (const char *e = getenv("ORBX_OCT_FAST")) h->oct_fast = atoi(e);
-    // ORBX_PYRAMID_TILES = "a[,tile width[,tile height[,min frames]]]": levels a + 1 .. last in one launch (0 = off = default).
-    // Bit-exact, and at 64 x 640x480 slower than the per-level launches (levels 3..7: 40 us against 27; without any store 30): the
-    // tiles' halos make it compute 1.8x the pixels, two waves per SIMD are all the 1920 tiles give.  Kept as an A/B switch.
-    if (const char *e = getenv("ORBX_PYRAMID_TILES")) { int a = 2, tw = 32, th = 32, mf = 8; const int n = sscanf(e, "%d,%d,%d,%d", &a, &tw, &th, &mf); if (n >= 1) h->tile_a = a; if (n >= 2) h->tile_w = tw; if (n >= 3) h->tile_h = th; if (n >= 4) h->tile_min_frames = mf; }
-    if (h->tile_w < 8 || h->tile_w > 128 || (h->tile_w & 3) || h->tile_h < 8 || h->tile_h > 128 || (h->tile_h & 3)) h->tile_a = 0;
-    if (const char *e = getenv("ORBX_PYRAMID_FUSE")) h->fuse_on = atoi(e);
-    if (const char *e = getenv("ORBX_OVERLAP_PYRAMID")) h->overlap_pyr = atoi(e) != 0;   // A/B switch for ORBX_OPT_OVERLAP_PYRAMID
-}
-static void free_all(orbx_extractor *h)
-{
-    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
-    if (!h) return;
-    hipSetDevice(h->device);
-    (void)hipHostFree(h->h_pyr);
-    hipFree(h->d_input); hipFree(h->d_pyr); hipFree(h->d_tab_i); hipFree(h->d_tab_s); hipFree(h->d_cells); hipFree(h->d_bands); hipFree(h->d_tiles);
-    hipFree(h->work.cand); hipFree(h->work.cand_count); hipFree(h->work.owner); hipFree(h->work.arena);
-    hipFree(h->work.sel); hipFree(h->work.nk); hipFree(h->work.ncand); hipFree(h->work.errflags);
-    hipFree(h->d_out); hipFree(h->d_color); (void)hipHostFree(h->h_color);
-    hipHostFree(h->h_in); hipHostFree(h->h_out);
-    if (h->graph_exec) hipGraphExecDestroy(h->graph_exec);
-    for (auto &g : h->bgraph) if (g) hipGraphExecDestroy(g);
-    delete h->pool;
-    for (auto &e : h->ev_up) if (e) hipEventDestroy(e);
-    for (auto &e : h->ev_done) if (e) hipEventDestroy(e);
-    for (auto &e : h->ev) if (e) hipEventDestroy(e);
-    for (auto &set : h->evr) for (auto &e : set) if (e) hipEventDestroy(e);
-    for (auto &e : h->ev_join) if (e) hipEventDestroy(e);
-    if (h->ev_fork) hipEventDestroy(h->ev_fork);
-    for (auto &a : h->aux) if (a) hipStreamDestroy(a);
-    if (h->stream) hipStreamDestroy(h->stream);
-    delete h;
-}
-
-extern "C" int orbx_create(orbx_extractor **out, int nfeatures, float scale_factor, int nlevels,
-                           int ini_th, int min_th, int device, int max_width, int max_height, int max_batch)
-{
-    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
-    if (!out) return fail(ORBX_E_INVALID, "out is NULL");
-    *out = nullptr;
-    if (nfeatures < 0 || nlevels < 1 || nlevels > ORBX_MAX_LEVELS || !(scale_factor > 1.0f) ||
-        max_width < 1 || max_height < 1 || max_batch < 1)
-        return fail(ORBX_E_INVALID, "bad constructor argument (nfeatures=%d scale=%g nlevels=%d max=%dx%dx%d)",
-                    nfeatures, scale_factor, nlevels, max_width, max_height, max_batch);
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-        return fail(ORBX_E_HIP, "no HIP device: liborbx has no CPU path");
-    if (device < 0 || device >= ndev) return fail(ORBX_E_INVALID, "device %d of %d", device, ndev);
-    HIPCHK(hipSetDevice(device));
-
-    struct FreeAll { void operator()(orbx_extractor *p) const { free_all(p); } };
-    std::unique_ptr<orbx_extractor, FreeAll> owner(new orbx_extractor());   // every failure exit below frees what was built so far
-    orbx_extractor *h = owner.get();
-    h->nfeatures = nfeatures; h->scale_factor = scale_factor; h->nlevels = nlevels;
-    h->ini_th = std::min(std::max(ini_th, 0), 255); h->min_th = std::min(std::max(min_th, 0), 255);
-    h->device = device; h->max_w = max_width; h->max_h = max_height; h->max_batch = max_batch;
-    memset(&h->work, 0, sizeof(h->work));
-    read_create_switches(h);
-    orbx_build_tables(h);
-
-    std::string why;
-    int rc = orbx_make_plan(*h, max_width, max_height, &h->max_plan, &why);
-    if (rc != ORBX_OK) return fail(rc, "max shape %dx%d: %s", max_width, max_height, why.c_str());
-    int max_list = 0;
-    for (int l = 0; l < nlevels; l++) max_list = std::max(max_list, h->max_plan.lv[l].list_cap);
-    h->oct_cap_max = std::max(max_list, 8);
-    h->oct_lds = orbx_octree_lds_bytes(h->oct_cap_max, 0, 0);
-    if (h->oct_lds > 150 * 1024) return fail(ORBX_E_INVALID, "nfeatures=%d needs %zu B of LDS for the quadtree (max 153600)", nfeatures, h->oct_lds);
-
-#define ALLOC(ptr, bytes)                                                                       \
-    do {                                                                                        \
-        hipError_t e_ = hipMalloc((void **)&(ptr), std::max<size_t>((bytes), 256));             \
-        if (e_ != hipSuccess) return fail(ORBX_E_HIP, "hipMalloc(%s, %zu): %s", #ptr, (size_t)(bytes), hipGetErrorString(e_)); \
-    } while (0)
-    const size_t B = (size_t)max_batch;
-    h->in_stride = (int)align_up(max_width, 64);
-    h->in_frame = align_up((size_t)h->in_stride * max_height, 256);
-    ALLOC(h->d_input, B * h->in_frame + 256);
-    size_t off = 0, tab_e = 0;
-    for (int l = 1; l < nlevels; l++) {
-        const OrbxLevel &L = h->max_plan.lv[l];
-        h->pyr_level_off[l] = off;
-        off += B * align_up(align_up(L.w, 64) * (size_t)L.h, 256);
-        tab_e += align_up((size_t)L.w + 4, 4) + align_up((size_t)L.h + 4, 4);
-    }
-    h->pyr_bytes = off; h->tab_elems = tab_e;
-    ALLOC(h->d_pyr, off + 256);   // slack: the 4x4 resize reads whole dwords around a row segment
-    ALLOC(h->d_tab_i, tab_e * sizeof(int));
-    ALLOC(h->d_tab_s, tab_e * sizeof(short2));
-    h->bands_cap = 2 * ((size_t)max_height / 8 + 4) * ORBX_MAX_LEVELS;
-    ALLOC(h->d_bands, h->bands_cap * sizeof(int4));
-    h->tiles_cap = 8192;
-    ALLOC(h->d_tiles, h->tiles_cap * sizeof(int4));
-    h->cells_cap = h->max_plan.ncells + 64 * nlevels;   // a smaller frame never has more cells; slack for rounding
-    ALLOC(h->d_cells, (size_t)h->cells_cap * sizeof(uint32_t));
-    const OrbxPlan &M = h->max_plan;
-    ALLOC(h->work.cand, B * M.cand_frame * sizeof(OrbxCand));
-    ALLOC(h->work.owner, B * M.cand_frame * sizeof(uint32_t));
-    ALLOC(h->work.arena, B * M.arena_frame * sizeof(OrbxNode));
-    ALLOC(h->work.sel, B * M.list_frame * sizeof(OrbxCand));
-    ALLOC(h->work.cand_count, B * ORBX_MAX_LEVELS * ORBX_CNT_STRIDE * sizeof(uint32_t));
-    ALLOC(h->work.nk, B * ORBX_MAX_LEVELS * sizeof(uint32_t));
-    ALLOC(h->work.ncand, B * ORBX_MAX_LEVELS * sizeof(uint32_t));
-    ALLOC(h->work.errflags, B * sizeof(uint32_t));
-    // the host-buffer entry points' staging outputs live in ONE block, [counts B | status B | keypoints B x cap | descriptors
-    // B x cap x 32], mirrored in pinned memory: a full batch (or a max_batch = 1 handle) comes back with a single copy
-    h->out_hdr = align_up(2 * B * sizeof(int32_t), 256);
-    h->out_kps_bytes = B * M.out_cap * sizeof(orbx_keypoint);
-    h->out_bytes = h->out_hdr + h->out_kps_bytes + B * M.out_cap * 32;
-    h->out_bytes += 256 * (B + 2);   // per-chunk blocks of orbx_extract_batch: one aligned header per chunk instead of one per batch
-    ALLOC(h->d_out, h->out_bytes);
-#undef ALLOC
-    if (hipHostMalloc((void **)&h->h_in, B * h->in_frame + 256) != hipSuccess ||
-        hipHostMalloc((void **)&h->h_out, h->out_bytes) != hipSuccess)
-        return fail(ORBX_E_HIP, "hipHostMalloc failed");
-    h->d_counts = reinterpret_cast<int32_t *>(h->d_out); h->d_status = h->d_counts + B;
-    h->d_kps = reinterpret_cast<orbx_keypoint *>(h->d_out + h->out_hdr); h->d_desc = h->d_out + h->out_hdr + h->out_kps_bytes;
-    h->h_counts = reinterpret_cast<int32_t *>(h->h_out); h->h_status = h->h_counts + B;
-    h->h_kps = reinterpret_cast<orbx_keypoint *>(h->h_out + h->out_hdr); h->h_desc = h->h_out + h->out_hdr + h->out_kps_bytes;
-    if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) return fail(ORBX_E_HIP, "hipStreamCreate failed");
-    for (auto &e : h->ev) if (hipEventCreate(&e) != hipSuccess) return fail(ORBX_E_HIP, "hipEventCreate failed");
-    for (auto &a : h->aux) if (hipStreamCreateWithFlags(&a, hipStreamNonBlocking) != hipSuccess) return fail(ORBX_E_HIP, "hipStreamCreate failed");
-    for (auto &e : h->ev_join) if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail(ORBX_E_HIP, "hipEventCreate failed");
-    if (hipEventCreateWithFlags(&h->ev_fork, hipEventDisableTiming) != hipSuccess) return fail(ORBX_E_HIP, "hipEventCreate failed");
-    if (orbx_upload_constants(h->umax, h->gauss_k) != 0) return fail(ORBX_E_HIP, "constant upload failed");
-    if (orbx_selftest_fp16() != 0) return fail(ORBX_E_HIP, "fp16 subnormal self-test failed: the FAST score tree needs fp16 subnormals enabled on this device");
-    *out = owner.release();
-    return ORBX_OK;
-}
-
-extern "C" void orbx_destroy(orbx_extractor *h) { free_all(h); }
-
-extern "C" int orbx_set_option(orbx_extractor *h, int option, int value)
-{
-    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; h->graph_w = h->graph_h = 0; }   // options are baked into the graph
-    for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
-    h->bgraph.clear(); h->bg_w = h->bg_h = h->bg_n = 0;
-    if (option == ORBX_OPT_BATCH_CHUNK && value >= 0 && value <= 4096) { h->batch_chunk = value; return ORBX_OK; }
-    if (option == ORBX_OPT_BLUR_ROUNDING && (value == 0 || value == 1)) { h->blur_mode = value; h->plan.blur_mode = value; return ORBX_OK; }
-    if (option == ORBX_OPT_SUBBATCHES && value >= 1 && value <= ORBX_MAX_SUB) { h->nsub = value; return ORBX_OK; }
-    if (option == ORBX_OPT_OVERLAP_PYRAMID && (value == 0 || value == 1)) { h->overlap_pyr = value; return ORBX_OK; }
-    return fail(ORBX_E_INVALID, "unknown option %d=%d", option, value);
-}
+// the captured graphs hold the options, the upload and (for colour) the conversion of the format they were captured with
 static void drop_graphs(orbx_extractor *h)
 {
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    h->graph_w = h->graph_h = h->graph_seen_w = h->graph_seen_h = 0;
-    for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
+    h->graph_exec.reset(); h->graph_w = h->graph_h = 0;
     h->bgraph.clear(); h->bg_w = h->bg_h = h->bg_n = 0;
+}
+extern "C" int orbx_set_option(orbx_extractor *h, int option, int value)
+{
+    if (!h) return xfail(ORBX_E_INVALID, "NULL handle");
+    if (option == ORBX_OPT_BATCH_CHUNK && value >= 0 && value <= 4096) h->batch_chunk = value;
+    else if (option == ORBX_OPT_BLUR_ROUNDING && (value == 0 || value == 1)) h->blur_mode = h->plan.blur_mode = value;
+    else if (option == ORBX_OPT_SUBBATCHES && value >= 1 && value <= ORBX_MAX_SUB) h->nsub = value;
+    else if (option == ORBX_OPT_OVERLAP_PYRAMID && (value == 0 || value == 1)) h->overlap_pyr = value;
+    else return xfail(ORBX_E_INVALID, "unknown option %d=%d", option, value);
+    drop_graphs(h);
+    return ORBX_OK;
 }
 extern "C" int orbx_set_input_format(orbx_extractor *h, int format)
 {
-    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
-    if (format < ORBX_FMT_GRAY8 || format > ORBX_FMT_RGBA8) return fail(ORBX_E_INVALID, "unknown input format %d", format);
-    if (h->inflight) return fail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle");
+    if (!h) return xfail(ORBX_E_INVALID, "NULL handle");
+    if (format < ORBX_FMT_GRAY8 || format > ORBX_FMT_RGBA8) return xfail(ORBX_E_INVALID, "unknown input format %d", format);
+    if (h->inflight) return xfail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle");
     if (format == h->fmt) return ORBX_OK;
-    drop_graphs(h);   // the captured graphs hold the upload and (for colour) the conversion of the format they were captured in
+    drop_graphs(h);
+    h->graph_seen_w = h->graph_seen_h = 0;   // the first call in the new format runs plainly
     h->fmt = format;
     return ORBX_OK;
 }
-extern "C" int orbx_get_input_format(const orbx_extractor *h) { return h ? h->fmt : fail(ORBX_E_INVALID, "NULL handle"); }
+extern "C" int orbx_get_input_format(const orbx_extractor *h) { return h ? h->fmt : xfail(ORBX_E_INVALID, "NULL handle"); }
 
-// Colour input.  The host entry points stage a colour frame with a pitch of its own row bytes rounded up to 64 (so every staged row is
-// aligned for the kernel's wide loads, and a BGR upload is 3x the grey one, not 4x); both blocks are sized for 4 channels at the
-// handle's maximum shape, which every smaller frame and every 3-channel frame fits.
 struct ColorSrc { const uint8_t *base; int stride; long long frame; };
-static int color_pitch(int W, int cn) { return (int)align_up((size_t)W * cn, 64); }
-static size_t color_frame(int W, int H, int cn) { return align_up((size_t)color_pitch(W, cn) * H, 256); }
-static int ensure_color(orbx_extractor *h)
-{
-    if (h->d_color && h->h_color) return ORBX_OK;
-    std::lock_guard<std::recursive_mutex> lk_(capture_mutex());   // allocation is a synchronous runtime call
-    const size_t bytes = (size_t)h->max_batch * color_frame(h->max_w, h->max_h, 4) + 256;
-    hipError_t e = hipMalloc((void **)&h->d_color, bytes);
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h->h_color, bytes);
-    if (e != hipSuccess) {
-        (void)hipFree(h->d_color); h->d_color = nullptr;
-        (void)hipGetLastError();
-        return fail(ORBX_E_HIP, "colour input buffers (%zu bytes, device and page-locked): %s", bytes, hipGetErrorString(e));
-    }
-    return ORBX_OK;
-}
 // one colour frame must be below 2 GiB and its row stride below 8 MiB (the conversion kernel's 32-bit offsets inside a frame)
 static int check_color_limits(int width, int height, int row_stride)
 {
     if (row_stride >= (1 << 23) || (long long)height * row_stride >= (1ll << 31))
-        return fail(ORBX_E_SHAPE, "colour frame %dx%d with row stride %d: one frame must be below 2 GiB, the stride below 8 MiB", width, height, row_stride);
+        return xfail(ORBX_E_SHAPE, "colour frame %dx%d with row stride %d: one frame must be below 2 GiB, the stride below 8 MiB", width, height, row_stride);
     return ORBX_OK;
 }
 
@@ -307,7 +78,7 @@ extern "C" int orbx_get_levels(const orbx_extractor *h) { return h ? h->nlevels 
 extern "C" float orbx_get_scale_factor(const orbx_extractor *h) { return h ? h->scale_factor : 0.f; }
 extern "C" int orbx_get_tables(const orbx_extractor *h, float *sf, float *isf, float *s2, float *is2)
 {
-    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
+    if (!h) return xfail(ORBX_E_INVALID, "NULL handle");
     for (int i = 0; i < h->nlevels; i++) {
         if (sf) sf[i] = h->scale[i];
         if (isf) isf[i] = h->inv_scale[i];
@@ -318,35 +89,25 @@ extern "C" int orbx_get_tables(const orbx_extractor *h, float *sf, float *isf, f
 }
 extern "C" int orbx_get_features_per_level(const orbx_extractor *h, int *q)
 {
-    if (!h || !q) return fail(ORBX_E_INVALID, "NULL argument");
+    if (!h || !q) return xfail(ORBX_E_INVALID, "NULL argument");
     for (int i = 0; i < h->nlevels; i++) q[i] = h->quota[i];
     return ORBX_OK;
 }
 extern "C" int orbx_capacity(const orbx_extractor *h) { return h ? h->max_plan.out_cap : 0; }
-extern "C" int orbx_set_profiling(orbx_extractor *h, int mode)
-{
-    if (!h || mode < 0 || mode > 2) return fail(ORBX_E_INVALID, "profiling mode %d", mode);
-    if (mode == 2 && !h->evr[0][0]) {
-        HIPCHK(hipSetDevice(h->device));
-        for (auto &set : h->evr) for (auto &e : set) HIPCHK(hipEventCreate(&e));
-    }
-    h->profiling = mode; h->ring_calls = 0;
-    return ORBX_OK;
-}
 extern "C" int orbx_stage_ms_ring(orbx_extractor *h, float *ms, int max_calls)
 {
-    if (!h || !ms || max_calls < 0) return fail(ORBX_E_INVALID, "bad argument");
-    if (h->profiling != 2) return fail(ORBX_E_INVALID, "ring profiling is off");
+    if (!h || !ms || max_calls < 0) return xfail(ORBX_E_INVALID, "bad argument");
+    if (h->profiling != 2) return xfail(ORBX_E_INVALID, "ring profiling is off");
     const int n = (int)std::min<long long>(std::min<long long>(h->ring_calls, ORBX_PROF_RING), max_calls);
     for (int i = 0; i < n; i++) {                           // newest first
-        hipEvent_t *e = h->evr[(h->ring_calls - 1 - i) % ORBX_PROF_RING];
+        const DevEvent *e = h->ring[(h->ring_calls - 1 - i) % ORBX_PROF_RING].e;
         for (int k = 0; k < 4; k++) HIPCHK(hipEventElapsedTime(&ms[4 * i + k], e[k], e[k + 1]));   // fails if the caller has not synchronised
     }
     return n;
 }
 extern "C" int orbx_last_stage_ms(orbx_extractor *h, float ms[4])
 {
-    if (!h || !ms) return fail(ORBX_E_INVALID, "NULL argument");
+    if (!h || !ms) return xfail(ORBX_E_INVALID, "NULL argument");
     memcpy(ms, h->stage_ms, sizeof(float) * 4);
     return ORBX_OK;
 }
@@ -357,14 +118,14 @@ extern "C" int orbx_last_stage_ms(orbx_extractor *h, float ms[4])
 static int ensure_plan(orbx_extractor *h, int W, int H)
 {
     if (W == h->cur_w && H == h->cur_h) return ORBX_OK;
-    if (W > h->max_w || H > h->max_h) return fail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", W, H, h->max_w, h->max_h);
+    if (W > h->max_w || H > h->max_h) return xfail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", W, H, h->max_w, h->max_h);
     ShapePlan S;
     std::string why;
     const int rc = orbx_plan_shape(*h, h->max_plan, W, H, &S, &why);
-    if (rc != ORBX_OK) return fail(rc, "frame %dx%d: %s", W, H, why.c_str());
+    if (rc != ORBX_OK) return xfail(rc, "frame %dx%d: %s", W, H, why.c_str());
     {   // a shape change rewrites tables that kernels of an earlier call may still be reading -- on the handle's stream, its aux
         // streams or a caller's stream (orbx_extract_batch_device): wait for the device, not only for h->stream (shape changes are rare)
-        std::lock_guard<std::recursive_mutex> lk_(capture_mutex());
+        std::lock_guard<std::recursive_mutex> lk_(orbx_capture_mutex());
         HIPCHK(hipDeviceSynchronize());
         hipError_t e = hipSuccess;
         auto up = [&e](void *dst, const void *src, size_t bytes) { if (e == hipSuccess && bytes) e = hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice); };
@@ -373,7 +134,7 @@ static int ensure_plan(orbx_extractor *h, int W, int H)
         up(h->d_cells, S.cells.data(), (size_t)S.plan.ncells * sizeof(uint32_t));
         up(h->d_tab_i, S.tab_i.data(), S.tab_used * sizeof(int));
         up(h->d_tab_s, S.tab_s.data(), S.tab_used * sizeof(short2));
-        if (e != hipSuccess) { h->cur_w = h->cur_h = 0; return fail(ORBX_E_HIP, "table upload for %dx%d: %s", W, H, hipGetErrorString(e)); }
+        if (e != hipSuccess) { h->cur_w = h->cur_h = 0; return xfail(ORBX_E_HIP, "table upload for %dx%d: %s", W, H, hipGetErrorString(e)); }
     }
     // commit: the plan with the device addresses filled in
     h->plan = S.plan;
@@ -475,7 +236,7 @@ static int enqueue(orbx_extractor *h, const uint8_t *d_images, int nframes, int 
     h->last_input = d_images; h->last_in_stride = row_stride; h->last_in_frame = frame_stride; h->last_batch = nframes;
 
     const bool prof = h->profiling == 1;          // mode 1 times one call in isolation; mode 2 only drops events into the stream
-    hipEvent_t *pe = h->profiling == 2 ? h->evr[h->ring_calls % ORBX_PROF_RING] : (prof ? h->ev : nullptr);
+    const DevEvent *pe = h->profiling == 2 ? h->ring[h->ring_calls % ORBX_PROF_RING].e : (prof ? h->ev : nullptr);
     if (h->need_clear) {   // the kernels leave the counters and flags zeroed; only the first call (or one after an error) clears
         HIPCHK(hipMemsetAsync(h->work.cand_count, 0, (size_t)h->max_batch * ORBX_MAX_LEVELS * ORBX_CNT_STRIDE * sizeof(uint32_t), s));
         HIPCHK(hipMemsetAsync(h->work.errflags, 0, (size_t)h->max_batch * sizeof(uint32_t), s));
@@ -554,16 +315,16 @@ extern "C" int orbx_extract_batch_device(orbx_extractor *h, const uint8_t *d_ima
                                          orbx_keypoint *d_keypoints, uint8_t *d_descriptors, int cap,
                                          int32_t *d_counts, int32_t *d_status, void *hip_stream)
 {
-    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
-    if (h->inflight) return fail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle (its workspace would be overwritten)");
-    if (!d_images || !d_keypoints || !d_descriptors || !d_counts || !d_status) return fail(ORBX_E_INVALID, "NULL device pointer");
-    if (nframes < 1 || nframes > h->max_batch) return fail(ORBX_E_INVALID, "nframes=%d (max_batch=%d)", nframes, h->max_batch);
+    if (!h) return xfail(ORBX_E_INVALID, "NULL handle");
+    if (h->inflight) return xfail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle (its workspace would be overwritten)");
+    if (!d_images || !d_keypoints || !d_descriptors || !d_counts || !d_status) return xfail(ORBX_E_INVALID, "NULL device pointer");
+    if (nframes < 1 || nframes > h->max_batch) return xfail(ORBX_E_INVALID, "nframes=%d (max_batch=%d)", nframes, h->max_batch);
     const int cn = orbx_format_channels(h->fmt);
-    if (width < 1 || height < 1 || row_stride / cn < width) return fail(ORBX_E_INVALID, "bad frame geometry %dx%d stride %d (%d channel%s)", width, height, row_stride, cn, cn > 1 ? "s" : "");
+    if (width < 1 || height < 1 || row_stride / cn < width) return xfail(ORBX_E_INVALID, "bad frame geometry %dx%d stride %d (%d channel%s)", width, height, row_stride, cn, cn > 1 ? "s" : "");
     // the kernels index one frame with 31-bit byte offsets and 24-bit row strides
     if (row_stride >= (1 << 23) || (long long)height * row_stride >= (1ll << 31))
-        return fail(ORBX_E_SHAPE, "frame %dx%d with row stride %d: one frame must be below 2 GiB, the stride below 8 MiB", width, height, row_stride);
-    if (cap != h->max_plan.out_cap) return fail(ORBX_E_CAPACITY, "device outputs must be laid out with cap == orbx_capacity() == %d (got %d)", h->max_plan.out_cap, cap);
+        return xfail(ORBX_E_SHAPE, "frame %dx%d with row stride %d: one frame must be below 2 GiB, the stride below 8 MiB", width, height, row_stride);
+    if (cap != h->max_plan.out_cap) return xfail(ORBX_E_CAPACITY, "device outputs must be laid out with cap == orbx_capacity() == %d (got %d)", h->max_plan.out_cap, cap);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : h->stream;
     int rc;
@@ -648,7 +409,7 @@ static const char *device_status_text(int st)
 static int download_outputs(orbx_extractor *h, int nframes, hipStream_t s)
 {
     if (nframes == h->max_batch) {
-        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_bytes, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->d_out.bytes(), hipMemcpyDeviceToHost, s));
     } else {
         const size_t n = (size_t)h->max_plan.out_cap * nframes;
         HIPCHK(hipMemcpyAsync(h->h_out, h->d_out, h->out_hdr, hipMemcpyDeviceToHost, s));
@@ -665,8 +426,8 @@ static int deliver_batch(orbx_extractor *h, int k0, int k1, orbx_keypoint *keypo
     const int ocap = h->max_plan.out_cap;
     for (int k = k0; k < k1; k++) {
         const int st = hs[k - k0];
-        if (st != ORBX_OK) return fail(st, "frame %d: device status %d (%s)", k, st, device_status_text(st));
-        if (hc[k - k0] > cap) return fail(ORBX_E_CAPACITY, "frame %d produced %d keypoints, caller capacity %d (use orbx_capacity())", k, hc[k - k0], cap);
+        if (st != ORBX_OK) return xfail(st, "frame %d: device status %d (%s)", k, st, device_status_text(st));
+        if (hc[k - k0] > cap) return xfail(ORBX_E_CAPACITY, "frame %d produced %d keypoints, caller capacity %d (use orbx_capacity())", k, hc[k - k0], cap);
     }
     auto unit = [&](int u) {
         const int k = k0 + u, n = hc[u];
@@ -738,21 +499,21 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
                                   int row_stride, size_t frame_stride, orbx_keypoint *keypoints,
                                   uint8_t *descriptors, int cap, int *counts)
 {
-    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
-    if (!counts) return fail(ORBX_E_INVALID, "counts is NULL");
+    if (!h) return xfail(ORBX_E_INVALID, "NULL handle");
+    if (!counts) return xfail(ORBX_E_INVALID, "counts is NULL");
     for (int k = 0; k < std::max(nframes, 0); k++) counts[k] = 0;
-    if (h->inflight) return fail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle");
+    if (h->inflight) return xfail(ORBX_E_INVALID, "an orbx_extract_begin call is in flight on this handle");
     if (!images || width <= 0 || height <= 0 || nframes <= 0) return ORBX_OK;   // :1048 empty image: silent return
-    if (!keypoints || !descriptors) return fail(ORBX_E_INVALID, "NULL output buffer");
-    if (nframes > h->max_batch) return fail(ORBX_E_INVALID, "nframes=%d (max_batch=%d)", nframes, h->max_batch);
+    if (!keypoints || !descriptors) return xfail(ORBX_E_INVALID, "NULL output buffer");
+    if (nframes > h->max_batch) return xfail(ORBX_E_INVALID, "nframes=%d (max_batch=%d)", nframes, h->max_batch);
     const int cn = orbx_format_channels(h->fmt);
-    if (row_stride / cn < width) return fail(ORBX_E_INVALID, "row_stride %d < width %d x %d channel%s", row_stride, width, cn, cn > 1 ? "s" : "");
-    if (width > h->max_w || height > h->max_h) return fail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", width, height, h->max_w, h->max_h);
+    if (row_stride / cn < width) return xfail(ORBX_E_INVALID, "row_stride %d < width %d x %d channel%s", row_stride, width, cn, cn > 1 ? "s" : "");
+    if (width > h->max_w || height > h->max_h) return xfail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", width, height, h->max_w, h->max_h);
     HIPCHK(hipSetDevice(h->device));
-    if (cn > 1) { int rcc = check_color_limits(width, height, color_pitch(width, cn)); if (rcc == ORBX_OK) rcc = ensure_color(h); if (rcc != ORBX_OK) return rcc; }
+    if (cn > 1) { int rcc = check_color_limits(width, height, color_pitch(width, cn)); if (rcc == ORBX_OK) rcc = orbx_ensure_color(h); if (rcc != ORBX_OK) return rcc; }
     if (!h->pool && nframes >= 8) {                         // staging threads: up to 6, leaving cores to the caller
         const unsigned hc = (unsigned)StagePool::usable_cpus();       // affinity mask and cgroup quota, not the machine's core count
-        h->pool = new StagePool((int)std::min<unsigned>(6u, hc > 2 ? hc / 2 - 1 : 0u));
+        h->pool.reset(new StagePool((int)std::min<unsigned>(6u, hc > 2 ? hc / 2 - 1 : 0u)));
     }
     // Chunked pipeline ("host-buffer batches"): while chunk c is uploaded and extracted, chunk c + 1 is repacked by the
     // staging threads; chunks alternate between two streams, so the upload of one runs under the kernels of the other, and each
@@ -783,26 +544,23 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
             h->chunk_off[c] = off;
             off += align_up((size_t)2 * nf * sizeof(int32_t), 256) + (size_t)nf * h->max_plan.out_cap * (sizeof(orbx_keypoint) + 32);
         }
-        if (off > h->out_bytes) return fail(ORBX_E_INVALID, "internal: chunk output blocks exceed the staging block");
+        if (off > h->d_out.bytes()) return xfail(ORBX_E_INVALID, "internal: chunk output blocks exceed the staging block");
     }
     hipStream_t st[3] = {h->stream, h->aux[0], h->aux[2]};
     const int nst = batch_streams();
     const bool have_graphs = !h->bg_off && h->bg_w == width && h->bg_h == height && h->bg_n == nframes && h->bg_chunk == chunk && (int)h->bgraph.size() == nch;
     if (!have_graphs && !h->bg_off) {                       // (re)build the per-chunk graphs for this shape
-        for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
-        h->bgraph.assign(nch, nullptr);
+        drop_graphs(h);
+        h->bgraph.resize(nch);
         bool ok = true;
-        std::lock_guard<std::recursive_mutex> lk_(capture_mutex());   // once around all chunk captures (capture_graph() takes it again: recursive)
+        std::lock_guard<std::recursive_mutex> lk_(orbx_capture_mutex());   // once around all chunk captures (capture_graph() takes it again: recursive)
         for (int c = 0; c < nch && ok; c++) {
             hipStream_t s = st[c % nst];
             h->bgraph[c] = capture_graph(s, [&] { return enqueue_chunk(h, c, cut[c], cut[c + 1], width, height, s) == ORBX_OK; });
             ok = h->bgraph[c] != nullptr;
         }
         if (ok) { h->bg_w = width; h->bg_h = height; h->bg_n = nframes; h->bg_chunk = chunk; }
-        else {
-            for (auto &g : h->bgraph) if (g) (void)hipGraphExecDestroy(g);
-            h->bgraph.clear(); h->bg_off = true; h->bg_w = h->bg_h = h->bg_n = 0;
-        }
+        else { drop_graphs(h); h->bg_off = true; }
     }
     const bool graphs = !h->bg_off && (int)h->bgraph.size() == nch;
     const bool trace = batch_trace();
@@ -810,11 +568,7 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
     // uploads go back to back on a stream of their own (on a chunk's compute stream the upload of chunk c + 2 would wait for
     // chunk c's kernels and downloads); each chunk's kernels wait for its own upload only
     hipStream_t up = h->aux[1];
-    while ((int)h->ev_up.size() < nch) {
-        hipEvent_t a = nullptr, b = nullptr;
-        HIPCHK(hipEventCreateWithFlags(&a, hipEventDisableTiming)); h->ev_up.push_back(a);
-        HIPCHK(hipEventCreateWithFlags(&b, hipEventDisableTiming)); h->ev_done.push_back(b);
-    }
+    XTRY(orbx_ensure_chunk_events(h, nch));
     const bool pinned_ok = batch_pinned_ok();
     // the answer for one buffer is remembered (a capture pipeline hands over the same page-locked block again and again; should it
     // have been unregistered meanwhile, the copies below are still correct -- the runtime stages them -- only slower)
@@ -837,11 +591,11 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
         else
             HIPCHK(hipMemcpyAsync(G.d_base + (size_t)k0 * G.frame, G.h_base + (size_t)k0 * G.frame,
                                   (size_t)(k1 - k0 - 1) * G.frame + G.stride * height, hipMemcpyHostToDevice, up));
-        HIPCHK(hipEventRecord(h->ev_up[c], up));
-        HIPCHK(hipStreamWaitEvent(s, h->ev_up[c], 0));
+        HIPCHK(hipEventRecord(h->chunk_ev[c].up, up));
+        HIPCHK(hipStreamWaitEvent(s, h->chunk_ev[c].up, 0));
         if (graphs) HIPCHK(hipGraphLaunch(h->bgraph[c], s));
         else { int rc = enqueue_chunk(h, c, k0, k1, width, height, s); if (rc != ORBX_OK) return rc; }
-        HIPCHK(hipEventRecord(h->ev_done[c], s));
+        HIPCHK(hipEventRecord(h->chunk_ev[c].done, s));
         if (trace) { t_stage += tb - ta; t_launch += now() - tb; }
     }
     const double t_issued = trace ? now() : 0;
@@ -851,7 +605,7 @@ extern "C" int orbx_extract_batch(orbx_extractor *h, const uint8_t *images, int 
     for (int c = 0; c < nch; c++) {
         const int k0 = cut[c], k1 = cut[c + 1];
         const double tw = trace ? now() : 0;
-        HIPCHK(hipEventSynchronize(h->ev_done[c]));
+        HIPCHK(hipEventSynchronize(h->chunk_ev[c].done));
         if (trace) t_wait += now() - tw;
         if (rcd == ORBX_OK) {
             const ChunkBlock Hb = chunk_block(h, h->h_out, c, k1 - k0);
@@ -876,18 +630,18 @@ static int upload_and_enqueue_one(orbx_extractor *h, int w, int hgt, hipStream_t
 
 extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int width, int height, int stride)
 {
-    if (!h) return fail(ORBX_E_INVALID, "NULL handle");
-    if (h->inflight) return fail(ORBX_E_INVALID, "orbx_extract_begin: a call is already in flight on this handle");
+    if (!h) return xfail(ORBX_E_INVALID, "NULL handle");
+    if (h->inflight) return xfail(ORBX_E_INVALID, "orbx_extract_begin: a call is already in flight on this handle");
     h->inflight_frames = 0;
     if (!image || width <= 0 || height <= 0) { h->inflight = 1; return ORBX_OK; }     // :1048 empty image
     const int cn = orbx_format_channels(h->fmt);
-    if (stride / cn < width) return fail(ORBX_E_INVALID, "row_stride %d < width %d x %d channel%s", stride, width, cn, cn > 1 ? "s" : "");
-    if (width > h->max_w || height > h->max_h) return fail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", width, height, h->max_w, h->max_h);
+    if (stride / cn < width) return xfail(ORBX_E_INVALID, "row_stride %d < width %d x %d channel%s", stride, width, cn, cn > 1 ? "s" : "");
+    if (width > h->max_w || height > h->max_h) return xfail(ORBX_E_SHAPE, "frame %dx%d exceeds the handle's max %dx%d", width, height, h->max_w, h->max_h);
     HIPCHK(hipSetDevice(h->device));
     hipStream_t s = h->stream;
     if (cn > 1) {
         int rcc = check_color_limits(width, height, color_pitch(width, cn));
-        if (rcc == ORBX_OK) rcc = ensure_color(h);
+        if (rcc == ORBX_OK) rcc = orbx_ensure_color(h);
         if (rcc != ORBX_OK) return rcc;
         const StageGeom G = stage_geom(h, width, height);
         for (int y = 0; y < height; y++) memcpy(G.h_base + (size_t)y * G.stride, image + (size_t)y * stride, G.row_bytes);
@@ -901,7 +655,6 @@ extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int w
         const bool second = graphable && h->graph_seen_w == width && h->graph_seen_h == height;
         h->graph_seen_w = width; h->graph_seen_h = height;
         if (second) {
-            if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
             h->graph_exec = capture_graph(s, [&] { return upload_and_enqueue_one(h, width, height, s) == ORBX_OK && download_outputs(h, 1, s) == ORBX_OK; });
             // a capture that failed or was invalidated (another thread's synchronous call) is not an error of this call; the capture
             // is tried again on a later call, three times at most
@@ -923,19 +676,19 @@ extern "C" int orbx_extract_begin(orbx_extractor *h, const uint8_t *image, int w
 
 extern "C" int orbx_extract_end(orbx_extractor *h, orbx_keypoint *keypoints, uint8_t *descriptors, int cap, int *n)
 {
-    if (!h || !n) return fail(ORBX_E_INVALID, "NULL argument");
+    if (!h || !n) return xfail(ORBX_E_INVALID, "NULL argument");
     *n = 0;
-    if (!h->inflight) return fail(ORBX_E_INVALID, "orbx_extract_end without orbx_extract_begin");
+    if (!h->inflight) return xfail(ORBX_E_INVALID, "orbx_extract_end without orbx_extract_begin");
     h->inflight = 0;
     if (h->inflight_frames == 0) return ORBX_OK;
-    if (!keypoints || !descriptors) return fail(ORBX_E_INVALID, "NULL output buffer");
+    if (!keypoints || !descriptors) return xfail(ORBX_E_INVALID, "NULL output buffer");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipStreamSynchronize(h->stream));
     int rc = finish_profile(h);
     if (rc != ORBX_OK) return rc;
-    if (h->h_status[0] != ORBX_OK) return fail(h->h_status[0], "device status %d (%s)", h->h_status[0], device_status_text(h->h_status[0]));
+    if (h->h_status[0] != ORBX_OK) return xfail(h->h_status[0], "device status %d (%s)", h->h_status[0], device_status_text(h->h_status[0]));
     const int cnt = h->h_counts[0];
-    if (cnt > cap) return fail(ORBX_E_CAPACITY, "%d keypoints, caller capacity %d (use orbx_capacity())", cnt, cap);
+    if (cnt > cap) return xfail(ORBX_E_CAPACITY, "%d keypoints, caller capacity %d (use orbx_capacity())", cnt, cap);
     memcpy(keypoints, h->h_kps, sizeof(orbx_keypoint) * cnt);
     memcpy(descriptors, h->h_desc, (size_t)32 * cnt);
     *n = cnt;
@@ -945,12 +698,12 @@ extern "C" int orbx_extract_end(orbx_extractor *h, orbx_keypoint *keypoints, uin
 extern "C" int orbx_extract(orbx_extractor *h, const uint8_t *image, int width, int height, int stride,
                             orbx_keypoint *keypoints, uint8_t *descriptors, int cap, int *n)
 {
-    if (!n) return fail(ORBX_E_INVALID, "n is NULL");
+    if (!n) return xfail(ORBX_E_INVALID, "n is NULL");
     if (h && h->max_batch == 1 && h->profiling == 0 && !h->inflight) {      // the two halves back to back: one HIP graph per shape
         *n = 0;
         int rc = orbx_extract_begin(h, image, width, height, stride);
         if (rc != ORBX_OK) return rc;
-        if (!keypoints || !descriptors) { h->inflight = 0; if (h->inflight_frames) (void)hipStreamSynchronize(h->stream); return fail(ORBX_E_INVALID, "NULL output buffer"); }
+        if (!keypoints || !descriptors) { h->inflight = 0; if (h->inflight_frames) (void)hipStreamSynchronize(h->stream); return xfail(ORBX_E_INVALID, "NULL output buffer"); }
         return orbx_extract_end(h, keypoints, descriptors, cap, n);
     }
     return orbx_extract_batch(h, image, 1, width, height, stride, (size_t)stride * (size_t)std::max(height, 0),
@@ -959,7 +712,7 @@ extern "C" int orbx_extract(orbx_extractor *h, const uint8_t *image, int width, 
 
 extern "C" int orbx_level_size(const orbx_extractor *h, int level, int *width, int *height)
 {
-    if (!h || level < 0 || level >= h->nlevels || h->cur_w == 0) return fail(ORBX_E_INVALID, "no plan / bad level");
+    if (!h || level < 0 || level >= h->nlevels || h->cur_w == 0) return xfail(ORBX_E_INVALID, "no plan / bad level");
     if (width) *width = h->plan.lv[level].w;
     if (height) *height = h->plan.lv[level].h;
     return ORBX_OK;
@@ -976,18 +729,18 @@ extern "C" int orbx_extract_batch_multi(orbx_extractor *const *handles, int nhan
                                         int height, int row_stride, size_t frame_stride, orbx_keypoint *keypoints,
                                         uint8_t *descriptors, int cap, int *counts)
 {
-    if (!handles || nhandles < 1) return fail(ORBX_E_INVALID, "no handles");
+    if (!handles || nhandles < 1) return xfail(ORBX_E_INVALID, "no handles");
     for (int i = 0; i < nhandles; i++) {
-        if (!handles[i]) return fail(ORBX_E_INVALID, "handle %d is NULL", i);
+        if (!handles[i]) return xfail(ORBX_E_INVALID, "handle %d is NULL", i);
         for (int j = 0; j < i; j++)
-            if (handles[j] == handles[i]) return fail(ORBX_E_INVALID, "handle %d is handle %d again: a handle is not re-entrant", i, j);
+            if (handles[j] == handles[i]) return xfail(ORBX_E_INVALID, "handle %d is handle %d again: a handle is not re-entrant", i, j);
     }
     for (int i = 1; i < nhandles; i++)
-        if (handles[i]->fmt != handles[0]->fmt) return fail(ORBX_E_INVALID, "handle %d has input format %d, handle 0 has %d: one batch has one format", i, handles[i]->fmt, handles[0]->fmt);
-    if (!counts) return fail(ORBX_E_INVALID, "counts is NULL");
+        if (handles[i]->fmt != handles[0]->fmt) return xfail(ORBX_E_INVALID, "handle %d has input format %d, handle 0 has %d: one batch has one format", i, handles[i]->fmt, handles[0]->fmt);
+    if (!counts) return xfail(ORBX_E_INVALID, "counts is NULL");
     for (int k = 0; k < std::max(nframes, 0); k++) counts[k] = 0;
     if (!images || width <= 0 || height <= 0 || nframes <= 0) return ORBX_OK;
-    if (!keypoints || !descriptors) return fail(ORBX_E_INVALID, "NULL output buffer");
+    if (!keypoints || !descriptors) return xfail(ORBX_E_INVALID, "NULL output buffer");
     const int nh = std::min(nhandles, nframes);
     std::vector<int> lo(nh + 1);
     for (int i = 0; i <= nh; i++) lo[i] = i * (nframes / nh) + std::min(i, nframes % nh);
@@ -1004,7 +757,7 @@ extern "C" int orbx_extract_batch_multi(orbx_extractor *const *handles, int nhan
     run(0);
     for (auto &t : th) t.join();
     for (int i = 0; i < nh; i++)
-        if (rc[i] != ORBX_OK) return fail(rc[i], "block %d (frames %d..%d, device %d): %s", i, lo[i], lo[i + 1] - 1, handles[i]->device, msg[i].c_str());
+        if (rc[i] != ORBX_OK) return xfail(rc[i], "block %d (frames %d..%d, device %d): %s", i, lo[i], lo[i + 1] - 1, handles[i]->device, msg[i].c_str());
     return ORBX_OK;
 }
 
@@ -1021,20 +774,16 @@ static inline int reflect101_host(int p, int len)
 static int download_levels(orbx_extractor *h, int frame, int l0, int l1, uint8_t *const *dst, const int *dst_stride, int border)
 {
     if (!dst || !dst_stride || l0 < 0 || l1 > h->nlevels || h->cur_w == 0 || frame < 0 || frame >= h->last_batch || border < 0)
-        return fail(ORBX_E_INVALID, "bad pyramid download argument");
+        return xfail(ORBX_E_INVALID, "bad pyramid download argument");
     HIPCHK(hipSetDevice(h->device));
     size_t need = 0, off[ORBX_MAX_LEVELS];
     for (int l = l0; l < l1; l++) {
         const OrbxLevel &L = h->plan.lv[l];
-        if (!dst[l - l0] || dst_stride[l - l0] < L.w + 2 * border) return fail(ORBX_E_INVALID, "level %d: NULL buffer or dst_stride too small", l);
+        if (!dst[l - l0] || dst_stride[l - l0] < L.w + 2 * border) return xfail(ORBX_E_INVALID, "level %d: NULL buffer or dst_stride too small", l);
         off[l] = need;
         need += ((size_t)L.w * L.h + 255) & ~(size_t)255;
     }
-    if (need > h->h_pyr_bytes) {
-        (void)hipHostFree(h->h_pyr); h->h_pyr = nullptr; h->h_pyr_bytes = 0;
-        HIPCHK(hipHostMalloc((void **)&h->h_pyr, need + need / 4));
-        h->h_pyr_bytes = need + need / 4;
-    }
+    XTRY(orbx_ensure_pyr_staging(h, need));
     HIPCHK(hipDeviceSynchronize());   // the last call may have run on a caller stream and the aux streams
     for (int l = l0; l < l1; l++) {
         OrbxLevel L = h->plan.lv[l];
@@ -1062,26 +811,26 @@ static int download_levels(orbx_extractor *h, int frame, int l0, int l1, uint8_t
 }
 extern "C" int orbx_download_level(orbx_extractor *h, int frame, int level, uint8_t *dst, int dst_stride, int border)
 {
-    if (!h || level < 0 || level >= h->nlevels) return fail(ORBX_E_INVALID, "bad download_level argument");
+    if (!h || level < 0 || level >= h->nlevels) return xfail(ORBX_E_INVALID, "bad download_level argument");
     return download_levels(h, frame, level, level + 1, &dst, &dst_stride, border);
 }
 extern "C" int orbx_download_pyramid(orbx_extractor *h, int frame, uint8_t *const *dst, const int *dst_stride, int border)
 {
-    if (!h) return fail(ORBX_E_INVALID, "bad download_pyramid argument");
+    if (!h) return xfail(ORBX_E_INVALID, "bad download_pyramid argument");
     return download_levels(h, frame, 0, h->nlevels, dst, dst_stride, border);
 }
 
 extern "C" int orbx_download_candidates(orbx_extractor *h, int frame, int level, int32_t *xyr, int cap)
 {
     if (!h || !xyr || level < 0 || level >= h->nlevels || h->cur_w == 0 || frame < 0 || frame >= h->last_batch)
-        return fail(ORBX_E_INVALID, "bad download_candidates argument");
+        return xfail(ORBX_E_INVALID, "bad download_candidates argument");
     HIPCHK(hipSetDevice(h->device));
     HIPCHK(hipDeviceSynchronize());
     uint32_t n = 0;
     HIPCHK(hipMemcpy(&n, h->work.ncand + (size_t)frame * h->nlevels + level, sizeof(n), hipMemcpyDeviceToHost));
     const OrbxLevel &L = h->plan.lv[level];
     n = std::min<uint32_t>(n, (uint32_t)L.cand_cap);
-    if ((int)n > cap) return fail(ORBX_E_CAPACITY, "%u candidates, capacity %d", n, cap);
+    if ((int)n > cap) return xfail(ORBX_E_CAPACITY, "%u candidates, capacity %d", n, cap);
     std::vector<OrbxCand> tmp(n ? n : 1);
     HIPCHK(hipMemcpy(tmp.data(), h->work.cand + (size_t)frame * h->plan.cand_frame + L.cand_off, sizeof(OrbxCand) * n, hipMemcpyDeviceToHost));
     for (uint32_t i = 0; i < n; i++) {

@@ -1,4 +1,4 @@
-// orbx_internal.h -- shared between the host side (the planner orbx_plan.hip, the handle and C ABI orbx_capi.hip) and the gfx950 kernels.
+// orbx_internal.h -- shared between the host side (the planner orbx_plan.cc, the handle orbx_handle.h / orbx_workspace.cc, the per-call path and C ABI orbx_capi.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-// orbx_plan.hip -- shape planning of the extractor: constructor tables, level sizes, cv::resize tables, the FAST cell table, the band and
+// orbx_plan.cc -- shape planning of the extractor: constructor tables, level sizes, cv::resize tables, the FAST cell table, the band and
 // tile plans of the fused pyramid kernels.  Host arithmetic that restates the reference constructor and OpenCV's resize planning
 // (citations: src/ORBextractor.cc of WChen09/My-SLAM); no kernel, no HIP call, no handle (orbx_plan.h).
 #include <cfloat>

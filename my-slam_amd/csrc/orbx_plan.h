@@ -1,4 +1,4 @@
-// orbx_plan.h -- the extractor's shape planner (orbx_plan.hip): host arithmetic only.  It makes no HIP call and never sees a handle;
+// orbx_plan.h -- the extractor's shape planner (orbx_plan.cc): host arithmetic only.  It makes no HIP call and never sees a handle;
 // orbx_capi.hip plans a shape into a ShapePlan, uploads its tables and only then commits it to the handle.
 #pragma once
 #include <string>

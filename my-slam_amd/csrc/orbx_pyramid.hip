@@ -497,7 +497,7 @@ void orbx_launch_resize_fused(const FuseArgs &A, int nframes, size_t lds_bytes, 
 // by exactly one tile: the x and y OWNED ranges of the tiles partition each level (images of the level-b tile grid under the
 // monotone xofs / yofs maps), the COMPUTED ranges (owned + footprint of the next level's computed range, lengthened to a multiple
 // of 4: the arithmetic works in 4x4 blocks counted from the range's own first pixel) overlap and are computed twice (+30 % pixels on
-// these small levels; rounding the ranges outwards to multiples of 4 in level coordinates, the first version, made it +90 %).  Planned on the host per axis (plan_tile_axis in orbx_plan.hip).
+// these small levels; rounding the ranges outwards to multiples of 4 in level coordinates, the first version, made it +90 %).  Planned on the host per axis (plan_tile_axis in orbx_plan.cc).
 // Arithmetic: resize_block6 on 4x4 blocks, blocks of the tile's region dealt to the 64 lanes.  Needs RESIZE_FAST6 on every fused level
 // and a >= 1 (the source of the first fused level is a pyramid level with slack behind its rows, never the caller's level 0).
 // -------------------------------------------------------------------------------------------------

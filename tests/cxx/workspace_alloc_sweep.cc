@@ -1,6 +1,6 @@
-// Allocation-failure sweep of the matcher-side handles' device memory (my-slam_amd/csrc/dev_buf.h and the *_workspace.cc files),
-// on the CPU: this program supplies the HIP calls that code uses, backed by malloc, with a live-block counter and an
-// "allocation number k fails" switch.  Built with -fsanitize=address,undefined by tests/test_workspace_alloc.py, so a double free
+// Creation-failure sweep of the handles' device memory, streams and events (my-slam_amd/csrc/dev_buf.h and the *_workspace.cc files),
+// on the CPU: this program supplies the HIP calls that code uses, backed by malloc, with counters of what is live and one
+// "creation number k fails" switch over device blocks, page-locked blocks, streams and events.  Built with -fsanitize=address,undefined by tests/test_workspace_alloc.py, so a double free
 // or a write through a stale pointer is reported by the sanitizer; everything else is checked here.
 #include <cstdio>
 #include <cstdlib>
@@ -11,9 +11,10 @@
 #include "orbm_internal.h"
 #include "orbv_internal.h"
 #include "orbk_internal.h"
+#include "orbx_handle.h"
 
 // ---- the HIP calls of the workspace code ----
-static int g_allocs = 0, g_fail_at = -1, g_streams = 0;
+static int g_allocs = 0, g_fail_at = -1, g_streams = 0, g_events = 0;      // g_allocs counts every creation
 static bool g_capturing = false;
 static std::set<void *> g_dev, g_pin;
 static int live() { return (int)(g_dev.size() + g_pin.size()); }
@@ -44,8 +45,24 @@ const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int) { return hipSuccess; }
 hipError_t hipDeviceSynchronize(void) { return hipSuccess; }
-hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned int) { *s = (hipStream_t)malloc(1); g_streams++; return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned int)
+{
+    *s = nullptr;
+    if (g_allocs++ == g_fail_at) return hipErrorOutOfMemory;
+    *s = (hipStream_t)malloc(1); g_streams++;
+    return hipSuccess;
+}
 hipError_t hipStreamDestroy(hipStream_t s) { free(s); g_streams--; return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned int)
+{
+    *e = nullptr;
+    if (g_allocs++ == g_fail_at) return hipErrorOutOfMemory;
+    *e = (hipEvent_t)malloc(1); g_events++;
+    return hipSuccess;
+}
+hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
+hipError_t hipEventDestroy(hipEvent_t e) { free(e); g_events--; return hipSuccess; }
+hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }       // no graph is captured here
 hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 hipError_t hipStreamIsCapturing(hipStream_t, hipStreamCaptureStatus *st)
 {
@@ -66,6 +83,11 @@ hipError_t orbk_launch_compact(const int32_t *src_ids, const double *src_vals, i
         }
     return hipSuccess;
 }
+
+// the device-side functions orbx_create calls (orbx_octree.hip, orbx_describe.hip, orbx_fast.hip)
+int orbx_upload_constants(const int *, const int *) { return 0; }
+int orbx_selftest_fp16(void) { return 0; }
+size_t orbx_octree_lds_bytes(int, int, int) { return 4096; }
 
 #define REQUIRE(cond, ...)                                                  \
     do {                                                                    \
@@ -107,7 +129,9 @@ template <class B> static void buffer_alone(const char *name)
     REQUIRE(live() == 0, "%s: %d live blocks after the buffers went out of scope", name, live());
 }
 
-// ---- the sweep: `call` on a fresh handle without failure (N allocations), then with allocation k failing for every k < N ----
+static bool nothing_live() { return live() == 0 && g_streams == 0 && g_events == 0; }
+
+// ---- the sweep: `call` on a fresh handle without failure (N creations), then with creation k failing for every k < N ----
 template <class H>
 static void sweep(const char *name, std::function<H *()> make, std::function<int(H *)> call, std::function<void(H *)> coherent,
                   std::function<void(H *)> full, std::function<void(H *)> destroy)
@@ -122,7 +146,7 @@ static void sweep(const char *name, std::function<H *()> make, std::function<int
     g_allocs = 0;
     REQUIRE(call(h) == ORBX_OK && g_allocs == 0, "%s: the same call again allocates nothing", name);
     destroy(h);
-    REQUIRE(live() == 0 && g_streams == 0, "%s: %d live blocks, %d streams after destroy", name, live(), g_streams);
+    REQUIRE(nothing_live(), "%s: %d live blocks, %d streams, %d events after destroy", name, live(), g_streams, g_events);
     for (int k = 0; k < N; k++) {
         h = make();
         g_allocs = 0; g_fail_at = k;
@@ -132,10 +156,12 @@ static void sweep(const char *name, std::function<H *()> make, std::function<int
         coherent(h);
         REQUIRE(call(h) == ORBX_OK, "%s repeated after failure %d of %d", name, k, N);
         coherent(h); full(h);
+        g_allocs = 0;
+        REQUIRE(call(h) == ORBX_OK && g_allocs == 0, "%s, failure %d: a third call creates nothing", name, k);
         destroy(h);
-        REQUIRE(live() == 0 && g_streams == 0, "%s, failure %d: %d live blocks, %d streams after destroy", name, k, live(), g_streams);
+        REQUIRE(nothing_live(), "%s, failure %d: %d live blocks, %d streams, %d events after destroy", name, k, live(), g_streams, g_events);
     }
-    printf("ok %-22s %d allocations swept\n", name, N);
+    printf("ok %-22s %d creations swept\n", name, N);
 }
 
 // ---- matcher ----
@@ -273,15 +299,83 @@ static void database_cases()
         }, destroy);
 }
 
+// ---- extractor: 1000 features, 8 levels, at most 2 frames of 322 x 241 ----
+static int create_extractor(orbx_extractor **h) { return orbx_create(h, 1000, 1.2f, 8, 20, 7, 0, 322, 241, 2); }
+static orbx_extractor *make_extractor()
+{
+    orbx_extractor *h = nullptr;
+    REQUIRE(create_extractor(&h) == ORBX_OK && h, "orbx_create: %s", orbx_last_error());
+    return h;
+}
+template <class T, bool P> static bool inside(const DevBuf<T, P> &b, const void *p, size_t bytes)
+{
+    const uint8_t *lo = (const uint8_t *)b.get(), *q = (const uint8_t *)p;
+    return lo && q >= lo && q + bytes <= lo + b.bytes();
+}
+static void extractor_coherent(orbx_extractor *h)
+{
+    const size_t B = (size_t)h->max_batch, LV = B * ORBX_MAX_LEVELS * 4, n = B * h->max_plan.out_cap;
+    const OrbxPlan &M = h->max_plan;
+    const OrbxWork &w = h->work;
+    REQUIRE(inside(h->w_cand, w.cand, B * M.cand_frame * sizeof(OrbxCand)) && inside(h->w_owner, w.owner, B * M.cand_frame * 4), "work.cand / owner outside their blocks");
+    REQUIRE(inside(h->w_arena, w.arena, B * M.arena_frame * sizeof(OrbxNode)) && inside(h->w_sel, w.sel, B * M.list_frame * sizeof(OrbxCand)), "work.arena / sel outside their blocks");
+    REQUIRE(inside(h->w_cand_count, w.cand_count, LV * ORBX_CNT_STRIDE) && inside(h->w_nk, w.nk, LV) && inside(h->w_ncand, w.ncand, LV) && inside(h->w_errflags, w.errflags, B * 4),
+            "work counters outside their blocks");
+    REQUIRE(inside(h->d_out, h->d_counts, B * 4) && inside(h->d_out, h->d_status, B * 4) && inside(h->d_out, h->d_kps, n * sizeof(orbx_keypoint)) && inside(h->d_out, h->d_desc, n * 32),
+            "device output views outside d_out");
+    REQUIRE(inside(h->h_out, h->h_counts, B * 4) && inside(h->h_out, h->h_status, B * 4) && inside(h->h_out, h->h_kps, n * sizeof(orbx_keypoint)) && inside(h->h_out, h->h_desc, n * 32),
+            "host output views outside h_out");
+    REQUIRE(!h->d_color == !h->h_color && h->d_color.bytes() == h->h_color.bytes(), "colour buffers: both or neither");
+    size_t nup = 0, ndone = 0, nring = 0;
+    for (const OrbxChunkEvents &p : h->chunk_ev) { nup += p.up.get() != nullptr; ndone += p.done.get() != nullptr; }
+    REQUIRE(nup == ndone && nup == h->chunk_ev.size(), "%zu upload events, %zu completion events", nup, ndone);
+    for (const OrbxRingSlot &r : h->ring) for (const DevEvent &e : r.e) nring += e.get() != nullptr;
+    REQUIRE(nring == 0 || nring == 5 * ORBX_PROF_RING, "%zu of the ring's events exist", nring);
+    REQUIRE(h->profiling != 2 || nring == 5 * ORBX_PROF_RING, "ring profiling is on without its events");
+}
+static void extractor_cases()
+{
+    // orbx_create: count its creations, then fail each
+    g_fail_at = -1; g_allocs = 0;
+    orbx_extractor *h = make_extractor();
+    const int N = g_allocs, blocks = live(), streams = g_streams, events = g_events;
+    extractor_coherent(h);
+    orbx_destroy(h);
+    REQUIRE(nothing_live(), "orbx_create + orbx_destroy: %d live blocks, %d streams, %d events", live(), g_streams, g_events);
+    REQUIRE(N == blocks + streams + events && blocks > 0 && streams > 0 && events > 0, "%d creations: %d blocks, %d streams, %d events", N, blocks, streams, events);
+    for (int k = 0; k < N; k++) {
+        h = (orbx_extractor *)16;
+        g_allocs = 0; g_fail_at = k;
+        const int rc = create_extractor(&h);
+        g_fail_at = -1;
+        REQUIRE(rc == ORBX_E_HIP && h == nullptr, "orbx_create with creation %d of %d failing returned %d, handle %p", k, N, rc, (void *)h);
+        REQUIRE(nothing_live(), "orbx_create, failure %d: %d live blocks, %d streams, %d events", k, live(), g_streams, g_events);
+    }
+    printf("ok %-22s %d creations swept (%d blocks, %d streams, %d events)\n", "orbx_create", N, blocks, streams, events);
+
+    auto destroy = [](orbx_extractor *e) { orbx_destroy(e); };
+    sweep<orbx_extractor>("orbx colour buffers", make_extractor, [](orbx_extractor *e) { return orbx_ensure_color(e); }, extractor_coherent,
+        [](orbx_extractor *e) { REQUIRE(e->d_color && e->h_color, "colour buffers after a successful call"); }, destroy);
+    sweep<orbx_extractor>("orbx pyramid staging", make_extractor, [](orbx_extractor *e) { return orbx_ensure_pyr_staging(e, 100000); }, extractor_coherent,
+        [](orbx_extractor *e) { REQUIRE(e->h_pyr.bytes() >= 100000, "staging %zu", e->h_pyr.bytes()); }, destroy);
+    sweep<orbx_extractor>("orbx chunk events", make_extractor,
+        [](orbx_extractor *e) { XTRY(orbx_ensure_chunk_events(e, 3)); return orbx_ensure_chunk_events(e, 5); }, extractor_coherent,
+        [](orbx_extractor *e) { REQUIRE(e->chunk_ev.size() == 5, "%zu chunk event pairs", e->chunk_ev.size()); }, destroy);
+    sweep<orbx_extractor>("orbx ring events", make_extractor, [](orbx_extractor *e) { return orbx_set_profiling(e, 2); }, extractor_coherent,
+        [](orbx_extractor *e) { REQUIRE(e->profiling == 2 && e->ring.size() == ORBX_PROF_RING, "profiling %d, %zu ring slots", e->profiling, e->ring.size()); }, destroy);
+}
+
 int main()
 {
+    setvbuf(stdout, nullptr, _IONBF, 0);      // a leak report ends the process without flushing
     buffer_alone<DevBuf<int32_t>>("DevBuf");
     buffer_alone<PinBuf<uint8_t>>("PinBuf");
     printf("ok buffer type\n");
     matcher_cases();
     vocabulary_case();
     database_cases();
-    REQUIRE(live() == 0 && g_streams == 0, "%d live blocks, %d streams at exit", live(), g_streams);
+    extractor_cases();
+    REQUIRE(nothing_live(), "%d live blocks, %d streams, %d events at exit", live(), g_streams, g_events);
     printf("sweep ok\n");
     return 0;
 }

@@ -563,3 +563,34 @@ def test_tile_switch_across_a_shape_change(orbx, synth, monkeypatch):
         ex(a)
         for l, (got, want) in enumerate(zip(ex.image_pyramid(), opyr.pyramid(a))):
             assert np.array_equal(got, want), "call %d (%dx%d): level %d differs" % (i, w, h, l)
+
+
+@pytest.mark.gpu
+def test_extractor_lifecycle_repeats(orbx, synth):
+    """Three create .. destroy cycles of one batch handle through everything it owns lazily: the chunk graphs and chunk events, the
+    colour blocks, the profiling ring, the pyramid download staging, the staging threads.  Every result against the oracle."""
+    import gray_oracle as G
+    W, Hh, B = 322, 241, 4
+    grey = [np.stack([synth.texture(800 + 4 * i + k, W, Hh) for k in range(B)]) for i in range(4)]
+    colour = [np.ascontiguousarray(np.stack([g, np.roll(g, 37, axis=2), 255 - g], -1)) for g in grey[:2]]
+    opyr = O.Extractor(1000)
+    for cycle in range(3):
+        ex = orbx.ORBextractor(1000, max_width=W, max_height=Hh, max_batch=B)
+        ex.set_batch_chunk(1)
+        for imgs in grey[:3]:                                   # plain, chunk-graph capture, replay
+            for got, a in zip(ex.extract_batch(imgs), imgs):
+                _same(got, a, 0)
+        ex.set_input_format(orbx.ORBX_FMT_BGR8)
+        for imgs in colour:                                     # capture in the new format, replay
+            for got, a in zip(ex.extract_batch(imgs), imgs):
+                _same(got, G.to_gray(a, G.FMT_BGR8), 0)
+        ex.set_input_format(orbx.ORBX_FMT_GRAY8)
+        ex.set_profiling(2)
+        for got, a in zip(ex.extract_batch(grey[3]), grey[3]):  # the call waits for its stream: the ring can be read
+            _same(got, a, 0)
+        ms = ex.stage_ms_ring()
+        assert ms.shape == (1, 4) and np.isfinite(ms).all() and (ms > 0).all(), (cycle, ms)
+        ex.set_profiling(0)
+        for l, (got, want) in enumerate(zip(ex.image_pyramid_all(border=0), opyr.pyramid(grey[3][0]))):
+            assert np.array_equal(got, want), "cycle %d: level %d differs" % (cycle, l)
+        ex.close()
