@@ -384,8 +384,11 @@ int orbm_distinctive_descriptors_device(orbm_matcher *m, int n_points, const int
  * orbm_camera is what the loop reads of a key frame (:219-234, :272-284, :314-316, :365, :392, :428): Rcw = GetRotation() (row-major),
  * tcw = GetTranslation(), Ow = GetCameraCenter(), the calibration, mb, mbf, mfScaleFactor and the per-level tables.  Key frame 1
  * (mpCurrentKeyFrame) has one block; the second views are `ncams2` blocks, and every match names its view, so several neighbours'
- * matches may share a call.  The reference's own caller goes one neighbour at a time (an accepted match changes the next
- * neighbour's SearchForTriangulation): ncams2 = 1.  The per-feature arrays of the second views are concatenated, view v owning
+ * matches may share a call.  The reference's own caller goes one neighbour at a time: ncams2 = 1.  What the next neighbour's
+ * SearchForTriangulation sees of an accepted match is only that pKF1->GetMapPoint(idx1) is no longer NULL, which removes that
+ * feature's row from the search; no other feature's match, and nothing in this loop, depends on the previous neighbour
+ * (orbm_create_new_map_points below runs all neighbours at once on that ground).
+ * The per-feature arrays of the second views are concatenated, view v owning
  * the features off2[v] .. off2[v+1]-1; off2 has ncams2 + 1 entries, off2[0] = 0.
  *   kps_un = mvKeysUn (pt and octave are read), keys_xy = mvKeys[i].pt as 2 floats per feature (UnprojectStereo reads the raw
  *   keys, not mvKeysUn), u_right = mvuRight, depth = mvDepth
@@ -425,7 +428,8 @@ typedef enum {
     ORBM_TRI_ZERO_DIST = 9,      /* :425 */
     ORBM_TRI_SCALE = 10,         /* :433 */
     ORBM_TRI_UNDEFINED = 11,     /* undefined in the reference: UnprojectStereo of a feature with mvDepth <= 0 */
-    ORBM_TRI_BAD_INDEX = 12      /* device-pointer form only: index, view or octave out of range */
+    ORBM_TRI_BAD_INDEX = 12,     /* device-pointer form only: index, view or octave out of range */
+    ORBM_TRI_NO_MATCH = 255      /* orbm_create_new_map_points only: the slot holds no pair (matches12 < 0) */
 } orbm_tri_status;
 typedef struct {
     float Rcw[9];                               /* GetRotation(), row-major */
@@ -448,6 +452,56 @@ int orbm_triangulate_matches_device(orbm_matcher *m, const orbm_camera *d_cam1, 
                                     const orbm_camera *d_cams2, int ncams2, const int32_t *d_off2, const orbx_keypoint *d_kps_un2,
                                     const float *d_keys_xy2, const float *d_u_right2, const float *d_depth2,
                                     const int32_t *d_matches, int n, uint8_t *d_status, float *d_x3d, void *hip_stream);
+
+/*
+ * ---- LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:209-454): every neighbour's search and triangulation in one call ----
+ * The reference's loop (:239-453) makes, per neighbour, one SearchForTriangulation (:270) and one pass over its pairs (:288-434).
+ * The matcher of :217 is ORBmatcher(0.6,false), so the rotation histogram never runs; vbMatched2 is never set; and before neighbour
+ * k's own turn the loop has written nothing that the search reads of it (:436-451 writes to mpCurrentKeyFrame and to the neighbour
+ * whose turn it is).  The result for feature idx1 of key frame 1 against neighbour k therefore depends on idx1, on neighbour k's
+ * features and MapPoint slots, on F12 and on the epipole -- on no other feature and no other neighbour -- with one exception:
+ * a feature that received a MapPoint from an earlier neighbour is skipped (:699-703), which removes its row and changes no other.
+ * So all searches and all triangulations run here on ONE snapshot taken before the loop, and the caller's loop replays the
+ * exception on the dense result: at neighbour v's turn it takes the slots (v, idx1) with matches12 >= 0 in ascending idx1 and keeps
+ * those whose pKF1->GetMapPoint(idx1) is still NULL (host/CreateNewMapPoints.h does that).
+ *
+ * Key frame 1: its orbm_camera, kps_un1 / keys_xy1 / u_right1 / depth1 as for orbm_triangulate_matches, desc1 (32 bytes per
+ * feature), has_mp1 = (GetMapPoint(idx) != NULL) and its FeatureVector as CSR (fv1_node ascending, fv1_off, fv1_idx, fv1_n nodes).
+ * `nviews` second views in the caller's order: cams2[v] (the epipole, 100*mvScaleFactors, 3.84*mvLevelSigma2 and everything the
+ * triangulation reads come from it), F12[9*v ..] = ComputeF12(pKF1, pKF2_v) row-major, off2[nviews+1] into the concatenated
+ * kps_un2 / keys_xy2 / u_right2 / depth2 / desc2 / has_mp2, and the views' FeatureVectors concatenated: view v owns the nodes
+ * fv2_view_off[v] .. fv2_view_off[v+1]-1 of fv2_node / fv2_off (fv2_off has fv2_view_off[nviews] + 1 entries and runs through
+ * all views), and the entries of fv2_idx are feature indices inside their view.  only_stereo as for orbm_search_for_triangulation.
+ * There is no check_orientation: the histogram cull (src/ORBmatcher.cc:764-810) depends on which features take part in the
+ * search, so it does not survive taking rows out afterwards; a caller that wants it keeps the per-neighbour calls.
+ *
+ * Outputs, one slot per (view, feature of key frame 1), slot = v*n1 + idx1:
+ *   matches12[slot] = idx2 inside view v, or -1            = orbm_search_for_triangulation(view v alone, check_orientation = 0)
+ *   status[slot]    = orbm_tri_status of the pair, or ORBM_TRI_NO_MATCH where matches12 < 0
+ *   x3d[3*slot ..]  = the new MapPoint's position for the accepted statuses, zeros otherwise
+ *                                                          = orbm_triangulate_matches on view v's pair list
+ *   nmatches[v]     = what orbm_search_for_triangulation returns in *nmatches for view v
+ * The candidate taken is the last of minimal distance, positions inside a node are clamped to 20 bits, and :315's `else
+ * if(bStereo2)`, :408's mpCurrentKeyFrame->mbf, the fp64 Jacobi and ORBM_TRI_UNDEFINED are orbm_triangulate_matches' (same code).
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: negative counts, NULL buffers, off2 / fv2_view_off / fv1_off /
+ * fv2_off not monotone from 0, node ids not ascending, a feature index outside its key frame or view, nlevels outside
+ * [1, ORBX_MAX_LEVELS], an octave outside its camera's levels -- of every feature, since the pairs are not known beforehand).
+ * nviews == 0 or n1 == 0 is ORBX_OK and touches nothing, the handle and the outputs included.  A call in which no feature of key
+ * frame 1 is left to search (no shared node, every feature has a MapPoint) is answered on the host; every other call needs the
+ * GPU, and a NULL handle behaves as in orbm_triangulate_matches.  The call runs on the handle's stream through its staging arena:
+ * one upload (key frame 1 once), the search launch over the queries of all views, the triangulation launch over the same queries
+ * (nothing returns to the host in between), one download.  It grows the handle when it is larger than its workspace and leaves the
+ * grid slots as it found them (orbm_grid_count() and window searches are unchanged by it).
+ */
+int orbm_create_new_map_points(orbm_matcher *m, const orbm_camera *cam1, const orbx_keypoint *kps_un1, const float *keys_xy1,
+                               const float *u_right1, const float *depth1, const uint8_t *desc1, int n1, const uint8_t *has_mp1,
+                               const int32_t *fv1_node, const int32_t *fv1_off, const int32_t *fv1_idx, int fv1_n,
+                               const orbm_camera *cams2, const float *F12, int nviews, const int32_t *off2,
+                               const orbx_keypoint *kps_un2, const float *keys_xy2, const float *u_right2, const float *depth2,
+                               const uint8_t *desc2, const uint8_t *has_mp2, const int32_t *fv2_view_off, const int32_t *fv2_node,
+                               const int32_t *fv2_off, const int32_t *fv2_idx, int only_stereo,
+                               int32_t *matches12, uint8_t *status, float *x3d, int32_t *nmatches);
 
 /*
  * ---- Frame::isInFrustum for all local MapPoints of a frame, and Tracking::SearchLocalPoints in one call ----

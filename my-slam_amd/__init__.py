@@ -35,6 +35,7 @@ assert VIEW_DTYPE.itemsize == 168
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
+ORBM_TRI_NO_MATCH = 255      # orbm_tri_status of a (view, feature) slot without a pair (ORBmatcher.create_new_map_points)
 ORBX_OPT_BLUR_ROUNDING = 1
 ORBX_OPT_SUBBATCHES = 2
 ORBX_OPT_OVERLAP_PYRAMID = 3
@@ -251,6 +252,9 @@ def _bind_matcher(L):
     L.orbm_triangulate_matches.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp]
     L.orbm_triangulate_matches_device.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp]
     L.orbm_triangulate_matches.restype = L.orbm_triangulate_matches_device.restype = C.c_int
+    L.orbm_create_new_map_points.argtypes = [vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, C.c_int,
+                                             vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.orbm_create_new_map_points.restype = C.c_int
     L.orbm_frustum.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_frustum_device.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_search_local_points.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_float,
@@ -611,6 +615,39 @@ class ORBmatcher:
         """The same on raw device pointers; nothing is synchronised.  Out-of-range indices get status 12 (ORBM_TRI_BAD_INDEX)."""
         _mchk(self.L.orbm_triangulate_matches_device(self.h, d_cam1, d_kps_un1, d_keys_xy1, d_u_right1, d_depth1, n1, d_cams2, ncams2, d_off2,
                                                      d_kps_un2, d_keys_xy2, d_u_right2, d_depth2, d_matches, n, d_status, d_x3d, stream))
+
+    def create_new_map_points(self, cam1, kps_un1, keys_xy1, u_right1, depth1, desc1, has_mp1, featvec1, cams2, F12, off2, kps_un2,
+                              keys_xy2, u_right2, depth2, desc2, has_mp2, fv2_view_off, featvec2, only_stereo=False):
+        """LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:209-454) for all neighbours in one call: SearchForTriangulation
+        against every second view and the per-match loop over what it found, on one snapshot.  Key frame 1 and the concatenated
+        second views as for triangulate_matches, plus descriptors, has_mp flags and FeatureVectors (featvec1 = (node, off, idx);
+        featvec2 = the views' (node, off, idx) concatenated, view v owning the nodes fv2_view_off[v]:fv2_view_off[v+1], indices
+        inside their view) and F12 float32 [nviews, 3, 3].  Returns (matches12 int32 [nviews, n1], status uint8 [nviews, n1],
+        x3d float32 [nviews, n1, 3], nmatches int32 [nviews]); status 255 (ORBM_TRI_NO_MATCH) where matches12 < 0."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        i32 = lambda a: np.ascontiguousarray(a, np.int32).reshape(-1)
+        cam1 = np.ascontiguousarray(cam1, CAM_DTYPE).reshape(1)
+        cams2 = np.ascontiguousarray(cams2, CAM_DTYPE).reshape(-1)
+        off2, fvo = i32(off2), i32(fv2_view_off)
+        k1, k2 = np.ascontiguousarray(kps_un1, KP_DTYPE), np.ascontiguousarray(kps_un2, KP_DTYPE)
+        x1, x2 = f32(keys_xy1).reshape(-1, 2), f32(keys_xy2).reshape(-1, 2)
+        u1, u2, z1, z2 = f32(u_right1), f32(u_right2), f32(depth1), f32(depth2)
+        d1, d2 = np.ascontiguousarray(desc1, np.uint8).reshape(-1, 32), np.ascontiguousarray(desc2, np.uint8).reshape(-1, 32)
+        h1, h2 = np.ascontiguousarray(has_mp1, np.uint8).reshape(-1), np.ascontiguousarray(has_mp2, np.uint8).reshape(-1)
+        n1n, n1o, n1i = [i32(a) for a in featvec1]
+        n2n, n2o, n2i = [i32(a) for a in featvec2]
+        F12 = f32(F12).reshape(-1, 9)
+        nv, n1 = len(cams2), len(k1)
+        if len(off2) != nv + 1 or len(fvo) != nv + 1 or len(F12) != nv or not (n1 == len(x1) == len(u1) == len(z1) == len(d1) == len(h1)) \
+                or not (len(k2) == len(x2) == len(u2) == len(z2) == len(d2) == len(h2) == int(off2[-1])) \
+                or len(n1o) != len(n1n) + 1 or len(n2o) != len(n2n) + 1 or int(fvo[-1]) != len(n2n) or int(n1o[-1]) != len(n1i) or int(n2o[-1]) != len(n2i):
+            raise OrbxError(ORBX_E_INVALID, "array lengths disagree: %d views, off2 %s, fv2_view_off %s, %d / %d features" % (nv, off2[-1:], fvo[-1:], n1, len(k2)))
+        m12 = np.full((nv, n1), -1, np.int32)
+        status, x3d, nm = np.full((nv, n1), 255, np.uint8), np.zeros((nv, n1, 3), np.float32), np.zeros(nv, np.int32)
+        _mchk(self.L.orbm_create_new_map_points(self.h, _p(cam1), _p(k1), _p(x1), _p(u1), _p(z1), _p(d1), n1, _p(h1), _p(n1n), _p(n1o), _p(n1i), len(n1n),
+                                                _p(cams2), _p(F12), nv, _p(off2), _p(k2), _p(x2), _p(u2), _p(z2), _p(d2), _p(h2), _p(fvo), _p(n2n), _p(n2o),
+                                                _p(n2i), 1 if only_stereo else 0, _p(m12), _p(status), _p(x3d), _p(nm)))
+        return m12, status, x3d, nm
 
     @staticmethod
     def _frustum_inputs(view, skip, xw, normal, mf_max, mf_min):

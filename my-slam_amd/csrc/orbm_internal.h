@@ -1,4 +1,5 @@
-// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip and orbm_frustum.hip
+// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip and
+// orbm_frustum.hip
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -15,196 +15,9 @@
 //
 // The two 4x4 fp64 matrices of the Jacobi live in named registers (D4 columns, every access a compile-time member): a private
 // array indexed by a loop variable would go to scratch memory.
+// The device functions (tri_one and what it calls) are in orbm_tri_body.h, which orbm_newpoints.hip includes as well.
 #include "orbm_internal.h"
-#include "sincos_cr.h"
-
-#define TRI_THREADS 64
-#define TRI_MAX_SWEEPS 12
-// a column pair is left alone once |p.q| <= TRI_TOL |p| |q| (2^-50)
-#define TRI_TOL 8.8817841970012523e-16
-
-struct D4 { double a, b, c, d; };
-
-__device__ __forceinline__ double d4_dot(const D4 &p, const D4 &q) { return ((p.a * q.a + p.b * q.b) + p.c * q.c) + p.d * q.d; }
-
-// one Jacobi rotation of the column pair (p, q) of U, applied to V as well; false when the pair is already orthogonal
-__device__ __forceinline__ bool jacobi_pair(D4 &up, D4 &uq, D4 &vp, D4 &vq)
-{
-    const double alpha = d4_dot(up, up), beta = d4_dot(uq, uq), gamma = d4_dot(up, uq);
-    if (!(fabs(gamma) > TRI_TOL * sqrt(alpha * beta))) return false;
-    const double zeta = (beta - alpha) / (2.0 * gamma);
-    const double t = copysign(1.0, zeta) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
-    const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
-    D4 n;
-    n.a = c * up.a - s * uq.a; uq.a = s * up.a + c * uq.a; up.a = n.a;
-    n.b = c * up.b - s * uq.b; uq.b = s * up.b + c * uq.b; up.b = n.b;
-    n.c = c * up.c - s * uq.c; uq.c = s * up.c + c * uq.c; up.c = n.c;
-    n.d = c * up.d - s * uq.d; uq.d = s * up.d + c * uq.d; up.d = n.d;
-    n.a = c * vp.a - s * vq.a; vq.a = s * vp.a + c * vq.a; vp.a = n.a;
-    n.b = c * vp.b - s * vq.b; vq.b = s * vp.b + c * vq.b; vp.b = n.b;
-    n.c = c * vp.c - s * vq.c; vq.c = s * vp.c + c * vq.c; vp.c = n.c;
-    n.d = c * vp.d - s * vq.d; vq.d = s * vp.d + c * vq.d; vp.d = n.d;
-    return true;
-}
-
-// the right singular vector of the smallest singular value of the 4x4 matrix with columns u0..u3 (the first column of minimal
-// norm after the sweeps)
-__device__ __forceinline__ D4 smallest_right_singular_vector(D4 u0, D4 u1, D4 u2, D4 u3)
-{
-    D4 v0 = {1.0, 0.0, 0.0, 0.0}, v1 = {0.0, 1.0, 0.0, 0.0}, v2 = {0.0, 0.0, 1.0, 0.0}, v3 = {0.0, 0.0, 0.0, 1.0};
-    for (int sweep = 0; sweep < TRI_MAX_SWEEPS; sweep++) {
-        bool any = jacobi_pair(u0, u1, v0, v1);
-        any |= jacobi_pair(u0, u2, v0, v2);
-        any |= jacobi_pair(u0, u3, v0, v3);
-        any |= jacobi_pair(u1, u2, v1, v2);
-        any |= jacobi_pair(u1, u3, v1, v3);
-        any |= jacobi_pair(u2, u3, v2, v3);
-        if (!any) break;                // every further sweep would leave every pair alone as well
-    }
-    double best = d4_dot(u0, u0);
-    D4 v = v0;
-    const double s1 = d4_dot(u1, u1), s2 = d4_dot(u2, u2), s3 = d4_dot(u3, u3);
-    if (s1 < best) { best = s1; v = v1; }
-    if (s2 < best) { best = s2; v = v2; }
-    if (s3 < best) { best = s3; v = v3; }
-    return v;
-}
-
-// cv::gemm's small-matrix path, the float sum of one row (orbm_internal.h gemm3)
-__device__ __forceinline__ float tri_sum3(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return __fadd_rn(__fadd_rn(__fmul_rn(a0, b0), __fmul_rn(a1, b1)), __fmul_rn(a2, b2));
-}
-// Mat::dot / the squares of cv::norm: float products are exact in double, the sum is double
-__device__ __forceinline__ double tri_dot3(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return ((double)a0 * (double)b0 + (double)a1 * (double)b1) + (double)a2 * (double)b2;
-}
-// one element of `alpha*rowA - rowB` (:325-328): MatOp_AddEx hands alpha != 1, beta = -1 to cv::addWeighted, whose 32f kernel works
-// in double and adds gamma = 0; alpha == 1 is cv::subtract in float
-__device__ __forceinline__ float tri_arow(float alpha, float a, float b)
-{
-    if (alpha == 1.0f) return __fsub_rn(a, b);
-    return (float)(((double)a * (double)alpha + (double)b * -1.0) + 0.0);
-}
-// cos(2*atan2(mb/2, depth)) of :314 / :316 with the float overloads, each function correctly rounded
-__device__ __forceinline__ float tri_cos_stereo(float mb, float depth)
-{
-    const float half = __fdiv_rn(mb, 2.0f);
-    const float at = (float)atan2((double)half, (double)depth);
-    const float ang = __fmul_rn(2.0f, at);
-    float cs, sn;
-    sincos_cr(fabsf(ang), &cs, &sn);    // |ang| <= 2 pi, cos is even
-    return cs;
-}
-
-struct TriView {                        // what :293-298 and UnprojectStereo read of one feature
-    float x, y, raw_x, raw_y, ur, depth;
-    int oct;
-};
-
-// KeyFrame::UnprojectStereo (src/KeyFrame.cc:615-631): false where the reference returns an empty matrix
-__device__ __forceinline__ bool tri_unproject(const orbm_camera *__restrict__ C, const TriView &f, float X[3])
-{
-    const float z = f.depth;
-    if (!(z > 0)) return false;
-    const float x = __fmul_rn(__fmul_rn(__fsub_rn(f.raw_x, C->cx), z), C->invfx);
-    const float y = __fmul_rn(__fmul_rn(__fsub_rn(f.raw_y, C->cy), z), C->invfy);
-    // Twc.rowRange(0,3).colRange(0,3) = Rcw^T, Twc.rowRange(0,3).col(3) = Ow (src/KeyFrame.cc:66-70)
-    X[0] = (float)((double)tri_sum3(C->Rcw[0], C->Rcw[3], C->Rcw[6], x, y, z) + (double)C->Ow[0]);
-    X[1] = (float)((double)tri_sum3(C->Rcw[1], C->Rcw[4], C->Rcw[7], x, y, z) + (double)C->Ow[1]);
-    X[2] = (float)((double)tri_sum3(C->Rcw[2], C->Rcw[5], C->Rcw[8], x, y, z) + (double)C->Ow[2]);
-    return true;
-}
-
-// the reprojection test of one view (:365-389 / :392-415); mbf is mpCurrentKeyFrame's in both (:382, :408)
-__device__ __forceinline__ bool tri_reprojection_fails(const orbm_camera *__restrict__ C, const TriView &f, bool stereo, float mbf,
-                                                       const float X[3], float z)
-{
-    const float sigma2 = C->level_sigma2[f.oct];
-    const float xc = (float)(tri_dot3(C->Rcw[0], C->Rcw[1], C->Rcw[2], X[0], X[1], X[2]) + (double)C->tcw[0]);
-    const float yc = (float)(tri_dot3(C->Rcw[3], C->Rcw[4], C->Rcw[5], X[0], X[1], X[2]) + (double)C->tcw[1]);
-    const float invz = (float)(1.0 / (double)z);
-    const float u = __fadd_rn(__fmul_rn(__fmul_rn(C->fx, xc), invz), C->cx);
-    const float v = __fadd_rn(__fmul_rn(__fmul_rn(C->fy, yc), invz), C->cy);
-    const float ex = __fsub_rn(u, f.x), ey = __fsub_rn(v, f.y);
-    const float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-    if (!stereo) return (double)e2 > 5.991 * (double)sigma2;
-    const float u_r = __fsub_rn(u, __fmul_rn(mbf, invz));
-    const float er = __fsub_rn(u_r, f.ur);
-    return (double)__fadd_rn(e2, __fmul_rn(er, er)) > 7.8 * (double)sigma2;
-}
-
-__device__ __forceinline__ int tri_one(const orbm_camera *__restrict__ C1, const orbm_camera *__restrict__ C2, const TriView &f1,
-                                       const TriView &f2, float X[3])
-{
-    const bool st1 = f1.ur >= 0, st2 = f2.ur >= 0;                                              // :295, :299
-    // Check parallax between rays :302-307
-    const float xn1x = __fmul_rn(__fsub_rn(f1.x, C1->cx), C1->invfx), xn1y = __fmul_rn(__fsub_rn(f1.y, C1->cy), C1->invfy);
-    const float xn2x = __fmul_rn(__fsub_rn(f2.x, C2->cx), C2->invfx), xn2y = __fmul_rn(__fsub_rn(f2.y, C2->cy), C2->invfy);
-    const float r1x = tri_sum3(C1->Rcw[0], C1->Rcw[3], C1->Rcw[6], xn1x, xn1y, 1.0f);
-    const float r1y = tri_sum3(C1->Rcw[1], C1->Rcw[4], C1->Rcw[7], xn1x, xn1y, 1.0f);
-    const float r1z = tri_sum3(C1->Rcw[2], C1->Rcw[5], C1->Rcw[8], xn1x, xn1y, 1.0f);
-    const float r2x = tri_sum3(C2->Rcw[0], C2->Rcw[3], C2->Rcw[6], xn2x, xn2y, 1.0f);
-    const float r2y = tri_sum3(C2->Rcw[1], C2->Rcw[4], C2->Rcw[7], xn2x, xn2y, 1.0f);
-    const float r2z = tri_sum3(C2->Rcw[2], C2->Rcw[5], C2->Rcw[8], xn2x, xn2y, 1.0f);
-    const double n1 = sqrt(tri_dot3(r1x, r1y, r1z, r1x, r1y, r1z)), n2 = sqrt(tri_dot3(r2x, r2y, r2z, r2x, r2y, r2z));
-    const float cos_rays = (float)(tri_dot3(r1x, r1y, r1z, r2x, r2y, r2z) / (n1 * n2));
-    float cos_st1 = __fadd_rn(cos_rays, 1.0f), cos_st2 = cos_st1;                               // :309-311
-    if (st1) cos_st1 = tri_cos_stereo(C1->mb, f1.depth);                                        // :313-316
-    else if (st2) cos_st2 = tri_cos_stereo(C2->mb, f2.depth);
-    const float cos_st = cos_st2 < cos_st1 ? cos_st2 : cos_st1;                                 // std::min :318
-    int accepted;
-    if (cos_rays < cos_st && cos_rays > 0 && (st1 || st2 || (double)cos_rays < 0.9998)) {       // :321
-        // Linear Triangulation Method :324-328; column j of A = element j of the four rows
-        const D4 u0 = {(double)tri_arow(xn1x, C1->Rcw[6], C1->Rcw[0]), (double)tri_arow(xn1y, C1->Rcw[6], C1->Rcw[3]),
-                       (double)tri_arow(xn2x, C2->Rcw[6], C2->Rcw[0]), (double)tri_arow(xn2y, C2->Rcw[6], C2->Rcw[3])};
-        const D4 u1 = {(double)tri_arow(xn1x, C1->Rcw[7], C1->Rcw[1]), (double)tri_arow(xn1y, C1->Rcw[7], C1->Rcw[4]),
-                       (double)tri_arow(xn2x, C2->Rcw[7], C2->Rcw[1]), (double)tri_arow(xn2y, C2->Rcw[7], C2->Rcw[4])};
-        const D4 u2 = {(double)tri_arow(xn1x, C1->Rcw[8], C1->Rcw[2]), (double)tri_arow(xn1y, C1->Rcw[8], C1->Rcw[5]),
-                       (double)tri_arow(xn2x, C2->Rcw[8], C2->Rcw[2]), (double)tri_arow(xn2y, C2->Rcw[8], C2->Rcw[5])};
-        const D4 u3 = {(double)tri_arow(xn1x, C1->tcw[2], C1->tcw[0]), (double)tri_arow(xn1y, C1->tcw[2], C1->tcw[1]),
-                       (double)tri_arow(xn2x, C2->tcw[2], C2->tcw[0]), (double)tri_arow(xn2y, C2->tcw[2], C2->tcw[1])};
-        const D4 v = smallest_right_singular_vector(u0, u1, u2, u3);                            // in place of :331-333
-        if ((float)v.d == 0) return ORBM_TRI_W_ZERO;                                            // :335
-        X[0] = (float)(v.a / v.d); X[1] = (float)(v.b / v.d); X[2] = (float)(v.c / v.d);        // :339
-        accepted = ORBM_TRI_SVD;
-    } else if (st1 && cos_st1 < cos_st2) {                                                      // :342
-        if (!tri_unproject(C1, f1, X)) return ORBM_TRI_UNDEFINED;
-        accepted = ORBM_TRI_STEREO1;
-    } else if (st2 && cos_st2 < cos_st1) {                                                      // :346
-        if (!tri_unproject(C2, f2, X)) return ORBM_TRI_UNDEFINED;
-        accepted = ORBM_TRI_STEREO2;
-    } else
-        return ORBM_TRI_LOW_PARALLAX;                                                           // :351
-    // Check triangulation in front of cameras :356-362
-    const float z1 = (float)(tri_dot3(C1->Rcw[6], C1->Rcw[7], C1->Rcw[8], X[0], X[1], X[2]) + (double)C1->tcw[2]);
-    if (z1 <= 0) return ORBM_TRI_BEHIND1;
-    const float z2 = (float)(tri_dot3(C2->Rcw[6], C2->Rcw[7], C2->Rcw[8], X[0], X[1], X[2]) + (double)C2->tcw[2]);
-    if (z2 <= 0) return ORBM_TRI_BEHIND2;
-    if (tri_reprojection_fails(C1, f1, st1, C1->mbf, X, z1)) return ORBM_TRI_REPROJ1;           // :365-389
-    if (tri_reprojection_fails(C2, f2, st2, C1->mbf, X, z2)) return ORBM_TRI_REPROJ2;           // :392-415
-    // Check scale consistency :418-433
-    const float a0 = __fsub_rn(X[0], C1->Ow[0]), a1 = __fsub_rn(X[1], C1->Ow[1]), a2 = __fsub_rn(X[2], C1->Ow[2]);
-    const float b0 = __fsub_rn(X[0], C2->Ow[0]), b1 = __fsub_rn(X[1], C2->Ow[1]), b2 = __fsub_rn(X[2], C2->Ow[2]);
-    const float dist1 = (float)sqrt(tri_dot3(a0, a1, a2, a0, a1, a2)), dist2 = (float)sqrt(tri_dot3(b0, b1, b2, b0, b1, b2));
-    if (dist1 == 0 || dist2 == 0) return ORBM_TRI_ZERO_DIST;
-    const float ratio_dist = __fdiv_rn(dist2, dist1);
-    const float ratio_octave = __fdiv_rn(C1->scale_factors[f1.oct], C2->scale_factors[f2.oct]);
-    const float ratio_factor = __fmul_rn(1.5f, C1->scale_factor);                               // :234
-    if (__fmul_rn(ratio_dist, ratio_factor) < ratio_octave || ratio_dist > __fmul_rn(ratio_octave, ratio_factor)) return ORBM_TRI_SCALE;
-    return accepted;
-}
-
-__device__ __forceinline__ TriView tri_load(const orbx_keypoint *__restrict__ kps, const float2 *__restrict__ keys,
-                                            const float *__restrict__ ur, const float *__restrict__ depth, long long i)
-{
-    TriView f;
-    f.x = kps[i].x; f.y = kps[i].y; f.oct = kps[i].octave;
-    const float2 raw = keys[i];
-    f.raw_x = raw.x; f.raw_y = raw.y; f.ur = ur[i]; f.depth = depth[i];
-    return f;
-}
+#include "orbm_tri_body.h"
 
 __global__ __launch_bounds__(TRI_THREADS) void k_triangulate(
     const orbm_camera *__restrict__ cam1, const orbx_keypoint *__restrict__ kps1, const float2 *__restrict__ keys1,
