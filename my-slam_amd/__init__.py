@@ -719,6 +719,11 @@ class ORBmatcher:
         _mchk(self.L.orbm_match_batch_device(self.h, d_q, d_kq, d_nq, d_t, d_kt, d_nt, cap, nbatch, th,
                                              self.mfNNratio, int(self.mbCheckOrientation), d_match12, d_nmatches, stream))
 
+    def best2_batch_device(self, d_q, d_nq, d_t, d_nt, cap, nbatch, d_best_idx, d_best_d, d_second_d, stream=None):
+        """best2 for nbatch device-resident pairs ([nbatch, cap, 32] descriptors, int32 counts per pair) into three int32
+        [nbatch, cap] arrays; -1 / 256 / 256 beyond a pair's query count.  Raw device pointers; nothing is synchronised."""
+        _mchk(self.L.orbm_best2_batch_device(self.h, d_q, d_nq, d_t, d_nt, cap, nbatch, d_best_idx, d_best_d, d_second_d, stream))
+
     # ---- N1: Frame grid (src/Frame.cc:230-245, 327-392) ----
     def grid_build(self, kps_un, min_x, max_x, min_y, max_y):
         """Frame::AssignFeaturesToGrid for mvKeysUn with the image bounds mnMinX..mnMaxY."""
