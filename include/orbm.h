@@ -296,6 +296,8 @@ int orbm_search_by_bow_kf(orbm_matcher *m,
  * vMatchedPairs is the list of (i, matches12[i]) with matches12[i] >= 0 in ascending i (:812-820).  Entirely on the GPU (one wave
  * per feature of KF1): this reference never sets vbMatched2, so no feature's search depends on another's; the candidate accepted
  * is the last one of minimal distance among those that pass the epipole and epipolar-line tests (:738-755).
+ * Both FeatureVectors are checked as orbm_create_new_map_points checks its own: offsets not monotone, node ids not ascending or a
+ * feature index outside [0, n) are refused with ORBX_E_INVALID before anything is queued (matches12 all -1, *nmatches = 0).
  */
 int orbm_search_for_triangulation(orbm_matcher *m,
                                   const orbx_keypoint *kps1, const uint8_t *desc1, int n1, const uint8_t *has_mp1, const float *u_right1,

@@ -139,28 +139,21 @@ __global__ __launch_bounds__(M_THREADS) void k_best2_csr(
     const uint4 q0 = Q[0], q1 = Q[1];
     const int lo = off[qi], hi = off[qi + 1];
     // pack = dist << 22 | position: min() picks the smallest distance, earliest position
-    uint32_t bp = (256u << 22) | 0x3FFFFFu;
-    int s = 256;
+    uint32_t bp = (256u << 22) | 0x3FFFFFu, s = 256;
     for (int c = lo + lane; c < hi; c += 64) {
         const uint4 *Tj = reinterpret_cast<const uint4 *>(t) + 2 * (long long)idx[c];
-        const int d = hamming256(q0, q1, Tj[0], Tj[1]);
-        const uint32_t p = ((uint32_t)d << 22) | (uint32_t)min(c - lo, 0x3FFFFF);
-        if (p < bp) { s = (int)(bp >> 22); bp = p; }
+        const uint32_t d = (uint32_t)hamming256(q0, q1, Tj[0], Tj[1]);
+        const uint32_t p = (d << 22) | (uint32_t)min(c - lo, 0x3FFFFF);
+        if (p < bp) { s = bp >> 22; bp = p; }
         else if (d < s) s = d;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t op = __shfl_xor(bp, o);
-        const int os = __shfl_xor(s, o);
-        const int loser = (int)(max(bp, op) >> 22);
-        bp = min(bp, op);
-        s = min(min(s, os), loser);
-    }
+    uint32_t B, S;
+    wave_best2<22>(bp, s, B, S);
     if (lane == 0) {
-        const int d = (int)(bp >> 22);
+        const int d = (int)(B >> 22);
         best_d[qi] = d;
-        second_d[qi] = s;
-        best_idx[qi] = d < 256 ? idx[lo + (int)(bp & 0x3FFFFFu)] : -1;
+        second_d[qi] = (int)S;
+        best_idx[qi] = d < 256 ? idx[lo + (int)(B & 0x3FFFFFu)] : -1;
     }
 }
 
@@ -494,8 +487,8 @@ __global__ __launch_bounds__(M_THREADS) void k_bow_select(
                     sk = med3u(bk, sk, key); bk = min(bk, key);
                 }
             }
-            const uint32_t B = wave_min_u32(bk);
-            const uint32_t S2 = wave_min_u32((bk == B) ? sk : bk);   // the winner's position is unique: every other lane offers its best
+            uint32_t B, S2;
+            wave_best2<0>(bk, sk, B, S2);            // the winner's position is unique: every other lane offers its best
             const int best1 = (int)(B >> 16), best2 = (int)(S2 >> 16);
             if (best1 <= th && (float)best1 < __fmul_rn(nnratio, (float)best2)) {     // :228-232 (th = TH_LOW), :598-600 (th = TH_LOW - 1)
                 const int pos = (int)(B & 0xFFFFu);

@@ -9,8 +9,7 @@
 
 #include <climits>
 #include <utility>
-#include "orbm_internal.h"
-#include "orbx_internal.h"
+#include "orbm_window.h"
 
 // -------------------------------------------------------------------------------------------------
 // k_grid_build: one 1024-thread workgroup.  Count per cell (LDS atomics) -> scan -> scatter -> each
@@ -96,27 +95,15 @@ __global__ __launch_bounds__(M_THREADS) void k_area_list(OrbmGrid g, const float
     if (q >= nq) return;
     const float x = qx[q], y = qy[q], r = qr[q];
     const int mn = minl[q], mx = maxl[q];
-    int n = 0, cx0, cx1, cy0, cy1;
-    if (window_cells(g, x, y, r, cx0, cx1, cy0, cy1)) {
-        const int base = MODE == 1 ? off[q] : 0;
-        for (int ix = cx0; ix <= cx1; ix++) {              // a cell column is one contiguous item range
-            const int s = g.cell_start[ix * ORBM_GRID_ROWS + cy0], e = g.cell_start[ix * ORBM_GRID_ROWS + cy1 + 1];
-            for (int j0 = s; j0 < e; j0 += 64) {
-                const int j = j0 + lane;
-                int i = -1;
-                bool ok = false;
-                if (j < e) { i = g.items[j]; ok = in_window(g, i, x, y, r, mn, mx); }
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-                if (MODE == 1 && ok) out[orbx_prefix_cnt(m, base + n)] = i;
-                n += __popcll(m);
-            }
-        }
-    }
+    const int base = MODE == 1 ? off[q] : 0;
+    const int n = window_walk(g, x, y, r, lane, [&](int i) { return in_window(g, i, x, y, r, mn, mx); },
+                              [&](int i, int pos) { if (MODE == 1) out[base + pos] = i; });
     if (MODE == 0 && lane == 0) counts[q] = n;
 }
 
 // fused window query + best / second-best (strict '<': first candidate wins ties, a tie with the best
-// becomes the second best).  Key = distance << 22 | position in the reference's candidate order.
+// becomes the second best).  Key = distance << 22 | position in the reference's candidate order; a keypoint
+// masked by skip[] is no member of the window and takes no position.
 __global__ __launch_bounds__(M_THREADS) void k_search_area(OrbmGrid g, const uint8_t *__restrict__ qdesc,
                                                           const float *__restrict__ qx, const float *__restrict__ qy,
                                                           const float *__restrict__ qr, const int32_t *__restrict__ minl,
@@ -132,46 +119,23 @@ __global__ __launch_bounds__(M_THREADS) void k_search_area(OrbmGrid g, const uin
     const int mn = minl[q], mx = maxl[q];
     const uint4 *Q = reinterpret_cast<const uint4 *>(qdesc) + 2 * (long long)q;
     const uint4 q0 = Q[0], q1 = Q[1];
-    uint32_t bp = (256u << 22) | 0x3FFFFFu;
-    int s2 = 256, bidx = -1, n = 0;
-    int cx0, cx1, cy0, cy1;
-    if (window_cells(g, x, y, r, cx0, cx1, cy0, cy1)) {
-        for (int ix = cx0; ix <= cx1; ix++) {
-            const int s = g.cell_start[ix * ORBM_GRID_ROWS + cy0], e = g.cell_start[ix * ORBM_GRID_ROWS + cy1 + 1];
-            for (int j0 = s; j0 < e; j0 += 64) {
-                const int j = j0 + lane;
-                int i = -1;
-                bool ok = false;
-                if (j < e) {
-                    i = g.items[j];
-                    ok = in_window(g, i, x, y, r, mn, mx) && !(skip && skip[i]);
-                }
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);
-                if (ok) {
+    const uint32_t none = (256u << 22) | 0x3FFFFFu;
+    uint32_t bp = none, s2 = 256;
+    int bidx = -1;
+    window_walk(g, x, y, r, lane, [&](int i) { return in_window(g, i, x, y, r, mn, mx) && !(skip && skip[i]); },
+                [&](int i, int pos) {
                     const uint4 *Tj = reinterpret_cast<const uint4 *>(tdesc) + 2 * (long long)i;
-                    const int d = hamming256(q0, q1, Tj[0], Tj[1]);
-                    const uint32_t p = ((uint32_t)d << 22) | (uint32_t)min(orbx_prefix_cnt(m, n), 0x3FFFFF);
-                    if (p < bp) { s2 = (int)(bp >> 22); bp = p; bidx = i; }
+                    const uint32_t d = (uint32_t)hamming256(q0, q1, Tj[0], Tj[1]);
+                    const uint32_t p = (d << 22) | (uint32_t)min(pos, 0x3FFFFF);
+                    if (p < bp) { s2 = bp >> 22; bp = p; bidx = i; }
                     else if (d < s2) s2 = d;
-                }
-                n += __popcll(m);
-            }
-        }
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const uint32_t op = __shfl_xor(bp, o);
-        const int os = __shfl_xor(s2, o);
-        const int oi = __shfl_xor(bidx, o);
-        const int loser = (int)(max(bp, op) >> 22);
-        if (op < bp) bidx = oi;
-        bp = min(bp, op);
-        s2 = min(min(s2, os), loser);
-    }
-    if (lane == 0) {
-        const int d = (int)(bp >> 22);
+                });
+    uint32_t B, S;
+    wave_best2<22>(bp, s2, B, S);
+    if (B == none ? lane == 0 : bp == B) {      // positions are unique: one lane holds the winner; an empty window is -1 / 256 / 256
+        const int d = (int)(B >> 22);
         best_d[q] = d;
-        second_d[q] = s2;
+        second_d[q] = (int)S;
         best_idx[q] = d < 256 ? bidx : -1;
     }
 }

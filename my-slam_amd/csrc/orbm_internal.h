@@ -1,5 +1,5 @@
 // orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip and
-// orbm_frustum.hip
+// orbm_frustum.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -57,31 +57,6 @@ struct OrbmGrid {               // device-resident Frame grid of the train frame
 };
 
 #ifdef __HIPCC__
-// cell range of a window, src/Frame.cc:332-346.  Returns false when the window misses the grid.
-__device__ __forceinline__ bool window_cells(const OrbmGrid &g, float x, float y, float r,
-                                             int &cx0, int &cx1, int &cy0, int &cy1)
-{
-    cx0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(x, g.qmin_x), r), g.inv_w)));
-    if (cx0 >= ORBM_GRID_COLS) return false;
-    cx1 = min(ORBM_GRID_COLS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(x, g.qmin_x), r), g.inv_w)));
-    if (cx1 < 0) return false;
-    cy0 = max(0, (int)floorf(__fmul_rn(__fsub_rn(__fsub_rn(y, g.qmin_y), r), g.inv_h)));
-    if (cy0 >= ORBM_GRID_ROWS) return false;
-    cy1 = min(ORBM_GRID_ROWS - 1, (int)ceilf(__fmul_rn(__fadd_rn(__fsub_rn(y, g.qmin_y), r), g.inv_h)));
-    if (cy1 < 0) return false;
-    return true;
-}
-
-__device__ __forceinline__ bool in_window(const OrbmGrid &g, int i, float x, float y, float r, int minl, int maxl)
-{
-    if ((minl > 0) || (maxl >= 0)) {                       // bCheckLevels :348
-        const int oct = g.koct[i];
-        if (oct < minl) return false;
-        if (maxl >= 0 && oct > maxl) return false;
-    }
-    return fabsf(__fsub_rn(g.kx[i], x)) < r && fabsf(__fsub_rn(g.ky[i], y)) < r;   // :368-372
-}
-
 // wave-wide minimum, every lane gets it: butterfly inside each row of 16 lanes with DPP (quad swaps, half-row and row mirror),
 // then the four row results through v_readlane.  ~10 instructions; six ds_bpermute steps are several hundred cycles.
 __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
@@ -93,6 +68,17 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v)
     const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)v, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)v, 16);
     const uint32_t r2 = (uint32_t)__builtin_amdgcn_readlane((int)v, 32), r3 = (uint32_t)__builtin_amdgcn_readlane((int)v, 48);
     return min(min(r0, r1), min(r2, r3));
+}
+
+// The wave's best key B and second-best S from every lane's own best key and second.  SHIFT = 0: `second` is a key like `best`;
+// SHIFT > 0: `second` is a distance and a key is distance << SHIFT | position.  The winning lane offers its second, every other lane
+// its best (a lane's second is never below its own best).  Precondition: the keys of the lanes that hold a candidate are unique (the
+// positions are), and when no lane holds one, all lanes hold the same sentinel pair, which then comes back as (B, S).
+template <int SHIFT>
+__device__ __forceinline__ void wave_best2(uint32_t best, uint32_t second, uint32_t &B, uint32_t &S)
+{
+    B = wave_min_u32(best);
+    S = wave_min_u32(best == B ? second : best >> SHIFT);
 }
 
 #endif
@@ -158,6 +144,8 @@ void orbm_frustum_launch(const orbm_frame_view *d_view, int n, const uint8_t *d_
 int orbm_frustum_check(const orbm_frame_view *view, const uint8_t *skip, const float *xw, const float *normal, const float *mf_max,
                        const float *mf_min, const uint8_t *status, const float *proj_x, const float *proj_y, const float *proj_xr,
                        const int32_t *pred_level, const float *view_cos, const int *n_to_match);
+// orbm_triangulate.hip: cam1's and every second view's nlevels in range, off2[0] == 0 and monotone (host arrays)
+int orbm_tri_check_views(const orbm_camera *cam1, const orbm_camera *cams2, int nviews, const int32_t *off2);
 // k_dist_csr (orbm.hip) for callers in other files: dist[c] of every CSR candidate, off has nq + 1 entries
 void orbm_launch_dist_csr(const uint8_t *d_q, int nq, const uint8_t *d_t, const int32_t *d_off, const int32_t *d_idx, int total,
                           int32_t *d_dist, hipStream_t s);

@@ -1,26 +1,25 @@
-// orbm_kf.hip -- the ORBmatcher methods of the LocalMapping / LoopClosing threads on gfx950.
+// orbm_kf.hip -- the windowed ORBmatcher methods of the LocalMapping / LoopClosing threads on gfx950.
 // Reference (WChen09/My-SLAM), all in src/ORBmatcher.cc:
 //   :290-403   SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th)      orbm_search_by_projection_sim3
 //   :522-655   SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12)                   orbm_search_by_bow_kf (orbm.hip, beside its sibling)
-//   :657-823   SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bStereo)  orbm_search_for_triangulation
+//   :657-823   SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bStereo)  orbm_search_for_triangulation (orbm_newpoints.hip)
 //   :825-975   Fuse(KeyFrame*, vpMapPoints, th)                                 orbm_fuse
 //   :977-1100  Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)               orbm_fuse_sim3
 //   :1102-1326 SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)         orbm_search_by_sim3
 // Division of labour, as for the Tracking-thread matchers (orbm_grid.hip): the cv::Mat algebra of a call (a handful of 3x3
 // products per MapPoint) runs on the host with OpenCV 3.1.0's arithmetic (orbm_sim3_decompose, orbm_project_points_kf, ...);
 // MapPoint::PredictScale stays with the caller's MapPoint; the windows (KeyFrame::GetFeaturesInArea), the per-candidate
-// predicates and the Hamming distances run on the GPU.  Four of the six inner loops carry no state from one MapPoint / feature
-// to the next (Fuse x 2, SearchBySim3's two directions, SearchForTriangulation -- its vbMatched2 is never set), so their
-// selection runs on the GPU too, one wave per query; SearchByProjection(KeyFrame*, Scw, ...) blocks a key-frame slot for every
-// later MapPoint (:375, :396), so its candidate lists and distances come back and the reference's scan runs on the host.
+// predicates and the Hamming distances run on the GPU.  Three of the window searches carry no state from one MapPoint to the next
+// (Fuse x 2, SearchBySim3's two directions), so their selection runs on the GPU too, one wave per query (k_search_kf);
+// SearchByProjection(KeyFrame*, Scw, ...) blocks a key-frame slot for every later MapPoint (:375, :396), so its candidate lists and
+// distances come back and the reference's scan runs on the host.
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "orbm_internal.h"
-#include "orbx_internal.h"
+#include "orbm_window.h"
 
 // -------------------------------------------------------------------------------------------------
 // host side: cv::Mat algebra as OpenCV 3.1.0 evaluates it
@@ -139,21 +138,11 @@ __global__ __launch_bounds__(M_THREADS) void k_search_kf(OrbmGrid g, const uint8
     const uint4 *Q = reinterpret_cast<const uint4 *>(qdesc) + 2 * (long long)q;
     const uint4 q0 = Q[0], q1 = Q[1];
     uint32_t bp = 0xFFFFFFFFu;
-    int bidx = -1, n = 0;
-    int cx0, cx1, cy0, cy1;
-    if (window_cells(g, x, y, r, cx0, cx1, cy0, cy1)) {
-        for (int ix = cx0; ix <= cx1; ix++) {
-            const int s = g.cell_start[ix * ORBM_GRID_ROWS + cy0], e = g.cell_start[ix * ORBM_GRID_ROWS + cy1 + 1];
-            for (int j0 = s; j0 < e; j0 += 64) {
-                const int j = j0 + lane;
-                int i = -1;
-                bool ok = false;
-                if (j < e) {
-                    i = g.items[j];
-                    ok = in_window(g, i, x, y, r, -1, -1);                // the window itself has no level test (src/KeyFrame.cc:569-606)
-                }
-                const unsigned long long m = __builtin_amdgcn_ballot_w64(ok);   // positions count every window member, as vIndices does
-                if (ok) {
+    int bidx = -1;
+    // the window itself has no level test (src/KeyFrame.cc:569-606): positions count every window member, as vIndices does, and the
+    // octave window and the chi-square gate drop candidates afterwards
+    window_walk(g, x, y, r, lane, [&](int i) { return in_window(g, i, x, y, r, -1, -1); },
+                [&](int i, int pos) {
                     const int oct = g.koct[i];
                     bool use = !(oct < lv - 1 || oct > lv);
                     if (use && gate.on) {
@@ -172,75 +161,16 @@ __global__ __launch_bounds__(M_THREADS) void k_search_kf(OrbmGrid g, const uint8
                     if (use) {
                         const uint4 *Tj = reinterpret_cast<const uint4 *>(tdesc) + 2 * (long long)i;
                         const int d = hamming256(q0, q1, Tj[0], Tj[1]);
-                        const uint32_t p = ((uint32_t)d << 22) | (uint32_t)min(orbx_prefix_cnt(m, n), 0x3FFFFF);
+                        const uint32_t p = ((uint32_t)d << 22) | (uint32_t)min(pos, 0x3FFFFF);
                         if (p < bp) { bp = p; bidx = i; }
                     }
-                }
-                n += __popcll(m);
-            }
-        }
-    }
+                });
     const uint32_t B = wave_min_u32(bp);
     if (B == 0xFFFFFFFFu) {
         if (lane == 0) { best_idx[q] = -1; best_d[q] = 256; }
     } else if (bp == B) {                       // positions are unique: one lane holds the winner
         best_idx[q] = bidx; best_d[q] = (int)(B >> 22);
     }
-}
-
-struct TriParams {
-    float F12[9];               // row-major
-    float ex, ey;               // epipole of camera 1 in image 2 (:664-670)
-    float thr_epipole[ORBX_MAX_LEVELS];     // 100*pKF2->mvScaleFactors[level]  (int * float -> float, :747)
-    double thr_line[ORBX_MAX_LEVELS];       // 3.84*pKF2->mvLevelSigma2[level]  (double * float -> double, :156)
-};
-#define TRI_KEY_NONE 0xFFFFFFFFu
-// SearchForTriangulation: one wave per feature of key frame 1 that has no MapPoint yet; the lanes walk the features of key frame 2
-// in the same vocabulary node.  The reference accepts a candidate when `dist <= TH_LOW && dist <= bestDist` and both epipolar tests
-// pass (:738-755), and bestDist only moves when a candidate is accepted: the result is the LAST candidate of minimal distance among
-// those that pass the stateless tests -> minimum of (distance, -position).
-__global__ __launch_bounds__(M_THREADS) void k_triangulation(const int4 *__restrict__ queries, int nq, const int32_t *__restrict__ idx2v,
-                                                            const uint8_t *__restrict__ desc1, const uint8_t *__restrict__ desc2,
-                                                            const float2 *__restrict__ xy1, const float2 *__restrict__ xy2,
-                                                            const int32_t *__restrict__ oct2, const uint8_t *__restrict__ flags2,
-                                                            TriParams P, int32_t *__restrict__ match)
-{
-    const int lane = threadIdx.x & 63;
-    const int q = blockIdx.x * (M_THREADS / 64) + (threadIdx.x >> 6);
-    if (q >= nq) return;
-    const int4 rec = queries[q];            // x = idx1, y / z = [lo, hi) in idx2v, w = bStereo1
-    const int idx1 = rec.x;
-    const uint4 *Q = reinterpret_cast<const uint4 *>(desc1) + 2 * (long long)idx1;
-    const uint4 q0 = Q[0], q1 = Q[1];
-    const float2 p1 = xy1[idx1];
-    // epipolar line in image 2, l = x1' F12 (:143-145)
-    const float a = __fadd_rn(__fadd_rn(__fmul_rn(p1.x, P.F12[0]), __fmul_rn(p1.y, P.F12[3])), P.F12[6]);
-    const float b = __fadd_rn(__fadd_rn(__fmul_rn(p1.x, P.F12[1]), __fmul_rn(p1.y, P.F12[4])), P.F12[7]);
-    const float c = __fadd_rn(__fadd_rn(__fmul_rn(p1.x, P.F12[2]), __fmul_rn(p1.y, P.F12[5])), P.F12[8]);
-    const float den = __fadd_rn(__fmul_rn(a, a), __fmul_rn(b, b));
-    uint32_t best = TRI_KEY_NONE;
-    for (int pos = rec.y + lane; pos < rec.z; pos += 64) {
-        const int idx2 = idx2v[pos];
-        const uint8_t f2 = flags2[idx2];     // bit 0: eligible (no MapPoint, stereo filter passed :725-732), bit 1: bStereo2
-        if (!(f2 & 1)) continue;
-        const uint4 *Tj = reinterpret_cast<const uint4 *>(desc2) + 2 * (long long)idx2;
-        const int d = hamming256(q0, q1, Tj[0], Tj[1]);
-        if (d > ORBM_TH_LOW) continue;                                           // :738
-        const float2 p2 = xy2[idx2];
-        const int o2 = min(max(oct2[idx2], 0), ORBX_MAX_LEVELS - 1);
-        if (!rec.w && !(f2 & 2)) {                                               // :743-749
-            const float dx = __fsub_rn(P.ex, p2.x), dy = __fsub_rn(P.ey, p2.y);
-            if (__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)) < P.thr_epipole[o2]) continue;
-        }
-        if (den == 0) continue;                                                  // CheckDistEpipolarLine :147-156
-        const float num = __fadd_rn(__fadd_rn(__fmul_rn(a, p2.x), __fmul_rn(b, p2.y)), c);
-        const float dsqr = __fdiv_rn(__fmul_rn(num, num), den);
-        if (!((double)dsqr < P.thr_line[o2])) continue;
-        const uint32_t key = ((uint32_t)d << 20) | (0xFFFFFu - (uint32_t)min(pos - rec.y, 0xFFFFF));
-        best = min(best, key);
-    }
-    const uint32_t B = wave_min_u32(best);
-    if (lane == 0) match[q] = B == TRI_KEY_NONE ? -1 : idx2v[rec.y + (int)(0xFFFFFu - (B & 0xFFFFFu))];
 }
 
 // the compacted queries of one stateless window search, and its launch
@@ -445,94 +375,5 @@ extern "C" int orbm_search_by_sim3(orbm_matcher *m,
         if (idx2 >= 0 && vnMatch2[idx2] == i1) { match12[i1] = idx2; nf++; }
     }
     *nfound = nf;
-    return ORBX_OK;
-}
-
-extern "C" int orbm_search_for_triangulation(orbm_matcher *m,
-                                             const orbx_keypoint *kps1, const uint8_t *desc1, int n1, const uint8_t *has_mp1, const float *u_right1,
-                                             const int32_t *fv1_node, const int32_t *fv1_off, const int32_t *fv1_idx, int fv1_n,
-                                             const orbx_keypoint *kps2, const uint8_t *desc2, int n2, const uint8_t *has_mp2, const float *u_right2,
-                                             const int32_t *fv2_node, const int32_t *fv2_off, const int32_t *fv2_idx, int fv2_n,
-                                             const float *Cw, const float *T2w, float fx2, float fy2, float cx2, float cy2, const float *F12,
-                                             const float *scale_factors2, const float *level_sigma2_2, int nlevels2, int only_stereo,
-                                             int check_orientation, int32_t *matches12, int *nmatches)
-{
-    if (!m) return mfail(ORBX_E_INVALID, "NULL handle");
-    if (n1 < 0 || n2 < 0 || fv1_n < 0 || fv2_n < 0 || !matches12 || !nmatches || !Cw || !T2w || !F12 || !scale_factors2 || !level_sigma2_2 ||
-        nlevels2 < 1 || nlevels2 > ORBX_MAX_LEVELS)
-        return mfail(ORBX_E_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n1; i++) matches12[i] = -1;                             // :678
-    if (n1 == 0 || n2 == 0 || fv1_n == 0 || fv2_n == 0) return ORBX_OK;
-    if (!kps1 || !desc1 || !has_mp1 || !u_right1 || !kps2 || !desc2 || !has_mp2 || !u_right2 || !fv1_node || !fv1_off || !fv1_idx || !fv2_node ||
-        !fv2_off || !fv2_idx)
-        return mfail(ORBX_E_INVALID, "NULL buffer");
-    TriParams P;
-    {   // epipole in the second image (:664-670)
-        const float C2x = gemm_row(T2w, 0, Cw), C2y = gemm_row(T2w, 1, Cw), C2z = gemm_row(T2w, 2, Cw);
-        const float invz = 1.0f / C2z;
-        P.ex = fx2 * C2x * invz + cx2; P.ey = fy2 * C2y * invz + cy2;
-    }
-    for (int k = 0; k < 9; k++) P.F12[k] = F12[k];
-    for (int l = 0; l < ORBX_MAX_LEVELS; l++) {
-        P.thr_epipole[l] = l < nlevels2 ? 100 * scale_factors2[l] : 0.f;
-        P.thr_line[l] = l < nlevels2 ? 3.84 * level_sigma2_2[l] : 0.0;
-    }
-    // queries: the features of key frame 1 in shared nodes that pass :699-709, in visiting order
-    std::vector<int4> qs;
-    for (int a = 0, b = 0; a < fv1_n && b < fv2_n;) {
-        if (fv1_node[a] == fv2_node[b]) {
-            if (fv2_off[b + 1] > fv2_off[b])
-                for (int c = fv1_off[a]; c < fv1_off[a + 1]; c++) {
-                    const int idx1 = fv1_idx[c];
-                    if (idx1 < 0 || idx1 >= n1) return mfail(ORBX_E_INVALID, "feature index %d outside [0,%d)", idx1, n1);
-                    if (has_mp1[idx1]) continue;
-                    const int st1 = u_right1[idx1] >= 0;
-                    if (only_stereo && !st1) continue;
-                    qs.push_back(make_int4(idx1, fv2_off[b], fv2_off[b + 1], st1));
-                }
-            a++; b++;
-        } else if (fv1_node[a] < fv2_node[b]) a++;
-        else b++;
-    }
-    const int nq = (int)qs.size(), ni2 = fv2_off[fv2_n];
-    if (nq == 0) return ORBX_OK;
-    std::vector<uint8_t> flags2((size_t)n2);
-    for (int i = 0; i < n2; i++) {
-        const int st2 = u_right2[i] >= 0;
-        flags2[i] = (uint8_t)(((!has_mp2[i] && (!only_stereo || st2)) ? 1 : 0) | (st2 ? 2 : 0));      // :725-732
-    }
-    for (int c = 0; c < ni2; c++)
-        if (fv2_idx[c] < 0 || fv2_idx[c] >= n2) return mfail(ORBX_E_INVALID, "feature index %d outside [0,%d)", fv2_idx[c], n2);
-    std::vector<float> xy1((size_t)2 * n1), xy2((size_t)2 * n2);
-    std::vector<int32_t> oct2((size_t)n2);
-    for (int i = 0; i < n1; i++) { xy1[2 * (size_t)i] = kps1[i].x; xy1[2 * (size_t)i + 1] = kps1[i].y; }
-    for (int i = 0; i < n2; i++) { xy2[2 * (size_t)i] = kps2[i].x; xy2[2 * (size_t)i + 1] = kps2[i].y; oct2[i] = kps2[i].octave; }
-    MHIPCHK(hipSetDevice(m->device));
-    MTRY(orbm_grow(m, nq, 0, 0));
-    MTRY(orbm_arena_begin(m));
-    hipStream_t s = m->stream;
-    InBlock in(m);
-    const int pq = in.add(qs.data(), (size_t)nq * 16), pi = in.add(fv2_idx, (size_t)ni2 * 4), pd1 = in.add(desc1, (size_t)n1 * 32), pd2 = in.add(desc2, (size_t)n2 * 32);
-    const int p1 = in.add(xy1.data(), (size_t)n1 * 8), p2 = in.add(xy2.data(), (size_t)n2 * 8), po = in.add(oct2.data(), (size_t)n2 * 4), pf = in.add(flags2.data(), (size_t)n2);
-    MTRY(in.upload(s));
-    hipLaunchKernelGGL(k_triangulation, dim3((nq + 3) / 4), dim3(M_THREADS), 0, s, in.at<int4>(pq), nq, in.at<int32_t>(pi), in.at<uint8_t>(pd1),
-                       in.at<uint8_t>(pd2), in.at<float2>(p1), in.at<float2>(p2), in.at<int32_t>(po), in.at<uint8_t>(pf), P, m->d_out);
-    MHIPCHK(hipGetLastError());
-    std::vector<int32_t> res((size_t)nq);
-    MTRY(orbm_d2h(m, res.data(), m->d_out, (size_t)nq * 4, s));
-    MTRY(orbm_sync(m, s));
-    // matches, rotation histogram and cull (:758-810) in visiting order
-    RotHist rot;                                     // tag = idx1
-    int nm = 0;
-    for (int k = 0; k < nq; k++) {
-        if (res[k] < 0) continue;
-        const int idx1 = qs[k].x, idx2 = res[k];
-        matches12[idx1] = idx2;
-        nm++;
-        if (check_orientation) MTRY(rot.add(kps1[idx1].angle, kps2[idx2].angle, idx1));
-    }
-    if (check_orientation) rot.cull([&](int idx1) { matches12[idx1] = -1; nm--; });
-    *nmatches = nm;
     return ORBX_OK;
 }

@@ -1,7 +1,8 @@
 // orbm_tri_body.h -- the arithmetic of one CreateNewMapPoints match (src/LocalMapping.cc:293-433 of WChen09/My-SLAM) as device
-// functions: tri_one() decides a match and gives its point, tri_load() reads what it needs of one feature.  Shared by k_triangulate
-// (orbm_triangulate.hip, a caller's match list) and k_triangulate_queries (orbm_newpoints.hip, the matches the batched search left on
-// the device), so both entry points evaluate the same sequence of operations.  Conventions: orbm_triangulate.hip's header comment.
+// functions: tri_one() decides a match and gives its point, tri_load() reads what it needs of one feature, tri_lanes() is the kernel
+// body around them.  Shared by k_triangulate (orbm_triangulate.hip, a caller's match list) and k_triangulate_queries
+// (orbm_newpoints.hip, the matches the batched search left on the device): the two kernels differ only in where a lane fetches its
+// pair.  Conventions: orbm_triangulate.hip's header comment.
 #pragma once
 #include "orbm_internal.h"
 #include "sincos_cr.h"
@@ -192,4 +193,53 @@ __device__ __forceinline__ TriView tri_load(const orbx_keypoint *__restrict__ kp
     const float2 raw = keys[i];
     f.raw_x = raw.x; f.raw_y = raw.y; f.ur = ur[i]; f.depth = depth[i];
     return f;
+}
+
+// The body of both triangulation kernels: lane k decides pair k of n.  fetch(k, idx1, idx2, view) gives the lane's pair and returns
+// false when there is none (ORBM_TRI_NO_MATCH); a pair whose indices or octaves do not fit the key frames is ORBM_TRI_BAD_INDEX (the
+// host entry points have checked them: reached only through the device-pointer form).  The camera blocks are read at wave-uniform
+// addresses (scalar loads): the lanes of a wave are served one second view at a time.
+template <class Fetch>
+__device__ __forceinline__ void tri_lanes(int k, int n, Fetch fetch,
+                                          const orbm_camera *__restrict__ cam1, const orbx_keypoint *__restrict__ kps1,
+                                          const float2 *__restrict__ keys1, const float *__restrict__ ur1, const float *__restrict__ depth1, int n1,
+                                          const orbm_camera *__restrict__ cams2, int ncams2, const int32_t *__restrict__ off2,
+                                          const orbx_keypoint *__restrict__ kps2, const float2 *__restrict__ keys2,
+                                          const float *__restrict__ ur2, const float *__restrict__ depth2,
+                                          uint8_t *__restrict__ status, float *__restrict__ x3d)
+{
+    int idx1 = 0, idx2 = 0, v = 0;
+    uint32_t view = 0xFFFFFFFFu;                    // 0xFFFFFFFF: nothing (left) to do in this lane
+    int st = ORBM_TRI_NO_MATCH;
+    float X[3] = {0.f, 0.f, 0.f};
+    TriView f1 = {};
+    if (k < n && fetch(k, idx1, idx2, v)) {
+        st = ORBM_TRI_BAD_INDEX;
+        if (v >= 0 && v < ncams2 && idx1 >= 0 && idx1 < n1 && idx2 >= 0) {
+            f1 = tri_load(kps1, keys1, ur1, depth1, idx1);
+            if (f1.oct >= 0 && f1.oct < min(cam1->nlevels, ORBX_MAX_LEVELS)) view = (uint32_t)v;
+        }
+    }
+    // the second views of this wave, one at a time; a pass retires every lane of its view, so there are at most 64
+    for (int pass = 0; pass < 64; pass++) {
+        const uint32_t vmin = wave_min_u32(view);
+        if (vmin == 0xFFFFFFFFu) break;
+        if (view == vmin) {
+            // every active lane holds vmin here; taken through readfirstlane the index is a scalar for the compiler as well (inside
+            // this branch it puts the lane's own `view` in vmin's place, and the camera block's address would become a vector)
+            const uint32_t vu = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
+            view = 0xFFFFFFFFu;
+            const orbm_camera *__restrict__ cam2 = cams2 + vu;
+            const int base = off2[vu], count = off2[vu + 1] - base;
+            if (idx2 < count) {
+                const TriView f2 = tri_load(kps2, keys2, ur2, depth2, (long long)base + idx2);
+                if (f2.oct >= 0 && f2.oct < min(cam2->nlevels, ORBX_MAX_LEVELS)) st = tri_one(cam1, cam2, f1, f2, X);
+            }
+        }
+    }
+    if (k < n) {
+        const bool ok = st <= ORBM_TRI_STEREO2;
+        status[k] = (uint8_t)st;
+        x3d[3 * (long long)k] = ok ? X[0] : 0.f; x3d[3 * (long long)k + 1] = ok ? X[1] : 0.f; x3d[3 * (long long)k + 2] = ok ? X[2] : 0.f;
+    }
 }

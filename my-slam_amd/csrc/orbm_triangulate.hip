@@ -3,7 +3,8 @@
 //
 // One lane per match, wave64, one wave per workgroup (a few hundred to a few thousand matches: the waves spread over the CUs).
 // The camera blocks are read at wave-uniform addresses (scalar loads): key frame 1 has one block, and the lanes of a wave are
-// served one second view at a time (with one second view per call, the reference's own use, that is one pass).
+// served one second view at a time (with one second view per call, the reference's own use, that is one pass).  The kernel body is
+// tri_lanes() (orbm_tri_body.h), which k_triangulate_queries (orbm_newpoints.hip) instantiates as well.
 //
 // Arithmetic: the reference's float expressions, operation by operation, no contraction -- 3x3 * 3x1 products
 // as cv::gemm's small-matrix path (float sum left to right, then (float)(t0*alpha + c*beta) in double), Mat::dot and cv::norm
@@ -15,7 +16,6 @@
 //
 // The two 4x4 fp64 matrices of the Jacobi live in named registers (D4 columns, every access a compile-time member): a private
 // array indexed by a loop variable would go to scratch memory.
-// The device functions (tri_one and what it calls) are in orbm_tri_body.h, which orbm_newpoints.hip includes as well.
 #include "orbm_internal.h"
 #include "orbm_tri_body.h"
 
@@ -26,43 +26,12 @@ __global__ __launch_bounds__(TRI_THREADS) void k_triangulate(
     const float2 *__restrict__ keys2, const float *__restrict__ ur2, const float *__restrict__ depth2,
     const int32_t *__restrict__ matches, int n, uint8_t *__restrict__ status, float *__restrict__ x3d)
 {
-    const int k = blockIdx.x * TRI_THREADS + threadIdx.x;
-    int idx1 = 0, idx2 = 0;
-    uint32_t view = 0xFFFFFFFFu;                    // 0xFFFFFFFF: nothing (left) to do in this lane
-    int st = ORBM_TRI_BAD_INDEX;
-    float X[3] = {0.f, 0.f, 0.f};
-    TriView f1 = {};
-    if (k < n) {
-        idx1 = matches[3 * (long long)k]; idx2 = matches[3 * (long long)k + 1];
-        const int v = matches[3 * (long long)k + 2];
-        if (v >= 0 && v < ncams2 && idx1 >= 0 && idx1 < n1 && idx2 >= 0) {
-            f1 = tri_load(kps1, keys1, ur1, depth1, idx1);
-            if (f1.oct >= 0 && f1.oct < min(cam1->nlevels, ORBX_MAX_LEVELS)) view = (uint32_t)v;
-        }
-    }
-    // the second views of this wave, one at a time, so that the camera block's address is wave-uniform; a pass retires every lane
-    // of its view, so there are at most 64
-    for (int pass = 0; pass < 64; pass++) {
-        const uint32_t vmin = wave_min_u32(view);
-        if (vmin == 0xFFFFFFFFu) break;
-        if (view == vmin) {
-            // every active lane holds vmin here; taken through readfirstlane the index is a scalar for the compiler as well (inside
-            // this branch it puts the lane's own `view` in vmin's place, and the camera block's address would become a vector)
-            const uint32_t v = (uint32_t)__builtin_amdgcn_readfirstlane((int)view);
-            view = 0xFFFFFFFFu;
-            const orbm_camera *__restrict__ cam2 = cams2 + v;
-            const int base = off2[v], count = off2[v + 1] - base;
-            if (idx2 < count) {
-                const TriView f2 = tri_load(kps2, keys2, ur2, depth2, (long long)base + idx2);
-                if (f2.oct >= 0 && f2.oct < min(cam2->nlevels, ORBX_MAX_LEVELS)) st = tri_one(cam1, cam2, f1, f2, X);
-            }
-        }
-    }
-    if (k < n) {
-        const bool ok = st <= ORBM_TRI_STEREO2;
-        status[k] = (uint8_t)st;
-        x3d[3 * (long long)k] = ok ? X[0] : 0.f; x3d[3 * (long long)k + 1] = ok ? X[1] : 0.f; x3d[3 * (long long)k + 2] = ok ? X[2] : 0.f;
-    }
+    tri_lanes(blockIdx.x * TRI_THREADS + threadIdx.x, n,
+              [&](int k, int &idx1, int &idx2, int &v) {
+                  idx1 = matches[3 * (long long)k]; idx2 = matches[3 * (long long)k + 1]; v = matches[3 * (long long)k + 2];
+                  return true;
+              },
+              cam1, kps1, keys1, ur1, depth1, n1, cams2, ncams2, off2, kps2, keys2, ur2, depth2, status, x3d);
 }
 
 static void tri_launch(const orbm_camera *cam1, const orbx_keypoint *kps1, const float *keys1, const float *ur1, const float *depth1, int n1,
@@ -72,6 +41,18 @@ static void tri_launch(const orbm_camera *cam1, const orbx_keypoint *kps1, const
     hipLaunchKernelGGL(k_triangulate, dim3((n + TRI_THREADS - 1) / TRI_THREADS), dim3(TRI_THREADS), 0, s, cam1, kps1,
                        reinterpret_cast<const float2 *>(keys1), ur1, depth1, n1, cams2, ncams2, off2, kps2,
                        reinterpret_cast<const float2 *>(keys2), ur2, depth2, matches, n, status, x3d);
+}
+
+// the cameras and the feature ranges of the second views, as both entry points that take them from the host require them
+int orbm_tri_check_views(const orbm_camera *cam1, const orbm_camera *cams2, int nviews, const int32_t *off2)
+{
+    if (cam1->nlevels < 1 || cam1->nlevels > ORBX_MAX_LEVELS) return mfail(ORBX_E_INVALID, "key frame 1 has nlevels=%d", cam1->nlevels);
+    if (off2[0] != 0) return mfail(ORBX_E_INVALID, "off2[0] must be 0");
+    for (int v = 0; v < nviews; v++) {
+        if (off2[v + 1] < off2[v]) return mfail(ORBX_E_INVALID, "off2 not monotone at %d", v);
+        if (cams2[v].nlevels < 1 || cams2[v].nlevels > ORBX_MAX_LEVELS) return mfail(ORBX_E_INVALID, "second view %d has nlevels=%d", v, cams2[v].nlevels);
+    }
+    return ORBX_OK;
 }
 
 static int tri_check_counts(int n1, int ncams2, int n)
@@ -93,12 +74,7 @@ extern "C" int orbm_triangulate_matches(orbm_matcher *m, const orbm_camera *cam1
         !matches || !status || !x3d)
         return mfail(ORBX_E_INVALID, "NULL buffer");
     if (ncams2 < 1) return mfail(ORBX_E_INVALID, "ncams2=%d with n=%d matches", ncams2, n);
-    if (cam1->nlevels < 1 || cam1->nlevels > ORBX_MAX_LEVELS) return mfail(ORBX_E_INVALID, "key frame 1 has nlevels=%d", cam1->nlevels);
-    if (off2[0] != 0) return mfail(ORBX_E_INVALID, "off2[0] must be 0");
-    for (int v = 0; v < ncams2; v++) {
-        if (off2[v + 1] < off2[v]) return mfail(ORBX_E_INVALID, "off2 not monotone at %d", v);
-        if (cams2[v].nlevels < 1 || cams2[v].nlevels > ORBX_MAX_LEVELS) return mfail(ORBX_E_INVALID, "second view %d has nlevels=%d", v, cams2[v].nlevels);
-    }
+    MTRY(orbm_tri_check_views(cam1, cams2, ncams2, off2));
     const int n2 = off2[ncams2];
     for (int k = 0; k < n; k++) {
         const int idx1 = matches[3 * (size_t)k], idx2 = matches[3 * (size_t)k + 1], v = matches[3 * (size_t)k + 2];
