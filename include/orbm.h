@@ -587,6 +587,43 @@ int orbm_search_local_points(orbm_matcher *m, const orbm_frame_view *view, int n
                              uint8_t *status, float *proj_x, float *proj_y, float *proj_xr, int32_t *pred_level, float *view_cos,
                              int *n_to_match, int32_t *cur_obs, int32_t *cur_match, int *nmatches);
 
+/*
+ * ---- Optimizer::PoseOptimization for a batch of independent problems ----
+ * Optimizer::PoseOptimization (src/Optimizer.cc:239-451) for B problems in one launch: the frames of a step, or the candidate
+ * key frames of Tracking::Relocalization (src/Tracking.cc:1447, 1463, 1478).  Problem p owns the observations off[p]:off[p+1] of
+ * obs (2 floats each), u_right, inv_sigma2 and xw (3 floats each), the camera cams[p] and the pose Tcw[16p .. 16p+16); per problem
+ * the meaning of every array is that of orbp_pose_optimization (include/orbp.h) with n = off[p+1] - off[p]:
+ *   u_right == NULL: every edge is monocular; otherwise u_right[i] < 0 marks a monocular edge and u_right[i] >= 0 a stereo edge
+ *   Tcw        = pFrame->mTcw (row-major 4x4) on entry, the optimised pose on return
+ *   outlier[i] = mvbOutlier of the observation; bytes outside the problems' ranges are not written
+ *   n_good[p]  = the function's return value (nInitialCorrespondences - nBad)
+ * A problem with fewer than 3 observations keeps its pose bit for bit, clears its flags and reports n_good[p] = 0 (:363-364).
+ *
+ * One workgroup solves one problem and restates the host path operation by operation in fp64: every per-edge
+ * quantity is bit-identical to orbp_pose_optimization's, and the sums over the edges are added in a fixed tree instead of in edge
+ * order, so the pose agrees with the host's to rounding (2e-6 on the fp32 output) and a flag can differ only for an edge whose
+ * chi2 lies within rounding of its threshold.  The result of a problem does not depend on the batch around it, on its position in
+ * the batch or on the run.  There is no limit on n.  Non-finite inputs and points at depth 0 are outside the contract.
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: a negative count, NULL buffers, off[0] != 0 or a decreasing off,
+ * and in the host variant a stereo edge in a problem whose camera has bf == 0); n_problems == 0 is ORBX_OK and touches nothing.
+ * Every other call needs the GPU: a NULL handle fails with ORBX_E_HIP where there is no HIP device ("no CPU path") and with
+ * ORBX_E_INVALID where there is one.  orbm_pose_optimization_batch runs on the handle's stream through its staging arena (one
+ * upload, one launch, one download) and grows the handle when the batch is larger than its workspace; the grids in the handle
+ * are not touched.  For a single frame the host path orbp_pose_optimization is the faster one (README).
+ *
+ * orbm_pose_optimization_batch_device: the same on device pointers (4-byte aligned; off and cams included).  Nothing is
+ * uploaded, downloaded, synchronised or grown; asynchronous on hip_stream (NULL = the handle's stream), capturable.
+ */
+typedef struct { float fx, fy, cx, cy, bf; } orbm_pose_camera;
+int orbm_pose_optimization_batch(orbm_matcher *m, int n_problems, const int32_t *off, const float *obs, const float *u_right,
+                                 const float *inv_sigma2, const float *xw, const orbm_pose_camera *cams, float *Tcw,
+                                 uint8_t *outlier, int32_t *n_good);
+int orbm_pose_optimization_batch_device(orbm_matcher *m, int n_problems, const int32_t *d_off, const float *d_obs,
+                                        const float *d_u_right, const float *d_inv_sigma2, const float *d_xw,
+                                        const orbm_pose_camera *d_cams, float *d_Tcw, uint8_t *d_outlier, int32_t *d_n_good,
+                                        void *hip_stream);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

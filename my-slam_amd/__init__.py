@@ -32,6 +32,9 @@ VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4",
                        ("cy", "<f4"), ("mbf", "<f4"), ("bounds", "<f4", (4,)), ("log_scale_factor", "<f4"), ("nlevels", "<i4"),
                        ("scale_factors", "<f4", (ORBX_MAX_LEVELS,))])
 assert VIEW_DTYPE.itemsize == 168
+# orbm_pose_camera (include/orbm.h): the calibration of one problem of pose_optimization_batch
+POSE_CAM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4")])
+assert POSE_CAM_DTYPE.itemsize == 20
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
@@ -260,6 +263,9 @@ def _bind_matcher(L):
     L.orbm_search_local_points.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, C.c_int, C.c_float, C.c_float,
                                            vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_frustum.restype = L.orbm_frustum_device.restype = L.orbm_search_local_points.restype = C.c_int
+    L.orbm_pose_optimization_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_pose_optimization_batch_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_pose_optimization_batch.restype = L.orbm_pose_optimization_batch_device.restype = C.c_int
     for name in ("orbm_reserve", "orbm_grid_build_kf", "orbm_sim3_decompose", "orbm_sim3_relative", "orbm_project_points_kf",
                  "orbm_project_points_sim3", "orbm_search_by_projection_sim3", "orbm_search_by_bow_kf", "orbm_search_for_triangulation",
                  "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_search_by_bow"):
@@ -678,6 +684,61 @@ class ORBmatcher:
         """The same on raw device pointers (the view block included); nothing is synchronised and nothing is counted."""
         _mchk(self.L.orbm_frustum_device(self.h, d_view, n, d_skip, d_xw, d_normal, d_mf_max, d_mf_min, C.c_float(viewing_cos_limit),
                                          d_status, d_proj_x, d_proj_y, d_proj_xr, d_pred_level, d_view_cos, stream))
+
+    @staticmethod
+    def pack_pose_problems(problems):
+        """The CSR arrays of orbm_pose_optimization_batch from a list of PoseOptimization argument tuples
+        (obs, inv_sigma2, xw, fx, fy, cx, cy, Tcw[, u_right[, bf]]) -> (off int32 [B+1], obs float32 [N, 2], u_right float32 [N] or
+        None when no problem has one, inv_sigma2 float32 [N], xw float32 [N, 3], cams POSE_CAM_DTYPE [B], Tcw float32 [B, 16]).
+        A problem without u_right gets -1 (monocular) on all its edges when another problem has one."""
+        B = len(problems)
+        off = np.zeros(B + 1, np.int32)
+        cams, T = np.zeros(B, POSE_CAM_DTYPE), np.zeros((B, 16), np.float32)
+        obs, s2, xw, ur = [], [], [], []
+        for p, args in enumerate(problems):
+            o, s, x, fx, fy, cx, cy, Tcw = args[:8]
+            u = args[8] if len(args) > 8 else None
+            bf = args[9] if len(args) > 9 else 0.0
+            o = np.ascontiguousarray(o, np.float32).reshape(-1, 2)
+            s = np.ascontiguousarray(s, np.float32).reshape(-1)
+            x = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+            u = None if u is None else np.ascontiguousarray(u, np.float32).reshape(-1)
+            if not (len(o) == len(s) == len(x)) or (u is not None and len(u) != len(o)):
+                raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %d / %d / %d" % (p, len(o), len(s), len(x)))
+            obs.append(o); s2.append(s); xw.append(x); ur.append(u)
+            off[p + 1] = off[p] + len(o)
+            cams[p] = (fx, fy, cx, cy, bf)
+            T[p] = np.asarray(Tcw, np.float32).reshape(16)
+        cat = lambda parts, shape: np.ascontiguousarray(np.concatenate(parts), np.float32) if parts else np.zeros(shape, np.float32)
+        u_all = None
+        if any(u is not None for u in ur):
+            u_all = cat([u if u is not None else np.full(len(o), -1, np.float32) for u, o in zip(ur, obs)], (0,))
+        return off, cat(obs, (0, 2)), u_all, cat(s2, (0,)), cat(xw, (0, 3)), cams, T
+
+    def pose_optimization_batch(self, problems):
+        """Optimizer::PoseOptimization (src/Optimizer.cc:239-451) for a list of independent problems in one launch, each an argument
+        tuple of PoseOptimization().  Returns a list of PoseOptimization()'s results: (Tcw 4x4 float32, mvbOutlier bool[n], n_inliers)."""
+        off, obs, ur, s2, xw, cams, T = self.pack_pose_problems(problems)
+        B = len(problems)
+        out, good = np.zeros(max(int(off[-1]), 1), np.uint8), np.zeros(max(B, 1), np.int32)
+        _mchk(self.L.orbm_pose_optimization_batch(self.h, B, _p(off), _p(obs), _p(ur), _p(s2), _p(xw), _p(cams), _p(T), _p(out), _p(good)))
+        return [(T[p].reshape(4, 4).copy(), out[off[p]:off[p + 1]].astype(bool), int(good[p])) for p in range(B)]
+
+    def pose_optimization_batch_device(self, n_problems, off, obs, u_right, inv_sigma2, xw, cams, Tcw, outlier, n_good, stream=None):
+        """The same on torch tensors on the handle's device: off int32 [B+1], obs float32 [N, 2], u_right float32 [N] or None,
+        inv_sigma2 float32 [N], xw float32 [N, 3], cams float32 [B, 5] (fx, fy, cx, cy, bf), Tcw float32 [B, 16] (in/out),
+        outlier uint8 [N], n_good int32 [B].  Nothing is copied or synchronised; stream: a torch stream, a raw hipStream_t or None
+        (the handle's stream)."""
+        import torch
+        want = ((off, torch.int32), (obs, torch.float32), (u_right, torch.float32), (inv_sigma2, torch.float32), (xw, torch.float32),
+                (cams, torch.float32), (Tcw, torch.float32), (outlier, torch.uint8), (n_good, torch.int32))
+        for t, dt in want:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise OrbxError(ORBX_E_INVALID, "pose_optimization_batch_device wants contiguous device tensors of the documented dtypes")
+        s = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _mchk(self.L.orbm_pose_optimization_batch_device(self.h, n_problems, ptr(off), ptr(obs), ptr(u_right), ptr(inv_sigma2), ptr(xw),
+                                                         ptr(cams), ptr(Tcw), ptr(outlier), ptr(n_good), s))
 
     def search_local_points(self, view, skip, xw, normal, mf_max, mf_min, mp_desc, mp_obs, kps_cur, desc_cur, cur_obs, th,
                             u_right=None, viewing_cos_limit=0.5):

@@ -1,5 +1,5 @@
-// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip and
-// orbm_frustum.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
+// orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip,
+// orbm_frustum.hip and orbm_pose.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
 #pragma once
 #include <algorithm>
 #include <cmath>

@@ -11,6 +11,7 @@
 #include <optional>
 #include <string>
 #include <vector>
+#include "../../include/orbm.h"
 #include "../../include/orbp.h"
 
 namespace ORB_SLAM2 {
@@ -85,6 +86,62 @@ public:
                                                 fx, fy, cx, cy, bf, Tcw.data(), o.data());
         outlier.assign(o.begin(), o.begin() + n);
         return good;
+    }
+
+    // One problem of PoseOptimizationBatch: the arguments of PoseOptimization above, and its results (outlier, nGood = the
+    // return value).  uRight empty: every edge of this problem is monocular.
+    struct PoseProblem {
+        std::vector<float> obs, uRight, invSigma2, Xw;
+        float fx = 0, fy = 0, cx = 0, cy = 0, bf = 0;
+        Pose Tcw{};
+        std::vector<bool> outlier;
+        int nGood = 0;
+    };
+    // PoseOptimization for every problem in one GPU launch (orbm_pose_optimization_batch, include/orbm.h): the frames of a step,
+    // or the candidates of Tracking::Relocalization.  Returns the ORBX status; on failure no problem is
+    // changed and *err receives orbm_last_error().
+    static int PoseOptimizationBatch(orbm_matcher *matcher, std::vector<PoseProblem> &problems, std::string *err = nullptr)
+    {
+        const int B = (int)problems.size();
+        std::vector<int32_t> off(B + 1, 0);
+        bool anyStereo = false;
+        for (int p = 0; p < B; p++) {
+            off[p + 1] = off[p] + (int32_t)problems[p].invSigma2.size();
+            anyStereo = anyStereo || !problems[p].uRight.empty();
+        }
+        const size_t N = (size_t)off[B];
+        std::vector<float> obs, ur, s2, xw, T(16 * (size_t)B);
+        std::vector<orbm_pose_camera> cams(B);
+        obs.reserve(2 * N); s2.reserve(N); xw.reserve(3 * N);
+        for (int p = 0; p < B; p++) {
+            const PoseProblem &P = problems[p];
+            const size_t n = P.invSigma2.size();
+            if (P.obs.size() != 2 * n || P.Xw.size() != 3 * n || (!P.uRight.empty() && P.uRight.size() != n)) {
+                if (err) *err = "PoseOptimizationBatch: array lengths of problem " + std::to_string(p) + " disagree";
+                return ORBX_E_INVALID;
+            }
+            obs.insert(obs.end(), P.obs.begin(), P.obs.end());
+            s2.insert(s2.end(), P.invSigma2.begin(), P.invSigma2.end());
+            xw.insert(xw.end(), P.Xw.begin(), P.Xw.end());
+            if (anyStereo) {
+                if (P.uRight.empty()) ur.insert(ur.end(), n, -1.0f);
+                else ur.insert(ur.end(), P.uRight.begin(), P.uRight.end());
+            }
+            cams[p] = {P.fx, P.fy, P.cx, P.cy, P.bf};
+            for (int k = 0; k < 16; k++) T[16 * (size_t)p + k] = P.Tcw[k];
+        }
+        std::vector<uint8_t> o(N + 1);
+        std::vector<int32_t> good(B + 1);
+        const int rc = orbm_pose_optimization_batch(matcher, B, off.data(), obs.data(), anyStereo ? ur.data() : nullptr, s2.data(), xw.data(),
+                                                    cams.data(), T.data(), o.data(), good.data());
+        if (rc != ORBX_OK) { if (err) *err = orbm_last_error(); return rc; }
+        for (int p = 0; p < B; p++) {
+            PoseProblem &P = problems[p];
+            for (int k = 0; k < 16; k++) P.Tcw[k] = T[16 * (size_t)p + k];
+            P.outlier.assign(o.begin() + off[p], o.begin() + off[p + 1]);
+            P.nGood = good[p];
+        }
+        return ORBX_OK;
     }
 };
 
