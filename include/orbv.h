@@ -15,9 +15,13 @@
  *
  * The tree descent runs on the GPU (one wave per descriptor, one child per lane); the two tiny ordered maps are
  * assembled on the host with DBoW2's contents and order (features sorted by (id, feature index), the same double
- * additions in the same order).  Deviation where the reference is
- * undefined: a trailing empty line of the text file makes loadFromTextFile append a node with an uninitialised
- * descriptor under the root; this loader ignores empty lines.
+ * additions in the same order).  Deviations where the reference is undefined:
+ *   - a trailing empty line of the text file (saveToTextFile writes one) makes loadFromTextFile append a node with an
+ *     uninitialised descriptor under the root; this loader ignores empty lines;
+ *   - in an unbalanced tree a feature can reach its leaf above level L - levelsup.  The reference then never writes nid
+ *     (TemplatedVocabulary.h:1251; the vector transform passes an uninitialised NodeId, :1151 / :1179), so the feature's
+ *     FeatureVector node is indeterminate; here its node id is 0, the root.
+ * Both are held against the reference's own DBoW2 by tests/test_reference_pin_dbow_gpu.py.
  */
 #ifndef ORBV_H
 #define ORBV_H

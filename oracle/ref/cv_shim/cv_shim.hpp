@@ -16,6 +16,9 @@
  *     driver only hands the extractor whole images.
  *   - KeyPointsFilter::retainBest is only reached from ComputeKeyPointsOld, which the
  *     reference never calls; it aborts.
+ *   - what Thirdparty/DBoW2 uses (oracle/ref/ref_dbow.cc): a descriptor is a 1 x 32 CV_8U row read through
+ *     ptr<T>(); FileStorage / FileNode are no-ops that only let the yml save / load members compile
+ *     (isOpened() is false, so both throw before they touch a node).
  */
 #ifndef ORBX_CV_SHIM_HPP
 #define ORBX_CV_SHIM_HPP
@@ -30,6 +33,7 @@
 #include <iterator>
 #include <list>
 #include <memory>
+#include <string>
 #include <vector>
 
 #include "orb_oracle.h"
@@ -175,6 +179,8 @@ public:
 
     uchar *ptr(int y = 0) { return data + (size_t)y * step; }
     const uchar *ptr(int y = 0) const { return data + (size_t)y * step; }
+    template <typename T> T *ptr(int y = 0) { return (T *)(data + (size_t)y * step); }
+    template <typename T> const T *ptr(int y = 0) const { return (const T *)(data + (size_t)y * step); }
     template <typename T> T &at(int y, int x) { return *(T *)(data + (size_t)y * step + (size_t)x * sizeof(T)); }
     template <typename T> const T &at(int y, int x) const { return *(const T *)(data + (size_t)y * step + (size_t)x * sizeof(T)); }
 
@@ -306,6 +312,29 @@ void copyMakeBorder(InputArray src, OutputArray dst, int top, int bottom, int le
                     const Scalar &value = Scalar());
 void GaussianBlur(InputArray src, OutputArray dst, Size ksize, double sigmaX, double sigmaY = 0,
                   int borderType = BORDER_DEFAULT);
+
+/* yml persistence is not provided: nothing is ever open, every node is empty */
+class FileNode {
+public:
+    FileNode operator[](const std::string &) const { return FileNode(); }
+    FileNode operator[](const char *) const { return FileNode(); }
+    FileNode operator[](int) const { return FileNode(); }
+    size_t size() const { return 0; }
+    operator int() const { return 0; }
+    operator double() const { return 0.0; }
+    operator std::string() const { return std::string(); }
+};
+
+class FileStorage {
+public:
+    enum { READ = 0, WRITE = 1 };
+    FileStorage() {}
+    FileStorage(const std::string &, int) {}
+    bool isOpened() const { return false; }
+    FileNode operator[](const std::string &) const { return FileNode(); }
+    FileNode operator[](const char *) const { return FileNode(); }
+};
+template <typename T> inline FileStorage &operator<<(FileStorage &fs, const T &) { return fs; }
 
 class KeyPointsFilter {
 public:

@@ -11,13 +11,47 @@ import pytest
 import oracle_lib as O
 
 
+def vocabulary_arrays(k, L, scoring, weighting, parent, leaf, desc, weight):
+    """The arrays the oracle needs, from per-node lists over nodes 1..nn-1 in file order (a node's id is its line number;
+    the root, node 0, has no line).  Built without the product loader."""
+    nn = len(parent) + 1
+    children = [[] for _ in range(nn)]
+    for i, p in enumerate(parent):
+        children[p].append(i + 1)
+    off = np.zeros(nn + 1, np.int32)
+    for i in range(nn):
+        off[i + 1] = off[i] + len(children[i])
+    ids = np.array([c for ch in children for c in ch], np.int32)
+    D = np.zeros((nn, 32), np.uint8); D[1:] = np.array(desc, np.uint8).reshape(-1, 32)
+    W = np.zeros(nn, np.float64); W[1:] = weight
+    word_of = np.zeros(nn, np.int32)
+    wid = 0
+    for i in range(1, nn):
+        if leaf[i - 1]:
+            word_of[i] = wid; wid += 1
+    par = np.zeros(nn, np.int32); par[1:] = parent
+    lf = np.zeros(nn, bool); lf[1:] = leaf
+    return dict(k=k, L=L, scoring=scoring, weighting=weighting, nnodes=nn, child_off=off, child_ids=ids, desc=D, word_of=word_of,
+                weight=W, nwords=wid, parent=par, leaf=lf)
+
+
+def write_vocabulary(path, voc, trailing_newline=True):
+    """The text format of TemplatedVocabulary::loadFromTextFile / saveToTextFile, from vocabulary_arrays' dict (so descriptors
+    or weights planted in the dict after generation reach the file)."""
+    lines = ["%d %d %d %d" % (voc["k"], voc["L"], voc["scoring"], voc["weighting"])]
+    for i in range(1, voc["nnodes"]):
+        lines.append("%d %d %s %.6f" % (voc["parent"][i], 1 if voc["leaf"][i] else 0, " ".join(str(int(x)) for x in voc["desc"][i]),
+                                        voc["weight"][i]))
+    with open(path, "w") as f:
+        f.write("\n".join(lines) + ("\n" if trailing_newline else ""))
+
+
 def make_vocabulary(path, k=8, depth=3, seed=0, scoring=0, weighting=0):
     """Random complete k-ary tree; returns the arrays the oracle needs (parsed independently of the product loader)."""
     rng = np.random.default_rng(seed)
     parent, leaf, desc, weight = [], [], [], []
     frontier = [0]
     nid = 1
-    lines = ["%d %d %d %d" % (k, depth, scoring, weighting)]
     for level in range(1, depth + 1):
         nxt = []
         for p in frontier:
@@ -31,28 +65,48 @@ def make_vocabulary(path, k=8, depth=3, seed=0, scoring=0, weighting=0):
                 w = float(np.round(rng.uniform(0.5, 9.0), 6)) if is_leaf else 0.0
                 if is_leaf and rng.uniform() < 0.03:
                     w = 0.0                                   # a stopped word
-                lines.append("%d %d %s %.6f" % (p, 1 if is_leaf else 0, " ".join(str(int(x)) for x in d), w))
                 parent.append(p); leaf.append(is_leaf); desc.append(d); weight.append(w)
                 nxt.append(nid); nid += 1
         frontier = nxt
-    open(path, "w").write("\n".join(lines) + "\n")
-    nn = nid
-    children = [[] for _ in range(nn)]
-    for i, p in enumerate(parent):
-        children[p].append(i + 1)
-    off = np.zeros(nn + 1, np.int32)
-    for i in range(nn):
-        off[i + 1] = off[i] + len(children[i])
-    ids = np.array([c for ch in children for c in ch], np.int32)
-    D = np.zeros((nn, 32), np.uint8); D[1:] = np.array(desc)
-    W = np.zeros(nn, np.float64); W[1:] = weight
-    word_of = np.zeros(nn, np.int32)
-    wid = 0
-    for i in range(1, nn):
-        if leaf[i - 1]:
-            word_of[i] = wid; wid += 1
-    return dict(k=k, L=depth, scoring=scoring, weighting=weighting, nnodes=nn, child_off=off, child_ids=ids, desc=D, word_of=word_of,
-                weight=W, nwords=wid)
+    voc = vocabulary_arrays(k, depth, scoring, weighting, parent, leaf, desc, weight)
+    write_vocabulary(path, voc)
+    return voc
+
+
+def make_vocabulary_tree(k, L, nchildren, seed=0, scoring=0, weighting=0, stop=0.03):
+    """The general form: any tree of depth <= L.  nchildren(level, ordinal) is the number of children of the ordinal-th node
+    of that level (the root is level 0, ordinal 0); 0 makes the node a leaf, and every node of level L is one.  k is only
+    the header's branching factor: neither loader limits a node's children.  Nodes are numbered level by level, as
+    make_vocabulary numbers them.  Siblings share a random base descriptor and differ in 40 // level flipped bits; leaf weights
+    are uniform in [0.5, 9), a share `stop` of them 0 (stopped words).  Nothing is written: plant descriptors or weights in
+    the returned dict, then write_vocabulary(path, voc)."""
+    rng = np.random.default_rng(seed)
+    parent, leaf, desc, weight = [], [], [], []
+    frontier = [0]
+    nid = 1
+    for level in range(1, L + 1):
+        nxt = []
+        for o, p in enumerate(frontier):
+            nc = int(nchildren(level - 1, o))
+            assert nc >= 0 and (nc > 0 or p != 0), "the root needs a child"
+            if nc == 0:
+                continue
+            base = rng.integers(0, 256, 32, dtype=np.uint8)
+            mask = np.zeros((nc, 256), np.uint8)
+            flips = rng.integers(0, 256, (nc, 40 // level))
+            for c in range(nc):
+                np.bitwise_xor.at(mask[c], flips[c], 1)
+            d = np.packbits(mask, axis=1, bitorder="little") ^ base
+            for c in range(nc):
+                parent.append(p); desc.append(d[c]); nxt.append(nid); nid += 1
+        frontier = nxt
+    has_child = np.zeros(nid, bool)
+    has_child[np.array(parent)] = True
+    leaf = [not has_child[i] for i in range(1, nid)]
+    w = np.round(rng.uniform(0.5, 9.0, nid - 1), 6)
+    w[rng.uniform(size=nid - 1) < stop] = 0.0
+    weight = [float(w[i]) if leaf[i] else 0.0 for i in range(nid - 1)]
+    return vocabulary_arrays(k, L, scoring, weighting, parent, leaf, desc, weight)
 
 
 class OroVoc(C.Structure):
@@ -114,8 +168,21 @@ def test_hip_vocabulary_equals_oracle(orbx, synth, tmp_path, k, depth, scoring, 
     bow, fv = v.transform(desc, levelsup)
     assert np.array_equal(bow[0], obow[0]) and np.array_equal(bow[1].view(np.uint64), obow[1].view(np.uint64))
     assert all(np.array_equal(a, b) for a, b in zip(fv, ofv))
-    O.lib().oro_voc_score_l1.restype = C.c_double
-    assert abs(v.score(bow, bow) - 1.0) < 1e-12 or scoring != 0
+    # L1Scoring::score of a vector with itself is its 1-norm (every term is -2 |v_i|, halved and negated): the oracle's bits,
+    # and what that norm must be under the vocabulary's own scoring type
+    L = O.lib()
+    L.oro_voc_score_l1.restype = C.c_double
+    p = lambda a: C.c_void_p(a.ctypes.data)
+    s = v.score(bow, bow)
+    assert np.float64(s).view(np.uint64) == np.float64(L.oro_voc_score_l1(p(obow[0]), p(obow[1]), len(obow[0]), p(obow[0]), p(obow[1]), len(obow[0]))).view(np.uint64)
+    assert len(bow[0]) > 10 and abs(s - np.abs(bow[1]).sum()) <= 1e-12 * max(1.0, s)
+    if scoring == 0:                                       # L1_NORM: normalised to 1-norm 1
+        assert abs(s - 1.0) < 1e-12
+    elif scoring == 1:                                     # L2_NORM: 2-norm 1, so the 1-norm is larger
+        assert abs(np.sqrt((bow[1] * bow[1]).sum()) - 1.0) < 1e-12 and s > 1.5
+    else:                                                  # DOT_PRODUCT with TF: summed weights over the number of words, as they are
+        assert scoring == 5 and weighting == 1
+        assert abs(s - wt[wt > 0].sum() / len(bow[0])) <= 1e-12 * s and s > 1.5
 
 
 @pytest.mark.gpu
