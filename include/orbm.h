@@ -290,6 +290,44 @@ int orbm_search_by_bow_kf(orbm_matcher *m,
                           float nnratio, int check_orientation, int32_t *matches12, int *nmatches);
 
 /*
+ * ---- SearchByBoW for ALL candidate key frames in one call (Tracking::Relocalization, src/Tracking.cc:1377-1398;
+ * LoopClosing::ComputeSim3, src/LoopClosing.cc:253-281) ----
+ * Both callers loop over their candidates with one SearchByBoW each.  The calls do not interact: each writes a table of its own
+ * and reads only its own key frame and the shared side (the lost frame, or mpCurrentKF), and the skip of :209 acts inside one call
+ * and one vocabulary node.  So all candidates are searched in one call: the shared side goes up once, every (candidate, shared node)
+ * pair is one wave of one launch (the walk of orbm_search_by_bow), the tables come back in one copy, and the rotation histogram runs
+ * on the host per candidate.  For every candidate c the table and the count are bit for bit what the one-candidate call returns.
+ *
+ * Checked before any device work, refused with ORBX_E_INVALID and every output untouched: negative counts, NULL buffers where the
+ * count is positive (the key-frame variant needs `valid` on both sides, as orbm_search_by_bow_kf does), fv_off not monotone from 0,
+ * node ids not strictly ascending, a feature index outside [0, n).  Of a side with n == 0 or fv_n == 0 nothing else is read (its
+ * candidate, or with an empty shared side every candidate, has 0 matches, as in the one-candidate calls).  nkf == 0 is ORBX_OK and
+ * touches nothing.  A call whose shared
+ * side is empty (n == 0 or fv_n == 0), or none of whose candidates shares a usable node with it, is answered on the host (-1 / 0)
+ * and needs no handle; everything else needs one (a NULL handle: as orbm_create_new_map_points).  A candidate that shares a node of
+ * more than 4096 lane-side features (the frame's in the first call, its own usable ones in the second), and every candidate when
+ * ORBM_BOW_HOST_SELECT=1 is in the environment, is answered by the one-candidate entry point after the launch.  The call grows the
+ * handle when the tables exceed its result buffer and leaves the grid slots as it found them.  One exception: a candidate that took
+ * the one-candidate path is subject to that entry point's growth, and when one of its sides has more descriptors than the handle's
+ * max_train, the growth drops the grid (orbm_grid_count() == -1), as a direct orbm_search_by_bow call does.  A failed call leaves the outputs as they were.
+ */
+typedef struct {
+    const uint8_t *desc; const orbx_keypoint *kps; int32_t n;   /* 32-byte descriptors, keypoints (only .angle is read) */
+    const uint8_t *valid;                                        /* pMP && !pMP->isBad() per feature; NULL = all valid (frame side: ignored) */
+    const int32_t *fv_node, *fv_off, *fv_idx; int32_t fv_n;      /* FeatureVector as orbv_feature_vector writes it */
+} orbm_bow_side;
+
+/* Relocalization: nkf key frames against one frame.  match_f[c*frame->n + i], nmatches[c]
+   == orbm_search_by_bow(kfs[c], frame) for every c. */
+int orbm_search_by_bow_batch(orbm_matcher *m, const orbm_bow_side *kfs, int nkf, const orbm_bow_side *frame,
+                             float nnratio, int check_orientation, int32_t *match_f, int32_t *nmatches);
+
+/* ComputeSim3: one key frame (kf1) against nkf key frames.  matches12[c*kf1->n + idx1], nmatches[c]
+   == orbm_search_by_bow_kf(kf1, kfs2[c]) for every c. */
+int orbm_search_by_bow_kf_batch(orbm_matcher *m, const orbm_bow_side *kf1, const orbm_bow_side *kfs2, int nkf,
+                                float nnratio, int check_orientation, int32_t *matches12, int32_t *nmatches);
+
+/*
  * ORBmatcher::SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bOnlyStereo) (src/ORBmatcher.cc:657-823; LocalMapping.cc:270).
  * has_mp = (GetMapPoint(idx) != NULL), u_right = mvuRight, kps = mvKeysUn; Cw = pKF1->GetCameraCenter(), T2w = pKF2's [R2w|t2w]
  * (row-major 4x4), the calibration, scale factors and level sigma^2 of pKF2, F12 row-major 3x3.  matches12[idx1] = idx2 or -1:

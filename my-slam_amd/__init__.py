@@ -266,6 +266,9 @@ def _bind_matcher(L):
     L.orbm_pose_optimization_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_pose_optimization_batch_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_pose_optimization_batch.restype = L.orbm_pose_optimization_batch_device.restype = C.c_int
+    L.orbm_search_by_bow_batch.argtypes = [vp, vp, C.c_int, vp, f, C.c_int, vp, vp]
+    L.orbm_search_by_bow_kf_batch.argtypes = [vp, vp, vp, C.c_int, f, C.c_int, vp, vp]
+    L.orbm_search_by_bow_batch.restype = L.orbm_search_by_bow_kf_batch.restype = C.c_int
     for name in ("orbm_reserve", "orbm_grid_build_kf", "orbm_sim3_decompose", "orbm_sim3_relative", "orbm_project_points_kf",
                  "orbm_project_points_sim3", "orbm_search_by_projection_sim3", "orbm_search_by_bow_kf", "orbm_search_for_triangulation",
                  "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_search_by_bow"):
@@ -279,6 +282,29 @@ def _bind_matcher(L):
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+class BowSide(C.Structure):
+    """orbm_bow_side (include/orbm.h): one side of a batched SearchByBoW"""
+    _fields_ = [("desc", C.c_void_p), ("kps", C.c_void_p), ("n", C.c_int32), ("valid", C.c_void_p),
+                ("fv_node", C.c_void_p), ("fv_off", C.c_void_p), ("fv_idx", C.c_void_p), ("fv_n", C.c_int32)]
+
+
+def bow_sides(sides):
+    """(kps, desc, featvec, valid) tuples -> (array of orbm_bow_side, the arrays it points into: keep them alive for the call)"""
+    arr = (BowSide * max(len(sides), 1))()
+    keep = []
+    for k, (kps, desc, featvec, valid) in enumerate(sides):
+        desc = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        kps = np.ascontiguousarray(kps, KP_DTYPE)
+        node, off, idx = [np.ascontiguousarray(a, np.int32) for a in featvec]
+        valid = None if valid is None else np.ascontiguousarray(valid, np.uint8)
+        if len(kps) != len(desc) or (valid is not None and len(valid) != len(desc)) or len(off) != len(node) + 1:
+            raise OrbxError(ORBX_E_INVALID, "side %d: %d keypoints, %d descriptors, %d node ids, %d offsets" % (k, len(kps), len(desc), len(node), len(off)))
+        keep.append((desc, kps, node, off, idx, valid))
+        a = lambda x: x.ctypes.data if x is not None and x.size else None
+        arr[k] = BowSide(a(desc), a(kps), len(desc), a(valid), a(node), off.ctypes.data, a(idx), len(node))
+    return arr, keep
 
 
 def _chk(rc):
@@ -1067,6 +1093,32 @@ class ORBmatcher:
                                         _p(desc_f), _p(kps_f), len(desc_f), _p(nf), _p(of), _p(i_f), len(nf),
                                         C.c_float(self.mfNNratio), 1 if self.mbCheckOrientation else 0, _p(match_f), C.byref(nm)))
         return match_f, nm.value
+
+    def SearchByBoWBatch(self, kfs, frame):
+        """SearchByBoW(pKF, F, ...) for every candidate key frame of Tracking::Relocalization in one call (orbm_search_by_bow_batch).
+        kfs: list of (kps, desc, featvec, valid) with valid None = every feature usable; frame: the same tuple (valid ignored).
+        Returns (len(kfs) x n_frame int32 table, len(kfs) int32 counts): row c == SearchByBoW(kfs[c], frame)."""
+        ks, keep_k = bow_sides(list(kfs))
+        fr, keep_f = bow_sides([frame])
+        nkf, nf = len(kfs), fr[0].n
+        table = np.full((nkf, nf), -1, np.int32)
+        counts = np.zeros(nkf, np.int32)
+        _mchk(self.L.orbm_search_by_bow_batch(self.h, C.cast(ks, C.c_void_p), nkf, C.cast(fr, C.c_void_p), C.c_float(self.mfNNratio),
+                                              1 if self.mbCheckOrientation else 0, _p(table), _p(counts)))
+        return table, counts
+
+    def SearchByBoWKFBatch(self, kf1, kfs2):
+        """SearchByBoW(pKF1, pKF2, ...) for every candidate key frame of LoopClosing::ComputeSim3 in one call
+        (orbm_search_by_bow_kf_batch).  Sides as for SearchByBoWBatch, `valid` required.  Returns (len(kfs2) x n1 int32 table,
+        len(kfs2) int32 counts): row c == SearchByBoWKF(kf1, kfs2[c])."""
+        k1, keep_1 = bow_sides([kf1])
+        ks, keep_k = bow_sides(list(kfs2))
+        nkf, n1 = len(kfs2), k1[0].n
+        table = np.full((nkf, n1), -1, np.int32)
+        counts = np.zeros(nkf, np.int32)
+        _mchk(self.L.orbm_search_by_bow_kf_batch(self.h, C.cast(k1, C.c_void_p), C.cast(ks, C.c_void_p), nkf, C.c_float(self.mfNNratio),
+                                                 1 if self.mbCheckOrientation else 0, _p(table), _p(counts)))
+        return table, counts
 
 
 class ORBVocabulary:

@@ -14,6 +14,7 @@
 
 #include "orbm_internal.h"
 #include "orbm_accept.h"
+#include "orbm_bow_body.h"
 
 // ---- pinned staging arena (see orbm_internal.h; orbm_arena_begin is in orbm_workspace.cc) ----
 static void *arena_take(orbm_matcher *m, size_t bytes)
@@ -424,88 +425,24 @@ extern "C" int orbm_best2_batch_device(orbm_matcher *m, const uint8_t *d_q, cons
 // earlier key-frame feature is skipped, :209), the lanes hold the node's frame features (position = chunk * 64 + lane, a
 // "taken" bit per chunk in a register), key = distance << 16 | position so that min() is "smallest distance, first in list".
 // A frame feature lives in exactly one node, so nodes do not interact. ----
-#define BOW_NONE ((256u << 16) | 0xFFFFu)
-#define BOW_MAX_NODE_FEATURES 4096      // 64 chunks of 64 lanes
-#define BOW_REG_CHUNKS 4                // frame features 0..255 of a node stay in registers
-
 __global__ __launch_bounds__(M_THREADS) void k_bow_select(
     const uint8_t *__restrict__ q, const uint8_t *__restrict__ t, const int32_t *__restrict__ kf_idx,
     const int32_t *__restrict__ f_idx, const int4 *__restrict__ pairs, int npairs, const uint8_t *__restrict__ valid,
     float nnratio, int th, int32_t *__restrict__ match_f)
 {
-    // the serial loop over a node's key-frame features must not wait for global memory: their descriptors are staged in LDS
-    // 64 at a time (lane j fetches feature j), and the first 256 frame features of the node stay in registers
-    __shared__ uint4 s_q[M_THREADS / 64][64][2];
-    __shared__ int s_ikf[M_THREADS / 64][64];
+    // the walk is bow_walk() (orbm_bow_body.h): key-frame features serial, frame features on the lanes
+    __shared__ BowStage st;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int w = blockIdx.x * (M_THREADS / 64) + wv;
+    const int w = blockIdx.x * BOW_WAVES + wv;
     if (w >= npairs) return;                 // whole waves leave; nothing below is a block-wide barrier
     const int4 p = pairs[w];                 // key-frame range [x, y) of kf_idx, frame range [z, w) of f_idx
-    const int nF = p.w - p.z;
-    const int nch = (nF + 63) >> 6;
-    uint4 ta[BOW_REG_CHUNKS], tb[BOW_REG_CHUNKS];
-#pragma unroll
-    for (int ch = 0; ch < BOW_REG_CHUNKS; ch++) {
-        const int pos = ch * 64 + lane;
-        const int fi = pos < nF ? f_idx[p.z + pos] : 0;
-        const uint4 *T = reinterpret_cast<const uint4 *>(t) + 2 * (long long)fi;
-        ta[ch] = T[0]; tb[ch] = T[1];
-    }
-    for (int pos = lane; pos < nF; pos += 64) match_f[f_idx[p.z + pos]] = -1;     // this wave owns these entries
-    unsigned long long taken = 0;
-    for (int c0 = p.x; c0 < p.y; c0 += 64) {
-        const int nb = min(64, p.y - c0);
-        {
-            int ikf = -1;
-            if (lane < nb) {
-                ikf = kf_idx[c0 + lane];
-                if (valid && !valid[ikf]) ikf = -1;      // :193-197
-            }
-            const uint4 *Q = reinterpret_cast<const uint4 *>(q) + 2 * (long long)max(ikf, 0);
-            s_q[wv][lane][0] = Q[0]; s_q[wv][lane][1] = Q[1];
-            s_ikf[wv][lane] = ikf;
-        }
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_s_waitcnt(0xc07f);      // lgkmcnt(0): this wave's LDS writes have landed
-        for (int j = 0; j < nb; j++) {
-            const int ikf = s_ikf[wv][j];
-            if (ikf < 0) continue;               // wave-uniform
-            const uint4 q0 = s_q[wv][j][0], q1 = s_q[wv][j][1];
-            uint32_t bk = BOW_NONE, sk = BOW_NONE;
-#pragma unroll
-            for (int ch = 0; ch < BOW_REG_CHUNKS; ch++) {
-                const int pos = ch * 64 + lane;
-                const uint32_t key = ((uint32_t)hamming256(q0, q1, ta[ch], tb[ch]) << 16) | (uint32_t)pos;
-                const uint32_t k2 = (pos < nF && !((taken >> ch) & 1ull)) ? key : BOW_NONE;
-                sk = med3u(bk, sk, k2); bk = min(bk, k2);
-            }
-            for (int ch = BOW_REG_CHUNKS; ch < nch; ch++) {
-                const int pos = ch * 64 + lane;
-                if (pos < nF && !((taken >> ch) & 1ull)) {
-                    const uint4 *Tj = reinterpret_cast<const uint4 *>(t) + 2 * (long long)f_idx[p.z + pos];
-                    const uint32_t key = ((uint32_t)hamming256(q0, q1, Tj[0], Tj[1]) << 16) | (uint32_t)pos;
-                    sk = med3u(bk, sk, key); bk = min(bk, key);
-                }
-            }
-            uint32_t B, S2;
-            wave_best2<0>(bk, sk, B, S2);            // the winner's position is unique: every other lane offers its best
-            const int best1 = (int)(B >> 16), best2 = (int)(S2 >> 16);
-            if (best1 <= th && (float)best1 < __fmul_rn(nnratio, (float)best2)) {     // :228-232 (th = TH_LOW), :598-600 (th = TH_LOW - 1)
-                const int pos = (int)(B & 0xFFFFu);
-                if (lane == (pos & 63)) {
-                    taken |= 1ull << (pos >> 6);
-                    match_f[f_idx[p.z + pos]] = ikf;
-                }
-            }
-        }
-        __builtin_amdgcn_wave_barrier();         // the next batch overwrites the staging
-    }
+    bow_walk(st, wv, lane, reinterpret_cast<const uint4 *>(q), reinterpret_cast<const uint4 *>(t), kf_idx, f_idx, p, valid, nnratio, th, match_f);
 }
 
 // ---- host helpers ----
 // rotation histogram + ComputeThreeMaxima cull of SearchByBoW (:236-246, :266-284) on a finished match table
-static int bow_rotation_cull(const orbx_keypoint *kps_kf, const orbx_keypoint *kps_f, int n_f, int check_orientation,
-                             int32_t *match_f, int *nmatches)
+int bow_rotation_cull(const orbx_keypoint *kps_kf, const orbx_keypoint *kps_f, int n_f, int check_orientation,
+                      int32_t *match_f, int *nmatches)
 {
     RotHist rot;
     int nm = 0;

@@ -16,6 +16,8 @@
 //     int SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, s12, R12, t12, th)                   :78
 //     int Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, const float th = 3.0)                :81
 //     int Fuse(KeyFrame *pKF, cv::Mat Scw, vpPoints, float th, vpReplacePoint)                           :84
+// Beside them, two overloads the reference does not have: SearchByBoW over a list of candidate key frames in one GPU call, for the
+// candidate loops of Tracking::Relocalization and LoopClosing::ComputeSim3.
 // Each method gathers exactly the members its reference body reads (listed above it) from the maintainer's own Frame /
 // KeyFrame / MapPoint classes into flat arrays, calls the C ABI of include/orbm.h (cv::Mat algebra on the host with OpenCV's
 // arithmetic, window queries, candidate predicates and Hamming distances on the GPU) and writes the result back the way the
@@ -294,6 +296,52 @@ public:
         for (int i = 0; i < n1; i++)
             if (S.match_[i] >= 0) vpMatches12[i] = vpMapPoints2[S.match_[i]];
         return nm;
+    }
+
+    // ---- SearchByBoW(pKF, F, ...) for every candidate of Tracking::Relocalization (src/Tracking.cc:1377-1398) in one GPU call ----
+    // (orbm_search_by_bow_batch).  Not in the reference's header: the caller's loop keeps its isBad() test, its nmatches<15 decision
+    // and its solver construction, and reads vnMatches[i] where it called SearchByBoW.
+    // reads: per candidate what SearchByBoW(pKF, F, ...) above reads, and pKF->isBad(); F's members once
+    // writes: vvpMapPointMatches[i] (F.N entries) and vnMatches[i] = nmatches for every candidate searched; an entry of the list that
+    //         is NULL or isBad() takes no part and gets an empty table and vnMatches[i] = -1
+    // returns: the number of candidates searched, or -1 when the GPU call failed (LastError(); every table empty, every count -1)
+    // A template only so that a list of a class derived from KeyFrame is accepted as well; in an ORB-SLAM2 tree KF is KeyFrame.
+    template <class KF>
+    int SearchByBoW(const std::vector<KF *> &vpKFs, Frame &F, std::vector<std::vector<MapPoint *> > &vvpMapPointMatches, std::vector<int> &vnMatches)
+    {
+        BowCandidates c;
+        bow_candidates(vpKFs, c, vvpMapPointMatches, vnMatches);
+        const int nk = (int)c.who.size();
+        if (nk == 0) return 0;
+        if (!ready()) return -1;
+        BowGather gf;
+        orbm_bow_side frame = bow_side(gf, F.mDescriptors, F.mvKeys, F.mFeatVec, F.N);
+        frame.valid = nullptr;
+        c.table.assign((size_t)nk * F.N, -1);
+        if (!ok(orbm_search_by_bow_batch(h_.m, c.sides.data(), nk, &frame, mfNNratio, mbCheckOrientation ? 1 : 0, c.table.data(), c.counts.data())))
+            return -1;
+        bow_scatter(c, F.N, vvpMapPointMatches, vnMatches);
+        return nk;
+    }
+
+    // ---- SearchByBoW(mpCurrentKF, pKF, ...) for every candidate of LoopClosing::ComputeSim3 (src/LoopClosing.cc:253-281) in one GPU
+    // call (orbm_search_by_bow_kf_batch).  As the overload above: vvpMatches12[i] has one entry per feature of pKF1.
+    template <class KF>
+    int SearchByBoW(KeyFrame *pKF1, const std::vector<KF *> &vpKFs2, std::vector<std::vector<MapPoint *> > &vvpMatches12, std::vector<int> &vnMatches)
+    {
+        BowCandidates c;
+        bow_candidates(vpKFs2, c, vvpMatches12, vnMatches);
+        const int nk = (int)c.who.size();
+        if (nk == 0) return 0;
+        if (!ready()) return -1;
+        BowGather g1;
+        g1.mps = pKF1->GetMapPointMatches();
+        const orbm_bow_side kf1 = bow_side(g1, pKF1->mDescriptors, pKF1->mvKeysUn, pKF1->mFeatVec);
+        c.table.assign((size_t)nk * kf1.n, -1);
+        if (!ok(orbm_search_by_bow_kf_batch(h_.m, &kf1, c.sides.data(), nk, mfNNratio, mbCheckOrientation ? 1 : 0, c.table.data(), c.counts.data())))
+            return -1;
+        bow_scatter(c, kf1.n, vvpMatches12, vnMatches);
+        return nk;
     }
 
     // ---- include/ORBmatcher.h:73, src/ORBmatcher.cc:657-823 (LocalMapping::CreateNewMapPoints, src/LocalMapping.cc:270) ----
@@ -629,6 +677,64 @@ protected:
             node.push_back((int32_t)it->first);
             for (size_t k = 0; k < it->second.size(); k++) idx.push_back((int32_t)it->second[k]);
             off.push_back((int32_t)idx.size());
+        }
+    }
+
+    // one side of a batched SearchByBoW: the gathers of :204-224 / :276-297 (MapPoints, their `pMP && !pMP->isBad()` flags, the
+    // flattened FeatureVector) and the orbm_bow_side that points into them.  n < 0: a key frame, one feature per MapPoint slot
+    struct BowGather {
+        std::vector<MapPoint *> mps;
+        std::vector<uint8_t> valid;
+        std::vector<int32_t> node, off, idx;
+    };
+    template <class FV> static orbm_bow_side bow_side(BowGather &g, const cv::Mat &desc, const std::vector<cv::KeyPoint> &kps, const FV &fv, int n = -1)
+    {
+        if (n < 0) {
+            n = (int)g.mps.size();
+            g.valid.assign(n, 0);
+            for (int i = 0; i < n; i++) g.valid[i] = g.mps[i] && !g.mps[i]->isBad();
+        }
+        flatten(fv, g.node, g.off, g.idx);
+        orbm_bow_side s;
+        s.desc = desc.ptr<unsigned char>(); s.kps = kp(kps); s.n = n; s.valid = g.valid.data();
+        s.fv_node = g.node.data(); s.fv_off = g.off.data(); s.fv_idx = g.idx.data(); s.fv_n = (int)g.node.size();
+        return s;
+    }
+
+    // the candidates of a list that take part in a batched SearchByBoW (not NULL, not isBad()): their places in the list, gathers and
+    // sides, and the call's outputs.  bow_candidates() also resets the caller's tables (empty) and counts (-1); bow_scatter() turns
+    // the rows of n entries (indices into a candidate's MapPoints) into the caller's pointer tables
+    struct BowCandidates {
+        std::vector<int> who;
+        std::vector<BowGather> g;
+        std::vector<orbm_bow_side> sides;
+        std::vector<int32_t> table, counts;
+    };
+    template <class KF> static void bow_candidates(const std::vector<KF *> &vpKFs, BowCandidates &c, std::vector<std::vector<MapPoint *> > &vvpMatches,
+                                                   std::vector<int> &vnMatches)
+    {
+        const int nKFs = (int)vpKFs.size();
+        vvpMatches.assign(nKFs, std::vector<MapPoint *>());
+        vnMatches.assign(nKFs, -1);
+        for (int i = 0; i < nKFs; i++)
+            if (vpKFs[i] && !vpKFs[i]->isBad()) c.who.push_back(i);
+        const int nk = (int)c.who.size();
+        c.g.resize(nk); c.sides.resize(nk); c.counts.assign(nk, 0);
+        for (int k = 0; k < nk; k++) {
+            KF *pKF = vpKFs[c.who[k]];
+            c.g[k].mps = pKF->GetMapPointMatches();
+            c.sides[k] = bow_side(c.g[k], pKF->mDescriptors, pKF->mvKeysUn, pKF->mFeatVec);
+        }
+    }
+    static void bow_scatter(const BowCandidates &c, int n, std::vector<std::vector<MapPoint *> > &vvpMatches, std::vector<int> &vnMatches)
+    {
+        for (size_t k = 0; k < c.who.size(); k++) {
+            std::vector<MapPoint *> &out = vvpMatches[c.who[k]];
+            out.assign(n, static_cast<MapPoint *>(NULL));
+            const int32_t *row = c.table.data() + k * (size_t)n;
+            for (int i = 0; i < n; i++)
+                if (row[i] >= 0) out[i] = c.g[k].mps[row[i]];
+            vnMatches[c.who[k]] = c.counts[k];
         }
     }
 
