@@ -209,10 +209,18 @@ int orbm_search_area_best2_device(orbm_matcher *m, const uint8_t *d_qdesc, const
  * (`if(vpMapPointMatches[realIdxF]) continue;` :209) -- so the scan order matters and is kept.  A frame feature lives in
  * exactly one node, hence nodes are independent: one wave per node walks its key-frame features in order with the node's
  * frame features across the lanes (best / second-best :214-226, TH_LOW and ratio :228-232); the rotation histogram
- * (:236-246, :266-284) runs on the host over the match table.  Nodes with more than 4096 frame features take the general
- * path: all node-mate distances in one GPU call, the same selection scan on the host.  match_f[i] = index of the key-frame feature matched to frame feature i, or -1
- * (the reference's vpMapPointMatches as indices); *nmatches = the function's return value.
- * kps_kf are the key frame's mvKeysUn, kps_f the frame's mvKeys (only .angle is read).
+ * (:236-246, :266-284) runs on the host over the match table.  A call in which a shared node has more than 4096 lane-side
+ * features (the frame's here, key frame 2's usable ones in orbm_search_by_bow_kf), and every call when ORBM_BOW_HOST_SELECT=1 is
+ * in the environment, takes the host selection: all node-mate distances in one GPU call, the same selection scan on the host.
+ * match_f[i] = index of the key-frame feature matched to frame feature i, or -1 (the reference's vpMapPointMatches as indices);
+ * *nmatches = the function's return value.  kps_kf are the key frame's mvKeysUn, kps_f the frame's mvKeys (only .angle is read).
+ *
+ * This call and orbm_search_by_bow_kf are the batch calls below with one candidate, and they check their arguments exactly as those
+ * do: the same conditions in the same order with the same ORBX_E_INVALID texts, before anything is written and before the handle
+ * is looked at, so an argument error leaves match_f / matches12 / *nmatches untouched.  A call with an empty side (n == 0 or
+ * fv_n == 0), or without a usable shared node, is answered on the host (-1 / 0) and needs no handle; everything else needs one
+ * (a NULL handle: as orbm_create_new_map_points, outputs untouched).  A failure after that (a HIP error) may leave the table partly
+ * written.  The calls grow the handle's result buffer when they need to and nothing else: no SearchByBoW call drops the grid.
  */
 int orbm_search_by_bow(orbm_matcher *m,
                        const uint8_t *desc_kf, const orbx_keypoint *kps_kf, int n_kf, const uint8_t *valid_kf,
@@ -295,8 +303,8 @@ int orbm_search_by_bow_kf(orbm_matcher *m,
  * Both callers loop over their candidates with one SearchByBoW each.  The calls do not interact: each writes a table of its own
  * and reads only its own key frame and the shared side (the lost frame, or mpCurrentKF), and the skip of :209 acts inside one call
  * and one vocabulary node.  So all candidates are searched in one call: the shared side goes up once, every (candidate, shared node)
- * pair is one wave of one launch (the walk of orbm_search_by_bow), the tables come back in one copy, and the rotation histogram runs
- * on the host per candidate.  For every candidate c the table and the count are bit for bit what the one-candidate call returns.
+ * pair is one wave of one launch, the tables come back in one copy, and the rotation histogram runs on the host per candidate.  The
+ * one-candidate calls are this with nkf == 1: for every candidate c the table and the count are bit for bit what they return.
  *
  * Checked before any device work, refused with ORBX_E_INVALID and every output untouched: negative counts, NULL buffers where the
  * count is positive (the key-frame variant needs `valid` on both sides, as orbm_search_by_bow_kf does), fv_off not monotone from 0,
@@ -306,10 +314,9 @@ int orbm_search_by_bow_kf(orbm_matcher *m,
  * side is empty (n == 0 or fv_n == 0), or none of whose candidates shares a usable node with it, is answered on the host (-1 / 0)
  * and needs no handle; everything else needs one (a NULL handle: as orbm_create_new_map_points).  A candidate that shares a node of
  * more than 4096 lane-side features (the frame's in the first call, its own usable ones in the second), and every candidate when
- * ORBM_BOW_HOST_SELECT=1 is in the environment, is answered by the one-candidate entry point after the launch.  The call grows the
- * handle when the tables exceed its result buffer and leaves the grid slots as it found them.  One exception: a candidate that took
- * the one-candidate path is subject to that entry point's growth, and when one of its sides has more descriptors than the handle's
- * max_train, the growth drops the grid (orbm_grid_count() == -1), as a direct orbm_search_by_bow call does.  A failed call leaves the outputs as they were.
+ * ORBM_BOW_HOST_SELECT=1 is in the environment, takes the host selection after the launch (distances on the GPU, the scan on the
+ * host).  The call grows the handle when the tables, or the host selection's distances, exceed its result buffer, and leaves the
+ * grid slots as it found them.  A failed call leaves the outputs as they were.
  */
 typedef struct {
     const uint8_t *desc; const orbx_keypoint *kps; int32_t n;   /* 32-byte descriptors, keypoints (only .angle is read) */

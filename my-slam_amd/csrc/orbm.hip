@@ -14,7 +14,6 @@
 
 #include "orbm_internal.h"
 #include "orbm_accept.h"
-#include "orbm_bow_body.h"
 
 // ---- pinned staging arena (see orbm_internal.h; orbm_arena_begin is in orbm_workspace.cc) ----
 static void *arena_take(orbm_matcher *m, size_t bytes)
@@ -180,18 +179,6 @@ void orbm_launch_dist_csr(const uint8_t *d_q, int nq, const uint8_t *d_t, const 
 {
     if (total > 0)
         hipLaunchKernelGGL(k_dist_csr, dim3((unsigned)((total + M_THREADS - 1) / M_THREADS)), dim3(M_THREADS), 0, s, d_q, nq, d_t, d_off, d_idx, total, d_dist);
-}
-
-// pairs given explicitly as (query << 16 | train), both below 65536: no per-thread binary search over off[]
-__global__ __launch_bounds__(M_THREADS) void k_dist_pairs16(const uint8_t *__restrict__ q, const uint8_t *__restrict__ t,
-                                                            const uint32_t *__restrict__ pairs, int total, int32_t *__restrict__ dist)
-{
-    const int c = blockIdx.x * M_THREADS + threadIdx.x;
-    if (c >= total) return;
-    const uint32_t p = pairs[c];
-    const uint4 *Q = reinterpret_cast<const uint4 *>(q) + 2 * (long long)(p >> 16);
-    const uint4 *Tj = reinterpret_cast<const uint4 *>(t) + 2 * (long long)(p & 0xFFFFu);
-    dist[c] = hamming256(Q[0], Q[1], Tj[0], Tj[1]);
 }
 
 __global__ __launch_bounds__(M_THREADS) void k_dist_dense(
@@ -417,238 +404,6 @@ extern "C" int orbm_best2_batch_device(orbm_matcher *m, const uint8_t *d_q, cons
     hipLaunchKernelGGL(k_merge_batch, dim3((cap + M_THREADS - 1) / M_THREADS, nbatch), dim3(M_THREADS), 0, s,
                        m->d_part, S, d_nq, cap, d_best_idx, d_best_d, d_second_d);
     MHIPCHK(hipGetLastError());
-    return ORBX_OK;
-}
-
-// ---- N2: SearchByBoW's selection on the GPU (src/ORBmatcher.cc:199-232).  One wave per pair of equal vocabulary nodes: the
-// node's key-frame features are visited in order (the loop is sequential in the reference because a frame feature taken by an
-// earlier key-frame feature is skipped, :209), the lanes hold the node's frame features (position = chunk * 64 + lane, a
-// "taken" bit per chunk in a register), key = distance << 16 | position so that min() is "smallest distance, first in list".
-// A frame feature lives in exactly one node, so nodes do not interact. ----
-__global__ __launch_bounds__(M_THREADS) void k_bow_select(
-    const uint8_t *__restrict__ q, const uint8_t *__restrict__ t, const int32_t *__restrict__ kf_idx,
-    const int32_t *__restrict__ f_idx, const int4 *__restrict__ pairs, int npairs, const uint8_t *__restrict__ valid,
-    float nnratio, int th, int32_t *__restrict__ match_f)
-{
-    // the walk is bow_walk() (orbm_bow_body.h): key-frame features serial, frame features on the lanes
-    __shared__ BowStage st;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int w = blockIdx.x * BOW_WAVES + wv;
-    if (w >= npairs) return;                 // whole waves leave; nothing below is a block-wide barrier
-    const int4 p = pairs[w];                 // key-frame range [x, y) of kf_idx, frame range [z, w) of f_idx
-    bow_walk(st, wv, lane, reinterpret_cast<const uint4 *>(q), reinterpret_cast<const uint4 *>(t), kf_idx, f_idx, p, valid, nnratio, th, match_f);
-}
-
-// ---- host helpers ----
-// rotation histogram + ComputeThreeMaxima cull of SearchByBoW (:236-246, :266-284) on a finished match table
-int bow_rotation_cull(const orbx_keypoint *kps_kf, const orbx_keypoint *kps_f, int n_f, int check_orientation,
-                      int32_t *match_f, int *nmatches)
-{
-    RotHist rot;
-    int nm = 0;
-    for (int i = 0; i < n_f; i++) {
-        if (match_f[i] < 0) continue;
-        nm++;
-        if (check_orientation) MTRY(rot.add(kps_kf[match_f[i]].angle, kps_f[i].angle, i));
-    }
-    if (check_orientation) rot.cull([&](int i) { match_f[i] = -1; nm--; });
-    *nmatches = nm;
-    return ORBX_OK;
-}
-
-// Returns 1 when the GPU selection does not apply (a node with more than BOW_MAX_NODE_FEATURES frame features, a match table larger
-// than the handle's result buffer, ORBM_BOW_HOST_SELECT=1 in the environment): the caller then takes the host-selection path.
-static int search_by_bow_device(orbm_matcher *m,
-                                const uint8_t *desc_kf, const orbx_keypoint *kps_kf, int n_kf, const uint8_t *valid_kf,
-                                const int32_t *fv_kf_node, const int32_t *fv_kf_off, const int32_t *fv_kf_idx, int fv_kf_n,
-                                const uint8_t *desc_f, const orbx_keypoint *kps_f, int n_f,
-                                const int32_t *fv_f_node, const int32_t *fv_f_off, const int32_t *fv_f_idx, int fv_f_n,
-                                float nnratio, int th, int check_orientation, int32_t *match_f, int *nmatches)
-{
-    static const bool force_host = [] { const char *e = getenv("ORBM_BOW_HOST_SELECT"); return e && e[0] == '1'; }();
-    if (force_host) return 1;
-    const int nki = fv_kf_off[fv_kf_n], nfi = fv_f_off[fv_f_n];
-    if (nki < 0 || nfi < 0) return 1;
-    std::vector<int4> pairs;
-    for (int a = 0, b = 0; a < fv_kf_n && b < fv_f_n;) {       // merge-join of the ascending node lists (:178-262)
-        if (fv_kf_node[a] == fv_f_node[b]) {
-            if (fv_f_off[b + 1] - fv_f_off[b] > BOW_MAX_NODE_FEATURES) return 1;
-            if (fv_kf_off[a + 1] > fv_kf_off[a] && fv_f_off[b + 1] > fv_f_off[b])
-                pairs.push_back(make_int4(fv_kf_off[a], fv_kf_off[a + 1], fv_f_off[b], fv_f_off[b + 1]));
-            a++; b++;
-        } else if (fv_kf_node[a] < fv_f_node[b]) a++;
-        else b++;
-    }
-    const int np = (int)pairs.size();
-    if (np == 0) return ORBX_OK;
-    for (int c = 0; c < nki; c++)
-        if (fv_kf_idx[c] < 0 || fv_kf_idx[c] >= n_kf) return mfail(ORBX_E_INVALID, "key-frame feature index %d outside [0,%d)", fv_kf_idx[c], n_kf);
-    for (int c = 0; c < nfi; c++)
-        if (fv_f_idx[c] < 0 || fv_f_idx[c] >= n_f) return mfail(ORBX_E_INVALID, "frame feature index %d outside [0,%d)", fv_f_idx[c], n_f);
-    if ((size_t)n_f > m->d_out.count()) return 1;     // the match table lives in d_out
-    MHIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    MTRY(orbm_arena_begin(m));
-    InBlock in(m);                                  // one copy up, one kernel, one copy back
-    const int pq = in.add(desc_kf, (size_t)n_kf * 32), pt = in.add(desc_f, (size_t)n_f * 32);
-    const int pki = in.add(fv_kf_idx, (size_t)nki * 4), pfi = in.add(fv_f_idx, (size_t)nfi * 4);
-    const int pp = in.add(pairs.data(), (size_t)np * 16), pv = in.add(valid_kf, valid_kf ? (size_t)n_kf : 0);
-    MTRY(in.upload(s));
-    hipLaunchKernelGGL(k_bow_select, dim3((np + M_THREADS / 64 - 1) / (M_THREADS / 64)), dim3(M_THREADS), 0, s,
-                       in.at<uint8_t>(pq), in.at<uint8_t>(pt), in.at<int32_t>(pki), in.at<int32_t>(pfi), in.at<int4>(pp), np,
-                       in.at<uint8_t>(pv), nnratio, th, m->d_out);
-    MHIPCHK(hipGetLastError());
-    std::vector<int32_t> out((size_t)n_f);
-    MTRY(orbm_d2h(m, out.data(), m->d_out, (size_t)n_f * 4, s));
-    MTRY(orbm_sync(m, s));
-    for (int k = 0; k < np; k++)         // the kernel wrote the entries of the paired nodes only
-        for (int c = pairs[k].z; c < pairs[k].w; c++) match_f[fv_f_idx[c]] = out[fv_f_idx[c]];
-    return bow_rotation_cull(kps_kf, kps_f, n_f, check_orientation, match_f, nmatches);
-}
-
-// ---- N2: SearchByBoW (src/ORBmatcher.cc:159-288).  Usual path: search_by_bow_device above (selection on the GPU).  The rest
-// of this function is the general fallback: every node-mate distance on the GPU, the order-dependent selection on the host ----
-static int search_by_bow_impl(orbm_matcher *m,
-                              const uint8_t *desc_kf, const orbx_keypoint *kps_kf, int n_kf, const uint8_t *valid_kf,
-                              const int32_t *fv_kf_node, const int32_t *fv_kf_off, const int32_t *fv_kf_idx, int fv_kf_n,
-                              const uint8_t *desc_f, const orbx_keypoint *kps_f, int n_f,
-                              const int32_t *fv_f_node, const int32_t *fv_f_off, const int32_t *fv_f_idx, int fv_f_n,
-                              float nnratio, int th, int check_orientation, int32_t *match_f, int *nmatches)
-{
-    if (!m) return mfail(ORBX_E_INVALID, "NULL handle");
-    if (n_kf < 0 || n_f < 0 || fv_kf_n < 0 || fv_f_n < 0 || !match_f || !nmatches) return mfail(ORBX_E_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n_f; i++) match_f[i] = -1;
-    if (n_kf == 0 || n_f == 0 || fv_kf_n == 0 || fv_f_n == 0) return ORBX_OK;
-    if (!desc_kf || !kps_kf || !desc_f || !kps_f || !fv_kf_node || !fv_kf_off || !fv_kf_idx || !fv_f_node || !fv_f_off || !fv_f_idx)
-        return mfail(ORBX_E_INVALID, "NULL buffer");
-    MTRY(orbm_grow(m, n_kf, n_f, 0));
-    {   // selection on the GPU when every matched node fits a wave's registers
-        int rc = search_by_bow_device(m, desc_kf, kps_kf, n_kf, valid_kf, fv_kf_node, fv_kf_off, fv_kf_idx, fv_kf_n, desc_f, kps_f, n_f,
-                                      fv_f_node, fv_f_off, fv_f_idx, fv_f_n, nnratio, th, check_orientation, match_f, nmatches);
-        if (rc != 1) return rc;    // 1 = not applicable: distances on the GPU, selection on the host (below)
-    }
-    // merge-join of the two ascending node lists (:178-262); queries = usable key-frame features in visiting order
-    struct Q { int kf, f_node; };
-    std::vector<Q> qs;
-    std::vector<int32_t> off;
-    qs.reserve((size_t)n_kf); off.reserve((size_t)n_kf + 1);
-    off.push_back(0);
-    long long pairs = 0;
-    for (int a = 0, b = 0; a < fv_kf_n && b < fv_f_n;) {
-        if (fv_kf_node[a] == fv_f_node[b]) {
-            const int nb = fv_f_off[b + 1] - fv_f_off[b];
-            for (int c = fv_kf_off[a]; c < fv_kf_off[a + 1]; c++) {
-                const int ikf = fv_kf_idx[c];
-                if (ikf < 0 || ikf >= n_kf) return mfail(ORBX_E_INVALID, "key-frame feature index %d outside [0,%d)", ikf, n_kf);
-                if (valid_kf && !valid_kf[ikf]) continue;
-                qs.push_back({ikf, b});
-                pairs += nb;
-                off.push_back((int32_t)pairs);
-            }
-            a++; b++;
-        } else if (fv_kf_node[a] < fv_f_node[b]) a++;   // lower_bound on an ascending list == advance
-        else b++;
-    }
-    const int nq = (int)qs.size();
-    if (nq == 0 || pairs == 0) return ORBX_OK;
-    MTRY(orbm_grow(m, 0, 0, pairs));                 // the distances come back through d_out
-    // Usual case (both frames below 65536 features): the key frame's descriptor block goes up as it is and every pair is
-    // (key-frame feature << 16 | frame feature).  Otherwise the query descriptors are compacted and the kernel finds a
-    // pair's query by binary search over the offsets.
-    const bool packed16 = n_kf < 65536 && n_f < 65536;
-    std::vector<uint8_t> qd;
-    if (!packed16) {
-        qd.resize((size_t)nq * 32);
-        for (int i = 0; i < nq; i++) memcpy(&qd[(size_t)i * 32], desc_kf + (size_t)qs[i].kf * 32, 32);
-    }
-    std::vector<int32_t> idx((size_t)pairs), dist((size_t)pairs);
-    for (int i = 0; i < nq; i++) {
-        const int b = qs[i].f_node;
-        const uint32_t hi = packed16 ? (uint32_t)qs[i].kf << 16 : 0u;
-        int32_t *dst = idx.data() + off[i];
-        for (int c = fv_f_off[b]; c < fv_f_off[b + 1]; c++) {
-            const int fi = fv_f_idx[c];
-            if (fi < 0 || fi >= n_f) return mfail(ORBX_E_INVALID, "frame feature index %d outside [0,%d)", fi, n_f);
-            *dst++ = (int32_t)(hi | (uint32_t)fi);
-        }
-    }
-    MHIPCHK(hipSetDevice(m->device));
-    hipStream_t s = m->stream;
-    MTRY(orbm_arena_begin(m));
-    InBlock in(m);
-    const int pq = packed16 ? in.add(desc_kf, (size_t)n_kf * 32) : in.add(qd.data(), qd.size()), pt = in.add(desc_f, (size_t)n_f * 32);
-    const int pi = in.add(idx.data(), (size_t)pairs * 4), po = in.add(off.data(), packed16 ? 0 : ((size_t)nq + 1) * 4);
-    MTRY(in.upload(s));
-    if (packed16)
-        hipLaunchKernelGGL(k_dist_pairs16, dim3((unsigned)((pairs + M_THREADS - 1) / M_THREADS)), dim3(M_THREADS), 0, s,
-                           in.at<uint8_t>(pq), in.at<uint8_t>(pt), in.at<uint32_t>(pi), (int)pairs, m->d_out);
-    else
-        orbm_launch_dist_csr(in.at<uint8_t>(pq), nq, in.at<uint8_t>(pt), in.at<int32_t>(po), in.at<int32_t>(pi), (int)pairs, m->d_out, s);
-    MHIPCHK(hipGetLastError());
-    MTRY(orbm_d2h(m, dist.data(), m->d_out, (size_t)pairs * 4, s));
-    MTRY(orbm_sync(m, s));
-    for (int i = 0; i < nq; i++) {                   // sequential selection (:199-232)
-        int best1 = 256, best2 = 256, bestF = -1;
-        for (int c = off[i]; c < off[i + 1]; c++) {
-            const int fi = packed16 ? (int)((uint32_t)idx[c] & 0xFFFFu) : idx[c];
-            if (match_f[fi] >= 0) continue;                 // :209
-            const int d = dist[c];
-            if (d < best1) { best2 = best1; best1 = d; bestF = fi; }
-            else if (d < best2) best2 = d;
-        }
-        if (best1 <= th && (float)best1 < nnratio * (float)best2) match_f[bestF] = qs[i].kf;
-    }
-    return bow_rotation_cull(kps_kf, kps_f, n_f, check_orientation, match_f, nmatches);
-}
-
-extern "C" int orbm_search_by_bow(orbm_matcher *m,
-                                  const uint8_t *desc_kf, const orbx_keypoint *kps_kf, int n_kf, const uint8_t *valid_kf,
-                                  const int32_t *fv_kf_node, const int32_t *fv_kf_off, const int32_t *fv_kf_idx, int fv_kf_n,
-                                  const uint8_t *desc_f, const orbx_keypoint *kps_f, int n_f,
-                                  const int32_t *fv_f_node, const int32_t *fv_f_off, const int32_t *fv_f_idx, int fv_f_n,
-                                  float nnratio, int check_orientation, int32_t *match_f, int *nmatches)
-{
-    return search_by_bow_impl(m, desc_kf, kps_kf, n_kf, valid_kf, fv_kf_node, fv_kf_off, fv_kf_idx, fv_kf_n, desc_f, kps_f, n_f,
-                              fv_f_node, fv_f_off, fv_f_idx, fv_f_n, nnratio, ORBM_TH_LOW, check_orientation, match_f, nmatches);
-}
-
-// ---- ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12) (src/ORBmatcher.cc:522-655) ----
-// The same node-by-node scan as the key-frame / frame variant above with three differences: features of BOTH key frames need a
-// usable MapPoint (:558-562, :576-580), the acceptance is the strict `bestDist1 < TH_LOW` (:598), and the table is indexed by the
-// OUTER key frame's features (vpMatches12[idx1]).  A feature of KF2 that can never be taken (no MapPoint, bad MapPoint) is dropped
-// from KF2's node lists before the scan -- skipping it inside the scan is the same thing --, the scan runs with th = TH_LOW - 1,
-// and the table it returns (inner feature -> outer feature, one-to-one by vbMatched2) is inverted.
-extern "C" int orbm_search_by_bow_kf(orbm_matcher *m,
-                                     const uint8_t *desc1, const orbx_keypoint *kps1, int n1, const uint8_t *valid1,
-                                     const int32_t *fv1_node, const int32_t *fv1_off, const int32_t *fv1_idx, int fv1_n,
-                                     const uint8_t *desc2, const orbx_keypoint *kps2, int n2, const uint8_t *valid2,
-                                     const int32_t *fv2_node, const int32_t *fv2_off, const int32_t *fv2_idx, int fv2_n,
-                                     float nnratio, int check_orientation, int32_t *matches12, int *nmatches)
-{
-    if (!m) return mfail(ORBX_E_INVALID, "NULL handle");
-    if (n1 < 0 || n2 < 0 || fv1_n < 0 || fv2_n < 0 || !matches12 || !nmatches) return mfail(ORBX_E_INVALID, "bad argument");
-    *nmatches = 0;
-    for (int i = 0; i < n1; i++) matches12[i] = -1;                             // :534
-    if (n1 == 0 || n2 == 0 || fv1_n == 0 || fv2_n == 0) return ORBX_OK;
-    if (!fv2_node || !fv2_off || !fv2_idx || !valid1 || !valid2) return mfail(ORBX_E_INVALID, "NULL buffer");
-    std::vector<int32_t> off2((size_t)fv2_n + 1, 0), idx2;
-    idx2.reserve((size_t)std::max(fv2_off[fv2_n], 0));
-    for (int b = 0; b < fv2_n; b++) {
-        for (int c = fv2_off[b]; c < fv2_off[b + 1]; c++) {
-            const int i2 = fv2_idx[c];
-            if (i2 < 0 || i2 >= n2) return mfail(ORBX_E_INVALID, "feature index %d outside [0,%d)", i2, n2);
-            if (valid2[i2]) idx2.push_back(i2);
-        }
-        off2[(size_t)b + 1] = (int32_t)idx2.size();
-    }
-    if (idx2.empty()) return ORBX_OK;
-    std::vector<int32_t> match2((size_t)n2, -1);
-    int rc = search_by_bow_impl(m, desc1, kps1, n1, valid1, fv1_node, fv1_off, fv1_idx, fv1_n, desc2, kps2, n2,
-                                fv2_node, off2.data(), idx2.data(), fv2_n, nnratio, ORBM_TH_LOW - 1, check_orientation, match2.data(), nmatches);
-    if (rc != ORBX_OK) return rc;
-    for (int i2 = 0; i2 < n2; i2++)
-        if (match2[i2] >= 0) matches12[match2[i2]] = i2;
     return ORBX_OK;
 }
 

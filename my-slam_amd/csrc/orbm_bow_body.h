@@ -1,7 +1,6 @@
 // orbm_bow_body.h -- SearchByBoW's selection for one pair of equal vocabulary nodes (src/ORBmatcher.cc:199-232 of WChen09/My-SLAM) as
-// a device function: bow_walk() is the body of one wave.  Shared by k_bow_select (orbm.hip: one candidate, every pointer is the
-// call's own array) and k_bow_select_batch (orbm_bow_batch.hip: many candidates, every pointer is the block of one work item's
-// side): the two kernels differ only in where a wave finds its arrays.
+// a device function: bow_walk() is the body of one wave of k_bow_select_batch (orbm_bow.hip), which finds a work item's arrays in
+// the one block a call uploads and serves the one-candidate and the batch entry points alike.
 //
 // The node's SERIAL-side features are visited in list order (the loop is sequential in the reference because a feature taken by an
 // earlier one is skipped, :209), staged 64 at a time in wave-private LDS; the lanes hold the node's LANE-side features (position =

@@ -1,5 +1,5 @@
 // orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip,
-// orbm_frustum.hip, orbm_pose.hip and orbm_bow_batch.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
+// orbm_frustum.hip, orbm_pose.hip and orbm_bow.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -149,11 +149,6 @@ int orbm_tri_check_views(const orbm_camera *cam1, const orbm_camera *cams2, int 
 // k_dist_csr (orbm.hip) for callers in other files: dist[c] of every CSR candidate, off has nq + 1 entries
 void orbm_launch_dist_csr(const uint8_t *d_q, int nq, const uint8_t *d_t, const int32_t *d_off, const int32_t *d_idx, int total,
                           int32_t *d_dist, hipStream_t s);
-
-// orbm.hip: rotation histogram + ComputeThreeMaxima cull of SearchByBoW (:236-246, :266-284) on a finished match table
-// (match_f[frame feature] = key-frame feature or -1); *nmatches = what is left
-int bow_rotation_cull(const orbx_keypoint *kps_kf, const orbx_keypoint *kps_f, int n_f, int check_orientation, int32_t *match_f,
-                      int *nmatches);
 
 // -------------------------------------------------------------------------------------------------
 // host-only helpers

@@ -1,7 +1,7 @@
 // orbm_kf.hip -- the windowed ORBmatcher methods of the LocalMapping / LoopClosing threads on gfx950.
 // Reference (WChen09/My-SLAM), all in src/ORBmatcher.cc:
 //   :290-403   SearchByProjection(KeyFrame*, Scw, vpPoints, vpMatched, th)      orbm_search_by_projection_sim3
-//   :522-655   SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12)                   orbm_search_by_bow_kf (orbm.hip, beside its sibling)
+//   :522-655   SearchByBoW(KeyFrame*, KeyFrame*, vpMatches12)                   orbm_search_by_bow_kf (orbm_bow.hip, beside its sibling)
 //   :657-823   SearchForTriangulation(pKF1, pKF2, F12, vMatchedPairs, bStereo)  orbm_search_for_triangulation (orbm_newpoints.hip)
 //   :825-975   Fuse(KeyFrame*, vpMapPoints, th)                                 orbm_fuse
 //   :977-1100  Fuse(KeyFrame*, Scw, vpPoints, th, vpReplacePoint)               orbm_fuse_sim3

@@ -292,7 +292,7 @@ def contest_case(variant):
 
 def fallback_case(variant="frame"):
     """a node of 4200 lane-side features next to one of 50: candidate 0 lives in the small node only and stays in the launch,
-    candidates 1 and 2 are in both and take the one-candidate path"""
+    candidates 1 and 2 are in both and take the host selection"""
     if variant == "frame":
         small = 3 + 7
         return make_case("fallback-frame", "frame", 55, 4250, [4200, 50], [{"n": 30, "nodes": {small}, "copy": 1.0}, {"n": 60}, {"n": 45}])

@@ -1,4 +1,4 @@
-"""No-GPU checks of orbm_search_by_bow_batch / orbm_search_by_bow_kf_batch (include/orbm.h): the entry points' argument checks and
+"""No-GPU checks of the four SearchByBoW entry points (include/orbm.h): the batch and the one-candidate calls' argument checks and
 host answers through ctypes with a NULL handle, and what the case module (tests/bow_batch_cases.py) plants, on the oracle's output
 alone."""
 import ctypes as C
@@ -66,12 +66,54 @@ class Call:
         return (self.table == 77).all() and (self.counts == 77).all()
 
 
+class SingleCall(Call):
+    """orbm_search_by_bow / orbm_search_by_bow_kf on the shared side and candidate `c` of a case: the same arrays, mutations and 77
+    fill as Call, with who = 0 for the one candidate"""
+
+    def __init__(self, orbx, variant, case=None, c=0):
+        super().__init__(orbx, variant, case)
+        self.cands, self.nkf = [self.cands[c]], 1
+        self.table = np.full(len(self.shared[1]), 77, np.int32)
+        self.counts = np.full(1, 77, np.int32)
+
+    def side(self, who, with_valid):
+        kps, desc, fv, valid = self.shared if who < 0 else self.cands[who]
+        a = dict(desc=p(desc), kps=p(kps), n=len(desc), valid=p(valid), fv_node=p(fv[0]), fv_off=p(fv[1]), fv_idx=p(fv[2]), fv_n=len(fv[0]))
+        a.update({field: None for w, field in self.null if w == who})
+        a.update({field: value for w, field, value in getattr(self, "counts_override", []) if w == who})
+        return [a["desc"], a["kps"], a["n"]] + ([a["valid"]] if with_valid else []) + [a["fv_node"], a["fv_off"], a["fv_idx"], a["fv_n"]]
+
+    def run(self, handle=None, nnratio=0.75, check_ori=1):
+        L = self.orbx.lib()
+        out = [C.c_float(nnratio), check_ori, None if "table" in self.null_args else p(self.table),
+               None if "counts" in self.null_args else p(self.counts)]
+        if self.variant == "frame":
+            return L.orbm_search_by_bow(handle, *(self.side(0, True) + self.side(-1, False) + out))
+        return L.orbm_search_by_bow_kf(handle, *(self.side(-1, True) + self.side(0, True) + out))
+
+
 def test_the_symbols_and_their_wrappers_exist(built):
-    """Fails on a library built without my-slam_amd/csrc/orbm_bow_batch.hip."""
+    """Fails on a library built without my-slam_amd/csrc/orbm_bow.hip."""
     L = C.CDLL(built.LIB_PATH)
     assert hasattr(L, "orbm_search_by_bow_batch") and hasattr(L, "orbm_search_by_bow_kf_batch")
     assert hasattr(built.ORBmatcher, "SearchByBoWBatch") and hasattr(built.ORBmatcher, "SearchByBoWKFBatch")
     assert C.sizeof(built.BowSide) == 64
+
+
+def side_mutations(variant, who):
+    """(mutation of a Call, text of the refusal) for every malformed side; who = -1: the shared side, else that candidate"""
+    FV = 2
+    side = lambda c: c.shared if who < 0 else c.cands[who]
+    yield lambda c: side(c)[FV][1].__setitem__(0, 1), b"fv_off[0] must be 0"
+    yield lambda c: side(c)[FV][1].__setitem__(2, int(side(c)[FV][1][1]) - 1), b"fv_off not monotone"
+    yield lambda c: side(c)[FV][0].__setitem__(1, int(side(c)[FV][0][0])), b"node ids not ascending"
+    yield lambda c: side(c)[FV][0].__setitem__(2, int(side(c)[FV][0][1]) - 1), b"node ids not ascending"
+    yield lambda c: side(c)[FV][2].__setitem__(3, len(side(c)[1])), b"feature index"
+    yield lambda c: side(c)[FV][2].__setitem__(len(side(c)[FV][2]) - 1, -1), b"feature index -1"
+    for field in ("desc", "kps", "fv_node", "fv_off", "fv_idx") + (("valid",) if variant == "kf" else ()):
+        yield lambda c, field=field: c.null.add((who, field)), b"NULL buffer"
+    yield lambda c: setattr(c, "counts_override", [(who, "n", -1)]), b"negative count"
+    yield lambda c: setattr(c, "counts_override", [(who, "fv_n", -3)]), b"negative count"
 
 
 @pytest.mark.parametrize("variant", ["frame", "kf"])
@@ -85,24 +127,65 @@ def test_argument_checks_come_before_any_device_work(built, variant):
         assert c.run() == built.ORBX_E_INVALID and text in L.orbm_last_error(), L.orbm_last_error()
         assert c.untouched()
 
-    FV = 2
     for who in (-1, 0, 2):                                # the shared side, the first and the last candidate
-        side = lambda c: c.shared if who < 0 else c.cands[who]
-        bad(lambda c: side(c)[FV][1].__setitem__(0, 1), b"fv_off[0] must be 0")
-        bad(lambda c: side(c)[FV][1].__setitem__(2, int(side(c)[FV][1][1]) - 1), b"fv_off not monotone")
-        bad(lambda c: side(c)[FV][0].__setitem__(1, int(side(c)[FV][0][0])), b"node ids not ascending")
-        bad(lambda c: side(c)[FV][0].__setitem__(2, int(side(c)[FV][0][1]) - 1), b"node ids not ascending")
-        bad(lambda c: side(c)[FV][2].__setitem__(3, len(side(c)[1])), b"feature index")
-        bad(lambda c: side(c)[FV][2].__setitem__(len(side(c)[FV][2]) - 1, -1), b"feature index -1")
-        for field in ("desc", "kps", "fv_node", "fv_off", "fv_idx"):
-            bad(lambda c: c.null.add((who, field)), b"NULL buffer")
-        bad(lambda c: setattr(c, "counts_override", [(who, "n", -1)]), b"negative count")
-        bad(lambda c: setattr(c, "counts_override", [(who, "fv_n", -3)]), b"negative count")
-        if variant == "kf":
-            bad(lambda c: c.null.add((who, "valid")), b"NULL buffer")
+        for mutate, text in side_mutations(variant, who):
+            bad(mutate, text)
     for out in ("table", "counts", "shared", "cands"):
         bad(lambda c: c.null_args.add(out), b"NULL buffer")
     bad(lambda c: setattr(c, "nkf", -1), b"nkf=-1")
+
+
+@pytest.mark.parametrize("cand", [0, 1])
+@pytest.mark.parametrize("variant", ["frame", "kf"])
+def test_the_one_candidate_calls_check_as_the_batch_calls_do(built, variant, cand):
+    """orbm_search_by_bow / orbm_search_by_bow_kf on one candidate of the same case, NULL handle: the same refusals with the same
+    texts before anything is written."""
+    L = built.lib()
+    seen = 0
+    for who in (-1, 0):
+        for mutate, text in side_mutations(variant, who):
+            c = SingleCall(built, variant, c=cand)
+            mutate(c)
+            assert c.run() == built.ORBX_E_INVALID and text in L.orbm_last_error(), (who, text, L.orbm_last_error())
+            assert c.untouched(), (who, text)
+            seen += 1
+    assert seen == 2 * (14 if variant == "kf" else 13)
+    for out in ("table", "counts"):
+        c = SingleCall(built, variant, c=cand)
+        c.null_args.add(out)
+        assert c.run() == built.ORBX_E_INVALID and b"NULL buffer" in L.orbm_last_error()
+        assert c.untouched()
+
+
+@pytest.mark.parametrize("variant", ["frame", "kf"])
+def test_a_one_candidate_call_without_a_shared_node_is_answered_on_the_host(built, variant):
+    """ORBX_OK, a table of -1 and a count of 0 without a handle: an empty side (n == 0 or no node, either side), a candidate in
+    nodes the shared side does not have, a candidate without a usable feature."""
+    case = B.make_case("absent", variant, 5, 40, [10, 10, 10, 10], [{"n": 25, "absent": True}, {"n": 0}, {"n": 18, "valid": "zero"}])
+    calls = [SingleCall(built, variant, case, c=k) for k in range(3)]
+    for who in (-1, 0):
+        for field in ("n", "fv_n"):
+            c = SingleCall(built, variant)
+            c.counts_override = [(who, field, 0)]
+            if (who, field) == (-1, "n"):
+                c.table = np.full(0, 77, np.int32)
+            calls.append(c)
+    for c in calls:
+        assert c.run() == built.ORBX_OK, built.lib().orbm_last_error()
+        assert (c.table == -1).all() and (c.counts == 0).all()
+
+
+@pytest.mark.parametrize("variant", ["frame", "kf"])
+def test_a_one_candidate_call_fails_loudly_without_a_handle(built, variant):
+    """device work without a handle: the batch calls' status, and the outputs as they were"""
+    import torch
+    L = built.lib()
+    c = SingleCall(built, variant)
+    if torch.cuda.is_available():
+        assert c.run() == built.ORBX_E_INVALID and b"NULL handle" in L.orbm_last_error()
+    else:
+        assert c.run() == built.ORBX_E_HIP and b"no CPU path" in L.orbm_last_error()
+    assert c.untouched()
 
 
 @pytest.mark.parametrize("variant", ["frame", "kf"])

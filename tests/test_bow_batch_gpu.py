@@ -1,6 +1,6 @@
-"""orbm_search_by_bow_batch / orbm_search_by_bow_kf_batch on the GPU (include/orbm.h): the tables and counts of one batch call
-against the CPU oracle called once per candidate (tests/oracle_lib.py) and against one GPU call per candidate on a second handle.
-Both must equal the batch as arrays, with no tolerance.  Inputs: tests/bow_batch_cases.py.
+"""The four SearchByBoW entry points on the GPU (include/orbm.h): the tables and counts of one batch call, and of one one-candidate
+call per candidate on a second handle, against the CPU oracle called once per candidate (tests/oracle_lib.py).  Both must equal the
+oracle as arrays, with no tolerance.  Inputs: tests/bow_batch_cases.py.
 
 Run as a program (`python tests/test_bow_batch_gpu.py`) it is the child of the forced-host-selection test: ORBM_BOW_HOST_SELECT is
 read once per process."""
@@ -39,7 +39,8 @@ def singles(m, case):
 
 
 def check(orbx, case, ref=None):
-    """one batch call on a fresh handle == the oracle == one call per candidate on a second handle"""
+    """one batch call on a fresh handle == the oracle == one call per candidate on a second handle (both calls are one
+    implementation, so each is held against the oracle itself)"""
     want_t, want_n = ref if ref is not None else B.oracle(case)
     m, m2 = orbx.ORBmatcher(case.nnratio, case.check_ori), orbx.ORBmatcher(case.nnratio, case.check_ori)
     try:
@@ -50,6 +51,8 @@ def check(orbx, case, ref=None):
     assert got_t.shape == want_t.shape and got_t.dtype == np.int32
     assert np.array_equal(got_n, want_n), (case.name, got_n, want_n)
     assert np.array_equal(got_t, want_t), (case.name, np.argwhere(got_t != want_t)[:8])
+    assert np.array_equal(one_n, want_n), (case.name, one_n, want_n)
+    assert np.array_equal(one_t, want_t), (case.name, np.argwhere(one_t != want_t)[:8])
     assert np.array_equal(one_n, got_n) and np.array_equal(one_t, got_t), case.name
     return got_t, got_n
 
@@ -112,7 +115,7 @@ def test_contests_and_ties(orbx, variant, nnratio):
 
 
 @pytest.mark.parametrize("variant", ["frame", "kf"])
-def test_a_node_beyond_the_lanes_takes_the_single_call_path(orbx, variant):
+def test_a_node_beyond_the_lanes_takes_the_host_selection(orbx, variant):
     """frame: 4200 lane-side features in the first node, 50 in the second; candidate 0 lives in the small node only and stays in the
     launch, candidates 1 and 2 are in both.  kf: candidate 1 brings a node of more than 4096 usable features of its own."""
     case = B.fallback_case(variant)
@@ -130,7 +133,7 @@ def test_a_node_beyond_the_lanes_takes_the_single_call_path(orbx, variant):
 
 
 def test_forced_host_selection_in_a_child_process():
-    """ORBM_BOW_HOST_SELECT=1 sends every candidate through the one-candidate entry point's host selection"""
+    """ORBM_BOW_HOST_SELECT=1 sends every candidate of a batch call and every one-candidate call through the host selection"""
     env = dict(os.environ, ORBM_BOW_HOST_SELECT="1")
     r = subprocess.run([sys.executable, os.path.abspath(__file__)], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
@@ -180,11 +183,59 @@ def test_the_grid_slots_stay_as_they_were(orbx):
         for v in ("frame", "kf"):
             batch(m, B.variants_case(v))
             assert m.grid_count() == 500
-        # candidates on the one-candidate path: the grid stays as long as no side exceeds the handle's max_train (8192 here)
+        # candidates that take the host selection, sides within the handle's max_train (8192 here); with sides beyond it:
+        # test_no_search_by_bow_call_drops_the_grid
         fb = B.fallback_case("frame")
         assert max(len(fb.shared), max(len(c) for c in fb.cands)) <= 8192
         batch(m, fb)
         assert m.grid_count() == 500
+    finally:
+        m.close()
+
+
+def test_a_small_handle_takes_a_one_candidate_call_as_its_first_call_and_grows(orbx):
+    """the 220-feature candidate on a handle made for 64: the result buffer grows in the call"""
+    for variant in ("frame", "kf"):
+        case = B.variants_case(variant).first(1)
+        assert len(case.cands[0]) >= 220 and len(case.shared) > 64
+        want_t, want_n = B.oracle(case)
+        m = orbx.ORBmatcher(case.nnratio, case.check_ori, max_queries=64, max_train=64, max_pairs=64)
+        try:
+            got = single(m, case, case.cands[0])
+            again = single(m, case, case.cands[0])          # the second call goes through the grown arena
+        finally:
+            m.close()
+        for t, n in (got, again):
+            assert np.array_equal(t, want_t[0]) and n == want_n[0], variant
+
+
+def test_no_search_by_bow_call_drops_the_grid(orbx):
+    """A handle whose train capacity (64) is below every side: the calls grow the result buffer alone, so the Frame grid and what
+    GetFeaturesInArea reads from it stay -- after a one-candidate call of either variant and after a batch whose candidates take the
+    host selection."""
+    m = orbx.ORBmatcher(0.75, True, max_train=64)
+    try:
+        kps = np.zeros(60, orbx.KP_DTYPE)
+        rng = np.random.default_rng(6)
+        kps["x"], kps["y"] = rng.uniform(0, 640, 60), rng.uniform(0, 480, 60)
+        m.grid_build(kps, 0.0, 640.0, 0.0, 480.0)
+        wx, wy, wr = np.array([100, 320, 500, 630], np.float32), np.array([80, 240, 400, 470], np.float32), np.float32(150)
+        off0, idx0 = m.GetFeaturesInArea(wx, wy, wr)
+        assert m.grid_count() == 60 and off0[-1] > 10
+
+        def grid_as_it_was():
+            off, idx = m.GetFeaturesInArea(wx, wy, wr)
+            return m.grid_count() == 60 and np.array_equal(off, off0) and np.array_equal(idx, idx0)
+
+        for variant in ("frame", "kf"):
+            case = B.variants_case(variant)
+            assert len(case.shared) > 64 and len(case.cands[0]) > 64
+            _, n = single(m, case, case.cands[0])
+            assert n >= 20 and grid_as_it_was(), variant
+        fb = B.fallback_case("frame")
+        assert len(fb.shared) > 64                      # the shared side of every host-selection call is above max_train
+        _, counts = batch(m, fb)
+        assert (counts >= 20).all() and grid_as_it_was()
     finally:
         m.close()
 
@@ -200,8 +251,9 @@ def _child():
         want_t, want_n = B.oracle(case)
         m = orbx.ORBmatcher(case.nnratio, case.check_ori)
         got_t, got_n = batch(m, case)
+        one_t, one_n = singles(m, case)
         m.close()
-        if not (np.array_equal(got_t, want_t) and np.array_equal(got_n, want_n)):
+        if not (np.array_equal(got_t, want_t) and np.array_equal(got_n, want_n) and np.array_equal(one_t, want_t) and np.array_equal(one_n, want_n)):
             print("forced host selection: %s differs from the oracle" % case.name)
             return 1
         n += 1

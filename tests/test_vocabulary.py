@@ -258,7 +258,7 @@ def test_search_by_bow_equals_oracle(orbx, synth, tmp_path, nnratio, check_ori, 
 @pytest.mark.parametrize("levelsup", [0, 1, 3])
 def test_search_by_bow_node_sizes(orbx, synth, tmp_path, levelsup):
     """Node granularity from single words (a handful of features per node) to the root (every feature in one node: 16
-    chunks of 64 lanes in k_bow_select, and every key-frame feature competes for every frame feature)."""
+    chunks of 64 lanes in k_bow_select_batch, and every key-frame feature competes for every frame feature)."""
     path = str(tmp_path / "voc.txt")
     make_vocabulary(path, 10, 3, seed=9)
     v = orbx.ORBVocabulary(path)

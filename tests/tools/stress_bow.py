@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Randomised GPU-vs-oracle sweep of ORBmatcher::SearchByBoW (k_bow_select): random vocabularies, node granularity, feature
+"""Randomised GPU-vs-oracle sweep of ORBmatcher::SearchByBoW (k_bow_select_batch): random vocabularies, node granularity, feature
 counts, ratios, MapPoint masks and image pairs; match table and return value must be identical.  usage: stress_bow.py [seconds] [seed]"""
 import os, sys, tempfile, time
 import numpy as np
