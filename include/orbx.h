@@ -136,7 +136,16 @@ int orbx_extract_batch_multi(orbx_extractor *const *handles, int nhandles, const
  * Device-resident batch: all pointers are HIP device pointers on the handle's device; the work is
  * enqueued on `hip_stream` (a hipStream_t, NULL = the handle's own stream) and NOT synchronised.
  * d_status[nframes] receives an orbx_status per frame.  The input must stay valid until the stream
- * has drained (level 0 of the pyramid is the input itself).  A colour handle reads d_images in the conversion kernel only: level 0
+ * has drained (level 0 of the pyramid is the input itself).
+ * Geometry: frame k starts at d_images + k*frame_stride, its rows are row_stride bytes apart (row_stride >= width).  d_images,
+ * row_stride and frame_stride may have ANY byte alignment (a region of a larger device image can be handed over as it is; bases
+ * and strides that are all multiples of 4 take slightly faster loads), frame_stride may exceed 32 bits, and the buffer may lie
+ * anywhere in the address space.  The pyramid kernels read nothing below the aligned dword that holds the call's first pixel and
+ * nothing above the one that holds its last (padding between rows and frames may be read; its content never reaches a result);
+ * nothing is written.
+ * Two limits: row_stride < 2^23 (8 MiB) and height * row_stride < 2^31 (one frame below 2 GiB), else ORBX_E_SHAPE and nothing
+ * is launched.  The outputs need the natural alignment of their element (4 bytes; 8 for d_descriptors).
+ * A colour handle reads d_images in the conversion kernel only: level 0
  * is then the handle's own grey plane, and row_stride (of the colour rows) is what must stay below 8 MiB, one colour frame below 2 GiB
  * (else ORBX_E_SHAPE).
  */

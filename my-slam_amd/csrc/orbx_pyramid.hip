@@ -63,6 +63,18 @@ __global__ __launch_bounds__(256) void k_resize_area2(
 // 6, and the horizontal blend is one v_dot2_u32_u16.  CHECK guards the last bytes of a caller-owned
 // level-0 buffer, which has no slack behind it.
 // -------------------------------------------------------------------------------------------------
+// bytes from the dword-aligned base of the last frame to the end of the caller's buffer, for the 32-bit guards of the CHECK kernels:
+// the last frame of a sub-batch that is not the call's last has every later frame behind it, possibly 4 GiB and more
+// (no test reaches the saturation: it takes sub-batches and more than 4 GiB of frames behind one of them; it rests on reading)
+__device__ __forceinline__ uint32_t rs_endoff(const uint8_t *src_end, const uint8_t *Sa)
+{
+    // uniform, and saturated on the scalar unit: all ones when the high word is set (left to the compiler, any form of this becomes a
+    // 64-bit unsigned compare, which only the vector unit has)
+    const uint64_t e = (uint64_t)(src_end - Sa);
+    uint32_t any_hi;
+    asm("s_min_u32 %0, %1, 1" : "=s"(any_hi) : "s"((uint32_t)(e >> 32)) : "scc");
+    return (uint32_t)e | (0u - any_hi);
+}
 template <bool CHECK>
 __global__ __launch_bounds__(RESIZE_THREADS) void k_resize_linear_4x4(
     const uint8_t *__restrict__ src, int sw, int sh, int sstride, long long sframe,
@@ -98,8 +110,13 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_resize_linear_4x4(
     // phase 1: issue every load of the 4x4 block (8 row-table words, 24 source dwords) before any use,
     // so one memory round trip covers the whole block instead of one per row.  Addresses are the uniform frame base
     // plus an unsigned 32-bit byte offset (one frame is below 2 GiB), which keeps the address arithmetic 32-bit.
-    const uint32_t s_lo = (uint32_t)(uintptr_t)S;
-    const uint32_t endoff = CHECK ? (uint32_t)(src_end - S) : 0u;   // only meaningful (and only used) for the last frame
+    // A caller-owned level 0 may start at any byte: the aligned dwords are addressed from the frame base rounded DOWN to a dword
+    // (Sa, uniform), so the lane offset never goes below zero (off - shift did, for the first block of an unaligned frame).
+    // CHECK == false only ever sees the handle's own levels and input block (frame bases are multiples of 256): nothing is taken off
+    // there and the arithmetic is what it always was.
+    const uint32_t s_mis = CHECK ? (uint32_t)(uintptr_t)S & 3u : 0u;
+    const uint8_t *Sa = S - s_mis;
+    const uint32_t endoff = CHECK ? rs_endoff(src_end, Sa) : 0u;   // only meaningful (and only used) for the last frame
     int b0v[4], b1v[4];
     uint32_t sh8[4][2], wv[4][2][3];
     // the row tables of the block's four rows in two 16-byte loads (y4 is a multiple of 4; the planner pads both tables to a
@@ -120,15 +137,18 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_resize_linear_4x4(
 #pragma unroll
         for (int rr = 0; rr < 2; rr++) {
             const uint32_t off = (uint32_t)(__mul24(rr ? sy1 : sy0, sstride) + base);   // 24-bit multiply is full rate
-            sh8[r][rr] = (s_lo + off) & 3u;
-            const uint32_t offa = off - sh8[r][rr];
+            const uint32_t t = (CHECK ? s_mis : (uint32_t)(uintptr_t)S) + off;
+            sh8[r][rr] = t & 3u;
+            const uint32_t offa = (CHECK ? t : off) - sh8[r][rr];   // from Sa
             if (CHECK && blockIdx.z == gridDim.z - 1) {   // only the last frame can end at the end of the caller's buffer
-                const uint32_t *q = reinterpret_cast<const uint32_t *>(S + offa);
+                // a dword is read whenever its FIRST byte lies before the end (the end need not be a multiple of 4, and an aligned
+                // dword never leaves the page of a valid byte)
+                const uint32_t *q = reinterpret_cast<const uint32_t *>(Sa + offa);
                 wv[r][rr][0] = q[0];
-                wv[r][rr][1] = (offa + 8u <= endoff) ? q[1] : 0u;
-                wv[r][rr][2] = (offa + 12u <= endoff) ? q[2] : 0u;
+                wv[r][rr][1] = (offa + 4u < endoff) ? q[1] : 0u;
+                wv[r][rr][2] = (offa + 8u < endoff) ? q[2] : 0u;
             } else {
-                const U3a4 q = *reinterpret_cast<const U3a4 *>(S + offa);
+                const U3a4 q = *reinterpret_cast<const U3a4 *>(Sa + offa);
                 wv[r][rr][0] = q.x; wv[r][rr][1] = q.y; wv[r][rr][2] = q.z;
             }
         }
@@ -199,25 +219,29 @@ __device__ __forceinline__ rs_gptr rs_scalar_ptr(const uint8_t *p)     // a wave
 }
 template <int SRC, bool CHECK>
 __device__ __forceinline__ void resize_block6(const uint8_t *S, int pitch, int row0, int rmax, int col, const uint32_t sel[4], const uint32_t al[4],
-                                              const int4 syv, const uint4 bwv, uint32_t endoff, bool last_frame, uint32_t out[4])
+                                              const int4 syv, const uint4 bwv, uint32_t s_mis, uint32_t endoff, bool last_frame, uint32_t out[4])
 {
     uint32_t HH[6][4];
     {
         uint32_t wv[6][3], sh8[6];
         // row j of the block = source row min(row0 + j, rmax): one add and one min per row on the byte offset
         const uint32_t off0 = (uint32_t)(__mul24(row0, pitch) + col), offmax = (uint32_t)(__mul24(rmax, pitch) + col);
+        // SRC == 0: S is the frame base rounded down to a dword and s_mis what was taken off (0 for the handle's own levels), so
+        // the lane offset of an aligned dword never goes below zero; endoff counts from S
         const rs_gptr Sg = rs_scalar_ptr(S);
 #pragma unroll
         for (int j = 0; j < 6; j++) {
             const uint32_t off = min(off0 + (uint32_t)(j * pitch), offmax);
             if (SRC == 0) {
-                sh8[j] = ((uint32_t)(uintptr_t)S + off) & 3u;
-                const uint32_t offa = off - sh8[j];
+                const uint32_t t = (CHECK ? s_mis : (uint32_t)(uintptr_t)S) + off;     // CHECK == false: an aligned level of the handle, s_mis == 0
+                sh8[j] = t & 3u;
+                const uint32_t offa = (CHECK ? t : off) - sh8[j];
                 if (CHECK && last_frame) {     // only the last frame can end at the end of the caller's buffer
+                    // a dword is read whenever its FIRST byte lies before the end (see k_resize_linear_4x4)
                     const uint32_t *q = reinterpret_cast<const uint32_t *>(S + offa);
                     wv[j][0] = q[0];
-                    wv[j][1] = (offa + 8u <= endoff) ? q[1] : 0u;
-                    wv[j][2] = (offa + 12u <= endoff) ? q[2] : 0u;
+                    wv[j][1] = (offa + 4u < endoff) ? q[1] : 0u;
+                    wv[j][2] = (offa + 8u < endoff) ? q[2] : 0u;
                 } else {
                     // (scalar frame base) + (32-bit lane offset): the global_load saddr form, no 64-bit vector arithmetic
                     const rs_U3a4 q = *(const __attribute__((address_space(1))) rs_U3a4 *)(Sg + offa);
@@ -285,8 +309,10 @@ __global__ __launch_bounds__(RESIZE_THREADS) void k_resize_linear_4x4s(
         if (x4 + i >= dw) { sx[i] = sx[0]; al[i] = al[0]; }
 #pragma unroll
     for (int i = 0; i < 4; i++) sel[i] = 0x0c010c00u + (uint32_t)(sx[i] - sx[0]) * 0x00010001u;
-    const uint32_t endoff = CHECK ? (uint32_t)(src_end - S) : 0u;
-    resize_block6<0, CHECK>(S, sstride, max(syv.x, 0), sh - 1, sx[0], sel, al, syv, bwv, endoff, CHECK && blockIdx.z == gridDim.z - 1, out);
+    const uint32_t s_mis = CHECK ? (uint32_t)(uintptr_t)S & 3u : 0u;  // a caller-owned level 0 may start at any byte (CHECK: see k_resize_linear_4x4)
+    const uint8_t *Sa = S - s_mis;
+    const uint32_t endoff = CHECK ? rs_endoff(src_end, Sa) : 0u;
+    resize_block6<0, CHECK>(Sa, sstride, max(syv.x, 0), sh - 1, sx[0], sel, al, syv, bwv, s_mis, endoff, CHECK && blockIdx.z == gridDim.z - 1, out);
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const int y = y4 + r;
@@ -568,7 +594,7 @@ __device__ __forceinline__ void tile_level(const TileArgs &A, int l, const int4 
         sel[1] = 0x0c010c00u + (uint32_t)(a.y - a.x) * 0x00010001u;
         sel[2] = 0x0c010c00u + (uint32_t)(a.z - a.x) * 0x00010001u;
         sel[3] = 0x0c010c00u + (uint32_t)(a.w - a.x) * 0x00010001u;
-        resize_block6<SRC, false>(S, ps, c.x, rmax, a.x, sel, al, make_int4(c.x, c.y, c.z, c.w), make_uint4((uint32_t)d.x, (uint32_t)d.y, (uint32_t)d.z, (uint32_t)d.w), 0u, false, out);
+        resize_block6<SRC, false>(S, ps, c.x, rmax, a.x, sel, al, make_int4(c.x, c.y, c.z, c.w), make_uint4((uint32_t)d.x, (uint32_t)d.y, (uint32_t)d.z, (uint32_t)d.w), 0u, 0u, false, out);
         uint32_t *dp = reinterpret_cast<uint32_t *>(dbuf + (uint32_t)(__mul24(4 * by, pd) + 4 * bx));
 #pragma unroll
         for (int r = 0; r < 4; r++) dp[r * (pd >> 2)] = out[r];
