@@ -18,6 +18,8 @@
  *     queried, and a repeated query id accumulates counts;
  *   - Deviation: the reference never initialises mLoopScore / mRelocScore (src/KeyFrame.cc:30-42), so reading one that
  *     was never written is undefined there.  Here it reads 0.0f.
+ *   - Deviation: a word id outside [0, nwords) indexes past mvInvertedFile in the reference (src/KeyFrameDatabase.cc:45,
+ *     :56, :88, :209): undefined there.  Here every entry point that takes a BowVector returns ORBX_E_INVALID for it.
  *   - Deviation: orbk_add of an id that is already in the database returns ORBX_E_INVALID (the reference would list the
  *     keyframe twice in the inverted file; it never does this itself).  orbk_erase of an absent id is a no-op.
  *
