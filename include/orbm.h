@@ -669,6 +669,86 @@ int orbm_pose_optimization_batch_device(orbm_matcher *m, int n_problems, const i
                                         const orbm_pose_camera *d_cams, float *d_Tcw, uint8_t *d_outlier, int32_t *d_n_good,
                                         void *hip_stream);
 
+/*
+ * ---- ORBmatcher::Fuse for ALL target key frames of LocalMapping::SearchInNeighbors in one call ----
+ * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:456-536) calls Fuse(pKFi, vpMapPointMatches) once per target key frame
+ * (:487-492) and once more with every MapPoint of those key frames against mpCurrentKeyFrame (:516).  orbm_fuse_views runs
+ * src/ORBmatcher.cc:852-952 for every (view, MapPoint) slot on ONE snapshot: projection, gates, PredictScale, the window, the octave
+ * window, the chi-square gate and the Hamming selection, without returning to the host in between.  What happens to a fused
+ * point (:954-970) is object-graph work and stays with the caller, who replays it in the reference's order; of everything the
+ * search reads, only a MapPoint's descriptor can change between two key frames of the loop (MapPoint::Replace ends with
+ * ComputeDistinctiveDescriptors on the survivor, src/MapPoint.cc:177-215), and only the Hamming selection (:940-949) reads it, so
+ * the caller re-selects on the host for the slots whose live descriptor differs from the snapshot's (host/ORBmatcher.h, DESIGN.md
+ * section 17).
+ *
+ * orbm_fuse_view is what the loop reads of a key frame beyond its features: Rcw / tcw / Ow = GetRotation(), GetTranslation(),
+ * GetCameraCenter(), the calibration, mbf, bounds = (float) mnMinX, mnMaxX, mnMinY, mnMaxY, log_scale_factor = mfLogScaleFactor,
+ * nlevels = mnScaleLevels, scale_factors = mvScaleFactors, inv_level_sigma2 = mvInvLevelSigma2 (entries past nlevels are not
+ * read) and grid as for orbm_grid_build_kf.  The views' features are concatenated: view v owns off[v] .. off[v+1]-1 of kps_un
+ * (mvKeysUn), u_right (mvuRight) and desc_kf (32 bytes each).
+ *   per slot (v, i), slot = v*n_mp + i:  skip = !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF_v) (:846-850)
+ *   per MapPoint i:  xw = GetWorldPos(), normal = GetNormal(), mf_max / mf_min = the raw mfMaxDistance / mfMinDistance (the 1.2f
+ *                    and 0.8f of the two getters are applied here, PredictScale divides the raw mfMaxDistance), mp_desc =
+ *                    GetDescriptor()
+ *   status[slot]     the line that decided the slot (orbm_fuse_status)
+ *   best_idx[slot]   ORBM_FUSE_MATCH: the feature inside view v the point is fused with (bestIdx at :952); -1 otherwise
+ *   best_dist[slot]  the smallest distance among the candidates that survived the octave window and the gate, also when it is
+ *                    above TH_LOW; 256 when there is none (and for a slot that was not searched)
+ *   proj_u, proj_v, proj_ur, pred_level = u, v, ur, nPredictedLevel of the slots that reached :887 (MATCH and NO_MATCH), zeros
+ *                    for every other slot
+ *   nfused[v]        the slots of view v with ORBM_FUSE_MATCH
+ * The first candidate in the reference's order (cell column, cell row, push_back order) wins a tie.
+ *
+ * Arithmetic: :852-890 operation by operation under the conventions of DESIGN.md section 2, without contraction: Rcw*p+tcw through
+ * cv::gemm's small-matrix path, invz = 1/z a float division, x = Pc0*invz and then u = fx*x+cx (the order of :860-864, not
+ * isInFrustum's), ur = u - bf*invz, cv::norm and Mat::dot accumulated in double, PO.dot(Pn) compared with 0.5*dist3D in double,
+ * PredictScale as float division, correctly rounded logf, float division, ceil (orbm_frustum's, same code), radius =
+ * th*scale_factors[level].  The reference's quirks are kept: z == +-0 passes :856 and fails :867, a NaN u or v fails
+ * KeyFrame::IsInImage ([min, max) on both axes; unlike isInFrustum), a NaN normal passes :884.  ORBM_FUSE_UNDEFINED as
+ * ORBM_FRUSTUM_UNDEFINED.  A key point whose octave lies outside its view's levels causes no out-of-range read: it is clamped
+ * into [0, ORBX_MAX_LEVELS) where mvInvLevelSigma2 is indexed, as orbm_fuse does (the octave window has dropped every such key
+ * point but octave -1 next to level 0, which is gated with level 0's sigma).
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: negative counts, NULL buffers where the count is positive, off
+ * not monotone from 0, nlevels outside [1, ORBX_MAX_LEVELS], grid cell sizes that are not positive; ORBX_E_CAPACITY: nviews *
+ * n_mp > 2^28 or more than 65535 views).  nviews == 0 or n_mp == 0 is ORBX_OK and touches nothing, the handle and the outputs
+ * included.  A call with every skip set, or with every view empty, is answered on the host (the same arithmetic) and needs no
+ * handle; every other call needs the GPU, and a NULL handle behaves as in orbm_create_new_map_points.  A failed call leaves
+ * every output as it was.  The call runs on the handle's stream through its staging arena: one upload, the grid launch (one
+ * workgroup per view) and the search launch with nothing returning to the host in between, one download, one synchronisation.
+ * It grows the handle as needed and keeps the views' grids in storage of its own: the two grid slots of the handle are left as
+ * found (orbm_grid_count() and a following windowed search are unchanged by it).  The result for a view does not depend on the
+ * views around it, on its position in the batch or on the run.
+ */
+typedef enum {
+    ORBM_FUSE_MATCH = 0,       /* reached :952 with bestDist <= TH_LOW; best_idx >= 0 */
+    ORBM_FUSE_SKIPPED = 1,     /* the caller's skip: :846-850 */
+    ORBM_FUSE_BEHIND = 2,      /* :856 */
+    ORBM_FUSE_OUT_IMAGE = 3,   /* :867, KeyFrame::IsInImage: [min, max) on both axes; a NaN u or v FAILS here (unlike isInFrustum) */
+    ORBM_FUSE_DISTANCE = 4,    /* :878 */
+    ORBM_FUSE_VIEW_ANGLE = 5,  /* :884: PO.dot(Pn) (double) < 0.5 * dist3D (double); NaN passes */
+    ORBM_FUSE_UNDEFINED = 6,   /* the int conversion in PredictScale, as ORBM_FRUSTUM_UNDEFINED */
+    ORBM_FUSE_NO_MATCH = 7     /* searched: empty window (:894), every member dropped by :911 / :925 / :936, or bestDist > TH_LOW */
+} orbm_fuse_status;
+typedef struct {
+    float Rcw[9], tcw[3], Ow[3];                /* GetRotation() (row-major), GetTranslation(), GetCameraCenter() */
+    float fx, fy, cx, cy, mbf;
+    float bounds[4];                            /* (float) mnMinX, mnMaxX, mnMinY, mnMaxY */
+    float log_scale_factor;                     /* mfLogScaleFactor */
+    int32_t nlevels;                            /* mnScaleLevels */
+    float scale_factors[ORBX_MAX_LEVELS];       /* mvScaleFactors */
+    float inv_level_sigma2[ORBX_MAX_LEVELS];    /* mvInvLevelSigma2 */
+    orbm_kf_grid grid;                          /* as for orbm_grid_build_kf */
+} orbm_fuse_view;
+int orbm_fuse_views(orbm_matcher *m, const orbm_fuse_view *views, int nviews, const int32_t *off,
+                    const orbx_keypoint *kps_un, const float *u_right, const uint8_t *desc_kf,
+                    int n_mp, const uint8_t *skip,
+                    const float *xw, const float *normal, const float *mf_max, const float *mf_min,
+                    const uint8_t *mp_desc, float th,
+                    uint8_t *status, int32_t *best_idx, int32_t *best_dist,
+                    float *proj_u, float *proj_v, float *proj_ur, int32_t *pred_level,
+                    int32_t *nfused);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

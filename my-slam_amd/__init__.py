@@ -32,6 +32,17 @@ VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4",
                        ("cy", "<f4"), ("mbf", "<f4"), ("bounds", "<f4", (4,)), ("log_scale_factor", "<f4"), ("nlevels", "<i4"),
                        ("scale_factors", "<f4", (ORBX_MAX_LEVELS,))])
 assert VIEW_DTYPE.itemsize == 168
+# orbm_fuse_view (include/orbm.h): what ORBmatcher::Fuse reads of a target key frame beyond its features; grid = orbm_kf_grid
+KF_GRID_DTYPE = np.dtype([("assign_min_x", "<f4"), ("assign_min_y", "<f4"), ("inv_w", "<f4"), ("inv_h", "<f4"), ("query_min_x", "<f4"),
+                          ("query_min_y", "<f4")])
+FUSE_VIEW_DTYPE = np.dtype([("Rcw", "<f4", (9,)), ("tcw", "<f4", (3,)), ("Ow", "<f4", (3,)), ("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"),
+                            ("cy", "<f4"), ("mbf", "<f4"), ("bounds", "<f4", (4,)), ("log_scale_factor", "<f4"), ("nlevels", "<i4"),
+                            ("scale_factors", "<f4", (ORBX_MAX_LEVELS,)), ("inv_level_sigma2", "<f4", (ORBX_MAX_LEVELS,)),
+                            ("grid", KF_GRID_DTYPE)])
+assert FUSE_VIEW_DTYPE.itemsize == 256      # sizeof(orbm_fuse_view): tests/test_fuse_views_cxx.py compares it with the C struct
+# orbm_fuse_status (include/orbm.h)
+(ORBM_FUSE_MATCH, ORBM_FUSE_SKIPPED, ORBM_FUSE_BEHIND, ORBM_FUSE_OUT_IMAGE, ORBM_FUSE_DISTANCE, ORBM_FUSE_VIEW_ANGLE, ORBM_FUSE_UNDEFINED,
+ ORBM_FUSE_NO_MATCH) = range(8)
 # orbm_pose_camera (include/orbm.h): the calibration of one problem of pose_optimization_batch
 POSE_CAM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4")])
 assert POSE_CAM_DTYPE.itemsize == 20
@@ -269,6 +280,8 @@ def _bind_matcher(L):
     L.orbm_search_by_bow_batch.argtypes = [vp, vp, C.c_int, vp, f, C.c_int, vp, vp]
     L.orbm_search_by_bow_kf_batch.argtypes = [vp, vp, vp, C.c_int, f, C.c_int, vp, vp]
     L.orbm_search_by_bow_batch.restype = L.orbm_search_by_bow_kf_batch.restype = C.c_int
+    L.orbm_fuse_views.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp, vp, vp, f, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbm_fuse_views.restype = C.c_int
     for name in ("orbm_reserve", "orbm_grid_build_kf", "orbm_sim3_decompose", "orbm_sim3_relative", "orbm_project_points_kf",
                  "orbm_project_points_sim3", "orbm_search_by_projection_sim3", "orbm_search_by_bow_kf", "orbm_search_for_triangulation",
                  "orbm_fuse", "orbm_fuse_sim3", "orbm_search_by_sim3", "orbm_search_by_bow"):
@@ -680,6 +693,35 @@ class ORBmatcher:
                                                 _p(cams2), _p(F12), nv, _p(off2), _p(k2), _p(x2), _p(u2), _p(z2), _p(d2), _p(h2), _p(fvo), _p(n2n), _p(n2o),
                                                 _p(n2i), 1 if only_stereo else 0, _p(m12), _p(status), _p(x3d), _p(nm)))
         return m12, status, x3d, nm
+
+    def fuse_views(self, views, off, kps_un, u_right, desc_kf, skip, xw, normal, mf_max, mf_min, mp_desc, th=3.0):
+        """ORBmatcher::Fuse(pKF, vpMapPoints, th) (src/ORBmatcher.cc:825-952) for all target key frames of
+        LocalMapping::SearchInNeighbors in one call, on one snapshot.  views: FUSE_VIEW_DTYPE records; the views' features
+        concatenated, view v owning off[v]:off[v+1] of kps_un / u_right / desc_kf; skip uint8 [nviews, n_mp]; xw, normal, mf_max,
+        mf_min (the raw mfMax / MinDistance) and mp_desc per MapPoint.  Returns (status uint8, best_idx int32, best_dist int32,
+        proj_u, proj_v, proj_ur float32, pred_level int32, all [nviews, n_mp], nfused int32 [nviews]): the orbm_fuse_status of
+        every slot, the feature inside its view a matched slot is fused with (-1 otherwise), and the projection of the slots that
+        were searched (status MATCH or NO_MATCH)."""
+        f32 = lambda a: np.ascontiguousarray(a, np.float32)
+        views = np.ascontiguousarray(views, FUSE_VIEW_DTYPE).reshape(-1)
+        off = np.ascontiguousarray(off, np.int32).reshape(-1)
+        kps = np.ascontiguousarray(kps_un, KP_DTYPE).reshape(-1)
+        ur, dk = f32(u_right).reshape(-1), np.ascontiguousarray(desc_kf, np.uint8).reshape(-1, 32)
+        xw, normal, mx, mn = f32(xw).reshape(-1, 3), f32(normal).reshape(-1, 3), f32(mf_max).reshape(-1), f32(mf_min).reshape(-1)
+        md = np.ascontiguousarray(mp_desc, np.uint8).reshape(-1, 32)
+        nv, n = len(views), len(xw)
+        skip = np.ascontiguousarray(skip, np.uint8).reshape(-1)
+        if len(off) != nv + 1 or not (len(kps) == len(ur) == len(dk) == int(off[-1])) or not (len(normal) == len(mx) == len(mn) == len(md) == n) \
+                or len(skip) != nv * n:
+            raise OrbxError(ORBX_E_INVALID, "array lengths disagree: %d views, off %s, %d / %d / %d features, %d MapPoints, %d skip flags"
+                            % (nv, off[-1:], len(kps), len(ur), len(dk), n, len(skip)))
+        status = np.full((nv, n), 255, np.uint8)
+        bi, bd, lv = np.full((nv, n), -1, np.int32), np.full((nv, n), 256, np.int32), np.zeros((nv, n), np.int32)
+        pu, pv, pr = np.zeros((nv, n), np.float32), np.zeros((nv, n), np.float32), np.zeros((nv, n), np.float32)
+        nf = np.zeros(nv, np.int32)
+        _mchk(self.L.orbm_fuse_views(self.h, _p(views), nv, _p(off), _p(kps), _p(ur), _p(dk), n, _p(skip), _p(xw), _p(normal), _p(mx), _p(mn),
+                                     _p(md), C.c_float(th), _p(status), _p(bi), _p(bd), _p(pu), _p(pv), _p(pr), _p(lv), _p(nf)))
+        return status, bi, bd, pu, pv, pr, lv, nf
 
     @staticmethod
     def _frustum_inputs(view, skip, xw, normal, mf_max, mf_min):

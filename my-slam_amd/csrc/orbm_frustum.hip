@@ -11,20 +11,11 @@
 // (src/MapPoint.cc:402-417) as float division, logf, float division, ceil.  logf is the correctly rounded fp32 logarithm: the
 // fp64 log rounded to float once.  tests/frustum_oracle.py is the same sequence of operations in numpy.
 #include "orbm_internal.h"
+#include "orbm_project.h"
 
 #define FRU_THREADS 64
 
-// cv::gemm's small-matrix path for one row of mRcw*P+mtcw (orbm_internal.h gemm_row)
-__device__ __forceinline__ float fru_gemm_row(const float *__restrict__ R, float t, float x, float y, float z)
-{
-    const float t0 = __fadd_rn(__fadd_rn(__fmul_rn(R[0], x), __fmul_rn(R[1], y)), __fmul_rn(R[2], z));
-    return (float)((double)t0 + (double)t);
-}
-// Mat::dot / the squares of cv::norm: float products are exact in double, the sum is double
-__device__ __forceinline__ double fru_dot3(float a0, float a1, float a2, float b0, float b1, float b2)
-{
-    return ((double)a0 * (double)b0 + (double)a1 * (double)b1) + (double)a2 * (double)b2;
-}
+// fru_gemm_row, fru_dot3, fru_predict_scale: orbm_project.h (shared with orbm_fuse.hip)
 
 struct FruOut { float u, v, ur, view_cos; int level; };
 
@@ -49,14 +40,9 @@ __device__ __forceinline__ int fru_one(const orbm_frame_view *__restrict__ V, fl
     if (dist < min_distance || dist > max_distance) return ORBM_FRUSTUM_DISTANCE;       // :302
     const float view_cos = (float)(fru_dot3(POx, POy, POz, Nx, Ny, Nz) / (double)dist); // :308
     if (view_cos < cos_limit) return ORBM_FRUSTUM_VIEW_COS;                             // :310 (NaN passes)
-    // MapPoint::PredictScale, src/MapPoint.cc:402-417
-    const float ratio = __fdiv_rn(mf_max, dist);                                        // :407
-    const float lg = (float)log((double)ratio);                                         // logf, correctly rounded
-    const float c = ceilf(__fdiv_rn(lg, V->log_scale_factor));                          // :410
-    if (!(c >= -2147483648.0f && c < 2147483648.0f)) return ORBM_FRUSTUM_UNDEFINED;     // no int holds it (NaN and +-inf included)
-    int level = (int)c;
-    if (level < 0) level = 0;                                                           // :411-414
-    else if (level >= V->nlevels) level = V->nlevels - 1;
+    // MapPoint::PredictScale, src/MapPoint.cc:402-417 (orbm_project.h)
+    int level;
+    if (!fru_predict_scale(mf_max, dist, V->log_scale_factor, V->nlevels, level)) return ORBM_FRUSTUM_UNDEFINED;
     o.u = u; o.v = v; o.ur = __fsub_rn(u, __fmul_rn(V->mbf, invz)); o.view_cos = view_cos; o.level = level;   // :318-322
     return ORBM_FRUSTUM_IN_VIEW;
 }

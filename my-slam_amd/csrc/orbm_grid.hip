@@ -14,9 +14,12 @@
 // -------------------------------------------------------------------------------------------------
 // k_grid_build: one 1024-thread workgroup.  Count per cell (LDS atomics) -> scan -> scatter -> each
 // cell's short list is sorted ascending, which restores push_back order (keypoint index order).
+// grid_build_body is that workgroup's work, shared with k_grid_build_views (one workgroup per key frame of orbm_fuse_views), so the
+// push_back order exists once.  LDS: 2 x 3072 + 1 counters and 17 wave sums = 24.1 KB per workgroup; a CU holds two 1024-thread
+// workgroups (32 waves), 48 KB of its 160 KB.
 // -------------------------------------------------------------------------------------------------
 #define G_THREADS 1024
-__global__ __launch_bounds__(G_THREADS) void k_grid_build(OrbmGrid g, const orbx_keypoint *__restrict__ kps)
+__device__ __forceinline__ void grid_build_body(const OrbmGrid &g, const orbx_keypoint *__restrict__ kps)
 {
     __shared__ int cnt[ORBM_GRID_CELLS];
     __shared__ int start[ORBM_GRID_CELLS + 1];
@@ -80,6 +83,19 @@ __global__ __launch_bounds__(G_THREADS) void k_grid_build(OrbmGrid g, const orbx
             g.items[j + 1] = v;
         }
     }
+}
+__global__ __launch_bounds__(G_THREADS) void k_grid_build(OrbmGrid g, const orbx_keypoint *__restrict__ kps) { grid_build_body(g, kps); }
+// one workgroup per view: view blockIdx.x owns grids[blockIdx.x] (its slices of the feature arrays, of items and of cell_start) and the
+// keypoints kps + off[blockIdx.x]
+__global__ __launch_bounds__(G_THREADS) void k_grid_build_views(const OrbmGrid *__restrict__ grids, const int32_t *__restrict__ off,
+                                                               const orbx_keypoint *__restrict__ kps)
+{
+    const OrbmGrid g = grids[blockIdx.x];
+    grid_build_body(g, kps + off[blockIdx.x]);
+}
+void orbm_grid_build_views_launch(const OrbmGrid *d_grids, const int32_t *d_off, const orbx_keypoint *d_kps, int nviews, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_grid_build_views, dim3(nviews), dim3(G_THREADS), 0, s, d_grids, d_off, d_kps);
 }
 
 // one wave per window; MODE 0 = count, 1 = write the list at off[q] in the reference's order

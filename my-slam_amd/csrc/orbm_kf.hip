@@ -137,36 +137,12 @@ __global__ __launch_bounds__(M_THREADS) void k_search_kf(OrbmGrid g, const uint8
     const float ur = gate.on ? gate.q_ur[q] : 0.f;
     const uint4 *Q = reinterpret_cast<const uint4 *>(qdesc) + 2 * (long long)q;
     const uint4 q0 = Q[0], q1 = Q[1];
-    uint32_t bp = 0xFFFFFFFFu;
-    int bidx = -1;
-    // the window itself has no level test (src/KeyFrame.cc:569-606): positions count every window member, as vIndices does, and the
-    // octave window and the chi-square gate drop candidates afterwards
-    window_walk(g, x, y, r, lane, [&](int i) { return in_window(g, i, x, y, r, -1, -1); },
-                [&](int i, int pos) {
-                    const int oct = g.koct[i];
-                    bool use = !(oct < lv - 1 || oct > lv);
-                    if (use && gate.on) {
-                        const float ex = __fsub_rn(x, g.kx[i]), ey = __fsub_rn(y, g.ky[i]);
-                        const float kr = gate.t_uright[i];
-                        const float inv = gate.inv_sigma2[min(max(oct, 0), ORBX_MAX_LEVELS - 1)];
-                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
-                        if (kr >= 0) {
-                            const float er = __fsub_rn(ur, kr);
-                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
-                            use = !((double)__fmul_rn(e2, inv) > 7.8);          // :925
-                        } else {
-                            use = !((double)__fmul_rn(e2, inv) > 5.99);         // :936
-                        }
-                    }
-                    if (use) {
-                        const uint4 *Tj = reinterpret_cast<const uint4 *>(tdesc) + 2 * (long long)i;
-                        const int d = hamming256(q0, q1, Tj[0], Tj[1]);
-                        const uint32_t p = ((uint32_t)d << 22) | (uint32_t)min(pos, 0x3FFFFF);
-                        if (p < bp) { bp = p; bidx = i; }
-                    }
-                });
+    int bidx;
+    // window, octave window, gate, distance and the packed key: kf_window_search (orbm_window.h), shared with k_fuse_views
+    const uint32_t bp = kf_window_search(g, x, y, r, lv, gate.on != 0, ur, gate.t_uright, [&](int l) { return gate.inv_sigma2[l]; }, q0, q1,
+                                         tdesc, lane, bidx);
     const uint32_t B = wave_min_u32(bp);
-    if (B == 0xFFFFFFFFu) {
+    if (B == KF_KEY_NONE) {
         if (lane == 0) { best_idx[q] = -1; best_d[q] = 256; }
     } else if (bp == B) {                       // positions are unique: one lane holds the winner
         best_idx[q] = bidx; best_d[q] = (int)(B >> 22);

@@ -54,3 +54,45 @@ __device__ __forceinline__ int window_walk(const OrbmGrid &g, float x, float y, 
     }
     return n;
 }
+
+#define KF_KEY_NONE 0xFFFFFFFFu
+// The stateless key-frame search of one window by one wave (k_search_kf in orbm_kf.hip, k_fuse_views in orbm_fuse.hip): KeyFrame::
+// GetFeaturesInArea(x, y, r) in the reference's order, the octave window [lv - 1, lv] (src/ORBmatcher.cc:380, :911, :1067, :1207),
+// with `gated` Fuse's chi-square gate (:914-938; ur = the query's u - bf*invz, t_uright = mvuRight, inv_sigma2(octave) =
+// mvInvLevelSigma2 with the octave clamped into [0, ORBX_MAX_LEVELS)), then the Hamming distance.  The window itself has no level test
+// (src/KeyFrame.cc:569-606): positions count every window member, as vIndices does, and the octave window and the gate drop candidates
+// afterwards.  Returns this lane's smallest key = distance << 22 | position (KF_KEY_NONE: none) and its feature in bidx; the wave's
+// minimum over the keys is the reference's strict '<' scan: the first candidate wins a tie.  Every lane of the wave must call it.
+template <class InvSigma2>
+__device__ __forceinline__ uint32_t kf_window_search(const OrbmGrid &g, float x, float y, float r, int lv, bool gated, float ur,
+                                                     const float *__restrict__ t_uright, InvSigma2 inv_sigma2, const uint4 &q0,
+                                                     const uint4 &q1, const uint8_t *__restrict__ tdesc, int lane, int &bidx)
+{
+    uint32_t bp = KF_KEY_NONE;
+    bidx = -1;
+    window_walk(g, x, y, r, lane, [&](int i) { return in_window(g, i, x, y, r, -1, -1); },
+                [&](int i, int pos) {
+                    const int oct = g.koct[i];
+                    bool use = !(oct < lv - 1 || oct > lv);
+                    if (use && gated) {
+                        const float ex = __fsub_rn(x, g.kx[i]), ey = __fsub_rn(y, g.ky[i]);
+                        const float kr = t_uright[i];
+                        const float inv = inv_sigma2(min(max(oct, 0), ORBX_MAX_LEVELS - 1));
+                        float e2 = __fadd_rn(__fmul_rn(ex, ex), __fmul_rn(ey, ey));
+                        if (kr >= 0) {
+                            const float er = __fsub_rn(ur, kr);
+                            e2 = __fadd_rn(e2, __fmul_rn(er, er));
+                            use = !((double)__fmul_rn(e2, inv) > 7.8);          // :925
+                        } else {
+                            use = !((double)__fmul_rn(e2, inv) > 5.99);         // :936
+                        }
+                    }
+                    if (use) {
+                        const uint4 *Tj = reinterpret_cast<const uint4 *>(tdesc) + 2 * (long long)i;
+                        const int d = hamming256(q0, q1, Tj[0], Tj[1]);
+                        const uint32_t p = ((uint32_t)d << 22) | (uint32_t)min(pos, 0x3FFFFF);
+                        if (p < bp) { bp = p; bidx = i; }
+                    }
+                });
+    return bp;
+}

@@ -129,3 +129,9 @@ int orbm_ensure_dd(orbm_matcher *m, size_t need, hipStream_t s)
     if (s && s != m->stream) MHIPCHK(hipStreamSynchronize(s));
     return m->d_dd.grow(need + need / 2, mfail, "MapPoint scratch");
 }
+int orbm_ensure_fuse(orbm_matcher *m, size_t need)
+{
+    if (need <= m->d_fuse.bytes()) return ORBX_OK;
+    MHIPCHK(hipStreamSynchronize(m->stream));
+    return m->d_fuse.grow(need + need / 2, mfail, "Fuse batch workspace");
+}

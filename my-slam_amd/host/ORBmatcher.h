@@ -16,8 +16,9 @@
 //     int SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, vpMatches12, s12, R12, t12, th)                   :78
 //     int Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, const float th = 3.0)                :81
 //     int Fuse(KeyFrame *pKF, cv::Mat Scw, vpPoints, float th, vpReplacePoint)                           :84
-// Beside them, two overloads the reference does not have: SearchByBoW over a list of candidate key frames in one GPU call, for the
-// candidate loops of Tracking::Relocalization and LoopClosing::ComputeSim3.
+// Beside them, three overloads the reference does not have: SearchByBoW over a list of candidate key frames in one GPU call, for the
+// candidate loops of Tracking::Relocalization and LoopClosing::ComputeSim3, and Fuse over a list of
+// target key frames in one GPU call, for the loop of LocalMapping::SearchInNeighbors (section 3k).
 // Each method gathers exactly the members its reference body reads (listed above it) from the maintainer's own Frame /
 // KeyFrame / MapPoint classes into flat arrays, calls the C ABI of include/orbm.h (cv::Mat algebra on the host with OpenCV's
 // arithmetic, window queries, candidate predicates and Hamming distances on the GPU) and writes the result back the way the
@@ -501,6 +502,149 @@ public:
             nFused++;
         }
         return nFused;
+    }
+
+    // ---- Fuse over ALL target key frames in one GPU call: the loop of LocalMapping::SearchInNeighbors, src/LocalMapping.cc:487-492
+    // (and :516 with std::vector<KeyFrame*>(1, mpCurrentKeyFrame)); orbm_fuse_views, INTEGRATION.md section 3k ----
+    // reads: per key frame what Fuse above reads, plus mfLogScaleFactor, mnScaleLevels and, for the slots whose MapPoint's descriptor
+    //        changed during the loop, GetFeaturesInArea(u, v, r); per MapPoint isBad(), IsInKeyFrame(pKF), GetWorldPos(), GetNormal(),
+    //        GetDistanceRange(mfMax, mfMin) (the accessor of INTEGRATION.md section 3i), GetDescriptor(), Observations()
+    // writes: the reference's own sequence (:954-970), key frame after key frame and point after point, as the loop of single calls does
+    // Returns the sum of the single calls' return values; pvnFused[v] = the return value of Fuse(vpTargetKFs[v], vpMapPoints, th);
+    // *pnReselected = the slots that were selected again on the host.
+    //
+    // Why one snapshot taken before the loop is enough, and where it is not.  Within one Fuse call no search reads what :954-970
+    // writes (see above).  Across key frames one thing does: MapPoint::Replace (src/MapPoint.cc:177-215) ends with
+    // pMP->ComputeDistinctiveDescriptors() on the surviving point, so a point of vpMapPoints can meet key frame v+1 with another
+    // descriptor than it had at key frame v.  Everything else the search reads stays: GetWorldPos, GetNormal and mfMax / MinDistance
+    // are written by UpdateNormalAndDepth, which runs only after both halves (src/LocalMapping.cc:529); pose, features and grid of a
+    // key frame are immutable; and eligibility (:849) can only be lost (Replace makes a point bad, AddObservation and Replace only
+    // add key frames to the survivor).  So for a slot (v, i) everything up to the candidate list -- the gates of :856-885, u, v, ur,
+    // the predicted level, the radius, the window's members that pass the octave window and the chi-square gate -- depends on the
+    // snapshot only, and the Hamming selection of :940-949 alone depends on the live descriptor.  The replay below therefore
+    // re-evaluates :849 on the live objects and, for exactly the slots whose MapPoint's 32 descriptor bytes differ from the
+    // snapshot's, runs :892-952 again on the host with the slot's u, v, ur and level from the batch.
+    // A template so that the members only this overload reads are asked of the classes of a caller that uses it; in an ORB-SLAM2 tree
+    // KF is KeyFrame and MP is MapPoint.
+    template <class KF, class MP>
+    int Fuse(const std::vector<KF *> &vpTargetKFs, const std::vector<MP *> &vpMapPoints, const float th = 3.0,
+             std::vector<int> *pvnFused = NULL, int *pnReselected = NULL)
+    {
+        const int nv = (int)vpTargetKFs.size(), n = (int)vpMapPoints.size();
+        if (pvnFused) pvnFused->assign(nv, 0);
+        if (pnReselected) *pnReselected = 0;
+        if (!ready() || nv == 0 || n == 0) return 0;
+        // the snapshot
+        const size_t slots = (size_t)nv * n;
+        std::vector<orbm_fuse_view> views(nv);
+        std::vector<int32_t> off(nv + 1, 0);
+        for (int v = 0; v < nv; v++) off[v + 1] = off[v] + (int)vpTargetKFs[v]->mvKeysUn.size();
+        const int nk = off[nv];
+        std::vector<orbx_keypoint> kps((size_t)nk);
+        std::vector<float> ur_kf((size_t)nk);
+        std::vector<uint8_t> desc_kf((size_t)nk * 32), skip(slots, 1);
+        for (int v = 0; v < nv; v++) {
+            KF *pKF = vpTargetKFs[v];
+            orbm_fuse_view &V = views[v];
+            memset(&V, 0, sizeof V);
+            const cv::Mat R = pKF->GetRotation();
+            for (int r = 0; r < 3; r++) for (int c = 0; c < 3; c++) V.Rcw[3 * r + c] = R.at<float>(r, c);
+            vec3(pKF->GetTranslation(), V.tcw);
+            vec3(pKF->GetCameraCenter(), V.Ow);
+            V.fx = pKF->fx; V.fy = pKF->fy; V.cx = pKF->cx; V.cy = pKF->cy; V.mbf = pKF->mbf;
+            kf_bounds(pKF, V.bounds);
+            V.log_scale_factor = pKF->mfLogScaleFactor;
+            V.nlevels = pKF->mnScaleLevels;
+            for (int l = 0; l < ORBX_MAX_LEVELS && l < (int)pKF->mvScaleFactors.size(); l++) V.scale_factors[l] = pKF->mvScaleFactors[l];
+            for (int l = 0; l < ORBX_MAX_LEVELS && l < (int)pKF->mvInvLevelSigma2.size(); l++) V.inv_level_sigma2[l] = pKF->mvInvLevelSigma2[l];
+            V.grid = kf_grid_of(pKF);
+            const int nkv = off[v + 1] - off[v];
+            if (nkv > 0) {
+                memcpy(&kps[off[v]], kp(pKF->mvKeysUn), (size_t)nkv * sizeof(orbx_keypoint));
+                memcpy(&ur_kf[off[v]], pKF->mvuRight.data(), (size_t)nkv * sizeof(float));
+                const cv::Mat &mDescriptors = pKF->mDescriptors;
+                memcpy(&desc_kf[(size_t)off[v] * 32], mDescriptors.ptr<unsigned char>(), (size_t)nkv * 32);
+            }
+            for (int i = 0; i < n; i++) {
+                MP *pMP = vpMapPoints[i];
+                skip[(size_t)v * n + i] = !pMP || pMP->isBad() || pMP->IsInKeyFrame(pKF);             // :846-850
+            }
+        }
+        std::vector<float> xw((size_t)n * 3, 0.f), normal((size_t)n * 3, 0.f), mf_max(n, 0.f), mf_min(n, 0.f);
+        std::vector<uint8_t> mp_desc((size_t)n * 32, 0);
+        for (int i = 0; i < n; i++) {
+            MP *pMP = vpMapPoints[i];
+            if (!pMP || pMP->isBad()) continue;
+            vec3(pMP->GetWorldPos(), &xw[(size_t)3 * i]);
+            vec3(pMP->GetNormal(), &normal[(size_t)3 * i]);
+            pMP->GetDistanceRange(mf_max[i], mf_min[i]);
+            copy_desc(pMP->GetDescriptor(), &mp_desc[(size_t)i * 32]);
+        }
+        std::vector<uint8_t> status(slots, ORBM_FUSE_SKIPPED);
+        std::vector<int32_t> best_idx(slots, -1), best_dist(slots, 256), pred_level(slots, 0), nfused(nv, 0);
+        std::vector<float> pu(slots, 0.f), pv(slots, 0.f), pr(slots, 0.f);
+        if (!ok(orbm_fuse_views(h_.m, views.data(), nv, off.data(), kps.data(), ur_kf.data(), desc_kf.data(), n, skip.data(), xw.data(), normal.data(),
+                                mf_max.data(), mf_min.data(), mp_desc.data(), th, status.data(), best_idx.data(), best_dist.data(), pu.data(),
+                                pv.data(), pr.data(), pred_level.data(), nfused.data())))
+            return 0;
+        // the replay
+        int nFusedAll = 0;
+        for (int v = 0; v < nv; v++) {
+            KF *pKF = vpTargetKFs[v];
+            int nFused = 0;
+            for (int i = 0; i < n; i++) {
+                MP *pMP = vpMapPoints[i];
+                if (!pMP) continue;
+                if (pMP->isBad() || pMP->IsInKeyFrame(pKF)) continue;                          // :849 on the live objects
+                const size_t k = (size_t)v * n + i;
+                if (status[k] != ORBM_FUSE_MATCH && status[k] != ORBM_FUSE_NO_MATCH) continue;    // :856-887, or skipped on the snapshot
+                int bestIdx = -1;
+                const cv::Mat dMP = pMP->GetDescriptor();
+                if (memcmp(dMP.ptr<unsigned char>(), &mp_desc[(size_t)i * 32], 32) == 0) {
+                    if (status[k] != ORBM_FUSE_MATCH) continue;
+                    bestIdx = best_idx[k];
+                } else {                                                                       // the descriptor changed: :892-952 again
+                    if (pnReselected) (*pnReselected)++;
+                    const float u = pu[k], vv = pv[k], ur = pr[k];
+                    const int nPredictedLevel = pred_level[k];
+                    const float radius = th * pKF->mvScaleFactors[nPredictedLevel];
+                    const std::vector<size_t> vIndices = pKF->GetFeaturesInArea(u, vv, radius);
+                    int bestDist = 256;
+                    for (std::vector<size_t>::const_iterator vit = vIndices.begin(), vend = vIndices.end(); vit != vend; vit++) {
+                        const size_t idx = *vit;
+                        const cv::KeyPoint &kpt = pKF->mvKeysUn[idx];
+                        const int &kpLevel = kpt.octave;
+                        if (kpLevel < nPredictedLevel - 1 || kpLevel > nPredictedLevel) continue;
+                        const float ex = u - kpt.pt.x, ey = vv - kpt.pt.y;
+                        if (pKF->mvuRight[idx] >= 0) {
+                            const float er = ur - pKF->mvuRight[idx];
+                            const float e2 = ex * ex + ey * ey + er * er;
+                            if (e2 * pKF->mvInvLevelSigma2[kpLevel] > 7.8) continue;
+                        } else {
+                            const float e2 = ex * ex + ey * ey;
+                            if (e2 * pKF->mvInvLevelSigma2[kpLevel] > 5.99) continue;
+                        }
+                        const int dist = DescriptorDistance(dMP, pKF->mDescriptors.row((int)idx));
+                        if (dist < bestDist) { bestDist = dist; bestIdx = (int)idx; }
+                    }
+                    if (bestDist > TH_LOW) continue;
+                }
+                MapPoint *pMPinKF = pKF->GetMapPoint(bestIdx);                                 // :954-970
+                if (pMPinKF) {
+                    if (!pMPinKF->isBad()) {
+                        if (pMPinKF->Observations() > pMP->Observations()) pMP->Replace(pMPinKF);
+                        else pMPinKF->Replace(pMP);
+                    }
+                } else {
+                    pMP->AddObservation(pKF, bestIdx);
+                    pKF->AddMapPoint(pMP, bestIdx);
+                }
+                nFused++;
+            }
+            if (pvnFused) (*pvnFused)[v] = nFused;
+            nFusedAll += nFused;
+        }
+        return nFusedAll;
     }
 
     // ---- include/ORBmatcher.h:84, src/ORBmatcher.cc:977-1100 (LoopClosing::SearchAndFuse, src/LoopClosing.cc:600) ----
