@@ -670,6 +670,48 @@ int orbm_pose_optimization_batch_device(orbm_matcher *m, int n_problems, const i
                                         void *hip_stream);
 
 /*
+ * ---- Sim3Solver: the hypotheses of all loop candidates in one call ----
+ * LoopClosing::ComputeSim3 (src/LoopClosing.cc:253-343) runs up to 300 RANSAC iterations per candidate key frame, five at a time
+ * (Sim3Solver::iterate, src/Sim3Solver.cc:140-207).  An iteration is a 3-point Horn solve (ComputeSim3, :226-337) and two
+ * projections of all correspondences (CheckInliers, :340-364); the draws do not depend on the results, so every hypothesis of
+ * every candidate can be evaluated at once.  orbm_sim3_hypotheses does that for B problems:
+ *   problem p owns the correspondences off[p]:off[p+1] of x3dc1 / x3dc2 (the point in camera 1 / 2, 3 floats each) and of
+ *   max_err1 / max_err2 (mvnMaxError1/2 as floats: orbp_sim3_get_problem), the calibrations and mbFixScale in cams[p], and
+ *   the hypotheses hyp_off[p]:hyp_off[p+1]; hypothesis h samples the correspondences triples[3h .. 3h+3) of its problem
+ *   (indices relative to off[p]: what orbp_sim3_draw records);
+ *   n_inliers[h] = mnInliersi, sRt[13h .. 13h+13) = ms12i, mR12i (row-major), mt12i;
+ *   masks: hypothesis h of problem p owns the W = ceil(n_p / 32) words from mask_off[p] + (h - hyp_off[p]) * W; bit i of them is
+ *   mvbInliersi[i], bits >= n_p are zero.  mask_off[0] = 0 and mask_off[p+1] = mask_off[p] + (hyp_off[p+1] - hyp_off[p]) * W.
+ * The outputs are the inputs of orbp_sim3_attach_results (include/orbp.h), after which Sim3Solver::iterate replays them.
+ *
+ * One wave evaluates one hypothesis with the text of the host solver (csrc/orbm_sim3_body.h: IEEE operations only, its own
+ * atan2 / sin / cos), so every output equals orbp_sim3_hypothesis' byte for byte.  The result of a hypothesis depends on its
+ * problem and its triple alone, not on the batch, its position or the run.  There is no limit on n.  A triple whose points are
+ * collinear or coincident within rounding is outside the value contract: its flags are still 0/1, its count is its mask's
+ * popcount and nothing outside its slots is written.  Points at depth 0 and non-finite inputs are outside the contract.
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: a negative count, NULL buffers, off / hyp_off / mask_off not
+ * starting at 0, a decreasing off or hyp_off, a mask_off that is not the layout above, a triple index outside its problem);
+ * n_problems == 0 or no hypothesis at all is ORBX_OK and touches nothing.  Every other call needs the GPU: a NULL handle fails
+ * with ORBX_E_HIP where there is no HIP device ("no CPU path") and with ORBX_E_INVALID where there is one.  The call runs on the
+ * handle's stream through its staging arena (one upload, one launch, one download) and grows the handle when the batch is larger
+ * than its workspace; the grids in the handle are not touched.
+ *
+ * orbm_sim3_hypotheses_device: the same on device pointers (4-byte aligned, mask_off 8-byte aligned).  total_hypotheses =
+ * hyp_off[n_problems] (the launch size: the host cannot read it).  The index arrays are not checked (a triple index outside its
+ * problem is clamped into it).  Nothing is uploaded, downloaded, synchronised or grown; asynchronous on hip_stream (NULL = the
+ * handle's stream), capturable.
+ */
+typedef struct { float K1[4], K2[4]; int32_t fix_scale; } orbm_sim3_camera;     /* {fx, fy, cx, cy} of key frame 1 / 2, mbFixScale */
+int orbm_sim3_hypotheses(orbm_matcher *m, int n_problems, const int32_t *off, const float *x3dc1, const float *x3dc2,
+                         const float *max_err1, const float *max_err2, const orbm_sim3_camera *cams, const int32_t *hyp_off,
+                         const int32_t *triples, const int64_t *mask_off, int32_t *n_inliers, float *sRt, uint32_t *masks);
+int orbm_sim3_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypotheses, const int32_t *d_off, const float *d_x3dc1,
+                                const float *d_x3dc2, const float *d_max_err1, const float *d_max_err2,
+                                const orbm_sim3_camera *d_cams, const int32_t *d_hyp_off, const int32_t *d_triples,
+                                const int64_t *d_mask_off, int32_t *d_n_inliers, float *d_sRt, uint32_t *d_masks, void *hip_stream);
+
+/*
  * ---- ORBmatcher::Fuse for ALL target key frames of LocalMapping::SearchInNeighbors in one call ----
  * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:456-536) calls Fuse(pKFi, vpMapPointMatches) once per target key frame
  * (:487-492) and once more with every MapPoint of those key frames against mpCurrentKeyFrame (:516).  orbm_fuse_views runs

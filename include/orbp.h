@@ -69,6 +69,62 @@ double orbp_epnp(int n, const double *pws, const double *us, double fu, double f
 int orbp_pose_optimization(int n, const float *obs, const float *u_right, const float *inv_sigma2, const float *xw,
                            float fx, float fy, float cx, float cy, float bf, float *Tcw, uint8_t *outlier);
 
+/*
+ * ---- Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h): RANSAC over 3-point Horn solves, LoopClosing::ComputeSim3 ----
+ *   src/Sim3Solver.cc:35-112   Sim3Solver::Sim3Solver   -> orbp_sim3_create (the caller does Rcw*Xw+tcw and drops NULL / bad
+ *                                                          MapPoints and those without an index, :62-103)
+ *   :114-138  SetRansacParameters -> orbp_sim3_set_ransac_parameters      :140-213  iterate / find -> orbp_sim3_iterate / _find
+ *   :226-337  ComputeSim3 (Horn 1987) and :340-403 CheckInliers / Project -> orbp_sim3_hypothesis (csrc/orbm_sim3_body.h)
+ *
+ * n correspondences: x3dc1 / x3dc2 = the point in camera 1 / 2 (3n floats each), sigma2_1 / sigma2_2 = mvLevelSigma2[octave] of
+ * its keypoint in key frame 1 / 2 (n each), K1 / K2 = {fx, fy, cx, cy}.  The thresholds are the reference's: mvnMaxError1/2 are
+ * std::vector<size_t>, so 9.210 * sigma2 is truncated to an integer before it is compared as a float (sigma2 = 1.44 -> 13).
+ *
+ * The hypotheses of a solver do not depend on each other, only on the draws, so they can be evaluated ahead of iterate():
+ * orbp_sim3_draw performs the draws of the next iterations exactly as iterate would (:163-177) and queues the index triples;
+ * orbm_sim3_hypotheses (include/orbm.h) evaluates the queued triples of many solvers in one GPU call; orbp_sim3_attach_results
+ * hands the results back, and iterate() then replays them: same counts, flags and poses, byte for byte, as evaluating in place,
+ * because host and kernel run one body.  iterate() consumes queued triples before it draws new ones, with or without results.
+ *
+ * What OpenCV does inside cv::eigen / cv::Rodrigues / gemm is "parity unpinned" as for EPnP above (csrc/orbm_sim3_body.h lists
+ * the choices).  Collinear or coincident sample points are outside the value contract (the flags are still 0/1).
+ */
+typedef struct orbp_sim3 orbp_sim3;
+int orbp_sim3_create(orbp_sim3 **out, int n, const float *x3dc1, const float *x3dc2, const float *sigma2_1, const float *sigma2_2,
+                     const float *K1, const float *K2, int fix_scale);   /* ends with SetRansacParameters() = (0.99, 6, 300) */
+void orbp_sim3_destroy(orbp_sim3 *s);
+/* fn(ctx) in [0, rand_max]; NULL restores libc rand() / RAND_MAX through RandomInt's formula (as orbp_pnp_set_rand). */
+void orbp_sim3_set_rand(orbp_sim3 *s, int (*fn)(void *), void *ctx, int rand_max);
+/* :114-138.  n == min_inliers gives 1 iteration; n < min_inliers (the reference's formula takes the log of a non-positive
+ * number there) is defined as 1 iteration as well: iterate() returns at once with no_more set in that case.  Resets the
+ * iteration count and drops queued triples and attached results; the best hypothesis so far stays, as in the reference. */
+int orbp_sim3_set_ransac_parameters(orbp_sim3 *s, double probability, int min_inliers, int max_iterations);
+void orbp_sim3_get_ransac_state(const orbp_sim3 *s, int *min_inliers, int *max_its, float *epsilon, int *iterations_done,
+                                int *best_inliers);      /* any pointer may be NULL */
+/* The solver as a problem of orbm_sim3_hypotheses: its correspondences x3dc1 / x3dc2 (3n floats each), max_err1 / max_err2
+ * (mvnMaxError1 / 2 as the floats CheckInliers compares with, n each), the calibrations (4 floats each) and mbFixScale.
+ * Returns n. */
+int orbp_sim3_get_problem(const orbp_sim3 *s, float *x3dc1, float *x3dc2, float *max_err1, float *max_err2, float *K1, float *K2,
+                          int32_t *fix_scale);
+/* Draws the triples of the next n_iterations iterations (capped at what remains of mRansacMaxIts after the queued ones; nothing
+ * when n < min_inliers or n < 3), appends them to the queue and to triples (3 per iteration; may be NULL).  Returns the number
+ * of iterations drawn, < 0 on bad arguments. */
+int orbp_sim3_draw(orbp_sim3 *s, int n_iterations, int32_t *triples);
+/* The queued, not yet consumed triples (3 * return value ints into triples when it is not NULL). */
+int orbp_sim3_queued(const orbp_sim3 *s, int32_t *triples);
+/* One hypothesis, stateless: R (9, row-major), t (3), *scale, inliers[n] (0/1), *n_inliers of the triple of correspondence indices. */
+int orbp_sim3_hypothesis(const orbp_sim3 *s, const int32_t *triple, float *R, float *t, float *scale, uint8_t *inliers, int *n_inliers);
+/* Results for ALL queued triples, in queue order, in the layout of orbm_sim3_hypotheses: counts[n_hyp], sRt[13 n_hyp] (s, R, t),
+ * masks[n_hyp * ceil(n / 32)] (bit i of a hypothesis' words = correspondence i).  n_hyp must equal orbp_sim3_queued(). */
+int orbp_sim3_attach_results(orbp_sim3 *s, int n_hyp, const int32_t *counts, const float *sRt, const uint32_t *masks);
+/* :140-207.  inliers[n] is cleared on every call.  Returns 1 and fills inliers, *n_inliers and T12 (row-major 4x4) when a pose
+ * is returned, 0 when the reference returns an empty cv::Mat, < 0 on bad arguments.  *no_more is set on the call that reaches
+ * mRansacMaxIts, also when that call returns a pose (the reference's early return reports it one call later, on a call that
+ * iterates nothing; ComputeSim3 discards the candidate either way after it has used the pose).  The state survives a returned pose: iterating on continues the same RANSAC.  n < 3 sets *no_more like n < min_inliers. */
+int orbp_sim3_iterate(orbp_sim3 *s, int n_iterations, int *no_more, uint8_t *inliers, int *n_inliers, float *T12);
+int orbp_sim3_find(orbp_sim3 *s, uint8_t *inliers, int *n_inliers, float *T12);
+/* GetEstimatedRotation / Translation / Scale: the best hypothesis so far; returns 0 before the first iteration. */
+int orbp_sim3_get_estimated(const orbp_sim3 *s, float *R, float *t, float *scale);
 const char *orbp_last_error(void);
 
 #ifdef __cplusplus

@@ -46,6 +46,9 @@ assert FUSE_VIEW_DTYPE.itemsize == 256      # sizeof(orbm_fuse_view): tests/test
 # orbm_pose_camera (include/orbm.h): the calibration of one problem of pose_optimization_batch
 POSE_CAM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("bf", "<f4")])
 assert POSE_CAM_DTYPE.itemsize == 20
+# orbm_sim3_camera (include/orbm.h): the two calibrations {fx, fy, cx, cy} and mbFixScale of one problem of sim3_hypotheses
+SIM3_CAM_DTYPE = np.dtype([("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("fix_scale", "<i4")])
+assert SIM3_CAM_DTYPE.itemsize == 36
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
@@ -134,6 +137,7 @@ def lib():
     _bind_matcher(L)
     _bind_voc(L)
     _bind_pose(L)
+    _bind_sim3(L)
     _bind_kfdb(L)
     _lib = L
     return L
@@ -201,6 +205,34 @@ def _bind_pose(L):
     for name in ("orbp_pnp_create", "orbp_pnp_set_ransac_parameters", "orbp_pnp_iterate", "orbp_pnp_find",
                  "orbp_pose_optimization"):
         getattr(L, name).restype = C.c_int
+
+
+def _bind_sim3(L):
+    vp, ip, fp = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float)
+    L.orbp_sim3_create.argtypes = [C.POINTER(vp), C.c_int, vp, vp, vp, vp, vp, vp, C.c_int]
+    L.orbp_sim3_destroy.argtypes = [vp]
+    L.orbp_sim3_destroy.restype = None
+    L.orbp_sim3_set_rand.argtypes = [vp, RAND_FN, vp, C.c_int]
+    L.orbp_sim3_set_rand.restype = None
+    L.orbp_sim3_set_ransac_parameters.argtypes = [vp, C.c_double, C.c_int, C.c_int]
+    L.orbp_sim3_get_ransac_state.argtypes = [vp, ip, ip, fp, ip, ip]
+    L.orbp_sim3_get_ransac_state.restype = None
+    L.orbp_sim3_get_problem.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.orbp_sim3_draw.argtypes = [vp, C.c_int, vp]
+    L.orbp_sim3_queued.argtypes = [vp, vp]
+    L.orbp_sim3_hypothesis.argtypes = [vp, vp, vp, vp, fp, vp, ip]
+    L.orbp_sim3_attach_results.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbp_sim3_iterate.argtypes = [vp, C.c_int, ip, vp, ip, vp]
+    L.orbp_sim3_find.argtypes = [vp, vp, ip, vp]
+    L.orbp_sim3_get_estimated.argtypes = [vp, vp, vp, fp]
+    L.orbp_sim3_math.argtypes = [C.c_int, C.c_double, C.c_double]
+    L.orbp_sim3_math.restype = C.c_double
+    for name in ("orbp_sim3_create", "orbp_sim3_set_ransac_parameters", "orbp_sim3_get_problem", "orbp_sim3_draw", "orbp_sim3_queued",
+                 "orbp_sim3_hypothesis", "orbp_sim3_attach_results", "orbp_sim3_iterate", "orbp_sim3_find", "orbp_sim3_get_estimated"):
+        getattr(L, name).restype = C.c_int
+    L.orbm_sim3_hypotheses.argtypes = [vp, C.c_int] + [vp] * 12
+    L.orbm_sim3_hypotheses_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 13
+    L.orbm_sim3_hypotheses.restype = L.orbm_sim3_hypotheses_device.restype = C.c_int
 
 
 def _bind_matcher(L):
@@ -808,6 +840,70 @@ class ORBmatcher:
         _mchk(self.L.orbm_pose_optimization_batch_device(self.h, n_problems, ptr(off), ptr(obs), ptr(u_right), ptr(inv_sigma2), ptr(xw),
                                                          ptr(cams), ptr(Tcw), ptr(outlier), ptr(n_good), s))
 
+    @staticmethod
+    def pack_sim3_problems(problems):
+        """The arrays of orbm_sim3_hypotheses from a list of problems, each a Sim3Solver (its queued triples) or a tuple
+        (x3dc1 [n, 3], x3dc2 [n, 3], max_err1 [n], max_err2 [n], K1 (4), K2 (4), fix_scale, triples [h, 3]) ->
+        (off int32 [B+1], x3dc1 float32 [N, 3], x3dc2, max_err1 float32 [N], max_err2, cams SIM3_CAM_DTYPE [B], hyp_off int32 [B+1],
+        triples int32 [H, 3], mask_off int64 [B+1])."""
+        B = len(problems)
+        off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
+        cams = np.zeros(B, SIM3_CAM_DTYPE)
+        x1s, x2s, e1s, e2s, tris = [], [], [], [], []
+        for p, pr in enumerate(problems):
+            if isinstance(pr, Sim3Solver):
+                pr = pr.problem()
+            x1, x2, e1, e2, K1, K2, fix, tri = pr
+            x1 = np.ascontiguousarray(x1, np.float32).reshape(-1, 3)
+            x2 = np.ascontiguousarray(x2, np.float32).reshape(-1, 3)
+            e1 = np.ascontiguousarray(e1, np.float32).reshape(-1)
+            e2 = np.ascontiguousarray(e2, np.float32).reshape(-1)
+            tri = np.ascontiguousarray(tri, np.int32).reshape(-1, 3)
+            if not (len(x1) == len(x2) == len(e1) == len(e2)):
+                raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %d / %d / %d / %d" % (p, len(x1), len(x2), len(e1), len(e2)))
+            x1s.append(x1); x2s.append(x2); e1s.append(e1); e2s.append(e2); tris.append(tri)
+            off[p + 1] = off[p] + len(x1)
+            hyp_off[p + 1] = hyp_off[p] + len(tri)
+            mask_off[p + 1] = mask_off[p] + len(tri) * ((len(x1) + 31) // 32)
+            cams[p] = (np.asarray(K1, np.float32).reshape(4), np.asarray(K2, np.float32).reshape(4), int(bool(fix)))
+        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(shape, dt)
+        return (off, cat(x1s, (0, 3), np.float32), cat(x2s, (0, 3), np.float32), cat(e1s, (0,), np.float32), cat(e2s, (0,), np.float32), cams,
+                hyp_off, cat(tris, (0, 3), np.int32), mask_off)
+
+    def sim3_hypotheses(self, problems):
+        """Every hypothesis of every problem in one launch (orbm_sim3_hypotheses; problems as in pack_sim3_problems).  Returns a list
+        of (n_inliers int32 [h], sRt float32 [h, 13], masks uint32 [h, ceil(n / 32)]) per problem: what Sim3Solver.attach_results takes."""
+        off, x1, x2, e1, e2, cams, hyp_off, tri, mask_off = self.pack_sim3_problems(problems)
+        B, H, MW = len(problems), int(hyp_off[-1]), int(mask_off[-1])
+        cnt, sRt, masks = np.zeros(max(H, 1), np.int32), np.zeros((max(H, 1), 13), np.float32), np.zeros(max(MW, 1), np.uint32)
+        _mchk(self.L.orbm_sim3_hypotheses(self.h, B, _p(off), _p(x1), _p(x2), _p(e1), _p(e2), _p(cams), _p(hyp_off), _p(tri), _p(mask_off),
+                                          _p(cnt), _p(sRt), _p(masks)))
+        out = []
+        for p in range(B):
+            h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
+            W = (int(off[p + 1]) - int(off[p]) + 31) // 32
+            out.append((cnt[h0:h1].copy(), sRt[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
+        return out
+
+    def sim3_hypotheses_device(self, n_problems, total_hypotheses, off, x3dc1, x3dc2, max_err1, max_err2, cams, hyp_off, triples, mask_off,
+                               n_inliers, sRt, masks, stream=None):
+        """The same on torch tensors on the handle's device: off int32 [B+1], x3dc1 / x3dc2 float32 [N, 3], max_err1 / max_err2
+        float32 [N], cams uint8 [B, 36] (SIM3_CAM_DTYPE bytes), hyp_off int32 [B+1], triples int32 [H, 3], mask_off int64 [B+1],
+        n_inliers int32 [H], sRt float32 [H, 13], masks int32 [mask words].  Nothing is copied or synchronised; stream: a torch
+        stream, a raw hipStream_t or None (the handle's stream)."""
+        import torch
+        want = ((off, torch.int32), (x3dc1, torch.float32), (x3dc2, torch.float32), (max_err1, torch.float32), (max_err2, torch.float32),
+                (cams, torch.uint8), (hyp_off, torch.int32), (triples, torch.int32), (mask_off, torch.int64), (n_inliers, torch.int32),
+                (sRt, torch.float32), (masks, torch.int32))
+        for t, dt in want:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise OrbxError(ORBX_E_INVALID, "sim3_hypotheses_device wants contiguous device tensors of the documented dtypes")
+        s = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _mchk(self.L.orbm_sim3_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(x3dc1), ptr(x3dc2), ptr(max_err1),
+                                                 ptr(max_err2), ptr(cams), ptr(hyp_off), ptr(triples), ptr(mask_off), ptr(n_inliers),
+                                                 ptr(sRt), ptr(masks), s))
+
     def search_local_points(self, view, skip, xw, normal, mf_max, mf_min, mp_desc, mp_obs, kps_cur, desc_cur, cur_obs, th,
                             u_right=None, viewing_cos_limit=0.5):
         """Tracking::SearchLocalPoints (src/Tracking.cc:1174-1199) in one call: frustum() followed by SearchByProjectionMap() on the
@@ -1376,6 +1472,138 @@ class PnPsolver:
         st = self.ransac_state()
         T, _, inl, n = self.iterate(st["max_its"])
         return T, inl, n
+
+
+class Sim3Solver:
+    """Mirror of ORB_SLAM2::Sim3Solver (include/Sim3Solver.h, src/Sim3Solver.cc) over orbp_sim3_*.  The KeyFrame / MapPoint
+    arguments of the reference constructor become the arrays it reads from them: x3dc1 / x3dc2 = Rcw*Xw+tcw of the matched pair in
+    key frame 1 / 2, sigma2_1 / sigma2_2 = mvLevelSigma2[octave] of its keypoints, K1 / K2 = (fx, fy, cx, cy)."""
+
+    def __init__(self, x3dc1, x3dc2, sigma2_1, sigma2_2, K1, K2, bFixScale=True, rand=None, rand_max=None):
+        self.L = lib()
+        self.x1 = np.ascontiguousarray(x3dc1, np.float32).reshape(-1, 3)
+        self.x2 = np.ascontiguousarray(x3dc2, np.float32).reshape(-1, 3)
+        s1, s2 = np.ascontiguousarray(sigma2_1, np.float32).reshape(-1), np.ascontiguousarray(sigma2_2, np.float32).reshape(-1)
+        self.K1, self.K2 = np.ascontiguousarray(K1, np.float32).reshape(4), np.ascontiguousarray(K2, np.float32).reshape(4)
+        self.fix_scale = bool(bFixScale)
+        self.N = len(self.x1)
+        if not (len(self.x2) == len(s1) == len(s2) == self.N):
+            raise OrbxError(ORBX_E_INVALID, "array lengths disagree: %d / %d / %d / %d" % (self.N, len(self.x2), len(s1), len(s2)))
+        if rand is not None and rand_max is None:
+            raise OrbxError(ORBX_E_INVALID, "Sim3Solver: rand needs rand_max, the largest value rand() returns")
+        self.W = (self.N + 31) // 32
+        self.h = C.c_void_p()
+        _pchk(self.L.orbp_sim3_create(C.byref(self.h), self.N, _p(self.x1), _p(self.x2), _p(s1), _p(s2), _p(self.K1), _p(self.K2),
+                                      int(self.fix_scale)))
+        self._cb = None
+        if rand is not None:
+            self._cb = RAND_FN(lambda ctx: int(rand()))
+            self.L.orbp_sim3_set_rand(self.h, self._cb, None, int(rand_max))
+
+    def close(self):
+        if self.h:
+            self.L.orbp_sim3_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def SetRansacParameters(self, probability=0.99, minInliers=6, maxIterations=300):
+        _pchk(self.L.orbp_sim3_set_ransac_parameters(self.h, probability, minInliers, maxIterations))
+
+    def ransac_state(self):
+        mi, mx, it, nb, ep = C.c_int(), C.c_int(), C.c_int(), C.c_int(), C.c_float()
+        self.L.orbp_sim3_get_ransac_state(self.h, C.byref(mi), C.byref(mx), C.byref(ep), C.byref(it), C.byref(nb))
+        return {"min_inliers": mi.value, "max_its": mx.value, "epsilon": ep.value, "iterations": it.value, "best_inliers": nb.value}
+
+    def max_errors(self):
+        """mvnMaxError1 / mvnMaxError2 as the floats CheckInliers compares with"""
+        n = max(self.N, 1)
+        x1, x2, e1, e2 = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        K1, K2, fix = np.zeros(4, np.float32), np.zeros(4, np.float32), C.c_int32()
+        _pchk(self.L.orbp_sim3_get_problem(self.h, _p(x1), _p(x2), _p(e1), _p(e2), _p(K1), _p(K2), C.byref(fix)))
+        return e1[:self.N], e2[:self.N]
+
+    def draw(self, nIterations):
+        """The triples of the next nIterations iterations (int32 [k, 3], k capped at what remains): drawn now, consumed by iterate()"""
+        tri = np.zeros((max(nIterations, 1), 3), np.int32)
+        k = _pchk(self.L.orbp_sim3_draw(self.h, nIterations, _p(tri)))
+        return tri[:k].copy()
+
+    def queued(self):
+        k = _pchk(self.L.orbp_sim3_queued(self.h, None))
+        tri = np.zeros((max(k, 1), 3), np.int32)
+        _pchk(self.L.orbp_sim3_queued(self.h, _p(tri)))
+        return tri[:k].copy()
+
+    def problem(self):
+        """This solver as a problem of ORBmatcher.sim3_hypotheses: its correspondences and its queued triples"""
+        e1, e2 = self.max_errors()
+        return self.x1, self.x2, e1, e2, self.K1, self.K2, self.fix_scale, self.queued()
+
+    def hypothesis(self, triple):
+        """One hypothesis on the host -> (R 3x3, t (3), scale, inliers bool[N], nInliers)"""
+        tri = np.ascontiguousarray(triple, np.int32).reshape(3)
+        R, t, sc, n = np.zeros(9, np.float32), np.zeros(3, np.float32), C.c_float(), C.c_int()
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        _pchk(self.L.orbp_sim3_hypothesis(self.h, _p(tri), _p(R), _p(t), C.byref(sc), _p(inl), C.byref(n)))
+        return R.reshape(3, 3), t, np.float32(sc.value), inl[:self.N].astype(bool), n.value
+
+    def hypotheses(self, triples):
+        """hypothesis() for each triple, in the layout of ORBmatcher.sim3_hypotheses: (n_inliers [h], sRt [h, 13], masks [h, W])"""
+        triples = np.asarray(triples, np.int32).reshape(-1, 3)
+        cnt, sRt, masks = np.zeros(len(triples), np.int32), np.zeros((len(triples), 13), np.float32), np.zeros((len(triples), self.W), np.uint32)
+        for k, tri in enumerate(triples):
+            R, t, sc, inl, n = self.hypothesis(tri)
+            cnt[k] = n
+            sRt[k, 0], sRt[k, 1:10], sRt[k, 10:13] = sc, R.reshape(9), t
+            bits = np.zeros(self.W * 32, np.uint8)
+            bits[:self.N] = inl
+            masks[k] = np.packbits(bits, bitorder="little").view("<u4")
+        return cnt, sRt, masks
+
+    def attach_results(self, n_inliers, sRt, masks):
+        cnt = np.ascontiguousarray(n_inliers, np.int32).reshape(-1)
+        sRt = np.ascontiguousarray(sRt, np.float32).reshape(-1)
+        masks = np.ascontiguousarray(masks, np.uint32).reshape(-1)
+        if len(sRt) != 13 * len(cnt) or len(masks) != self.W * len(cnt):
+            raise OrbxError(ORBX_E_INVALID, "results of %d hypotheses: %d floats, %d mask words" % (len(cnt), len(sRt), len(masks)))
+        _pchk(self.L.orbp_sim3_attach_results(self.h, len(cnt), _p(cnt), _p(sRt), _p(masks)))
+
+    def iterate(self, nIterations):
+        """-> (T12 4x4 float32 or None, bNoMore, vbInliers bool[N] (all False without a pose), nInliers)"""
+        no_more, ninl = C.c_int(), C.c_int()
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        T = np.zeros(16, np.float32)
+        got = _pchk(self.L.orbp_sim3_iterate(self.h, nIterations, C.byref(no_more), _p(inl), C.byref(ninl), _p(T)))
+        return (T.reshape(4, 4) if got else None), bool(no_more.value), inl[:self.N].astype(bool), ninl.value
+
+    def find(self):
+        ninl = C.c_int()
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        T = np.zeros(16, np.float32)
+        got = _pchk(self.L.orbp_sim3_find(self.h, _p(inl), C.byref(ninl), _p(T)))
+        return (T.reshape(4, 4) if got else None), inl[:self.N].astype(bool), ninl.value
+
+    def estimated(self):
+        """GetEstimatedRotation / Translation / Scale -> (R 3x3, t (3), scale), or None before the first iteration"""
+        R, t, sc = np.zeros(9, np.float32), np.zeros(3, np.float32), C.c_float()
+        if not _pchk(self.L.orbp_sim3_get_estimated(self.h, _p(R), _p(t), C.byref(sc))):
+            return None
+        return R.reshape(3, 3), t, np.float32(sc.value)
+
+    @staticmethod
+    def EvaluateAll(solvers, matcher):
+        """LoopClosing::ComputeSim3's batch step: draws every solver's remaining triples (None entries are skipped), evaluates all of
+        them in ONE ORBmatcher.sim3_hypotheses call and attaches the results, so that every later iterate() is a replay."""
+        live = [s for s in solvers if s is not None]
+        for s in live:
+            s.draw(s.ransac_state()["max_its"])
+        for s, res in zip(live, matcher.sim3_hypotheses(live)):
+            s.attach_results(*res)
 
 
 def epnp(pws, us, fu, fv, uc, vc):

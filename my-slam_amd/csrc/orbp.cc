@@ -12,6 +12,7 @@
 #include <vector>
 #include "../../include/orbp.h"
 #include "../../include/orbx.h"
+#include "orbp_internal.h"
 
 static thread_local char g_perr[256] = "";
 static int pfail(int code, const char *fmt, ...)
@@ -23,6 +24,7 @@ static int pfail(int code, const char *fmt, ...)
     return code;
 }
 extern "C" const char *orbp_last_error(void) { return g_perr; }
+void orbp_set_error(const char *text) { snprintf(g_perr, sizeof g_perr, "%s", text); }
 
 // -------------------------------------------------------------------------------------------------
 // Small dense linear algebra (row-major)

@@ -718,6 +718,17 @@ public:
     bool Valid() { return ready(); }
     const std::string &LastError() const { return err_; }
 
+    // orbm_sim3_hypotheses (include/orbm.h) on this matcher's handle: the one GPU call of Sim3Solver::EvaluateAll (Sim3Solver.h)
+    int Sim3Hypotheses(int nProblems, const int32_t *off, const float *x3Dc1, const float *x3Dc2, const float *maxErr1, const float *maxErr2,
+                       const orbm_sim3_camera *cams, const int32_t *hypOff, const int32_t *triples, const int64_t *maskOff, int32_t *nInliers,
+                       float *sRt, uint32_t *masks)
+    {
+        if (!ready()) return ORBX_E_HIP;
+        const int rc = orbm_sim3_hypotheses(h_.m, nProblems, off, x3Dc1, x3Dc2, maxErr1, maxErr2, cams, hypOff, triples, maskOff, nInliers, sRt, masks);
+        ok(rc);
+        return rc;
+    }
+
 protected:
     static_assert(sizeof(cv::KeyPoint) == sizeof(orbx_keypoint), "orbx_keypoint mirrors cv::KeyPoint");
     static const orbx_keypoint *kp(const std::vector<cv::KeyPoint> &v) { return reinterpret_cast<const orbx_keypoint *>(v.data()); }
