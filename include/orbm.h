@@ -712,6 +712,50 @@ int orbm_sim3_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypot
                                 const int64_t *d_mask_off, int32_t *d_n_inliers, float *d_sRt, uint32_t *d_masks, void *hip_stream);
 
 /*
+ * ---- PnPsolver: the EPnP hypotheses of all Relocalization candidates in one call ----
+ * Tracking::Relocalization (src/Tracking.cc:1348-1509) runs PnPsolver::iterate(5, ...) per candidate key frame (:1405-1418); with
+ * the reference's `while(mnIterations<mRansacMaxIts || nCurrentIterations<nIterations)` (src/PnPsolver.cc:182) the first call runs
+ * all mRansacMaxIts iterations unless a refined pose comes back earlier.  An iteration is an EPnP solve on the drawn set
+ * (compute_pose, :458-508) and a projection of all correspondences (CheckInliers, :312-344); the draws do not depend on the results,
+ * so every hypothesis of every candidate can be evaluated at once.  orbm_pnp_hypotheses does that for B problems:
+ *   problem p owns the correspondences off[p]:off[p+1] of p2d (mvP2D, 2 floats each), p3d (mvP3Dw, 3 floats) and max_err
+ *   (mvMaxError = sigma2 * th2 as the float CheckInliers compares with: orbp_pnp_get_problem), cams[p] = the calibration and
+ *   mRansacMinSet, and the hypotheses hyp_off[p]:hyp_off[p+1]; hypothesis h samples the correspondences
+ *   samples[8h .. 8h + set_size) of its problem (indices relative to off[p]: what orbp_pnp_draw records); the stride is 8 ints
+ *   (ORBM_PNP_MAX_SET) whatever set_size is, the entries from set_size on are -1 and are not read;
+ *   n_inliers[h] = mnInliersi, Rt[12h .. 12h+12) = mRi (row-major), then mti, as the doubles the host solver holds;
+ *   masks: as for orbm_sim3_hypotheses above (W = ceil(n_p / 32) words per hypothesis from mask_off[p] on, bit i = mvbInliersi[i]).
+ * The outputs are the inputs of orbp_pnp_attach_results (include/orbp.h), after which PnPsolver::iterate replays them; Refine stays
+ * on the host.
+ *
+ * One wave evaluates one hypothesis with the text of the host solver (csrc/orbp_epnp_body.h: IEEE + - * / sqrt only, every sum in
+ * the host's order), so every output equals orbp_pnp_hypothesis' byte for byte.  The result of a hypothesis depends on its problem
+ * and its sample alone.  There is no limit on n; set_size is 4 to 8 (a solver with a larger mRansacMinSet stays on the host).  A
+ * sample with coincident, collinear or otherwise degenerate points is outside the value contract: its flags are still 0/1, its
+ * count is its mask's popcount and nothing outside its slots is written.  Non-finite inputs are outside the contract.
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: a negative count, NULL buffers, off / hyp_off / mask_off not
+ * starting at 0, a decreasing off or hyp_off, a mask_off that is not the layout above, a set_size outside [4, 8] on a problem with
+ * hypotheses, a sample index outside its problem or repeated within its sample); n_problems == 0 or no hypothesis at all is
+ * ORBX_OK and touches nothing.  NULL handle, stream, staging arena and growth as for orbm_sim3_hypotheses; the grids in the
+ * handle are not touched.
+ *
+ * orbm_pnp_hypotheses_device: the same on device pointers (4-byte aligned; Rt and mask_off 8-byte aligned).  total_hypotheses =
+ * hyp_off[n_problems].  The index arrays are not checked (a sample index outside its problem is clamped into it, a set_size
+ * outside [4, 8] into that range).  Nothing is uploaded, downloaded, synchronised or grown; asynchronous on hip_stream (NULL = the
+ * handle's stream), capturable.
+ */
+#define ORBM_PNP_MAX_SET 8
+typedef struct { float fx, fy, cx, cy; int32_t set_size; } orbm_pnp_camera;
+int orbm_pnp_hypotheses(orbm_matcher *m, int n_problems, const int32_t *off, const float *p2d, const float *p3d, const float *max_err,
+                        const orbm_pnp_camera *cams, const int32_t *hyp_off, const int32_t *samples, const int64_t *mask_off,
+                        int32_t *n_inliers, double *Rt, uint32_t *masks);
+int orbm_pnp_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypotheses, const int32_t *d_off, const float *d_p2d,
+                               const float *d_p3d, const float *d_max_err, const orbm_pnp_camera *d_cams, const int32_t *d_hyp_off,
+                               const int32_t *d_samples, const int64_t *d_mask_off, int32_t *d_n_inliers, double *d_Rt, uint32_t *d_masks,
+                               void *hip_stream);
+
+/*
  * ---- ORBmatcher::Fuse for ALL target key frames of LocalMapping::SearchInNeighbors in one call ----
  * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:456-536) calls Fuse(pKFi, vpMapPointMatches) once per target key frame
  * (:487-492) and once more with every MapPoint of those key frames against mpCurrentKeyFrame (:516).  orbm_fuse_views runs

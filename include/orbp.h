@@ -1,8 +1,10 @@
 /*
  * orbp.h -- C ABI of the host-side pose solvers of liborbx.so: "next" row N4 of SURVEY.md 8(f).
  *
- * SURVEY 8(f) N4 keeps these on the host ("tiny dense fp64 solves"): they are plain C++ inside liborbx.so, take the
- * outputs of the device path (orbx_extract -> orbv_* -> orbm_search_by_bow) and close BASELINE config 5's loop.
+ * They are plain C++ inside liborbx.so, take the outputs of the device path (orbx_extract -> orbv_* -> orbm_search_by_bow) and
+ * close BASELINE config 5's loop.  SURVEY 8(f) N4 keeps one such solve on the host ("tiny dense fp64 solves"); the RANSAC
+ * hypotheses of a whole Relocalization or ComputeSim3 step are hundreds of independent ones, and those have a GPU call each
+ * (orbm_pnp_hypotheses, orbm_sim3_hypotheses in include/orbm.h) that the solvers here draw for and replay.
  *
  * Reference (WChen09/My-SLAM):
  *   src/PnPsolver.cc:66-109    PnPsolver::PnPsolver          -> orbp_pnp_create   (caller drops NULL / bad MapPoints)
@@ -56,6 +58,38 @@ void orbp_pnp_get_ransac_state(const orbp_pnp *s, int *min_inliers, int *max_its
  * reference returns an empty cv::Mat (inliers untouched, *n_inliers = 0), < 0 on bad arguments. */
 int orbp_pnp_iterate(orbp_pnp *s, int n_iterations, int *no_more, uint8_t *inliers, int *n_inliers, float *Tcw);
 int orbp_pnp_find(orbp_pnp *s, uint8_t *inliers, int *n_inliers, float *Tcw);
+
+/*
+ * The hypotheses of a solver do not depend on each other, only on the draws: compute_pose + CheckInliers (:206-210) read the
+ * problem and the sample, and only the walk that keeps the best set, calls Refine and decides what iterate returns is sequential.
+ * So they can be evaluated ahead of iterate(), as for Sim3Solver below: orbp_pnp_draw performs the draws of the coming iterations
+ * exactly as iterate would (:188-204) and queues the index sets; orbm_pnp_hypotheses (include/orbm.h) evaluates the queued sets of
+ * many solvers in one GPU call; orbp_pnp_attach_results hands the results back, and iterate() replays them: it restores mRi, mti,
+ * mvbInliersi and mnInliersi from them and runs everything after CheckInliers as written (the > mnBestInliers rule, Refine on the
+ * best set so far with its strict > mRansacMinInliers, bNoMore).  Same return values, poses, flags and counts, byte for byte, as
+ * evaluating in place, because host and kernel run one body (csrc/orbp_epnp_body.h).  iterate() consumes queued sets before it
+ * draws new ones; a queued set without results is evaluated in place.  Refine (an n-point EPnP) stays on the host.  A solver that
+ * was never drawn ahead behaves as it always did.  orbp_pnp_set_ransac_parameters drops queued sets and attached results.
+ */
+/* The solver as a problem of orbm_pnp_hypotheses: p2d (2n floats), p3d (3n floats), max_err (n: mvMaxError = sigma2 * th2 as the
+ * float CheckInliers compares with), K = {fx, fy, cx, cy}, *min_set = mRansacMinSet.  Returns n. */
+int orbp_pnp_get_problem(const orbp_pnp *s, float *p2d, float *p3d, float *max_err, float *K, int32_t *min_set);
+/* Draws the index sets (min_set indices each) of the iterations a following iterate(n_iterations) consumes beyond the queued
+ * ones: the reference's loop is `while(mnIterations<mRansacMaxIts || nCurrentIterations<nIterations)` (:182), so that call runs
+ * until BOTH counts are reached unless a pose comes back earlier: it consumes max(max_its - iterations_done, n_iterations) sets,
+ * and the number drawn is that less the queued ones (nothing when the queue already covers the call, so calling it twice draws
+ * once).  Nothing is drawn when n < min_inliers (iterate returns at once).
+ * Appends the sets to the queue and to samples (min_set ints per set; may be NULL).  Returns the number of sets drawn, < 0 on bad
+ * arguments. */
+int orbp_pnp_draw(orbp_pnp *s, int n_iterations, int32_t *samples);
+/* The queued, not yet consumed sets (min_set * return value ints into samples when it is not NULL). */
+int orbp_pnp_queued(const orbp_pnp *s, int32_t *samples);
+/* One hypothesis, stateless: R (9, row-major) and t (3) are mRi / mti in double, inliers[n] (0/1) and *n_inliers of the sample of
+ * min_set distinct correspondence indices. */
+int orbp_pnp_hypothesis(const orbp_pnp *s, const int32_t *sample, double *R, double *t, uint8_t *inliers, int *n_inliers);
+/* Results for ALL queued sets, in queue order, in the layout of orbm_pnp_hypotheses: counts[n_hyp], Rt[12 n_hyp] (R row-major,
+ * then t), masks[n_hyp * ceil(n / 32)] (bit i of a hypothesis' words = correspondence i).  n_hyp must equal orbp_pnp_queued(). */
+int orbp_pnp_attach_results(orbp_pnp *s, int n_hyp, const int32_t *counts, const double *Rt, const uint32_t *masks);
 
 /* PnPsolver::compute_pose on n >= 4 correspondences (pws 3n, us 2n doubles): R row-major, t; returns the mean
  * reprojection error of the chosen solution. */

@@ -49,6 +49,10 @@ assert POSE_CAM_DTYPE.itemsize == 20
 # orbm_sim3_camera (include/orbm.h): the two calibrations {fx, fy, cx, cy} and mbFixScale of one problem of sim3_hypotheses
 SIM3_CAM_DTYPE = np.dtype([("K1", "<f4", (4,)), ("K2", "<f4", (4,)), ("fix_scale", "<i4")])
 assert SIM3_CAM_DTYPE.itemsize == 36
+# orbm_pnp_camera (include/orbm.h): the calibration and mRansacMinSet of one problem of pnp_hypotheses
+PNP_CAM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("set_size", "<i4")])
+assert PNP_CAM_DTYPE.itemsize == 20
+ORBM_PNP_MAX_SET = 8
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
@@ -201,9 +205,18 @@ def _bind_pose(L):
     L.orbp_epnp.argtypes = [C.c_int, vp, vp, C.c_double, C.c_double, C.c_double, C.c_double, vp, vp]
     L.orbp_epnp.restype = C.c_double
     L.orbp_pose_optimization.argtypes = [C.c_int, vp, vp, vp, vp, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, vp, vp]
+    L.orbp_pnp_get_problem.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.orbp_pnp_draw.argtypes = [vp, C.c_int, vp]
+    L.orbp_pnp_queued.argtypes = [vp, vp]
+    L.orbp_pnp_hypothesis.argtypes = [vp, vp, vp, vp, vp, ip]
+    L.orbp_pnp_attach_results.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbm_pnp_hypotheses.argtypes = [vp, C.c_int] + [vp] * 11
+    L.orbm_pnp_hypotheses_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
+    L.orbm_pnp_hypotheses.restype = L.orbm_pnp_hypotheses_device.restype = C.c_int
     L.orbp_last_error.restype = C.c_char_p
     for name in ("orbp_pnp_create", "orbp_pnp_set_ransac_parameters", "orbp_pnp_iterate", "orbp_pnp_find",
-                 "orbp_pose_optimization"):
+                 "orbp_pose_optimization", "orbp_pnp_get_problem", "orbp_pnp_draw", "orbp_pnp_queued", "orbp_pnp_hypothesis",
+                 "orbp_pnp_attach_results"):
         getattr(L, name).restype = C.c_int
 
 
@@ -904,6 +917,74 @@ class ORBmatcher:
                                                  ptr(max_err2), ptr(cams), ptr(hyp_off), ptr(triples), ptr(mask_off), ptr(n_inliers),
                                                  ptr(sRt), ptr(masks), s))
 
+    @staticmethod
+    def pack_pnp_problems(problems):
+        """The arrays of orbm_pnp_hypotheses from a list of problems, each a PnPsolver (its queued samples) or a tuple
+        (p2d [n, 2], p3d [n, 3], max_err [n], K (fx, fy, cx, cy), set_size, samples [h, set_size]) ->
+        (off int32 [B+1], p2d float32 [N, 2], p3d float32 [N, 3], max_err float32 [N], cams PNP_CAM_DTYPE [B], hyp_off int32 [B+1],
+        samples int32 [H, 8] (padded with -1), mask_off int64 [B+1])."""
+        B = len(problems)
+        off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
+        cams = np.zeros(B, PNP_CAM_DTYPE)
+        p2s, p3s, es, sms = [], [], [], []
+        for p, pr in enumerate(problems):
+            if isinstance(pr, PnPsolver):
+                pr = pr.problem()
+            p2d, p3d, e, K, set_size, sm = pr
+            p2d = np.ascontiguousarray(p2d, np.float32).reshape(-1, 2)
+            p3d = np.ascontiguousarray(p3d, np.float32).reshape(-1, 3)
+            e = np.ascontiguousarray(e, np.float32).reshape(-1)
+            set_size = int(set_size)
+            sm = np.ascontiguousarray(sm, np.int32).reshape(-1, set_size) if set_size > 0 else np.zeros((0, 0), np.int32)
+            if not (len(p2d) == len(p3d) == len(e)):
+                raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %d / %d / %d" % (p, len(p2d), len(p3d), len(e)))
+            padded = np.full((len(sm), ORBM_PNP_MAX_SET), -1, np.int32)
+            k = min(set_size, ORBM_PNP_MAX_SET)      # a larger set is refused by the call (cams carries its true size)
+            padded[:, :k] = sm[:, :k]
+            p2s.append(p2d); p3s.append(p3d); es.append(e); sms.append(padded)
+            off[p + 1] = off[p] + len(p2d)
+            hyp_off[p + 1] = hyp_off[p] + len(sm)
+            mask_off[p + 1] = mask_off[p] + len(sm) * ((len(p2d) + 31) // 32)
+            K = np.asarray(K, np.float32).reshape(4)
+            cams[p] = (K[0], K[1], K[2], K[3], set_size)
+        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(shape, dt)
+        return (off, cat(p2s, (0, 2), np.float32), cat(p3s, (0, 3), np.float32), cat(es, (0,), np.float32), cams, hyp_off,
+                cat(sms, (0, ORBM_PNP_MAX_SET), np.int32), mask_off)
+
+    def pnp_hypotheses(self, problems):
+        """Every EPnP hypothesis of every problem in one launch (orbm_pnp_hypotheses; problems as in pack_pnp_problems).  Returns a
+        list of (n_inliers int32 [h], Rt float64 [h, 12], masks uint32 [h, ceil(n / 32)]) per problem: what
+        PnPsolver.attach_results takes."""
+        off, p2d, p3d, e, cams, hyp_off, sm, mask_off = self.pack_pnp_problems(problems)
+        B, H, MW = len(problems), int(hyp_off[-1]), int(mask_off[-1])
+        cnt, Rt, masks = np.zeros(max(H, 1), np.int32), np.zeros((max(H, 1), 12), np.float64), np.zeros(max(MW, 1), np.uint32)
+        _mchk(self.L.orbm_pnp_hypotheses(self.h, B, _p(off), _p(p2d), _p(p3d), _p(e), _p(cams), _p(hyp_off), _p(sm), _p(mask_off),
+                                         _p(cnt), _p(Rt), _p(masks)))
+        out = []
+        for p in range(B):
+            h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
+            W = (int(off[p + 1]) - int(off[p]) + 31) // 32
+            out.append((cnt[h0:h1].copy(), Rt[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
+        return out
+
+    def pnp_hypotheses_device(self, n_problems, total_hypotheses, off, p2d, p3d, max_err, cams, hyp_off, samples, mask_off, n_inliers, Rt,
+                              masks, stream=None):
+        """The same on torch tensors on the handle's device: off int32 [B+1], p2d float32 [N, 2], p3d float32 [N, 3], max_err float32
+        [N], cams uint8 [B, 20] (PNP_CAM_DTYPE bytes), hyp_off int32 [B+1], samples int32 [H, 8], mask_off int64 [B+1], n_inliers
+        int32 [H], Rt float64 [H, 12], masks int32 [mask words].  Nothing is copied or synchronised; stream: a torch stream, a raw
+        hipStream_t or None (the handle's stream)."""
+        import torch
+        want = ((off, torch.int32), (p2d, torch.float32), (p3d, torch.float32), (max_err, torch.float32), (cams, torch.uint8),
+                (hyp_off, torch.int32), (samples, torch.int32), (mask_off, torch.int64), (n_inliers, torch.int32), (Rt, torch.float64),
+                (masks, torch.int32))
+        for t, dt in want:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise OrbxError(ORBX_E_INVALID, "pnp_hypotheses_device wants contiguous device tensors of the documented dtypes")
+        s = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _mchk(self.L.orbm_pnp_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(p2d), ptr(p3d), ptr(max_err), ptr(cams),
+                                                ptr(hyp_off), ptr(samples), ptr(mask_off), ptr(n_inliers), ptr(Rt), ptr(masks), s))
+
     def search_local_points(self, view, skip, xw, normal, mf_max, mf_min, mp_desc, mp_obs, kps_cur, desc_cur, cur_obs, th,
                             u_right=None, viewing_cos_limit=0.5):
         """Tracking::SearchLocalPoints (src/Tracking.cc:1174-1199) in one call: frustum() followed by SearchByProjectionMap() on the
@@ -1472,6 +1553,86 @@ class PnPsolver:
         st = self.ransac_state()
         T, _, inl, n = self.iterate(st["max_its"])
         return T, inl, n
+
+    def _problem(self):
+        n = max(self.N, 1)
+        p2d, p3d, e = np.zeros((n, 2), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+        K, ms = np.zeros(4, np.float32), C.c_int32()
+        _pchk(self.L.orbp_pnp_get_problem(self.h, _p(p2d), _p(p3d), _p(e), _p(K), C.byref(ms)))
+        return p2d[:self.N], p3d[:self.N], e[:self.N], K, ms.value
+
+    @property
+    def min_set(self):
+        return self._problem()[4]
+
+    def max_errors(self):
+        """mvMaxError = sigma2 * th2 as the floats CheckInliers compares with"""
+        return self._problem()[2]
+
+    def draw(self, nIterations):
+        """The index sets (int32 [k, min_set]) of the iterations a following iterate(nIterations) consumes beyond the queued ones,
+        k = max(max_its - iterations, nIterations) - queued because of the reference's `||` loop: drawn now, consumed by iterate()"""
+        st, ms = self.ransac_state(), self.min_set
+        room = max(st["max_its"] - st["iterations"], nIterations, 1)
+        sm = np.zeros((room, ms), np.int32)
+        k = _pchk(self.L.orbp_pnp_draw(self.h, nIterations, _p(sm)))
+        return sm[:k].copy()
+
+    def queued(self):
+        ms = self.min_set
+        k = _pchk(self.L.orbp_pnp_queued(self.h, None))
+        sm = np.zeros((max(k, 1), ms), np.int32)
+        _pchk(self.L.orbp_pnp_queued(self.h, _p(sm)))
+        return sm[:k].copy()
+
+    def problem(self):
+        """This solver as a problem of ORBmatcher.pnp_hypotheses: its correspondences and its queued samples"""
+        p2d, p3d, e, K, ms = self._problem()
+        return p2d, p3d, e, K, ms, self.queued()
+
+    def hypothesis(self, sample):
+        """One hypothesis on the host -> (R 3x3 float64, t (3) float64, inliers bool[N], nInliers)"""
+        sm = np.ascontiguousarray(sample, np.int32).reshape(-1)
+        if len(sm) != self.min_set:
+            raise OrbxError(ORBX_E_INVALID, "a sample of %d indices for min_set %d" % (len(sm), self.min_set))
+        R, t, n = np.zeros(9), np.zeros(3), C.c_int()
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        _pchk(self.L.orbp_pnp_hypothesis(self.h, _p(sm), _p(R), _p(t), _p(inl), C.byref(n)))
+        return R.reshape(3, 3), t, inl[:self.N].astype(bool), n.value
+
+    def hypotheses(self, samples):
+        """hypothesis() for each sample, in the layout of ORBmatcher.pnp_hypotheses: (n_inliers [h], Rt [h, 12], masks [h, W])"""
+        samples = np.asarray(samples, np.int32).reshape(-1, self.min_set)
+        W = (self.N + 31) // 32
+        cnt, Rt, masks = np.zeros(len(samples), np.int32), np.zeros((len(samples), 12)), np.zeros((len(samples), W), np.uint32)
+        for k, sm in enumerate(samples):
+            R, t, inl, n = self.hypothesis(sm)
+            cnt[k] = n
+            Rt[k, :9], Rt[k, 9:] = R.reshape(9), t
+            bits = np.zeros(W * 32, np.uint8)
+            bits[:self.N] = inl
+            masks[k] = np.packbits(bits, bitorder="little").view("<u4")
+        return cnt, Rt, masks
+
+    def attach_results(self, n_inliers, Rt, masks):
+        cnt = np.ascontiguousarray(n_inliers, np.int32).reshape(-1)
+        Rt = np.ascontiguousarray(Rt, np.float64).reshape(-1)
+        masks = np.ascontiguousarray(masks, np.uint32).reshape(-1)
+        W = (self.N + 31) // 32
+        if len(Rt) != 12 * len(cnt) or len(masks) != W * len(cnt):
+            raise OrbxError(ORBX_E_INVALID, "results of %d hypotheses: %d doubles, %d mask words" % (len(cnt), len(Rt), len(masks)))
+        _pchk(self.L.orbp_pnp_attach_results(self.h, len(cnt), _p(cnt), _p(Rt), _p(masks)))
+
+    @staticmethod
+    def EvaluateAll(solvers, matcher, n_iterations=5):
+        """Tracking::Relocalization's batch step: draws for every solver what its next iterate(n_iterations) consumes (solver by
+        solver; None entries and solvers with min_set > 8 are skipped and stay on the host), evaluates all of it in ONE
+        ORBmatcher.pnp_hypotheses call and attaches the results, so that the iterations that follow are replays."""
+        live = [s for s in solvers if s is not None and s.min_set <= ORBM_PNP_MAX_SET]
+        for s in live:
+            s.draw(n_iterations)
+        for s, res in zip(live, matcher.pnp_hypotheses(live)):
+            s.attach_results(*res)
 
 
 class Sim3Solver:

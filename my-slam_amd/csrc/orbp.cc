@@ -1,6 +1,7 @@
 // orbp.cc -- host-side pose solvers behind include/orbp.h (EPnP RANSAC + motion-only pose optimisation).
-// Plain C++, fp64, no device code: SURVEY keeps these "tiny dense solves" on the host.  Each function names the
-// reference lines it follows; the linear algebra the reference borrows from OpenCV / Eigen is written here.
+// Plain C++, fp64, no device code.  Each function names the reference lines it follows; the linear algebra the reference borrows
+// from OpenCV / Eigen is written here.  One EPnP hypothesis (csrc/orbp_epnp_body.h) is shared with the kernel of orbm_pnp.hip, which
+// evaluates the hypotheses of all Relocalization candidates at once; the RANSAC state machine, Refine and PoseOptimization stay here.
 #include <algorithm>
 #include <cfloat>
 #include <climits>
@@ -12,6 +13,7 @@
 #include <vector>
 #include "../../include/orbp.h"
 #include "../../include/orbx.h"
+#include "orbp_epnp_body.h"
 #include "orbp_internal.h"
 
 static thread_local char g_perr[256] = "";
@@ -27,136 +29,14 @@ extern "C" const char *orbp_last_error(void) { return g_perr; }
 void orbp_set_error(const char *text) { snprintf(g_perr, sizeof g_perr, "%s", text); }
 
 // -------------------------------------------------------------------------------------------------
-// Small dense linear algebra (row-major)
-// -------------------------------------------------------------------------------------------------
-// One-sided (Hestenes) Jacobi SVD of A (m x n, m >= n): A = U diag(W) V^T, W descending, U m x n, V n x n.
-// Columns of U that belong to a zero singular value are left zero; V is always orthonormal.
-static void jacobi_svd(const double *A, int m, int n, double *U, double *W, double *V)
-{
-    std::vector<double> B(A, A + (size_t)m * n);
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < n; j++) V[i * n + j] = i == j;
-    for (int sweep = 0; sweep < 60; sweep++) {
-        bool rotated = false;
-        for (int p = 0; p < n - 1; p++)
-            for (int q = p + 1; q < n; q++) {
-                double a = 0, b = 0, g = 0;
-                for (int i = 0; i < m; i++) {
-                    const double x = B[i * n + p], y = B[i * n + q];
-                    a += x * x; b += y * y; g += x * y;
-                }
-                if (std::fabs(g) <= DBL_EPSILON * std::sqrt(a * b) || g == 0.0) continue;
-                rotated = true;
-                const double zeta = (b - a) / (2.0 * g);
-                const double t = (zeta >= 0 ? 1.0 : -1.0) / (std::fabs(zeta) + std::sqrt(1.0 + zeta * zeta));
-                const double c = 1.0 / std::sqrt(1.0 + t * t), s = c * t;
-                for (int i = 0; i < m; i++) {
-                    const double x = B[i * n + p], y = B[i * n + q];
-                    B[i * n + p] = c * x - s * y;
-                    B[i * n + q] = s * x + c * y;
-                }
-                for (int i = 0; i < n; i++) {
-                    const double x = V[i * n + p], y = V[i * n + q];
-                    V[i * n + p] = c * x - s * y;
-                    V[i * n + q] = s * x + c * y;
-                }
-            }
-        if (!rotated) break;
-    }
-    std::vector<double> w(n);
-    std::vector<int> order(n);
-    for (int j = 0; j < n; j++) {
-        double s = 0;
-        for (int i = 0; i < m; i++) s += B[i * n + j] * B[i * n + j];
-        w[j] = std::sqrt(s);
-        order[j] = j;
-    }
-    std::stable_sort(order.begin(), order.end(), [&](int x, int y) { return w[x] > w[y]; });
-    std::vector<double> Vs((size_t)n * n);
-    for (int k = 0; k < n; k++) {
-        const int j = order[k];
-        W[k] = w[j];
-        for (int i = 0; i < m; i++) U[i * n + k] = w[j] > 0 ? B[i * n + j] / w[j] : 0.0;
-        for (int i = 0; i < n; i++) Vs[i * n + k] = V[i * n + j];
-    }
-    memcpy(V, Vs.data(), sizeof(double) * n * n);
-}
-
-// x = pinv(A) b through the SVD, singular values below 2 eps sum(w) dropped (cvSolve / cvInvert with CV_SVD).
-static void svd_solve(const double *A, int m, int n, const double *b, int nrhs, double *x)
-{
-    std::vector<double> U((size_t)m * n), W(n), V((size_t)n * n);
-    jacobi_svd(A, m, n, U.data(), W.data(), V.data());
-    double thr = 0;
-    for (int i = 0; i < n; i++) thr += W[i];
-    thr *= 2 * DBL_EPSILON;
-    for (int r = 0; r < nrhs; r++) {
-        for (int i = 0; i < n; i++) x[i * nrhs + r] = 0;
-        for (int k = 0; k < n; k++) {
-            if (!(W[k] > thr)) continue;
-            double s = 0;
-            for (int i = 0; i < m; i++) s += U[i * n + k] * b[i * nrhs + r];
-            s /= W[k];
-            for (int i = 0; i < n; i++) x[i * nrhs + r] += V[i * n + k] * s;
-        }
-    }
-}
-
-static inline double dot3(const double *a, const double *b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
-static inline double dist2_3(const double *a, const double *b)
-{
-    return (a[0] - b[0]) * (a[0] - b[0]) + (a[1] - b[1]) * (a[1] - b[1]) + (a[2] - b[2]) * (a[2] - b[2]);
-}
-
-// Householder QR least squares for the 6 x 4 Gauss-Newton system (PnPsolver.cc:878-957: scaled columns, R's diagonal
-// kept aside).  Returns false on a zero column, which leaves x untouched like the reference's early return.
-static bool qr_solve_6x4(double *A, double *b, double *x)
-{
-    const int nr = 6, nc = 4;
-    double a1[4], a2[4];
-    for (int k = 0; k < nc; k++) {
-        double eta = 0;
-        for (int i = k; i < nr; i++) eta = std::max(eta, std::fabs(A[i * nc + k]));
-        if (eta == 0) return false;
-        double sum = 0;
-        const double inv_eta = 1. / eta;
-        for (int i = k; i < nr; i++) { A[i * nc + k] *= inv_eta; sum += A[i * nc + k] * A[i * nc + k]; }
-        double sigma = std::sqrt(sum);
-        if (A[k * nc + k] < 0) sigma = -sigma;
-        A[k * nc + k] += sigma;
-        a1[k] = sigma * A[k * nc + k];
-        a2[k] = -eta * sigma;
-        for (int j = k + 1; j < nc; j++) {
-            double s = 0;
-            for (int i = k; i < nr; i++) s += A[i * nc + k] * A[i * nc + j];
-            const double tau = s / a1[k];
-            for (int i = k; i < nr; i++) A[i * nc + j] -= tau * A[i * nc + k];
-        }
-    }
-    for (int j = 0; j < nc; j++) {          // b <- Q^T b
-        double tau = 0;
-        for (int i = j; i < nr; i++) tau += A[i * nc + j] * b[i];
-        tau /= a1[j];
-        for (int i = j; i < nr; i++) b[i] -= tau * A[i * nc + j];
-    }
-    x[nc - 1] = b[nc - 1] / a2[nc - 1];     // back substitution
-    for (int i = nc - 2; i >= 0; i--) {
-        double s = 0;
-        for (int j = i + 1; j < nc; j++) s += A[i * nc + j] * x[j];
-        x[i] = (b[i] - s) / a2[i];
-    }
-    return true;
-}
-
-// -------------------------------------------------------------------------------------------------
-// EPnP (PnPsolver.cc:346-876)
+// EPnP (PnPsolver.cc:346-957): the arithmetic is csrc/orbp_epnp_body.h, the text the kernel of orbm_pnp.hip runs as well.
+// This wrapper owns the per-point arrays of an n-point solve (Refine, orbp_epnp); a RANSAC sample uses the same path.
 // -------------------------------------------------------------------------------------------------
 namespace {
 struct Epnp {
     double fu, fv, uc, vc;
     int n = 0;
     std::vector<double> pws, us, alphas, pcs;
-    double cws[4][3], ccs[4][3];
 
     void reset() { n = 0; pws.clear(); us.clear(); }
     void add(double X, double Y, double Z, double u, double v)
@@ -165,262 +45,15 @@ struct Epnp {
         us.push_back(u); us.push_back(v);
         n++;
     }
-
-    void choose_control_points()             // :346-384
-    {
-        for (int j = 0; j < 3; j++) cws[0][j] = 0;
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < 3; j++) cws[0][j] += pws[3 * i + j];
-        for (int j = 0; j < 3; j++) cws[0][j] /= n;
-        double c[9] = {0};
-        for (int i = 0; i < n; i++) {
-            double d[3];
-            for (int j = 0; j < 3; j++) d[j] = pws[3 * i + j] - cws[0][j];
-            for (int r = 0; r < 3; r++)
-                for (int s = 0; s < 3; s++) c[3 * r + s] += d[r] * d[s];
-        }
-        double U[9], W[3], V[9];
-        jacobi_svd(c, 3, 3, U, W, V);        // symmetric PSD: V holds the principal axes
-        for (int i = 1; i < 4; i++) {
-            // The sign of a principal axis is the SVD routine's choice (OpenCV's in the reference) and, with noisy
-            // points, changes which local minimum the betas reach.  Fixed here: largest component positive.
-            int big = 0;
-            for (int j = 1; j < 3; j++)
-                if (std::fabs(V[3 * j + (i - 1)]) > std::fabs(V[3 * big + (i - 1)])) big = j;
-            const double sgn = V[3 * big + (i - 1)] < 0 ? -1.0 : 1.0;
-            const double k = sgn * std::sqrt(W[i - 1] / n);
-            for (int j = 0; j < 3; j++) cws[i][j] = cws[0][j] + k * V[3 * j + (i - 1)];
-        }
-    }
-
-    void compute_barycentric_coordinates()   // :386-412
-    {
-        double cc[9], ci[9], eye[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        for (int i = 0; i < 3; i++)
-            for (int j = 1; j < 4; j++) cc[3 * i + j - 1] = cws[j][i] - cws[0][i];
-        svd_solve(cc, 3, 3, eye, 3, ci);     // pseudo-inverse (cvInvert CV_SVD)
-        alphas.resize((size_t)4 * n);
-        for (int i = 0; i < n; i++) {
-            const double *pi = &pws[3 * i];
-            double *a = &alphas[4 * i];
-            for (int j = 0; j < 3; j++)
-                a[1 + j] = ci[3 * j] * (pi[0] - cws[0][0]) + ci[3 * j + 1] * (pi[1] - cws[0][1]) + ci[3 * j + 2] * (pi[2] - cws[0][2]);
-            a[0] = 1.0f - a[1] - a[2] - a[3];
-        }
-    }
-
-    void compute_ccs(const double *betas, const double *vt)    // :431-444; vt row r = r-th singular vector
-    {
-        for (int i = 0; i < 4; i++) ccs[i][0] = ccs[i][1] = ccs[i][2] = 0.0;
-        for (int i = 0; i < 4; i++) {
-            const double *v = vt + 12 * (11 - i);
-            for (int j = 0; j < 4; j++)
-                for (int k = 0; k < 3; k++) ccs[j][k] += betas[i] * v[3 * j + k];
-        }
-    }
-
-    void compute_pcs()                        // :446-456
-    {
-        pcs.resize((size_t)3 * n);
-        for (int i = 0; i < n; i++) {
-            const double *a = &alphas[4 * i];
-            for (int j = 0; j < 3; j++)
-                pcs[3 * i + j] = a[0] * ccs[0][j] + a[1] * ccs[1][j] + a[2] * ccs[2][j] + a[3] * ccs[3][j];
-        }
-    }
-
-    void solve_for_sign()                     // :610-624
-    {
-        if (pcs[2] < 0.0) {
-            for (int i = 0; i < 4; i++)
-                for (int j = 0; j < 3; j++) ccs[i][j] = -ccs[i][j];
-            for (size_t i = 0; i < pcs.size(); i++) pcs[i] = -pcs[i];
-        }
-    }
-
-    double reprojection_error(const double R[3][3], const double t[3]) const     // :528-546
-    {
-        double sum = 0.0;
-        for (int i = 0; i < n; i++) {
-            const double *pw = &pws[3 * i];
-            const double Xc = dot3(R[0], pw) + t[0], Yc = dot3(R[1], pw) + t[1];
-            const double inv_Zc = 1.0 / (dot3(R[2], pw) + t[2]);
-            const double ue = uc + fu * Xc * inv_Zc, ve = vc + fv * Yc * inv_Zc;
-            const double u = us[2 * i], v = us[2 * i + 1];
-            sum += std::sqrt((u - ue) * (u - ue) + (v - ve) * (v - ve));
-        }
-        return sum / n;
-    }
-
-    void estimate_R_and_t(double R[3][3], double t[3]) const     // :548-601 (absolute orientation, Arun et al.)
-    {
-        double pc0[3] = {0, 0, 0}, pw0[3] = {0, 0, 0};
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < 3; j++) { pc0[j] += pcs[3 * i + j]; pw0[j] += pws[3 * i + j]; }
-        for (int j = 0; j < 3; j++) { pc0[j] /= n; pw0[j] /= n; }
-        double abt[9] = {0};
-        for (int i = 0; i < n; i++)
-            for (int j = 0; j < 3; j++)
-                for (int k = 0; k < 3; k++) abt[3 * j + k] += (pcs[3 * i + j] - pc0[j]) * (pws[3 * i + k] - pw0[k]);
-        double U[9], W[3], V[9];
-        jacobi_svd(abt, 3, 3, U, W, V);
-        if (!(W[2] > 2 * DBL_EPSILON * (W[0] + W[1] + W[2]))) {
-            // rank-deficient (coplanar points): complete U to an orthonormal basis.  In OpenCV's Jacobi SVD the third
-            // left vector is what rounding noise leaves after orthogonalisation against the other two, i.e. +-(u1 x u2)
-            // with a sign nobody chose; the reference is implementation-defined here.
-            const double a[3] = {U[0], U[3], U[6]}, b[3] = {U[1], U[4], U[7]};
-            U[2] = a[1] * b[2] - a[2] * b[1]; U[5] = a[2] * b[0] - a[0] * b[2]; U[8] = a[0] * b[1] - a[1] * b[0];
-        }
-        for (int i = 0; i < 3; i++)
-            for (int j = 0; j < 3; j++) R[i][j] = U[3 * i] * V[3 * j] + U[3 * i + 1] * V[3 * j + 1] + U[3 * i + 2] * V[3 * j + 2];
-        const double det = R[0][0] * R[1][1] * R[2][2] + R[0][1] * R[1][2] * R[2][0] + R[0][2] * R[1][0] * R[2][1] -
-                           R[0][2] * R[1][1] * R[2][0] - R[0][1] * R[1][0] * R[2][2] - R[0][0] * R[1][2] * R[2][1];
-        if (det < 0) { R[2][0] = -R[2][0]; R[2][1] = -R[2][1]; R[2][2] = -R[2][2]; }
-        for (int j = 0; j < 3; j++) t[j] = pc0[j] - dot3(R[j], pw0);
-    }
-
-    double compute_R_and_t(const double *vt, const double *betas, double R[3][3], double t[3])     // :626-637
-    {
-        compute_ccs(betas, vt);
-        compute_pcs();
-        solve_for_sign();
-        estimate_R_and_t(R, t);
-        return reprojection_error(R, t);
-    }
-
-    // betas10 = [B11 B12 B22 B13 B23 B33 B14 B24 B34 B44]; the three linearisations :639-757
-    static void sub_solve(const double *L, const double *rho, const int *cols, int nc, double *out)
-    {
-        double A[6 * 5];
-        for (int i = 0; i < 6; i++)
-            for (int j = 0; j < nc; j++) A[i * nc + j] = L[10 * i + cols[j]];
-        svd_solve(A, 6, nc, rho, 1, out);
-    }
-    static void find_betas_approx_1(const double *L, const double *rho, double *betas)
-    {
-        const int cols[4] = {0, 1, 3, 6};
-        double b4[4];
-        sub_solve(L, rho, cols, 4, b4);
-        if (b4[0] < 0) {
-            betas[0] = std::sqrt(-b4[0]);
-            betas[1] = -b4[1] / betas[0]; betas[2] = -b4[2] / betas[0]; betas[3] = -b4[3] / betas[0];
-        } else {
-            betas[0] = std::sqrt(b4[0]);
-            betas[1] = b4[1] / betas[0]; betas[2] = b4[2] / betas[0]; betas[3] = b4[3] / betas[0];
-        }
-    }
-    static void find_betas_approx_2(const double *L, const double *rho, double *betas)
-    {
-        const int cols[3] = {0, 1, 2};
-        double b3[3];
-        sub_solve(L, rho, cols, 3, b3);
-        if (b3[0] < 0) {
-            betas[0] = std::sqrt(-b3[0]);
-            betas[1] = (b3[2] < 0) ? std::sqrt(-b3[2]) : 0.0;
-        } else {
-            betas[0] = std::sqrt(b3[0]);
-            betas[1] = (b3[2] > 0) ? std::sqrt(b3[2]) : 0.0;
-        }
-        if (b3[1] < 0) betas[0] = -betas[0];
-        betas[2] = 0.0; betas[3] = 0.0;
-    }
-    static void find_betas_approx_3(const double *L, const double *rho, double *betas)
-    {
-        const int cols[5] = {0, 1, 2, 3, 4};
-        double b5[5];
-        sub_solve(L, rho, cols, 5, b5);
-        if (b5[0] < 0) {
-            betas[0] = std::sqrt(-b5[0]);
-            betas[1] = (b5[2] < 0) ? std::sqrt(-b5[2]) : 0.0;
-        } else {
-            betas[0] = std::sqrt(b5[0]);
-            betas[1] = (b5[2] > 0) ? std::sqrt(b5[2]) : 0.0;
-        }
-        if (b5[1] < 0) betas[0] = -betas[0];
-        betas[2] = b5[3] / betas[0];
-        betas[3] = 0.0;
-    }
-
-    static void compute_L_6x10(const double *vt, double *L)      // :760-801
-    {
-        const double *v[4] = {vt + 12 * 11, vt + 12 * 10, vt + 12 * 9, vt + 12 * 8};
-        double dv[4][6][3];
-        for (int i = 0; i < 4; i++) {
-            int a = 0, b = 1;
-            for (int j = 0; j < 6; j++) {
-                for (int k = 0; k < 3; k++) dv[i][j][k] = v[i][3 * a + k] - v[i][3 * b + k];
-                if (++b > 3) { a++; b = a + 1; }
-            }
-        }
-        for (int i = 0; i < 6; i++) {
-            double *row = L + 10 * i;
-            row[0] = dot3(dv[0][i], dv[0][i]);
-            row[1] = 2.0f * dot3(dv[0][i], dv[1][i]);
-            row[2] = dot3(dv[1][i], dv[1][i]);
-            row[3] = 2.0f * dot3(dv[0][i], dv[2][i]);
-            row[4] = 2.0f * dot3(dv[1][i], dv[2][i]);
-            row[5] = dot3(dv[2][i], dv[2][i]);
-            row[6] = 2.0f * dot3(dv[0][i], dv[3][i]);
-            row[7] = 2.0f * dot3(dv[1][i], dv[3][i]);
-            row[8] = 2.0f * dot3(dv[2][i], dv[3][i]);
-            row[9] = dot3(dv[3][i], dv[3][i]);
-        }
-    }
-
-    static void gauss_newton(const double *L, const double *rho, double *be)      // :813-876
-    {
-        for (int k = 0; k < 5; k++) {
-            double A[24], b[6], x[4] = {0, 0, 0, 0};
-            for (int i = 0; i < 6; i++) {
-                const double *r = L + 10 * i;
-                double *a = A + 4 * i;
-                a[0] = 2 * r[0] * be[0] + r[1] * be[1] + r[3] * be[2] + r[6] * be[3];
-                a[1] = r[1] * be[0] + 2 * r[2] * be[1] + r[4] * be[2] + r[7] * be[3];
-                a[2] = r[3] * be[0] + r[4] * be[1] + 2 * r[5] * be[2] + r[8] * be[3];
-                a[3] = r[6] * be[0] + r[7] * be[1] + r[8] * be[2] + 2 * r[9] * be[3];
-                b[i] = rho[i] - (r[0] * be[0] * be[0] + r[1] * be[0] * be[1] + r[2] * be[1] * be[1] + r[3] * be[0] * be[2] +
-                                 r[4] * be[1] * be[2] + r[5] * be[2] * be[2] + r[6] * be[0] * be[3] + r[7] * be[1] * be[3] +
-                                 r[8] * be[2] * be[3] + r[9] * be[3] * be[3]);
-            }
-            if (!qr_solve_6x4(A, b, x)) continue;    // singular column: the reference leaves X as it was
-            for (int i = 0; i < 4; i++) be[i] += x[i];
-        }
-    }
-
     double compute_pose(double R[3][3], double t[3])       // :458-508
     {
-        choose_control_points();
-        compute_barycentric_coordinates();
-        double mtm[144] = {0};
-        for (int i = 0; i < n; i++) {        // rows of M (:414-429) accumulated straight into M^T M
-            const double *as = &alphas[4 * i];
-            const double u = us[2 * i], v = us[2 * i + 1];
-            double m1[12], m2[12];
-            for (int j = 0; j < 4; j++) {
-                m1[3 * j] = as[j] * fu; m1[3 * j + 1] = 0.0; m1[3 * j + 2] = as[j] * (uc - u);
-                m2[3 * j] = 0.0; m2[3 * j + 1] = as[j] * fv; m2[3 * j + 2] = as[j] * (vc - v);
-            }
-            for (int r = 0; r < 12; r++)
-                for (int c = 0; c < 12; c++) mtm[12 * r + c] += m1[r] * m1[c] + m2[r] * m2[c];
-        }
-        double U[144], W[12], V[144], vt[144];
-        jacobi_svd(mtm, 12, 12, U, W, V);    // symmetric PSD: eigenvectors = columns of V, eigenvalues descending
-        for (int r = 0; r < 12; r++)
-            for (int c = 0; c < 12; c++) vt[12 * r + c] = V[12 * c + r];
-        double L[60], rho[6];
-        compute_L_6x10(vt, L);
-        rho[0] = dist2_3(cws[0], cws[1]); rho[1] = dist2_3(cws[0], cws[2]); rho[2] = dist2_3(cws[0], cws[3]);
-        rho[3] = dist2_3(cws[1], cws[2]); rho[4] = dist2_3(cws[1], cws[3]); rho[5] = dist2_3(cws[2], cws[3]);
-        double Betas[4][4], err[4], Rs[4][3][3], ts[4][3];
-        find_betas_approx_1(L, rho, Betas[1]); gauss_newton(L, rho, Betas[1]); err[1] = compute_R_and_t(vt, Betas[1], Rs[1], ts[1]);
-        find_betas_approx_2(L, rho, Betas[2]); gauss_newton(L, rho, Betas[2]); err[2] = compute_R_and_t(vt, Betas[2], Rs[2], ts[2]);
-        find_betas_approx_3(L, rho, Betas[3]); gauss_newton(L, rho, Betas[3]); err[3] = compute_R_and_t(vt, Betas[3], Rs[3], ts[3]);
-        int N = 1;
-        if (err[2] < err[1]) N = 2;
-        if (err[3] < err[N]) N = 3;
-        memcpy(R, Rs[N], sizeof(double) * 9);
-        memcpy(t, ts[N], sizeof(double) * 3);
-        return err[N];
+        alphas.resize((size_t)4 * n);
+        pcs.resize((size_t)3 * n);
+        EpnpProblem p;
+        p.fu = fu; p.fv = fv; p.uc = uc; p.vc = vc; p.n = n;
+        p.pws = pws.data(); p.us = us.data(); p.alphas = alphas.data(); p.pcs = pcs.data();
+        EpnpWork wk;
+        return epnp_compute_pose(p, wk, &R[0][0], t);
     }
 };
 }   // namespace
@@ -467,23 +100,41 @@ struct orbp_pnp {
             T[4 * i + 3] = (float)ti[i];
         }
     }
+    // drawn, not yet consumed samples: queue[min_set * head ..]; att_n of them, from queue entry att_base on, have results
+    std::vector<int32_t> queue; size_t head = 0;
+    size_t att_base = 0, att_n = 0;
+    std::vector<int32_t> att_counts; std::vector<double> att_Rt; std::vector<uint32_t> att_masks;
+
+    int words() const { return (N + 31) / 32; }
+    size_t queued() const { return queue.size() / (size_t)min_set - head; }
+    void clear_queue() { queue.clear(); head = 0; att_base = att_n = 0; att_counts.clear(); att_Rt.clear(); att_masks.clear(); }
+    void draw_one(int32_t *idx)               // draw without replacement (:193-204)
+    {
+        std::vector<int> avail(N);
+        for (int i = 0; i < N; i++) avail[i] = i;
+        for (int i = 0; i < min_set; ++i) {
+            const int r = random_int(0, (int)avail.size() - 1);
+            idx[i] = avail[r];
+            avail[r] = avail.back();
+            avail.pop_back();
+        }
+    }
     void check_inliers()                      // :312-344, with its float/double mix
     {
         n_inl_i = 0;
         for (int i = 0; i < N; i++) {
-            const float X = p3d[3 * i], Y = p3d[3 * i + 1], Z = p3d[3 * i + 2];
-            const float Xc = (float)(Ri[0][0] * X + Ri[0][1] * Y + Ri[0][2] * Z + ti[0]);
-            const float Yc = (float)(Ri[1][0] * X + Ri[1][1] * Y + Ri[1][2] * Z + ti[1]);
-            const float invZc = (float)(1 / (Ri[2][0] * X + Ri[2][1] * Y + Ri[2][2] * Z + ti[2]));
-            const double ue = e.uc + e.fu * Xc * invZc;
-            const double ve = e.vc + e.fv * Yc * invZc;
-            const float dx = (float)(p2d[2 * i] - ue), dy = (float)(p2d[2 * i + 1] - ve);
-            const float error2 = dx * dx + dy * dy;
-            inl_i[i] = error2 < max_error[i];
+            inl_i[i] = epnp_check_one(&Ri[0][0], ti, e.fu, e.fv, e.uc, e.vc, &p3d[3 * (size_t)i], &p2d[2 * (size_t)i], max_error[i]);
             n_inl_i += inl_i[i];
         }
     }
     void add_corr(int idx) { e.add(p3d[3 * idx], p3d[3 * idx + 1], p3d[3 * idx + 2], p2d[2 * idx], p2d[2 * idx + 1]); }
+    void evaluate(const int32_t *idx)         // compute_pose on the sample + CheckInliers -> Ri, ti, inl_i, n_inl_i (:206-210)
+    {
+        e.reset();
+        for (int i = 0; i < min_set; i++) add_corr(idx[i]);
+        e.compute_pose(Ri, ti);
+        check_inliers();
+    }
     bool refine()                             // :260-309
     {
         e.reset();
@@ -503,6 +154,7 @@ extern "C" int orbp_pnp_set_ransac_parameters(orbp_pnp *s, double probability, i
 {
     if (!s) return pfail(ORBX_E_INVALID, "solver is NULL");
     if (min_set < 4) return pfail(ORBX_E_INVALID, "min_set %d < 4: EPnP needs four points", min_set);
+    s->clear_queue();                          // samples drawn ahead belong to the old parameters
     s->prob = probability; s->min_inliers = min_inliers; s->max_its = max_iterations; s->eps = epsilon; s->min_set = min_set;
     const int N = s->N;                        // :128-157
     int nmin = (int)(N * s->eps);
@@ -563,21 +215,29 @@ extern "C" int orbp_pnp_iterate(orbp_pnp *s, int n_iterations, int *no_more, uin
     *no_more = 0; *n_inliers = 0;              // :168-170
     const int N = s->N;
     if (N < s->min_inliers) { *no_more = 1; return 0; }
-    std::vector<int> avail;
+    std::vector<int32_t> idx(s->min_set);
+    const size_t W = (size_t)s->words();
     int cur = 0;
     while (s->n_iter < s->max_its || cur < n_iterations) {
         cur++; s->n_iter++;
-        s->e.reset();
-        avail.resize(N);
-        for (int i = 0; i < N; i++) avail[i] = i;
-        for (int i = 0; i < s->min_set; ++i) {         // draw without replacement (:193-204)
-            const int r = s->random_int(0, (int)avail.size() - 1);
-            s->add_corr(avail[r]);
-            avail[r] = avail.back();
-            avail.pop_back();
+        if (s->queued()) {                             // a sample drawn ahead (orbp_pnp_draw): the oldest first
+            const size_t at = s->head++;
+            if (at >= s->att_base && at - s->att_base < s->att_n) {      // with results: mRi, mti, mvbInliersi, mnInliersi restored
+                const size_t k = at - s->att_base;
+                memcpy(s->Ri, &s->att_Rt[12 * k], sizeof s->Ri);
+                memcpy(s->ti, &s->att_Rt[12 * k + 9], sizeof s->ti);
+                const uint32_t *mk = &s->att_masks[W * k];
+                for (int i = 0; i < N; i++) s->inl_i[i] = (mk[i >> 5] >> (i & 31)) & 1u;
+                s->n_inl_i = s->att_counts[k];
+            } else {
+                memcpy(idx.data(), &s->queue[(size_t)s->min_set * at], sizeof(int32_t) * s->min_set);
+                s->evaluate(idx.data());
+            }
+            if (!s->queued()) s->clear_queue();
+        } else {
+            s->draw_one(idx.data());
+            s->evaluate(idx.data());
         }
-        s->e.compute_pose(s->Ri, s->ti);
-        s->check_inliers();
         if (s->n_inl_i >= s->min_inliers) {
             if (s->n_inl_i > s->n_best) {
                 s->inl_best = s->inl_i;
@@ -601,6 +261,82 @@ extern "C" int orbp_pnp_iterate(orbp_pnp *s, int n_iterations, int *no_more, uin
             return 1;
         }
     }
+    return 0;
+}
+
+extern "C" int orbp_pnp_get_problem(const orbp_pnp *s, float *p2d, float *p3d, float *max_err, float *K, int32_t *min_set)
+{
+    if (!s || !K || !min_set || (s->N > 0 && (!p2d || !p3d || !max_err))) return pfail(ORBX_E_INVALID, "NULL argument");
+    if (s->N) {
+        memcpy(p2d, s->p2d.data(), sizeof(float) * 2 * s->N); memcpy(p3d, s->p3d.data(), sizeof(float) * 3 * s->N);
+        memcpy(max_err, s->max_error.data(), sizeof(float) * s->N);
+    }
+    K[0] = (float)s->e.fu; K[1] = (float)s->e.fv; K[2] = (float)s->e.uc; K[3] = (float)s->e.vc;      // they came in as floats
+    *min_set = s->min_set;
+    return s->N;
+}
+
+extern "C" int orbp_pnp_draw(orbp_pnp *s, int n_iterations, int32_t *samples)
+{
+    if (!s || n_iterations < 0) return pfail(ORBX_E_INVALID, "bad arguments");
+    if (s->N < s->min_inliers) return 0;
+    // iterate's loop is `while(mnIterations<mRansacMaxIts || nCurrentIterations<nIterations)` (:182)
+    // so iterate(n_iterations) consumes max(max_its - iterations_done, n_iterations) sets unless a pose comes back earlier
+    const long long consumes = std::max<long long>((long long)s->max_its - s->n_iter, n_iterations);
+    const int n = (int)std::max<long long>(consumes - (long long)s->queued(), 0);
+    for (int k = 0; k < n; k++) {
+        const size_t at = s->queue.size();
+        s->queue.resize(at + s->min_set);
+        s->draw_one(&s->queue[at]);
+        if (samples) memcpy(samples + (size_t)s->min_set * k, &s->queue[at], sizeof(int32_t) * s->min_set);
+    }
+    return n;
+}
+
+extern "C" int orbp_pnp_queued(const orbp_pnp *s, int32_t *samples)
+{
+    if (!s) return pfail(ORBX_E_INVALID, "solver is NULL");
+    const size_t n = s->queued();
+    if (samples && n) memcpy(samples, s->queue.data() + (size_t)s->min_set * s->head, n * s->min_set * sizeof(int32_t));
+    return (int)n;
+}
+
+extern "C" int orbp_pnp_hypothesis(const orbp_pnp *s, const int32_t *sample, double *R, double *t, uint8_t *inliers, int *n_inliers)
+{
+    if (!s || !sample || !R || !t || !n_inliers || (s->N > 0 && !inliers)) return pfail(ORBX_E_INVALID, "NULL argument");
+    for (int k = 0; k < s->min_set; k++) {
+        if (sample[k] < 0 || sample[k] >= s->N) return pfail(ORBX_E_INVALID, "sample index %d outside [0, %d)", sample[k], s->N);
+        for (int j = 0; j < k; j++)
+            if (sample[j] == sample[k]) return pfail(ORBX_E_INVALID, "sample index %d repeated", sample[k]);
+    }
+    Epnp e;
+    e.fu = s->e.fu; e.fv = s->e.fv; e.uc = s->e.uc; e.vc = s->e.vc;
+    for (int k = 0; k < s->min_set; k++) {
+        const size_t i = (size_t)sample[k];
+        e.add(s->p3d[3 * i], s->p3d[3 * i + 1], s->p3d[3 * i + 2], s->p2d[2 * i], s->p2d[2 * i + 1]);
+    }
+    double Rm[3][3];
+    e.compute_pose(Rm, t);
+    memcpy(R, Rm, sizeof Rm);
+    int n = 0;
+    for (int i = 0; i < s->N; i++) {
+        inliers[i] = epnp_check_one(R, t, e.fu, e.fv, e.uc, e.vc, &s->p3d[3 * (size_t)i], &s->p2d[2 * (size_t)i], s->max_error[i]);
+        n += inliers[i];
+    }
+    *n_inliers = n;
+    return 0;
+}
+
+extern "C" int orbp_pnp_attach_results(orbp_pnp *s, int n_hyp, const int32_t *counts, const double *Rt, const uint32_t *masks)
+{
+    if (!s || n_hyp < 0) return pfail(ORBX_E_INVALID, "bad arguments");
+    if ((size_t)n_hyp != s->queued()) return pfail(ORBX_E_INVALID, "%d results for %zu queued samples", n_hyp, s->queued());
+    if (n_hyp > 0 && (!counts || !Rt || !masks)) return pfail(ORBX_E_INVALID, "NULL argument");
+    const size_t W = (size_t)s->words();
+    s->att_base = s->head; s->att_n = (size_t)n_hyp;
+    s->att_counts.assign(counts, counts + n_hyp);
+    s->att_Rt.assign(Rt, Rt + 12 * (size_t)n_hyp);
+    s->att_masks.assign(masks, masks + W * (size_t)n_hyp);
     return 0;
 }
 

@@ -729,6 +729,16 @@ public:
         return rc;
     }
 
+    // orbm_pnp_hypotheses (include/orbm.h) on this matcher's handle: the one GPU call of PnPsolver::EvaluateAll (PnPsolver.h)
+    int PnPHypotheses(int nProblems, const int32_t *off, const float *p2D, const float *p3D, const float *maxErr, const orbm_pnp_camera *cams,
+                      const int32_t *hypOff, const int32_t *samples, const int64_t *maskOff, int32_t *nInliers, double *Rt, uint32_t *masks)
+    {
+        if (!ready()) return ORBX_E_HIP;
+        const int rc = orbm_pnp_hypotheses(h_.m, nProblems, off, p2D, p3D, maxErr, cams, hypOff, samples, maskOff, nInliers, Rt, masks);
+        ok(rc);
+        return rc;
+    }
+
 protected:
     static_assert(sizeof(cv::KeyPoint) == sizeof(orbx_keypoint), "orbx_keypoint mirrors cv::KeyPoint");
     static const orbx_keypoint *kp(const std::vector<cv::KeyPoint> &v) { return reinterpret_cast<const orbx_keypoint *>(v.data()); }

@@ -4,7 +4,8 @@
 // object graph, so the constructor here takes what the reference constructor reads out of them
 // (src/PnPsolver.cc:78-106); INTEGRATION.md 3d shows the five-line gather that keeps the original signature.
 // Poses are row-major 4x4 float (the layout of the reference's CV_32F Tcw); an empty optional stands for the empty
-// cv::Mat the reference returns.
+// cv::Mat the reference returns.  PnPsolver::EvaluateAll is the one addition to the reference's interface: the EPnP
+// hypotheses of all Relocalization candidates in one GPU call (orbm_pnp_hypotheses), replayed by iterate.
 #pragma once
 #include <array>
 #include <cstdint>
@@ -37,6 +38,9 @@ public:
         if (s_ && orbp_pnp_set_ransac_parameters(s_, probability, minInliers, maxIterations, minSet, epsilon, th2) < 0) err_ = orbp_last_error();
     }
 
+    // the uniform source of the RANSAC draws (orbp_pnp_set_rand): fn(ctx) in [0, randMax]; NULL restores libc rand()
+    void SetRand(int (*fn)(void *), void *ctx, int randMax) { if (s_) orbp_pnp_set_rand(s_, fn, ctx, randMax); }
+
     std::optional<Pose> find(std::vector<bool> &vbInliers, int &nInliers)
     {
         bool flag;
@@ -62,10 +66,79 @@ public:
         return T;
     }
 
+    // The batch step of Tracking::Relocalization, one line in front of `while(nCandidates>0 && !bMatch)` (src/Tracking.cc:1403):
+    // every solver draws what its next iterate(nIterations) consumes (solver by solver, so the rand() stream is the one the
+    // reference's first round of iterate calls consumes), all drawn sets are evaluated by ONE orbm_pnp_hypotheses call on the
+    // matcher's handle, and the results are attached: the iterate calls that follow replay them.  NULL entries (discarded
+    // candidates) and solvers with mRansacMinSet > 8 are skipped; the latter evaluate on the host as before.  Returns the ORBX
+    // status; on failure (*err receives the text) the solvers keep their drawn sets and evaluate them on the host.
+    static int EvaluateAll(const std::vector<PnPsolver *> &vpPnPsolvers, orbm_matcher *m, int nIterations = 5, std::string *err = nullptr)
+    {
+        return EvaluateAllWith(vpPnPsolvers, nIterations, err, [m](auto... a) { return orbm_pnp_hypotheses(m, a...); },
+                               [] { return std::string(orbm_last_error()); });
+    }
+    // the same through ORBmatcher::PnPHypotheses (ORBmatcher.h), which owns the handle
+    template <class Matcher>
+    static int EvaluateAll(const std::vector<PnPsolver *> &vpPnPsolvers, Matcher &matcher, int nIterations = 5, std::string *err = nullptr)
+    {
+        return EvaluateAllWith(vpPnPsolvers, nIterations, err, [&matcher](auto... a) { return matcher.PnPHypotheses(a...); },
+                               [&matcher] { return std::string(matcher.LastError()); });
+    }
+
     bool Valid() const { return s_ != nullptr; }
     const std::string &LastError() const { return err_; }
 
 private:
+    template <class Call, class Text>
+    static int EvaluateAllWith(const std::vector<PnPsolver *> &vpPnPsolvers, int nIterations, std::string *err, Call call, Text text)
+    {
+        std::vector<PnPsolver *> live;
+        std::vector<int32_t> off(1, 0), hypOff(1, 0), samples;
+        std::vector<int64_t> maskOff(1, 0);
+        std::vector<float> p2d, p3d, maxErr;
+        std::vector<orbm_pnp_camera> cams;
+        std::vector<int32_t> sets;
+        for (PnPsolver *p : vpPnPsolvers) {
+            if (!p || !p->s_) continue;
+            orbp_pnp *s = p->s_;
+            const int n = (int)p->mvKeyPointIndices.size();
+            const size_t c0 = maxErr.size();
+            p2d.resize(2 * (c0 + n)); p3d.resize(3 * (c0 + n)); maxErr.resize(c0 + n);
+            float K[4];
+            int32_t minSet = 0;
+            orbp_pnp_get_problem(s, p2d.data() + 2 * c0, p3d.data() + 3 * c0, maxErr.data() + c0, K, &minSet);
+            if (minSet > ORBM_PNP_MAX_SET) { p2d.resize(2 * c0); p3d.resize(3 * c0); maxErr.resize(c0); continue; }
+            orbp_pnp_draw(s, nIterations, nullptr);
+            const int h = orbp_pnp_queued(s, nullptr);
+            sets.resize((size_t)h * minSet + 1);
+            orbp_pnp_queued(s, sets.data());
+            const size_t s0 = samples.size();
+            samples.resize(s0 + (size_t)ORBM_PNP_MAX_SET * h, -1);
+            for (int k = 0; k < h; k++)
+                for (int j = 0; j < minSet; j++) samples[s0 + (size_t)ORBM_PNP_MAX_SET * k + j] = sets[(size_t)k * minSet + j];
+            cams.push_back({K[0], K[1], K[2], K[3], minSet});
+            off.push_back(off.back() + n);
+            hypOff.push_back(hypOff.back() + h);
+            maskOff.push_back(maskOff.back() + (int64_t)h * ((n + 31) / 32));
+            live.push_back(p);
+        }
+        const size_t H = (size_t)hypOff.back();
+        std::vector<int32_t> counts(H + 1);
+        std::vector<double> Rt(12 * H + 1);
+        std::vector<uint32_t> masks((size_t)maskOff.back() + 1);
+        samples.push_back(-1);       // never an empty vector's NULL data()
+        const int rc = call((int)live.size(), (const int32_t *)off.data(), (const float *)p2d.data(), (const float *)p3d.data(),
+                            (const float *)maxErr.data(), (const orbm_pnp_camera *)cams.data(), (const int32_t *)hypOff.data(),
+                            (const int32_t *)samples.data(), (const int64_t *)maskOff.data(), counts.data(), Rt.data(), masks.data());
+        if (rc != ORBX_OK) { if (err) *err = text(); return rc; }
+        for (size_t k = 0; k < live.size(); k++)
+            if (orbp_pnp_attach_results(live[k]->s_, hypOff[k + 1] - hypOff[k], counts.data() + hypOff[k], Rt.data() + 12 * (size_t)hypOff[k],
+                                        masks.data() + maskOff[k]) < 0) {
+                if (err) *err = orbp_last_error();
+                return ORBX_E_INVALID;
+            }
+        return ORBX_OK;
+    }
     orbp_pnp *s_ = nullptr;
     std::vector<size_t> mvKeyPointIndices;
     size_t mnFrameFeatures;
