@@ -756,6 +756,66 @@ int orbm_pnp_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypoth
                                void *hip_stream);
 
 /*
+ * ---- Initializer: the H / F hypotheses of Tracking::MonocularInitialization and the CheckRT passes, one call each ----
+ * Initializer::Initialize (src/Initializer.cc:44-121) draws all its index sets first (:77-97), then evaluates mMaxIterations
+ * homographies (FindHomography, :148-171) and as many fundamental matrices (FindFundamental, :199-222): each is one small SVD on
+ * the 8 drawn matches and a pass over all matches.  orbm_init_hypotheses does that for B problems (one per camera or session):
+ *   problem p owns the matches off[p]:off[p+1] of uv (4 floats each: kp1.pt.x, kp1.pt.y, kp2.pt.x, kp2.pt.y of mvMatches12[i]) and
+ *   pn (the same four after Normalize, :132-133), params[p] = T1, T2 (row-major 3 x 3) and sigma, and the hypotheses
+ *   hyp_off[p]:hyp_off[p+1]; hypothesis h runs model models[h] (0: ComputeH21 + CheckHomography, 1: ComputeF21 +
+ *   CheckFundamental) on the matches sets[8h .. 8h+8) of its problem (indices relative to off[p]: what orbp_init_draw records);
+ *   score_M[10h] = currentScore, score_M[10h+1 .. 10h+10) = H21i / F21i (row-major), n_inliers[h] = the number of set flags;
+ *   masks: W = ceil(n_p / 32) words per hypothesis from mask_off[p] on, bit i = vbCurrentInliers[i] (as orbm_sim3_hypotheses).
+ * The outputs are the inputs of orbp_init_attach_results (include/orbp.h), after which the two walks are a replay.
+ *
+ * One wave evaluates one hypothesis with the text of the host solver (csrc/orbp_init_body.h: IEEE + - * / sqrt only, every sum in
+ * the host's order; the score is added in match order, term 1 then term 2, never by a tree), so every output equals
+ * orbp_init_hypothesis' byte for byte.  The result of a hypothesis depends on its problem, its set and its model alone.  A set
+ * with collinear, repeated or otherwise degenerate points is outside the value contract: its flags are still 0/1, its count is its
+ * mask's popcount and nothing outside its slots is written.  Non-finite inputs are outside the contract.
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: a negative count, NULL buffers, off / hyp_off / mask_off not
+ * starting at 0, a decreasing off or hyp_off, a mask_off that is not the layout above, a model other than 0 / 1, a set index outside
+ * its problem); n_problems == 0 or no hypothesis at all is ORBX_OK and touches nothing.  NULL handle, stream, staging arena and
+ * growth as for orbm_sim3_hypotheses; the grids in the handle are not touched.
+ *
+ * orbm_init_hypotheses_device: the same on device pointers (4-byte aligned, mask_off 8-byte aligned).  total_hypotheses =
+ * hyp_off[n_problems].  The index arrays are not checked (a set index outside its problem is clamped into it, a model other than 0
+ * runs as 1).  Nothing is uploaded, downloaded, synchronised or grown; asynchronous on hip_stream (NULL = the handle's stream).
+ *
+ * orbm_init_check_rt: CheckRT (:798-907) of n_motions candidate motions (Rt: 12 floats each, R row-major then t; 4 from
+ * ReconstructF, 8 from ReconstructH) on the n matches uv of ONE problem, one lane per (motion, match): for pair g = motion * n +
+ * match, status[g] names the line that decided it (orbm_init_rt_status), cos_parallax[g] is cosParallax (0 before it is computed),
+ * p3d[3g .. 3g+3) is p3dC1 when the status is one of the two GOOD and 0 otherwise.  K = {fx, fy, cx, cy}, th2 = 4 * mSigma2.
+ * inliers[n] (0/1) = vbMatchesInliers.  Counting nGood, sorting vCosParallax and the acceptance rules stay on the host
+ * (orbp_init_attach_check_rt).  Byte for byte orbp_init_check_rt_matches.  The _device form takes device pointers (K stays a host
+ * pointer: it is passed by value) and neither copies nor synchronises.
+ */
+#define ORBM_INIT_MAX_MOTIONS 8
+typedef struct { float T1[9], T2[9], sigma; } orbm_init_params;
+typedef enum {
+    ORBM_INIT_RT_GOOD = 0,              /* :888-893: counted, vP3D written, vbGood set */
+    ORBM_INIT_RT_GOOD_LOW_PARALLAX = 1, /* the same with cosParallax >= 0.99998: vbGood stays false (:892) */
+    ORBM_INIT_RT_NOT_INLIER = 2,        /* :832 */
+    ORBM_INIT_RT_NOT_FINITE = 3,        /* :841 */
+    ORBM_INIT_RT_BEHIND1 = 4,           /* :857 */
+    ORBM_INIT_RT_BEHIND2 = 5,           /* :863 */
+    ORBM_INIT_RT_REPROJ1 = 6,           /* :874 */
+    ORBM_INIT_RT_REPROJ2 = 7            /* :885 */
+} orbm_init_rt_status;
+int orbm_init_hypotheses(orbm_matcher *m, int n_problems, const int32_t *off, const float *uv, const float *pn,
+                         const orbm_init_params *params, const int32_t *hyp_off, const int32_t *sets, const int32_t *models,
+                         const int64_t *mask_off, float *score_M, int32_t *n_inliers, uint32_t *masks);
+int orbm_init_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypotheses, const int32_t *d_off, const float *d_uv,
+                                const float *d_pn, const orbm_init_params *d_params, const int32_t *d_hyp_off, const int32_t *d_sets,
+                                const int32_t *d_models, const int64_t *d_mask_off, float *d_score_M, int32_t *d_n_inliers,
+                                uint32_t *d_masks, void *hip_stream);
+int orbm_init_check_rt(orbm_matcher *m, int n, const float *uv, const uint8_t *inliers, const float *K, float th2, int n_motions,
+                       const float *Rt, uint8_t *status, float *cos_parallax, float *p3d);
+int orbm_init_check_rt_device(orbm_matcher *m, int n, const float *d_uv, const uint8_t *d_inliers, const float *K, float th2,
+                              int n_motions, const float *d_Rt, uint8_t *d_status, float *d_cos_parallax, float *d_p3d, void *hip_stream);
+
+/*
  * ---- ORBmatcher::Fuse for ALL target key frames of LocalMapping::SearchInNeighbors in one call ----
  * LocalMapping::SearchInNeighbors (src/LocalMapping.cc:456-536) calls Fuse(pKFi, vpMapPointMatches) once per target key frame
  * (:487-492) and once more with every MapPoint of those key frames against mpCurrentKeyFrame (:516).  orbm_fuse_views runs

@@ -3,8 +3,9 @@
  *
  * They are plain C++ inside liborbx.so, take the outputs of the device path (orbx_extract -> orbv_* -> orbm_search_by_bow) and
  * close BASELINE config 5's loop.  SURVEY 8(f) N4 keeps one such solve on the host ("tiny dense fp64 solves"); the RANSAC
- * hypotheses of a whole Relocalization or ComputeSim3 step are hundreds of independent ones, and those have a GPU call each
- * (orbm_pnp_hypotheses, orbm_sim3_hypotheses in include/orbm.h) that the solvers here draw for and replay.
+ * hypotheses of a whole Relocalization, ComputeSim3 or MonocularInitialization step are hundreds of independent ones, and those
+ * have a GPU call each (orbm_pnp_hypotheses, orbm_sim3_hypotheses, orbm_init_hypotheses in include/orbm.h) that the solvers here
+ * draw for and replay.  The monocular Initializer (src/Initializer.cc) is the third of them, further down.
  *
  * Reference (WChen09/My-SLAM):
  *   src/PnPsolver.cc:66-109    PnPsolver::PnPsolver          -> orbp_pnp_create   (caller drops NULL / bad MapPoints)
@@ -159,6 +160,74 @@ int orbp_sim3_iterate(orbp_sim3 *s, int n_iterations, int *no_more, uint8_t *inl
 int orbp_sim3_find(orbp_sim3 *s, uint8_t *inliers, int *n_inliers, float *T12);
 /* GetEstimatedRotation / Translation / Scale: the best hypothesis so far; returns 0 before the first iteration. */
 int orbp_sim3_get_estimated(const orbp_sim3 *s, float *R, float *t, float *scale);
+/*
+ * ---- Initializer (src/Initializer.cc, include/Initializer.h): Tracking::MonocularInitialization's two-view reconstruction ----
+ *   src/Initializer.cc:33-42    Initializer::Initializer -> orbp_init_create (keys1 = mvKeysUn[i].pt of the reference frame,
+ *                                                           {fx, fy, cx, cy} of mK)
+ *   :44-121   Initialize        -> orbp_init_set_current + orbp_init_initialize      :82-97 the draws -> orbp_init_draw
+ *   :124-223  FindHomography / FindFundamental -> orbp_init_find over orbp_init_hypothesis (csrc/orbp_init_body.h)
+ *   :470-732  ReconstructF / ReconstructH -> orbp_init_motions, orbp_init_check_rt and the acceptance rules inside _initialize
+ *   :749-795  Normalize (over ALL keys of a frame) -> inside orbp_init_set_current (orbp_init_normalized reads it back)
+ *
+ * The 2 * mMaxIterations hypotheses of a call do not depend on each other, only on the draws, and all draws come first: orbp_init_draw
+ * performs them, orbm_init_hypotheses (include/orbm.h) evaluates them in one GPU call, orbp_init_attach_results hands the results
+ * back and the walks replay them; likewise orbm_init_check_rt / orbp_init_attach_check_rt for the 4 or 8 CheckRT passes.  Same
+ * scores, matrices, flags, motions and points, byte for byte, as evaluating in place, because host and kernels run one body.
+ * What OpenCV does inside cv::SVDecomp / invert / gemm is "parity unpinned" as above (the body's header lists the choices, the sign
+ * of the null vector among them).  The reference runs the two walks on two threads; the results do not depend on that.
+ *
+ * Defined here where the reference is not: fewer than 8 matches (RandomInt(0, -1)) is refused by orbp_init_draw and by
+ * orbp_init_initialize with ORBX_E_INVALID; SH == SF == 0 (RH is NaN and the reference decomposes an empty matrix) makes
+ * orbp_init_initialize return 0.  With the default source the first draw of the process calls srand(0), once (SeedRandOnce(0), :80).
+ * Models: 0 = homography, 1 = fundamental matrix.  Matrices are row-major 3 x 3 floats.
+ */
+typedef struct orbp_init orbp_init;
+int orbp_init_create(orbp_init **out, const float *keys1, int n1, float fx, float fy, float cx, float cy, float sigma, int iterations);
+void orbp_init_destroy(orbp_init *s);
+/* fn(ctx) in [0, rand_max]; NULL restores libc rand() / RAND_MAX through RandomInt's formula (as orbp_sim3_set_rand). */
+void orbp_init_set_rand(orbp_init *s, int (*fn)(void *), void *ctx, int rand_max);
+/* :49-63 and both Normalize calls: keys2 = mvKeysUn[i].pt of the current frame (2 n2 floats), matches12[n1] = vMatches12 (< 0: no
+ * match).  Drops the sets and every attached result of the frame before.  Returns N = mvMatches12.size(). */
+int orbp_init_set_current(orbp_init *s, const float *keys2, int n2, const int32_t *matches12);
+int orbp_init_get_sizes(const orbp_init *s, int *n1, int *n2, int *n_matches, int *iterations, int *drawn);    /* any pointer may be NULL */
+/* :82-97: mMaxIterations sets of 8 match indices into sets (may be NULL) and into the solver.  Returns the number of sets;
+ * ORBX_E_INVALID with nothing drawn when N < 8. */
+int orbp_init_draw(orbp_init *s, int32_t *sets);
+/* The solver as a problem of orbm_init_hypotheses / orbm_init_check_rt: uv and pn (4 N floats each), params[24] = T1 (9), T2 (9),
+ * sigma, fx, fy, cx, cy, th2 = 4 * mSigma2 (the first 19 are an orbm_init_params), the drawn sets (8 * iterations ints, when drawn),
+ * m1 / m2 = mvMatches12[i].first / .second.  Any pointer may be NULL.  Returns N. */
+int orbp_init_get_problem(const orbp_init *s, float *uv, float *pn, float *params, int32_t *sets, int32_t *m1, int32_t *m2);
+/* vPn1 (2 n1 floats), T1, vPn2 (2 n2), T2 of the current pair; any pointer may be NULL */
+int orbp_init_normalized(const orbp_init *s, float *pn1, float *T1, float *pn2, float *T2);
+/* One hypothesis, stateless: M = H21i / F21i, *score = currentScore, inliers[N] (0/1) and their number. */
+int orbp_init_hypothesis(const orbp_init *s, int model, const int32_t *set, float *M, float *score, uint8_t *inliers, int *n_inliers);
+/* Results of ALL 2 * iterations hypotheses in the layout of orbm_init_hypotheses: the H of every set in draw order, then the F. */
+int orbp_init_attach_results(orbp_init *s, int n_hyp, const float *score_M, const int32_t *counts, const uint32_t *masks);
+/* The walk of :148-171 (model 0) / :199-222 (model 1): strict >, so the first of equal scores wins; over the attached results when
+ * there are any, evaluating in place otherwise.  Returns 1 and the winner's matrix, score, flags and iteration, 0 when no score
+ * exceeded 0 (M and inliers zero, *best_iteration = -1). */
+int orbp_init_find(orbp_init *s, int model, float *M, float *score, uint8_t *inliers, int *best_iteration);
+/* The candidate motions of ReconstructF (4: DecomposeE's (R1, t) (R2, t) (R1, -t) (R2, -t)) or ReconstructH (8, Faugeras) of M into
+ * Rt (12 floats each: R row-major, t; room for 8).  Returns 1, or 0 at ReconstructH's d1/d2 < 1.00001 || d2/d3 < 1.00001 exit. */
+int orbp_init_motions(const orbp_init *s, int model, const float *M, float *Rt, int *n_motions);
+/* CheckRT (:798-907) of one motion on the host: p3d[3 n1] = vP3D, good[n1] = vbGood, *parallax, *n_good = the return value. */
+int orbp_init_check_rt(const orbp_init *s, const float *R, const float *t, const uint8_t *inliers, float *p3d, uint8_t *good,
+                       float *parallax, int *n_good);
+/* The per-match part of CheckRT for n_motions motions, in the layout of orbm_init_check_rt (status, cos_parallax: n_motions * N,
+ * p3d: 3 * n_motions * N). */
+int orbp_init_check_rt_matches(const orbp_init *s, int n_motions, const float *Rt, const uint8_t *inliers, uint8_t *status,
+                               float *cos_parallax, float *p3d);
+/* Hands the outputs of orbm_init_check_rt back: orbp_init_initialize uses them for the motions and flags they were computed for
+ * (compared by value) and computes every other CheckRT in place. */
+int orbp_init_attach_check_rt(orbp_init *s, int n_motions, const float *Rt, const uint8_t *inliers, const uint8_t *status,
+                              const float *cos_parallax, const float *p3d);
+/* Initialize up to its CheckRT calls: both walks, RH = SH / (SH + SF) > 0.40, the motions of the chosen model.  *model, M, its
+ * inlier flags (N) and Rt (room for 8 motions).  Returns the number of motions; 0 where Initialize returns false before CheckRT. */
+int orbp_init_plan_check_rt(orbp_init *s, int *model, float *M, uint8_t *inliers, float *Rt, int *n_motions);
+/* The whole of Initialize (:99-120) after orbp_init_set_current: draws unless drawn, both walks, the ratio, ReconstructH /
+ * ReconstructF (minParallax 1.0, minTriangulated 50).  Returns 1 and fills R21 (9), t21 (3), p3d[3 n1] = vP3D and
+ * triangulated[n1] = vbTriangulated; 0 when the reference returns false (outputs untouched); < 0 on bad arguments or N < 8. */
+int orbp_init_initialize(orbp_init *s, float *R21, float *t21, float *p3d, uint8_t *triangulated);
 const char *orbp_last_error(void);
 
 #ifdef __cplusplus

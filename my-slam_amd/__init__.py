@@ -53,6 +53,14 @@ assert SIM3_CAM_DTYPE.itemsize == 36
 PNP_CAM_DTYPE = np.dtype([("fx", "<f4"), ("fy", "<f4"), ("cx", "<f4"), ("cy", "<f4"), ("set_size", "<i4")])
 assert PNP_CAM_DTYPE.itemsize == 20
 ORBM_PNP_MAX_SET = 8
+# orbm_init_params (include/orbm.h): Normalize's T1, T2 (row-major 3 x 3) and sigma of one problem of init_hypotheses
+INIT_PARAMS_DTYPE = np.dtype([("T1", "<f4", (9,)), ("T2", "<f4", (9,)), ("sigma", "<f4")])
+assert INIT_PARAMS_DTYPE.itemsize == 76
+INIT_MODEL_H, INIT_MODEL_F = 0, 1
+ORBM_INIT_MAX_MOTIONS = 8
+# orbm_init_rt_status (include/orbm.h): the line of Initializer::CheckRT that decided a match
+(ORBM_INIT_RT_GOOD, ORBM_INIT_RT_GOOD_LOW_PARALLAX, ORBM_INIT_RT_NOT_INLIER, ORBM_INIT_RT_NOT_FINITE, ORBM_INIT_RT_BEHIND1,
+ ORBM_INIT_RT_BEHIND2, ORBM_INIT_RT_REPROJ1, ORBM_INIT_RT_REPROJ2) = range(8)
 
 ORBX_OK = 0
 ORBX_E_INVALID, ORBX_E_CAPACITY, ORBX_E_SHAPE, ORBX_E_HIP, ORBX_E_CAND_OVERFLOW, ORBX_E_TREE_OVERFLOW = -1, -2, -3, -4, -5, -6
@@ -142,6 +150,7 @@ def lib():
     _bind_voc(L)
     _bind_pose(L)
     _bind_sim3(L)
+    _bind_init(L)
     _bind_kfdb(L)
     _lib = L
     return L
@@ -246,6 +255,38 @@ def _bind_sim3(L):
     L.orbm_sim3_hypotheses.argtypes = [vp, C.c_int] + [vp] * 12
     L.orbm_sim3_hypotheses_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 13
     L.orbm_sim3_hypotheses.restype = L.orbm_sim3_hypotheses_device.restype = C.c_int
+
+
+def _bind_init(L):
+    vp, ip, fp, f = C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_float), C.c_float
+    L.orbp_init_create.argtypes = [C.POINTER(vp), vp, C.c_int, f, f, f, f, f, C.c_int]
+    L.orbp_init_destroy.argtypes = [vp]
+    L.orbp_init_destroy.restype = None
+    L.orbp_init_set_rand.argtypes = [vp, RAND_FN, vp, C.c_int]
+    L.orbp_init_set_rand.restype = None
+    L.orbp_init_set_current.argtypes = [vp, vp, C.c_int, vp]
+    L.orbp_init_get_sizes.argtypes = [vp, ip, ip, ip, ip, ip]
+    L.orbp_init_draw.argtypes = [vp, vp]
+    L.orbp_init_get_problem.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.orbp_init_normalized.argtypes = [vp, vp, vp, vp, vp]
+    L.orbp_init_hypothesis.argtypes = [vp, C.c_int, vp, vp, fp, vp, ip]
+    L.orbp_init_attach_results.argtypes = [vp, C.c_int, vp, vp, vp]
+    L.orbp_init_find.argtypes = [vp, C.c_int, vp, fp, vp, ip]
+    L.orbp_init_motions.argtypes = [vp, C.c_int, vp, vp, ip]
+    L.orbp_init_check_rt.argtypes = [vp, vp, vp, vp, vp, vp, fp, ip]
+    L.orbp_init_check_rt_matches.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.orbp_init_attach_check_rt.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp]
+    L.orbp_init_plan_check_rt.argtypes = [vp, ip, vp, vp, vp, ip]
+    L.orbp_init_initialize.argtypes = [vp, vp, vp, vp, vp]
+    for name in ("create", "set_current", "get_sizes", "draw", "get_problem", "normalized", "hypothesis", "attach_results", "find", "motions",
+                 "check_rt", "check_rt_matches", "attach_check_rt", "plan_check_rt", "initialize"):
+        getattr(L, "orbp_init_" + name).restype = C.c_int
+    L.orbm_init_hypotheses.argtypes = [vp, C.c_int] + [vp] * 11
+    L.orbm_init_hypotheses_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
+    L.orbm_init_check_rt.argtypes = [vp, C.c_int, vp, vp, vp, f, C.c_int, vp, vp, vp, vp]
+    L.orbm_init_check_rt_device.argtypes = [vp, C.c_int, vp, vp, vp, f, C.c_int, vp, vp, vp, vp, vp]
+    L.orbm_init_hypotheses.restype = L.orbm_init_hypotheses_device.restype = C.c_int
+    L.orbm_init_check_rt.restype = L.orbm_init_check_rt_device.restype = C.c_int
 
 
 def _bind_matcher(L):
@@ -916,6 +957,99 @@ class ORBmatcher:
         _mchk(self.L.orbm_sim3_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(x3dc1), ptr(x3dc2), ptr(max_err1),
                                                  ptr(max_err2), ptr(cams), ptr(hyp_off), ptr(triples), ptr(mask_off), ptr(n_inliers),
                                                  ptr(sRt), ptr(masks), s))
+
+    @staticmethod
+    def pack_init_problems(problems):
+        """The arrays of orbm_init_hypotheses from a list of problems, each an Initializer (its drawn sets: the H of every set, then
+        the F) or a tuple (uv [n, 4], pn [n, 4], T1 (9), T2 (9), sigma, sets [h, 8], models [h]) ->
+        (off int32 [B+1], uv float32 [N, 4], pn float32 [N, 4], params INIT_PARAMS_DTYPE [B], hyp_off int32 [B+1], sets int32 [H, 8],
+        models int32 [H], mask_off int64 [B+1])."""
+        B = len(problems)
+        off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
+        params = np.zeros(B, INIT_PARAMS_DTYPE)
+        uvs, pns, setss, modelss = [], [], [], []
+        for p, pr in enumerate(problems):
+            if isinstance(pr, Initializer):
+                pr = pr.problem()
+            uv, pn, T1, T2, sigma, sets, models = pr
+            uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 4)
+            pn = np.ascontiguousarray(pn, np.float32).reshape(-1, 4)
+            sets = np.ascontiguousarray(sets, np.int32).reshape(-1, 8)
+            models = np.ascontiguousarray(models, np.int32).reshape(-1)
+            if len(uv) != len(pn) or len(sets) != len(models):
+                raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %d / %d matches, %d / %d hypotheses"
+                                % (p, len(uv), len(pn), len(sets), len(models)))
+            uvs.append(uv); pns.append(pn); setss.append(sets); modelss.append(models)
+            off[p + 1] = off[p] + len(uv)
+            hyp_off[p + 1] = hyp_off[p] + len(sets)
+            mask_off[p + 1] = mask_off[p] + len(sets) * ((len(uv) + 31) // 32)
+            params[p] = (np.asarray(T1, np.float32).reshape(9), np.asarray(T2, np.float32).reshape(9), np.float32(sigma))
+        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(shape, dt)
+        return (off, cat(uvs, (0, 4), np.float32), cat(pns, (0, 4), np.float32), params, hyp_off, cat(setss, (0, 8), np.int32),
+                cat(modelss, (0,), np.int32), mask_off)
+
+    def init_hypotheses(self, problems):
+        """Every H / F hypothesis of every problem in one launch (orbm_init_hypotheses; problems as in pack_init_problems).  Returns a
+        list of (score_M float32 [h, 10], n_inliers int32 [h], masks uint32 [h, ceil(n / 32)]) per problem: what
+        Initializer.attach_results takes."""
+        off, uv, pn, params, hyp_off, sets, models, mask_off = self.pack_init_problems(problems)
+        B, H, MW = len(problems), int(hyp_off[-1]), int(mask_off[-1])
+        sm, cnt, masks = np.zeros((max(H, 1), 10), np.float32), np.zeros(max(H, 1), np.int32), np.zeros(max(MW, 1), np.uint32)
+        _mchk(self.L.orbm_init_hypotheses(self.h, B, _p(off), _p(uv), _p(pn), _p(params), _p(hyp_off), _p(sets), _p(models), _p(mask_off),
+                                          _p(sm), _p(cnt), _p(masks)))
+        out = []
+        for p in range(B):
+            h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
+            W = (int(off[p + 1]) - int(off[p]) + 31) // 32
+            out.append((sm[h0:h1].copy(), cnt[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
+        return out
+
+    def init_hypotheses_device(self, n_problems, total_hypotheses, off, uv, pn, params, hyp_off, sets, models, mask_off, score_M, n_inliers,
+                               masks, stream=None):
+        """The same on torch tensors on the handle's device: off int32 [B+1], uv / pn float32 [N, 4], params uint8 [B, 76]
+        (INIT_PARAMS_DTYPE bytes), hyp_off int32 [B+1], sets int32 [H, 8], models int32 [H], mask_off int64 [B+1], score_M float32
+        [H, 10], n_inliers int32 [H], masks int32 [mask words].  Nothing is copied or synchronised; stream: a torch stream, a raw
+        hipStream_t or None (the handle's stream)."""
+        import torch
+        want = ((off, torch.int32), (uv, torch.float32), (pn, torch.float32), (params, torch.uint8), (hyp_off, torch.int32),
+                (sets, torch.int32), (models, torch.int32), (mask_off, torch.int64), (score_M, torch.float32), (n_inliers, torch.int32),
+                (masks, torch.int32))
+        for t, dt in want:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise OrbxError(ORBX_E_INVALID, "init_hypotheses_device wants contiguous device tensors of the documented dtypes")
+        s = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _mchk(self.L.orbm_init_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(uv), ptr(pn), ptr(params), ptr(hyp_off),
+                                                 ptr(sets), ptr(models), ptr(mask_off), ptr(score_M), ptr(n_inliers), ptr(masks), s))
+
+    def init_check_rt(self, uv, inliers, K, th2, Rt):
+        """CheckRT's per-match part for every motion of Rt [k, 12] in one launch (orbm_init_check_rt) ->
+        (status uint8 [k, n], cos_parallax float32 [k, n], p3d float32 [k, n, 3])."""
+        uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 4)
+        inl = np.ascontiguousarray(inliers, np.uint8).reshape(-1)
+        K = np.ascontiguousarray(K, np.float32).reshape(4)
+        Rt = np.ascontiguousarray(Rt, np.float32).reshape(-1, 12)
+        n, k = len(uv), len(Rt)
+        if len(inl) != n:
+            raise OrbxError(ORBX_E_INVALID, "init_check_rt: %d matches, %d flags" % (n, len(inl)))
+        status, cosp, p3d = np.zeros((k, n), np.uint8), np.zeros((k, n), np.float32), np.zeros((k, n, 3), np.float32)
+        _mchk(self.L.orbm_init_check_rt(self.h, n, _p(uv), _p(inl), _p(K), float(th2), k, _p(Rt), _p(status), _p(cosp), _p(p3d)))
+        return status, cosp, p3d
+
+    def init_check_rt_device(self, n, uv, inliers, K, th2, n_motions, Rt, status, cos_parallax, p3d, stream=None):
+        """The same on torch tensors on the handle's device: uv float32 [n, 4], inliers uint8 [n], Rt float32 [k, 12], status uint8
+        [k, n], cos_parallax float32 [k, n], p3d float32 [k, n, 3]; K = (fx, fy, cx, cy) and th2 are host values."""
+        import torch
+        want = ((uv, torch.float32), (inliers, torch.uint8), (Rt, torch.float32), (status, torch.uint8), (cos_parallax, torch.float32),
+                (p3d, torch.float32))
+        for t, dt in want:
+            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise OrbxError(ORBX_E_INVALID, "init_check_rt_device wants contiguous device tensors of the documented dtypes")
+        K = np.ascontiguousarray(K, np.float32).reshape(4)
+        s = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _mchk(self.L.orbm_init_check_rt_device(self.h, n, ptr(uv), ptr(inliers), _p(K), float(th2), n_motions, ptr(Rt), ptr(status),
+                                               ptr(cos_parallax), ptr(p3d), s))
 
     @staticmethod
     def pack_pnp_problems(problems):
@@ -1765,6 +1899,202 @@ class Sim3Solver:
             s.draw(s.ransac_state()["max_its"])
         for s, res in zip(live, matcher.sim3_hypotheses(live)):
             s.attach_results(*res)
+
+
+class Initializer:
+    """Mirror of ORB_SLAM2::Initializer (include/Initializer.h, src/Initializer.cc) over orbp_init_*.  The Frame arguments of the
+    reference become the arrays it reads from them: keys = mvKeysUn[i].pt, K = (fx, fy, cx, cy) of mK."""
+
+    def __init__(self, keys1, K, sigma=1.0, iterations=200, rand=None, rand_max=None):
+        self.L = lib()
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        self.K = np.ascontiguousarray(K, np.float32).reshape(4)
+        self.n1, self.iterations, self.sigma = len(self.keys1), int(iterations), float(sigma)
+        if rand is not None and rand_max is None:
+            raise OrbxError(ORBX_E_INVALID, "Initializer: rand needs rand_max, the largest value rand() returns")
+        self.h = C.c_void_p()
+        _pchk(self.L.orbp_init_create(C.byref(self.h), _p(self.keys1), self.n1, *[float(k) for k in self.K], self.sigma, self.iterations))
+        self._cb = None
+        if rand is not None:
+            self._cb = RAND_FN(lambda ctx: int(rand()))
+            self.L.orbp_init_set_rand(self.h, self._cb, None, int(rand_max))
+        self.N = self.n2 = 0
+        self.use_gpu = True
+        self.last_error = ""
+
+    def close(self):
+        if self.h:
+            self.L.orbp_init_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def SetRand(self, rand, rand_max):
+        self._cb = RAND_FN(lambda ctx: int(rand())) if rand is not None else None
+        self.L.orbp_init_set_rand(self.h, self._cb if self._cb is not None else C.cast(None, RAND_FN), None, int(rand_max or 0))
+
+    def SetUseGpu(self, on):
+        self.use_gpu = bool(on)
+
+    def LastError(self):
+        return self.last_error
+
+    def set_current(self, keys2, matches12):
+        """Initialize's first lines (:49-63) and both Normalize calls; returns N = mvMatches12.size()"""
+        keys2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m = np.ascontiguousarray(matches12, np.int32).reshape(-1)
+        if len(m) != self.n1:
+            raise OrbxError(ORBX_E_INVALID, "matches12 has %d entries for %d reference keys" % (len(m), self.n1))
+        self.n2 = len(keys2)
+        self.N = _pchk(self.L.orbp_init_set_current(self.h, _p(keys2), self.n2, _p(m)))
+        self.W = (self.N + 31) // 32
+        return self.N
+
+    def normalized(self):
+        """-> (vPn1 [n1, 2], T1 3x3, vPn2 [n2, 2], T2 3x3) of Normalize (:749-795)"""
+        pn1, pn2 = np.zeros((max(self.n1, 1), 2), np.float32), np.zeros((max(self.n2, 1), 2), np.float32)
+        T1, T2 = np.zeros(9, np.float32), np.zeros(9, np.float32)
+        _pchk(self.L.orbp_init_normalized(self.h, _p(pn1), _p(T1), _p(pn2), _p(T2)))
+        return pn1[:self.n1], T1.reshape(3, 3), pn2[:self.n2], T2.reshape(3, 3)
+
+    def draw(self):
+        """mvSets (:82-97): int32 [iterations, 8]"""
+        sets = np.zeros((max(self.iterations, 1), 8), np.int32)
+        k = _pchk(self.L.orbp_init_draw(self.h, _p(sets)))
+        return sets[:k].copy()
+
+    def _get(self):
+        n = max(self.N, 1)
+        uv, pn, params = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32), np.zeros(24, np.float32)
+        sets, m1, m2 = np.zeros((max(self.iterations, 1), 8), np.int32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        drawn = C.c_int()
+        _pchk(self.L.orbp_init_get_sizes(self.h, None, None, None, None, C.byref(drawn)))
+        _pchk(self.L.orbp_init_get_problem(self.h, _p(uv), _p(pn), _p(params), _p(sets), _p(m1), _p(m2)))
+        return uv[:self.N], pn[:self.N], params, sets[:self.iterations if drawn.value else 0], m1[:self.N], m2[:self.N]
+
+    def matches(self):
+        """mvMatches12 as (first int32 [N], second int32 [N])"""
+        g = self._get()
+        return g[4], g[5]
+
+    def problem(self):
+        """This solver as a problem of ORBmatcher.init_hypotheses: the H of every drawn set, then the F"""
+        uv, pn, params, sets, _, _ = self._get()
+        models = np.repeat(np.array([INIT_MODEL_H, INIT_MODEL_F], np.int32), len(sets))
+        return uv, pn, params[:9], params[9:18], params[18], np.concatenate([sets, sets]), models
+
+    def check_rt_inputs(self):
+        """-> (uv [N, 4], K (4), th2) of ORBmatcher.init_check_rt"""
+        uv, _, params, _, _, _ = self._get()
+        return uv, params[19:23].copy(), float(params[23])
+
+    def hypothesis(self, model, set8):
+        """One hypothesis on the host -> (M 3x3, score float32, inliers bool[N], nInliers)"""
+        st = np.ascontiguousarray(set8, np.int32).reshape(8)
+        M, sc, n = np.zeros(9, np.float32), C.c_float(), C.c_int()
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        _pchk(self.L.orbp_init_hypothesis(self.h, int(model), _p(st), _p(M), C.byref(sc), _p(inl), C.byref(n)))
+        return M.reshape(3, 3), np.float32(sc.value), inl[:self.N].astype(bool), n.value
+
+    def hypotheses(self, sets, models):
+        """hypothesis() for each (set, model), in the layout of ORBmatcher.init_hypotheses: (score_M [h, 10], n_inliers [h], masks [h, W])"""
+        sets = np.asarray(sets, np.int32).reshape(-1, 8)
+        models = np.asarray(models, np.int32).reshape(-1)
+        sm, cnt, masks = np.zeros((len(sets), 10), np.float32), np.zeros(len(sets), np.int32), np.zeros((len(sets), self.W), np.uint32)
+        for k, (st, md) in enumerate(zip(sets, models)):
+            M, sc, inl, n = self.hypothesis(md, st)
+            cnt[k] = n
+            sm[k, 0], sm[k, 1:] = sc, M.reshape(9)
+            bits = np.zeros(self.W * 32, np.uint8)
+            bits[:self.N] = inl
+            masks[k] = np.packbits(bits, bitorder="little").view("<u4")
+        return sm, cnt, masks
+
+    def attach_results(self, score_M, n_inliers, masks):
+        sm = np.ascontiguousarray(score_M, np.float32).reshape(-1)
+        cnt = np.ascontiguousarray(n_inliers, np.int32).reshape(-1)
+        masks = np.ascontiguousarray(masks, np.uint32).reshape(-1)
+        if len(sm) != 10 * len(cnt) or len(masks) != self.W * len(cnt):
+            raise OrbxError(ORBX_E_INVALID, "results of %d hypotheses: %d floats, %d mask words" % (len(cnt), len(sm), len(masks)))
+        _pchk(self.L.orbp_init_attach_results(self.h, len(cnt), _p(sm), _p(cnt), _p(masks)))
+
+    def find(self, model):
+        """FindHomography (model 0) / FindFundamental (1) -> (M 3x3, score, inliers bool[N], winning iteration or -1)"""
+        M, sc, it = np.zeros(9, np.float32), C.c_float(), C.c_int()
+        inl = np.zeros(max(self.N, 1), np.uint8)
+        _pchk(self.L.orbp_init_find(self.h, int(model), _p(M), C.byref(sc), _p(inl), C.byref(it)))
+        return M.reshape(3, 3), np.float32(sc.value), inl[:self.N].astype(bool), it.value
+
+    def motions(self, model, M):
+        """-> Rt float32 [k, 12] (R row-major, t): 4 for F, 8 for H, none at ReconstructH's singular-value exit"""
+        M = np.ascontiguousarray(M, np.float32).reshape(9)
+        Rt, n = np.zeros((8, 12), np.float32), C.c_int()
+        _pchk(self.L.orbp_init_motions(self.h, int(model), _p(M), _p(Rt), C.byref(n)))
+        return Rt[:n.value].copy()
+
+    def check_rt(self, R, t, inliers):
+        """CheckRT on the host -> (nGood, vP3D [n1, 3], vbGood bool[n1], parallax)"""
+        R, t = np.ascontiguousarray(R, np.float32).reshape(9), np.ascontiguousarray(t, np.float32).reshape(3)
+        inl = np.ascontiguousarray(np.asarray(inliers).astype(np.uint8)).reshape(-1)
+        if len(inl) != self.N:
+            raise OrbxError(ORBX_E_INVALID, "check_rt: %d flags for %d matches" % (len(inl), self.N))
+        inl = np.concatenate([inl, np.zeros(1, np.uint8)])
+        p3d, good = np.zeros((max(self.n1, 1), 3), np.float32), np.zeros(max(self.n1, 1), np.uint8)
+        par, n = C.c_float(), C.c_int()
+        _pchk(self.L.orbp_init_check_rt(self.h, _p(R), _p(t), _p(inl), _p(p3d), _p(good), C.byref(par), C.byref(n)))
+        return n.value, p3d[:self.n1], good[:self.n1].astype(bool), np.float32(par.value)
+
+    def check_rt_matches(self, Rt, inliers):
+        """The per-match part of CheckRT on the host, in the layout of ORBmatcher.init_check_rt"""
+        Rt = np.ascontiguousarray(Rt, np.float32).reshape(-1, 12)
+        inl = np.concatenate([np.asarray(inliers).astype(np.uint8).reshape(-1), np.zeros(1, np.uint8)])
+        k, n = len(Rt), self.N
+        status, cosp, p3d = np.zeros((k, max(n, 1)), np.uint8), np.zeros((k, max(n, 1)), np.float32), np.zeros((k, max(n, 1), 3), np.float32)
+        if n:
+            _pchk(self.L.orbp_init_check_rt_matches(self.h, k, _p(Rt), _p(inl), _p(status), _p(cosp), _p(p3d)))
+        return status[:, :n], cosp[:, :n], p3d[:, :n]
+
+    def attach_check_rt(self, Rt, inliers, status, cos_parallax, p3d):
+        Rt = np.ascontiguousarray(Rt, np.float32).reshape(-1, 12)
+        inl = np.concatenate([np.asarray(inliers).astype(np.uint8).reshape(-1), np.zeros(1, np.uint8)])
+        _pchk(self.L.orbp_init_attach_check_rt(self.h, len(Rt), _p(Rt), _p(inl), _p(np.ascontiguousarray(status, np.uint8)),
+                                               _p(np.ascontiguousarray(cos_parallax, np.float32)), _p(np.ascontiguousarray(p3d, np.float32))))
+
+    def plan_check_rt(self):
+        """Initialize up to its CheckRT calls -> (model, M 3x3, inliers bool[N], Rt [k, 12]); k = 0: Initialize returns false before them"""
+        model, n = C.c_int(), C.c_int()
+        M, Rt, inl = np.zeros(9, np.float32), np.zeros((8, 12), np.float32), np.zeros(max(self.N, 1), np.uint8)
+        _pchk(self.L.orbp_init_plan_check_rt(self.h, C.byref(model), _p(M), _p(inl), _p(Rt), C.byref(n)))
+        return model.value, M.reshape(3, 3), inl[:self.N].astype(bool), Rt[:n.value].copy()
+
+    def initialize(self):
+        """orbp_init_initialize on the current pair -> (ok, R21 3x3, t21 (3), vP3D [n1, 3], vbTriangulated bool[n1])"""
+        R, t = np.zeros(9, np.float32), np.zeros(3, np.float32)
+        p3d, tri = np.zeros((max(self.n1, 1), 3), np.float32), np.zeros(max(self.n1, 1), np.uint8)
+        ok = _pchk(self.L.orbp_init_initialize(self.h, _p(R), _p(t), _p(p3d), _p(tri)))
+        return bool(ok), R.reshape(3, 3), t, p3d[:self.n1], tri[:self.n1].astype(bool)
+
+    def Initialize(self, keys2, matches12, matcher=None):
+        """Initializer::Initialize (:44-121) -> (ok, R21, t21, vP3D, vbTriangulated).  With a matcher (and SetUseGpu(True)) the
+        hypotheses and the CheckRT passes are one GPU call each; when a GPU call fails the host path gives the same bytes and
+        LastError() says why."""
+        self.set_current(keys2, matches12)
+        self.draw()
+        self.last_error = ""
+        if matcher is not None and self.use_gpu:
+            try:
+                self.attach_results(*matcher.init_hypotheses([self])[0])
+                model, M, inl, Rt = self.plan_check_rt()
+                if len(Rt):
+                    uv, K, th2 = self.check_rt_inputs()
+                    self.attach_check_rt(Rt, inl, *matcher.init_check_rt(uv, inl, K, th2, Rt))
+            except OrbxError as e:
+                self.last_error = str(e)
+        return self.initialize()
 
 
 def epnp(pws, us, fu, fv, uc, vc):

@@ -1,5 +1,5 @@
 // orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip,
-// orbm_frustum.hip, orbm_pose.hip, orbm_bow.hip and orbm_sim3.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
+// orbm_frustum.hip, orbm_pose.hip, orbm_bow.hip, orbm_sim3.hip, orbm_pnp.hip and orbm_init.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
 #pragma once
 #include <algorithm>
 #include <cmath>

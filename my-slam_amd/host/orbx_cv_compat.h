@@ -28,6 +28,8 @@
 namespace cv {
 template <class T> struct Point_ { T x = 0, y = 0; Point_() {} Point_(T x_, T y_) : x(x_), y(y_) {} };
 typedef Point_<float> Point2f;
+template <class T> struct Point3_ { T x = 0, y = 0, z = 0; Point3_() {} Point3_(T x_, T y_, T z_) : x(x_), y(y_), z(z_) {} };
+typedef Point3_<float> Point3f;
 struct KeyPoint {                      // field order of cv::KeyPoint (28 bytes)
     Point2f pt; float size = 0, angle = -1, response = 0; int octave = 0, class_id = -1;
 };
