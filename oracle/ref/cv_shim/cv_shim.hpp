@@ -19,6 +19,9 @@
  *   - what Thirdparty/DBoW2 uses (oracle/ref/ref_dbow.cc): a descriptor is a 1 x 32 CV_8U row read through
  *     ptr<T>(); FileStorage / FileNode are no-ops that only let the yml save / load members compile
  *     (isOpened() is false, so both throw before they touch a node).
+ *   - with CV_SHIM_LINALG defined (oracle/ref/solver_standin.h), and only then: CV_64F matrices and the linear algebra that
+ *     src/Sim3Solver.cc, src/PnPsolver.cc and src/Initializer.cc use, in cv_linalg.hpp.  Without the macro this header is the
+ *     text the pins above have always compiled.
  */
 #ifndef ORBX_CV_SHIM_HPP
 #define ORBX_CV_SHIM_HPP
@@ -45,6 +48,10 @@ typedef unsigned char uchar;
 #define CV_32F 5
 #define CV_32FC1 5
 #define CV_PI 3.1415926535897932384626433832795
+#ifdef CV_SHIM_LINALG            /* the solvers' pin (cv_linalg.hpp): double matrices beside the two above */
+#define CV_64F 6
+#define CV_64FC1 6
+#endif
 
 namespace cv {
 
@@ -72,6 +79,14 @@ template <typename T> struct Point_ {
 typedef Point_<int> Point2i;
 typedef Point_<int> Point;
 typedef Point_<float> Point2f;
+#ifdef CV_SHIM_LINALG
+template <typename T> struct Point3_ {
+    T x, y, z;
+    Point3_() : x(0), y(0), z(0) {}
+    Point3_(T x_, T y_, T z_) : x(x_), y(y_), z(z_) {}
+};
+typedef Point3_<float> Point3f;
+#endif
 
 /* OpenCV: a.x = saturate_cast<T>(a.x * b) -- a float product for Point2f */
 inline Point2f &operator*=(Point2f &a, float b)
@@ -118,6 +133,9 @@ public:
 };
 
 struct MatZeros { int rows, cols, type; };
+#ifdef CV_SHIM_LINALG
+class MatExpr;
+#endif
 
 class Mat {
 public:
@@ -199,6 +217,15 @@ public:
     /* into a new CV_32F matrix (from 8-bit or float), then assigned to dst (which may be this matrix) */
     void convertTo(Mat &dst, int rtype) const
     {
+#ifdef CV_SHIM_LINALG
+        if (rtype == CV_32F && type_ == CV_64F) {                 /* each double rounded to float once */
+            Mat narrow(rows, cols, CV_32F);
+            for (int y = 0; y < rows; y++)
+                for (int x = 0; x < cols; x++) narrow.at<float>(y, x) = (float)at<double>(y, x);
+            dst = narrow;
+            return;
+        }
+#endif
         if (rtype != CV_32F) { std::fprintf(stderr, "cv_shim: convertTo is CV_32F only\n"); std::abort(); }
         Mat out(rows, cols, CV_32F);
         for (int y = 0; y < rows; y++)
@@ -232,10 +259,40 @@ public:
         for (int y = 0; y < rows; y++) std::memcpy(dst.ptr(y), tmp.ptr(y), (size_t)cols * elemSize());
     }
 
+#ifdef CV_SHIM_LINALG
+    /* cv_linalg.hpp: what src/Sim3Solver.cc, src/PnPsolver.cc and src/Initializer.cc use beyond the above */
+    Mat(int r, int c, int type, const Scalar &s);
+    Mat(const MatZeros &z) : Mat() { *this = z; }
+    Mat &operator=(const MatExpr &e);
+    Mat &operator*=(double s);
+    MatExpr t() const;
+    MatExpr inv() const;
+    double dot(const Mat &b) const;
+    Mat cross(const Mat &b) const;
+    Mat col(int x) const { return colRange(x, x + 1); }
+    Mat reshape(int cn, int new_rows) const;
+    static Mat eye(int r, int c, int type);
+    static Mat diag(const Mat &d);
+    void copyTo(Mat &&view) const;
+    /* one index: a vector's element (a column vector may be a view with a step) or a matrix element in row-major order */
+    template <typename T> T &at(int i)
+    {
+        return *(T *)(data + (cols == 1 ? (size_t)i * step : (size_t)(i / cols) * step + (size_t)(i % cols) * sizeof(T)));
+    }
+    template <typename T> const T &at(int i) const { return const_cast<Mat *>(this)->at<T>(i); }
+#endif
+
 private:
+#ifdef CV_SHIM_LINALG
+    static size_t elem(int type) { return type == CV_64F ? 8 : type == CV_32F ? 4 : 1; }
+#else
     static size_t elem(int type) { return type == CV_32F ? 4 : 1; }
+#endif
     static void check_type(int type)
     {
+#ifdef CV_SHIM_LINALG
+        if (type == CV_64F) return;
+#endif
         if (type != CV_8UC1 && type != CV_32F) { std::fprintf(stderr, "cv_shim: only CV_8UC1 and CV_32F\n"); std::abort(); }
     }
     static void check_range(int a, int b, int n)
@@ -248,6 +305,7 @@ private:
     std::shared_ptr<std::vector<uchar> > buf_;
 };
 
+#ifndef CV_SHIM_LINALG           /* cv_linalg.hpp has both as MatExpr, with the same arithmetic */
 /* scalar * Mat and Mat - Mat on CV_32F: each element rounded to float once, as saturate_cast<float> does */
 inline Mat operator*(double s, const Mat &m)
 {
@@ -269,6 +327,7 @@ inline Mat operator-(const Mat &a, const Mat &b)
         for (int x = 0; x < a.cols; x++) out.at<float>(y, x) = a.at<float>(y, x) - b.at<float>(y, x);
     return out;
 }
+#endif
 
 /* NORM_L1 of a - b for CV_32F: the differences in float, their absolute values summed in double */
 inline double norm(const Mat &a, const Mat &b, int normType)
@@ -346,5 +405,9 @@ public:
 };
 
 } // namespace cv
+
+#ifdef CV_SHIM_LINALG
+#include "cv_linalg.hpp"
+#endif
 
 #endif
