@@ -670,6 +670,40 @@ int orbm_pose_optimization_batch_device(orbm_matcher *m, int n_problems, const i
                                         void *hip_stream);
 
 /*
+ * ---- Optimizer::OptimizeSim3 for a batch of independent problems ----
+ * Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241) for B problems in one launch: the loop candidates of one round of
+ * LoopClosing::ComputeSim3 (src/LoopClosing.cc:287-343) whose Sim3Solver returned a Scm.  Problem p owns the pairs
+ * off[p]:off[p+1] of x1c, x2c (3 floats each), obs1, obs2 (2 floats each), inv_sigma2_1 and inv_sigma2_2, the two calibrations
+ * cams[8p .. 8p+8) = {fx1, fy1, cx1, cy1, fx2, fy2, cx2, cy2}, th2[p], fix_scale[p] (0 / not 0) and S12[8p .. 8p+8) (doubles, in
+ * and out); per problem the meaning of every array is that of orbp_optimize_sim3 (include/orbp.h) with n = off[p+1] - off[p]:
+ *   flags[i] = 1 where the reference sets vpMatches1[idx] = NULL; bytes outside the problems' ranges are not written
+ *   n_in[p]  = the function's return value; 0 with S12 of the problem untouched bit for bit when fewer than 10 pairs survive the
+ *              first pass (:1211-1212)
+ *
+ * One workgroup solves one problem with the text of the host path (csrc/orbp_sim3opt_body.h is compiled by both); the sums over
+ * the pairs are added in a fixed tree instead of in edge order, so S12 agrees with the host's to the spread
+ * of tests/golden/sim3opt/tolerance.json and a flag can differ only for a pair whose chi2 lies within rounding of th2.  The result
+ * of a problem does not depend on the batch around it, on its position in the batch or on the run.  There is no limit on n.
+ * Non-finite correspondences and points at depth 0 are outside the contract.
+ *
+ * Argument checks come before any device work (ORBX_E_INVALID: a negative count, NULL buffers, off[0] != 0 or a decreasing off,
+ * and in the host variant a non-finite S12); n_problems == 0 is ORBX_OK and touches nothing.  Every other call needs the GPU: a
+ * NULL handle fails with ORBX_E_HIP where there is no HIP device and with ORBX_E_INVALID where there is one.
+ * orbm_optimize_sim3_batch runs on the handle's stream through its staging arena (one upload, one launch, one download) and grows
+ * the handle when the batch is larger than its workspace; the grids in the handle are not touched.
+ *
+ * orbm_optimize_sim3_batch_device: the same on device pointers (4-byte aligned, d_S12 8-byte aligned).  Nothing is uploaded,
+ * downloaded, synchronised or grown; asynchronous on hip_stream (NULL = the handle's stream), capturable.
+ */
+int orbm_optimize_sim3_batch(orbm_matcher *m, int n_problems, const int32_t *off, const float *x1c, const float *x2c, const float *obs1,
+                             const float *obs2, const float *inv_sigma2_1, const float *inv_sigma2_2, const float *cams,
+                             const float *th2, const int32_t *fix_scale, double *S12, uint8_t *flags, int32_t *n_in);
+int orbm_optimize_sim3_batch_device(orbm_matcher *m, int n_problems, const int32_t *d_off, const float *d_x1c, const float *d_x2c,
+                                    const float *d_obs1, const float *d_obs2, const float *d_inv_sigma2_1,
+                                    const float *d_inv_sigma2_2, const float *d_cams, const float *d_th2, const int32_t *d_fix_scale,
+                                    double *d_S12, uint8_t *d_flags, int32_t *d_n_in, void *hip_stream);
+
+/*
  * ---- Sim3Solver: the hypotheses of all loop candidates in one call ----
  * LoopClosing::ComputeSim3 (src/LoopClosing.cc:253-343) runs up to 300 RANSAC iterations per candidate key frame, five at a time
  * (Sim3Solver::iterate, src/Sim3Solver.cc:140-207).  An iteration is a 3-point Horn solve (ComputeSim3, :226-337) and two

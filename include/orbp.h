@@ -105,6 +105,31 @@ int orbp_pose_optimization(int n, const float *obs, const float *u_right, const 
                            float fx, float fy, float cx, float cy, float bf, float *Tcw, uint8_t *outlier);
 
 /*
+ * ---- Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241), LoopClosing::ComputeSim3's call at src/LoopClosing.cc:327 ----
+ * One free VertexSim3Expmap; both point vertices of every correspondence are fixed (:1121, :1129), so the graph is one dense 7x7
+ * system and a sum over the edges.  With g2o's Sim3 (types/sim3.h), EdgeSim3ProjectXYZ / EdgeInverseSim3ProjectXYZ
+ * (types/types_seven_dof_expmap.h:130-171; their linearizeOplus is commented out, so the Jacobian is g2o's numeric one,
+ * core/base_binary_edge.hpp:130-205: central differences with delta 1e-9), RobustKernelHuber and the Levenberg loop of
+ * orbp_pose_optimization.  csrc/orbp_sim3opt_body.h cites each quirk at its line.
+ *
+ * Correspondence i (the caller gathers as :1099-1178 does and skips what the reference skips):
+ *   x1c, x2c   (3n floats each) R1w * P3D1w + t1w and R2w * P3D2w + t2w as the float cv::Mat holds them
+ *   obs1, obs2 (2n floats each) pKF1->mvKeysUn[i].pt and pKF2->mvKeysUn[i2].pt
+ *   inv_sigma2_1, inv_sigma2_2  mvInvLevelSigma2[octave] of the two key points
+ * K1, K2 = {fx, fy, cx, cy} of pKF1 and pKF2; th2 and fix_scale as the reference's arguments.
+ * S12: g2oS12 in the order of g2o::Sim3::operator[] (sim3.h:239-264): qx, qy, qz, qw, tx, ty, tz, s; in and out, never normalised.
+ * flags[i] = 1 where the reference sets vpMatches1[idx] = NULL, in either flagging pass (:1193-1202, :1227-1231).
+ * Returns nIn; 0 with S12 untouched and the first pass's flags set when nCorrespondences - nBad < 10 (:1211-1212); ORBX_E_INVALID
+ * on n < 0, a NULL pointer or a non-finite S12.
+ */
+int orbp_optimize_sim3(int n, const float *x1c, const float *x2c, const float *obs1, const float *obs2, const float *inv_sigma2_1,
+                       const float *inv_sigma2_2, const float *K1, const float *K2, float th2, int fix_scale, double *S12,
+                       uint8_t *flags);
+/* g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) (src/LoopClosing.cc:326) in the order of S12 above: R row-major
+ * (9 floats), t (3 floats); the quaternion is Eigen's Quaterniond(Matrix3d), not normalised. */
+int orbp_sim3_from_rts(const float *R, const float *t, float s, double *out);
+
+/*
  * ---- Sim3Solver (src/Sim3Solver.cc, include/Sim3Solver.h): RANSAC over 3-point Horn solves, LoopClosing::ComputeSim3 ----
  *   src/Sim3Solver.cc:35-112   Sim3Solver::Sim3Solver   -> orbp_sim3_create (the caller does Rcw*Xw+tcw and drops NULL / bad
  *                                                          MapPoints and those without an index, :62-103)

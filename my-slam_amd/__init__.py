@@ -222,6 +222,9 @@ def _bind_pose(L):
     L.orbm_pnp_hypotheses.argtypes = [vp, C.c_int] + [vp] * 11
     L.orbm_pnp_hypotheses_device.argtypes = [vp, C.c_int, C.c_int] + [vp] * 12
     L.orbm_pnp_hypotheses.restype = L.orbm_pnp_hypotheses_device.restype = C.c_int
+    L.orbp_optimize_sim3.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
+    L.orbp_sim3_from_rts.argtypes = [vp, vp, C.c_float, vp]
+    L.orbp_optimize_sim3.restype = L.orbp_sim3_from_rts.restype = C.c_int
     L.orbp_last_error.restype = C.c_char_p
     for name in ("orbp_pnp_create", "orbp_pnp_set_ransac_parameters", "orbp_pnp_iterate", "orbp_pnp_find",
                  "orbp_pose_optimization", "orbp_pnp_get_problem", "orbp_pnp_draw", "orbp_pnp_queued", "orbp_pnp_hypothesis",
@@ -363,6 +366,9 @@ def _bind_matcher(L):
     L.orbm_pose_optimization_batch.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_pose_optimization_batch_device.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.orbm_pose_optimization_batch.restype = L.orbm_pose_optimization_batch_device.restype = C.c_int
+    L.orbm_optimize_sim3_batch.argtypes = [vp, C.c_int] + [vp] * 13
+    L.orbm_optimize_sim3_batch_device.argtypes = [vp, C.c_int] + [vp] * 14
+    L.orbm_optimize_sim3_batch.restype = L.orbm_optimize_sim3_batch_device.restype = C.c_int
     L.orbm_search_by_bow_batch.argtypes = [vp, vp, C.c_int, vp, f, C.c_int, vp, vp]
     L.orbm_search_by_bow_kf_batch.argtypes = [vp, vp, vp, C.c_int, f, C.c_int, vp, vp]
     L.orbm_search_by_bow_batch.restype = L.orbm_search_by_bow_kf_batch.restype = C.c_int
@@ -893,6 +899,58 @@ class ORBmatcher:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
         _mchk(self.L.orbm_pose_optimization_batch_device(self.h, n_problems, ptr(off), ptr(obs), ptr(u_right), ptr(inv_sigma2), ptr(xw),
                                                          ptr(cams), ptr(Tcw), ptr(outlier), ptr(n_good), s))
+
+    @staticmethod
+    def pack_sim3opt_problems(problems):
+        """The CSR arrays of orbm_optimize_sim3_batch from a list of OptimizeSim3 argument tuples
+        (x1c, x2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, K1, K2, th2, fix_scale, S12) -> (off int32 [B+1], x1c float32 [N, 3], x2c,
+        obs1 float32 [N, 2], obs2, inv_sigma2_1 float32 [N], inv_sigma2_2, cams float32 [B, 8], th2 float32 [B], fix_scale int32 [B],
+        S12 float64 [B, 8])."""
+        B = len(problems)
+        off = np.zeros(B + 1, np.int32)
+        cams, th2, fix, S = np.zeros((B, 8), np.float32), np.zeros(B, np.float32), np.zeros(B, np.int32), np.zeros((B, 8), np.float64)
+        cols = [[] for _ in range(6)]
+        widths = (3, 3, 2, 2, 1, 1)
+        for p, args in enumerate(problems):
+            arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, w) for a, w in zip(args[:6], widths)]
+            if len(set(len(a) for a in arrs)) != 1:
+                raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %s" % (p, [len(a) for a in arrs]))
+            for c, a in zip(cols, arrs):
+                c.append(a)
+            off[p + 1] = off[p] + len(arrs[0])
+            cams[p, :4], cams[p, 4:] = np.asarray(args[6], np.float32), np.asarray(args[7], np.float32)
+            th2[p], fix[p] = args[8], 1 if args[9] else 0
+            S[p] = np.asarray(args[10], np.float64).reshape(8)
+        cat = lambda parts, w: np.ascontiguousarray(np.concatenate(parts), np.float32) if parts else np.zeros((0, w), np.float32)
+        x1, x2, o1, o2, s1, s2 = (cat(c, w) for c, w in zip(cols, widths))
+        return off, x1, x2, o1, o2, s1.reshape(-1), s2.reshape(-1), cams, th2, fix, S
+
+    def optimize_sim3_batch(self, problems):
+        """Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241) for a list of independent problems in one launch, each an argument
+        tuple of OptimizeSim3().  Returns a list of OptimizeSim3()'s results: (S12 float64 [8], flags bool[n], nIn)."""
+        off, x1, x2, o1, o2, s1, s2, cams, th2, fix, S = self.pack_sim3opt_problems(problems)
+        B = len(problems)
+        flags, n_in = np.zeros(max(int(off[-1]), 1), np.uint8), np.zeros(max(B, 1), np.int32)
+        _mchk(self.L.orbm_optimize_sim3_batch(self.h, B, _p(off), _p(x1), _p(x2), _p(o1), _p(o2), _p(s1), _p(s2), _p(cams), _p(th2), _p(fix),
+                                              _p(S), _p(flags), _p(n_in)))
+        return [(S[p].copy(), flags[off[p]:off[p + 1]].astype(bool), int(n_in[p])) for p in range(B)]
+
+    def optimize_sim3_batch_device(self, n_problems, off, x1c, x2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, cams, th2, fix_scale, S12,
+                                   flags, n_in, stream=None):
+        """The same on torch tensors on the handle's device: off int32 [B+1], x1c / x2c float32 [N, 3], obs1 / obs2 float32 [N, 2],
+        inv_sigma2_1 / inv_sigma2_2 float32 [N], cams float32 [B, 8], th2 float32 [B], fix_scale int32 [B], S12 float64 [B, 8]
+        (in/out), flags uint8 [N], n_in int32 [B].  Nothing is copied or synchronised; stream: a torch stream, a raw hipStream_t or
+        None (the handle's stream)."""
+        import torch
+        f32 = torch.float32
+        want = ((off, torch.int32), (x1c, f32), (x2c, f32), (obs1, f32), (obs2, f32), (inv_sigma2_1, f32), (inv_sigma2_2, f32), (cams, f32),
+                (th2, f32), (fix_scale, torch.int32), (S12, torch.float64), (flags, torch.uint8), (n_in, torch.int32))
+        for t, dt in want:
+            if (t is None and n_problems != 0) or (t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous())):
+                raise OrbxError(ORBX_E_INVALID, "optimize_sim3_batch_device wants contiguous device tensors of the documented dtypes")
+        s = getattr(stream, "cuda_stream", stream)
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        _mchk(self.L.orbm_optimize_sim3_batch_device(self.h, n_problems, *[ptr(t) for t, _ in want], s))
 
     @staticmethod
     def pack_sim3_problems(problems):
@@ -2106,6 +2164,38 @@ def epnp(pws, us, fu, fv, uc, vc):
     if err < 0:
         raise OrbxError(ORBX_E_INVALID, lib().orbp_last_error().decode())
     return R, t, err
+
+
+def sim3_from_rts(R, t, s):
+    """g2o::Sim3(Converter::toMatrix3d(R), Converter::toVector3d(t), s) (src/LoopClosing.cc:326) -> float64 [8] in the order of
+    g2o::Sim3::operator[]: qx, qy, qz, qw, tx, ty, tz, s."""
+    R = np.ascontiguousarray(R, np.float32).reshape(9)
+    t = np.ascontiguousarray(t, np.float32).reshape(3)
+    out = np.zeros(8, np.float64)
+    _pchk(lib().orbp_sim3_from_rts(_p(R), _p(t), s, _p(out)))
+    return out
+
+
+def OptimizeSim3(x1c, x2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, K1, K2, th2, fix_scale, S12):
+    """Optimizer::OptimizeSim3 (src/Optimizer.cc:1046-1241) on the host -> (S12 float64 [8], flags bool[n], nIn).  x1c / x2c:
+    R1w*P3D1w+t1w and R2w*P3D2w+t2w of the gathered correspondences, obs1 / obs2 their key points, K1 / K2 = (fx, fy, cx, cy), S12 =
+    g2oS12 as sim3_from_rts() orders it.  flags marks the correspondences the reference sets to NULL in vpMatches1."""
+    x1c = np.ascontiguousarray(x1c, np.float32).reshape(-1, 3)
+    x2c = np.ascontiguousarray(x2c, np.float32).reshape(-1, 3)
+    obs1 = np.ascontiguousarray(obs1, np.float32).reshape(-1, 2)
+    obs2 = np.ascontiguousarray(obs2, np.float32).reshape(-1, 2)
+    s1 = np.ascontiguousarray(inv_sigma2_1, np.float32).reshape(-1)
+    s2 = np.ascontiguousarray(inv_sigma2_2, np.float32).reshape(-1)
+    n = len(x1c)
+    if not (len(x2c) == len(obs1) == len(obs2) == len(s1) == len(s2) == n):
+        raise OrbxError(ORBX_E_INVALID, "OptimizeSim3: array lengths disagree")
+    K1 = np.ascontiguousarray(K1, np.float32).reshape(4)
+    K2 = np.ascontiguousarray(K2, np.float32).reshape(4)
+    S = np.ascontiguousarray(S12, np.float64).reshape(8).copy()
+    flags = np.zeros(max(n, 1), np.uint8)
+    n_in = _pchk(lib().orbp_optimize_sim3(n, _p(x1c), _p(x2c), _p(obs1), _p(obs2), _p(s1), _p(s2), _p(K1), _p(K2), th2,
+                                          1 if fix_scale else 0, _p(S), _p(flags)))
+    return S, flags[:n].astype(bool), n_in
 
 
 def PoseOptimization(obs, inv_sigma2, xw, fx, fy, cx, cy, Tcw, u_right=None, bf=0.0):

@@ -717,6 +717,8 @@ public:
     static const int HISTO_LENGTH = ORBM_HISTO_LENGTH;
     bool Valid() { return ready(); }
     const std::string &LastError() const { return err_; }
+    // this matcher's handle, for the batch calls that take one (Optimizer::OptimizeSim3Batch, PnPsolver.h); NULL when it cannot be made
+    orbm_matcher *Handle() { return ready() ? h_.m : nullptr; }
 
     // orbm_sim3_hypotheses (include/orbm.h) on this matcher's handle: the one GPU call of Sim3Solver::EvaluateAll (Sim3Solver.h)
     int Sim3Hypotheses(int nProblems, const int32_t *off, const float *x3Dc1, const float *x3Dc2, const float *maxErr1, const float *maxErr2,

@@ -216,6 +216,131 @@ public:
         }
         return ORBX_OK;
     }
+
+    // ---- Optimizer::OptimizeSim3 (include/Optimizer.h, src/Optimizer.cc:1046-1241; LoopClosing::ComputeSim3, src/LoopClosing.cc:327) ----
+    // One problem: what the reference feeds to g2o (:1059-1178), and its results.  index[k] = vnIndexEdge[k], the slot of vpMatches1
+    // correspondence k came from; S12 is g2oS12 in the order of g2o::Sim3::operator[] (qx, qy, qz, qw, tx, ty, tz, s), in and out.
+    struct Sim3Problem {
+        std::vector<float> x1c, x2c, obs1, obs2, invSigma2_1, invSigma2_2;
+        std::vector<size_t> index;
+        float K1[4] = {0, 0, 0, 0}, K2[4] = {0, 0, 0, 0};
+        float th2 = 10.f;
+        bool fixScale = true;
+        double S12[8] = {0, 0, 0, 1, 0, 0, 0, 1};
+        std::vector<bool> removed;          // per correspondence: the reference sets vpMatches1[index[k]] = NULL
+        int nIn = 0;                        // the return value
+    };
+    // The gather of :1059-1178 with its skips (:1101, :1112-1136) and GetIndexInKeyFrame (:1110).  g2oS12 is read through operator[]
+    // only.  The calibration is read from pKF->fx, fy, cx, cy (the entries of the mK the reference reads).
+    template <class KeyFrameT, class MapPointT, class Sim3T>
+    static void GatherSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, const std::vector<MapPointT *> &vpMatches1, const Sim3T &g2oS12, const float th2,
+                           const bool bFixScale, Sim3Problem &P)
+    {
+        P = Sim3Problem();
+        P.K1[0] = pKF1->fx; P.K1[1] = pKF1->fy; P.K1[2] = pKF1->cx; P.K1[3] = pKF1->cy;
+        P.K2[0] = pKF2->fx; P.K2[1] = pKF2->fy; P.K2[2] = pKF2->cx; P.K2[3] = pKF2->cy;
+        P.th2 = th2; P.fixScale = bFixScale;
+        for (int k = 0; k < 8; k++) P.S12[k] = g2oS12[k];
+        const auto R1w = pKF1->GetRotation(), t1w = pKF1->GetTranslation(), R2w = pKF2->GetRotation(), t2w = pKF2->GetTranslation();
+        const int N = (int)vpMatches1.size();
+        const std::vector<MapPointT *> vpMapPoints1 = pKF1->GetMapPointMatches();
+        for (int i = 0; i < N; i++) {
+            if (!vpMatches1[i]) continue;                                   // :1101
+            MapPointT *pMP1 = vpMapPoints1[i];
+            MapPointT *pMP2 = vpMatches1[i];
+            const int i2 = pMP2->GetIndexInKeyFrame(pKF2);                  // :1110
+            if (!(pMP1 && pMP2)) continue;                                  // :1112, :1135-1136
+            if (!(!pMP1->isBad() && !pMP2->isBad() && i2 >= 0)) continue;   // :1114, :1132-1133
+            sim3_to_camera(R1w, t1w, pMP1->GetWorldPos(), P.x1c);           // :1117-1119
+            sim3_to_camera(R2w, t2w, pMP2->GetWorldPos(), P.x2c);           // :1125-1127
+            const auto &kpUn1 = pKF1->mvKeysUn[i];
+            P.obs1.push_back(kpUn1.pt.x); P.obs1.push_back(kpUn1.pt.y);
+            P.invSigma2_1.push_back(pKF1->mvInvLevelSigma2[kpUn1.octave]);
+            const auto &kpUn2 = pKF2->mvKeysUn[i2];
+            P.obs2.push_back(kpUn2.pt.x); P.obs2.push_back(kpUn2.pt.y);
+            P.invSigma2_2.push_back(pKF2->mvInvLevelSigma2[kpUn2.octave]);
+            P.index.push_back((size_t)i);                                   // :1177
+        }
+    }
+    // the results of a solved problem on the caller's objects: NULL into vpMatches1 from the flags (:1196, :1230), g2oS12 through
+    // operator[] (:1238; a problem that returned at :1212 holds the S12 it came with)
+    template <class MapPointT, class Sim3T>
+    static int ScatterSim3(const Sim3Problem &P, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12)
+    {
+        for (size_t k = 0; k < P.index.size(); k++)
+            if (P.removed[k]) vpMatches1[P.index[k]] = static_cast<MapPointT *>(NULL);
+        for (int k = 0; k < 8; k++) g2oS12[k] = P.S12[k];
+        return P.nIn;
+    }
+    // The reference's signature (MapPointT deduces to MapPoint), so src/LoopClosing.cc:327 compiles unchanged; on the host
+    // (orbp_optimize_sim3), which is the faster call for one candidate (README).  < 0 on bad arguments (orbp_last_error()).
+    template <class KeyFrameT, class MapPointT, class Sim3T>
+    static int OptimizeSim3(KeyFrameT *pKF1, KeyFrameT *pKF2, std::vector<MapPointT *> &vpMatches1, Sim3T &g2oS12, const float th2, const bool bFixScale)
+    {
+        Sim3Problem P;
+        GatherSim3(pKF1, pKF2, vpMatches1, g2oS12, th2, bFixScale, P);
+        const int n = (int)P.index.size();
+        std::vector<uint8_t> flags(n + 1);
+        const int nIn = orbp_optimize_sim3(n, P.x1c.data(), P.x2c.data(), P.obs1.data(), P.obs2.data(), P.invSigma2_1.data(), P.invSigma2_2.data(),
+                                           P.K1, P.K2, th2, bFixScale ? 1 : 0, P.S12, flags.data());
+        if (nIn < 0) return nIn;
+        P.removed.assign(flags.begin(), flags.begin() + n);
+        P.nIn = nIn;
+        return ScatterSim3(P, vpMatches1, g2oS12);
+    }
+    // OptimizeSim3 for every problem in one GPU launch (orbm_optimize_sim3_batch, include/orbm.h): the candidates of one round of
+    // LoopClosing::ComputeSim3 that returned a Scm.  Returns the ORBX status; on failure no problem is changed and
+    // *err receives the text.
+    static int OptimizeSim3Batch(orbm_matcher *matcher, std::vector<Sim3Problem> &problems, std::string *err = nullptr)
+    {
+        const int B = (int)problems.size();
+        std::vector<int32_t> off(B + 1, 0), fix(B + 1);
+        for (int p = 0; p < B; p++) off[p + 1] = off[p] + (int32_t)problems[p].index.size();
+        const size_t N = (size_t)off[B];
+        std::vector<float> x1, x2, o1, o2, s1, s2, cams(8 * (size_t)B + 1), th2(B + 1);
+        std::vector<double> S(8 * (size_t)B + 1);
+        x1.reserve(3 * N + 1); x2.reserve(3 * N + 1); o1.reserve(2 * N + 1); o2.reserve(2 * N + 1); s1.reserve(N + 1); s2.reserve(N + 1);
+        for (int p = 0; p < B; p++) {
+            const Sim3Problem &P = problems[p];
+            const size_t n = P.index.size();
+            if (P.x1c.size() != 3 * n || P.x2c.size() != 3 * n || P.obs1.size() != 2 * n || P.obs2.size() != 2 * n || P.invSigma2_1.size() != n ||
+                P.invSigma2_2.size() != n) {
+                if (err) *err = "OptimizeSim3Batch: array lengths of problem " + std::to_string(p) + " disagree";
+                return ORBX_E_INVALID;
+            }
+            x1.insert(x1.end(), P.x1c.begin(), P.x1c.end()); x2.insert(x2.end(), P.x2c.begin(), P.x2c.end());
+            o1.insert(o1.end(), P.obs1.begin(), P.obs1.end()); o2.insert(o2.end(), P.obs2.begin(), P.obs2.end());
+            s1.insert(s1.end(), P.invSigma2_1.begin(), P.invSigma2_1.end()); s2.insert(s2.end(), P.invSigma2_2.begin(), P.invSigma2_2.end());
+            for (int k = 0; k < 4; k++) { cams[8 * (size_t)p + k] = P.K1[k]; cams[8 * (size_t)p + 4 + k] = P.K2[k]; }
+            th2[p] = P.th2; fix[p] = P.fixScale ? 1 : 0;
+            for (int k = 0; k < 8; k++) S[8 * (size_t)p + k] = P.S12[k];
+        }
+        x1.push_back(0.f); x2.push_back(0.f); o1.push_back(0.f); o2.push_back(0.f); s1.push_back(0.f); s2.push_back(0.f);      // never NULL
+        std::vector<uint8_t> flags(N + 1);
+        std::vector<int32_t> nIn(B + 1);
+        const int rc = orbm_optimize_sim3_batch(matcher, B, off.data(), x1.data(), x2.data(), o1.data(), o2.data(), s1.data(), s2.data(), cams.data(),
+                                                th2.data(), fix.data(), S.data(), flags.data(), nIn.data());
+        if (rc != ORBX_OK) { if (err) *err = orbm_last_error(); return rc; }
+        for (int p = 0; p < B; p++) {
+            Sim3Problem &P = problems[p];
+            for (int k = 0; k < 8; k++) P.S12[k] = S[8 * (size_t)p + k];
+            P.removed.assign(flags.begin() + off[p], flags.begin() + off[p + 1]);
+            P.nIn = nIn[p];
+        }
+        return ORBX_OK;
+    }
+
+private:
+    // R*X+t as one cv::gemm evaluates it: three float products summed in float, the translation added in double (Sim3Solver.h)
+    template <class MatT>
+    static void sim3_to_camera(const MatT &R, const MatT &t, const MatT &X, std::vector<float> &out)
+    {
+        const float x = X.template at<float>(0), y = X.template at<float>(1), z = X.template at<float>(2);
+        for (int r = 0; r < 3; r++) {
+            const float t0 = R.template at<float>(r, 0) * x + R.template at<float>(r, 1) * y + R.template at<float>(r, 2) * z;
+            out.push_back((float)((double)t0 + (double)t.template at<float>(r)));
+        }
+    }
 };
 
 }  // namespace ORB_SLAM2
