@@ -661,6 +661,43 @@ def _mchk(rc):
         raise OrbxError(rc, lib().orbm_last_error().decode())
 
 
+def _device_ptrs(method, want, stream, none_ok=True):
+    """The argument check of the *_device methods: want = (tensor, name of its torch dtype) pairs.  Returns (the tensors' device
+    pointers, None for a None tensor; the raw stream of a torch stream, a raw hipStream_t or None)."""
+    import torch
+    for t, dt in want:
+        if (t is None and not none_ok) or (t is not None and (not t.is_cuda or t.dtype != getattr(torch, dt) or not t.is_contiguous())):
+            raise OrbxError(ORBX_E_INVALID, "%s wants contiguous device tensors of the documented dtypes" % method)
+    return [None if t is None else C.c_void_p(t.data_ptr()) for t, _ in want], getattr(stream, "cuda_stream", stream)
+
+
+def _cat(parts, shape, dtype):
+    """The problems' arrays back to back; `shape` is that of no problem at all."""
+    return np.ascontiguousarray(np.concatenate(parts), dtype) if parts else np.zeros(shape, dtype)
+
+
+def _hyp_offsets(counts):
+    """(off int32, hyp_off int32, mask_off int64), B + 1 entries each, from every problem's (correspondences n, hypotheses h): the
+    frame of the hypothesis kernels (csrc/orbm_hyp.h), a hypothesis owning ceil(n / 32) mask words."""
+    B = len(counts)
+    off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
+    for p, (n, h) in enumerate(counts):
+        off[p + 1] = off[p] + n
+        hyp_off[p + 1] = hyp_off[p] + h
+        mask_off[p + 1] = mask_off[p] + h * ((n + 31) // 32)
+    return off, hyp_off, mask_off
+
+
+def _split_hypotheses(off, hyp_off, mask_off, first, second, masks):
+    """The flat results of a hypothesis call -> per problem (first [h, ...], second [h, ...], masks uint32 [h, ceil(n / 32)])."""
+    out = []
+    for p in range(len(off) - 1):
+        h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
+        W = (int(off[p + 1]) - int(off[p]) + 31) // 32
+        out.append((first[h0:h1].copy(), second[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
+    return out
+
+
 class ORBmatcher:
     """Python mirror of the Hamming primitives of ORB_SLAM2::ORBmatcher (include/ORBmatcher.h:41-89)."""
     TH_HIGH, TH_LOW, HISTO_LENGTH = 100, 50, 30
@@ -869,11 +906,11 @@ class ORBmatcher:
             off[p + 1] = off[p] + len(o)
             cams[p] = (fx, fy, cx, cy, bf)
             T[p] = np.asarray(Tcw, np.float32).reshape(16)
-        cat = lambda parts, shape: np.ascontiguousarray(np.concatenate(parts), np.float32) if parts else np.zeros(shape, np.float32)
+        f32 = np.float32
         u_all = None
         if any(u is not None for u in ur):
-            u_all = cat([u if u is not None else np.full(len(o), -1, np.float32) for u, o in zip(ur, obs)], (0,))
-        return off, cat(obs, (0, 2)), u_all, cat(s2, (0,)), cat(xw, (0, 3)), cams, T
+            u_all = _cat([u if u is not None else np.full(len(o), -1, f32) for u, o in zip(ur, obs)], (0,), f32)
+        return off, _cat(obs, (0, 2), f32), u_all, _cat(s2, (0,), f32), _cat(xw, (0, 3), f32), cams, T
 
     def pose_optimization_batch(self, problems):
         """Optimizer::PoseOptimization (src/Optimizer.cc:239-451) for a list of independent problems in one launch, each an argument
@@ -889,16 +926,10 @@ class ORBmatcher:
         inv_sigma2 float32 [N], xw float32 [N, 3], cams float32 [B, 5] (fx, fy, cx, cy, bf), Tcw float32 [B, 16] (in/out),
         outlier uint8 [N], n_good int32 [B].  Nothing is copied or synchronised; stream: a torch stream, a raw hipStream_t or None
         (the handle's stream)."""
-        import torch
-        want = ((off, torch.int32), (obs, torch.float32), (u_right, torch.float32), (inv_sigma2, torch.float32), (xw, torch.float32),
-                (cams, torch.float32), (Tcw, torch.float32), (outlier, torch.uint8), (n_good, torch.int32))
-        for t, dt in want:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise OrbxError(ORBX_E_INVALID, "pose_optimization_batch_device wants contiguous device tensors of the documented dtypes")
-        s = getattr(stream, "cuda_stream", stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _mchk(self.L.orbm_pose_optimization_batch_device(self.h, n_problems, ptr(off), ptr(obs), ptr(u_right), ptr(inv_sigma2), ptr(xw),
-                                                         ptr(cams), ptr(Tcw), ptr(outlier), ptr(n_good), s))
+        want = ((off, "int32"), (obs, "float32"), (u_right, "float32"), (inv_sigma2, "float32"), (xw, "float32"), (cams, "float32"),
+                (Tcw, "float32"), (outlier, "uint8"), (n_good, "int32"))
+        ptrs, s = _device_ptrs("pose_optimization_batch_device", want, stream)
+        _mchk(self.L.orbm_pose_optimization_batch_device(self.h, n_problems, *ptrs, s))
 
     @staticmethod
     def pack_sim3opt_problems(problems):
@@ -921,8 +952,7 @@ class ORBmatcher:
             cams[p, :4], cams[p, 4:] = np.asarray(args[6], np.float32), np.asarray(args[7], np.float32)
             th2[p], fix[p] = args[8], 1 if args[9] else 0
             S[p] = np.asarray(args[10], np.float64).reshape(8)
-        cat = lambda parts, w: np.ascontiguousarray(np.concatenate(parts), np.float32) if parts else np.zeros((0, w), np.float32)
-        x1, x2, o1, o2, s1, s2 = (cat(c, w) for c, w in zip(cols, widths))
+        x1, x2, o1, o2, s1, s2 = (_cat(c, (0, w), np.float32) for c, w in zip(cols, widths))
         return off, x1, x2, o1, o2, s1.reshape(-1), s2.reshape(-1), cams, th2, fix, S
 
     def optimize_sim3_batch(self, problems):
@@ -941,16 +971,11 @@ class ORBmatcher:
         inv_sigma2_1 / inv_sigma2_2 float32 [N], cams float32 [B, 8], th2 float32 [B], fix_scale int32 [B], S12 float64 [B, 8]
         (in/out), flags uint8 [N], n_in int32 [B].  Nothing is copied or synchronised; stream: a torch stream, a raw hipStream_t or
         None (the handle's stream)."""
-        import torch
-        f32 = torch.float32
-        want = ((off, torch.int32), (x1c, f32), (x2c, f32), (obs1, f32), (obs2, f32), (inv_sigma2_1, f32), (inv_sigma2_2, f32), (cams, f32),
-                (th2, f32), (fix_scale, torch.int32), (S12, torch.float64), (flags, torch.uint8), (n_in, torch.int32))
-        for t, dt in want:
-            if (t is None and n_problems != 0) or (t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous())):
-                raise OrbxError(ORBX_E_INVALID, "optimize_sim3_batch_device wants contiguous device tensors of the documented dtypes")
-        s = getattr(stream, "cuda_stream", stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _mchk(self.L.orbm_optimize_sim3_batch_device(self.h, n_problems, *[ptr(t) for t, _ in want], s))
+        f32 = "float32"
+        want = ((off, "int32"), (x1c, f32), (x2c, f32), (obs1, f32), (obs2, f32), (inv_sigma2_1, f32), (inv_sigma2_2, f32), (cams, f32),
+                (th2, f32), (fix_scale, "int32"), (S12, "float64"), (flags, "uint8"), (n_in, "int32"))
+        ptrs, s = _device_ptrs("optimize_sim3_batch_device", want, stream, none_ok=n_problems == 0)
+        _mchk(self.L.orbm_optimize_sim3_batch_device(self.h, n_problems, *ptrs, s))
 
     @staticmethod
     def pack_sim3_problems(problems):
@@ -958,9 +983,7 @@ class ORBmatcher:
         (x3dc1 [n, 3], x3dc2 [n, 3], max_err1 [n], max_err2 [n], K1 (4), K2 (4), fix_scale, triples [h, 3]) ->
         (off int32 [B+1], x3dc1 float32 [N, 3], x3dc2, max_err1 float32 [N], max_err2, cams SIM3_CAM_DTYPE [B], hyp_off int32 [B+1],
         triples int32 [H, 3], mask_off int64 [B+1])."""
-        B = len(problems)
-        off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
-        cams = np.zeros(B, SIM3_CAM_DTYPE)
+        cams = np.zeros(len(problems), SIM3_CAM_DTYPE)
         x1s, x2s, e1s, e2s, tris = [], [], [], [], []
         for p, pr in enumerate(problems):
             if isinstance(pr, Sim3Solver):
@@ -974,13 +997,10 @@ class ORBmatcher:
             if not (len(x1) == len(x2) == len(e1) == len(e2)):
                 raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %d / %d / %d / %d" % (p, len(x1), len(x2), len(e1), len(e2)))
             x1s.append(x1); x2s.append(x2); e1s.append(e1); e2s.append(e2); tris.append(tri)
-            off[p + 1] = off[p] + len(x1)
-            hyp_off[p + 1] = hyp_off[p] + len(tri)
-            mask_off[p + 1] = mask_off[p] + len(tri) * ((len(x1) + 31) // 32)
             cams[p] = (np.asarray(K1, np.float32).reshape(4), np.asarray(K2, np.float32).reshape(4), int(bool(fix)))
-        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(shape, dt)
-        return (off, cat(x1s, (0, 3), np.float32), cat(x2s, (0, 3), np.float32), cat(e1s, (0,), np.float32), cat(e2s, (0,), np.float32), cams,
-                hyp_off, cat(tris, (0, 3), np.int32), mask_off)
+        off, hyp_off, mask_off = _hyp_offsets([(len(x1), len(tri)) for x1, tri in zip(x1s, tris)])
+        return (off, _cat(x1s, (0, 3), np.float32), _cat(x2s, (0, 3), np.float32), _cat(e1s, (0,), np.float32), _cat(e2s, (0,), np.float32),
+                cams, hyp_off, _cat(tris, (0, 3), np.int32), mask_off)
 
     def sim3_hypotheses(self, problems):
         """Every hypothesis of every problem in one launch (orbm_sim3_hypotheses; problems as in pack_sim3_problems).  Returns a list
@@ -990,12 +1010,7 @@ class ORBmatcher:
         cnt, sRt, masks = np.zeros(max(H, 1), np.int32), np.zeros((max(H, 1), 13), np.float32), np.zeros(max(MW, 1), np.uint32)
         _mchk(self.L.orbm_sim3_hypotheses(self.h, B, _p(off), _p(x1), _p(x2), _p(e1), _p(e2), _p(cams), _p(hyp_off), _p(tri), _p(mask_off),
                                           _p(cnt), _p(sRt), _p(masks)))
-        out = []
-        for p in range(B):
-            h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
-            W = (int(off[p + 1]) - int(off[p]) + 31) // 32
-            out.append((cnt[h0:h1].copy(), sRt[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
-        return out
+        return _split_hypotheses(off, hyp_off, mask_off, cnt, sRt, masks)
 
     def sim3_hypotheses_device(self, n_problems, total_hypotheses, off, x3dc1, x3dc2, max_err1, max_err2, cams, hyp_off, triples, mask_off,
                                n_inliers, sRt, masks, stream=None):
@@ -1003,18 +1018,10 @@ class ORBmatcher:
         float32 [N], cams uint8 [B, 36] (SIM3_CAM_DTYPE bytes), hyp_off int32 [B+1], triples int32 [H, 3], mask_off int64 [B+1],
         n_inliers int32 [H], sRt float32 [H, 13], masks int32 [mask words].  Nothing is copied or synchronised; stream: a torch
         stream, a raw hipStream_t or None (the handle's stream)."""
-        import torch
-        want = ((off, torch.int32), (x3dc1, torch.float32), (x3dc2, torch.float32), (max_err1, torch.float32), (max_err2, torch.float32),
-                (cams, torch.uint8), (hyp_off, torch.int32), (triples, torch.int32), (mask_off, torch.int64), (n_inliers, torch.int32),
-                (sRt, torch.float32), (masks, torch.int32))
-        for t, dt in want:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise OrbxError(ORBX_E_INVALID, "sim3_hypotheses_device wants contiguous device tensors of the documented dtypes")
-        s = getattr(stream, "cuda_stream", stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _mchk(self.L.orbm_sim3_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(x3dc1), ptr(x3dc2), ptr(max_err1),
-                                                 ptr(max_err2), ptr(cams), ptr(hyp_off), ptr(triples), ptr(mask_off), ptr(n_inliers),
-                                                 ptr(sRt), ptr(masks), s))
+        want = ((off, "int32"), (x3dc1, "float32"), (x3dc2, "float32"), (max_err1, "float32"), (max_err2, "float32"), (cams, "uint8"),
+                (hyp_off, "int32"), (triples, "int32"), (mask_off, "int64"), (n_inliers, "int32"), (sRt, "float32"), (masks, "int32"))
+        ptrs, s = _device_ptrs("sim3_hypotheses_device", want, stream)
+        _mchk(self.L.orbm_sim3_hypotheses_device(self.h, n_problems, total_hypotheses, *ptrs, s))
 
     @staticmethod
     def pack_init_problems(problems):
@@ -1022,9 +1029,7 @@ class ORBmatcher:
         the F) or a tuple (uv [n, 4], pn [n, 4], T1 (9), T2 (9), sigma, sets [h, 8], models [h]) ->
         (off int32 [B+1], uv float32 [N, 4], pn float32 [N, 4], params INIT_PARAMS_DTYPE [B], hyp_off int32 [B+1], sets int32 [H, 8],
         models int32 [H], mask_off int64 [B+1])."""
-        B = len(problems)
-        off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
-        params = np.zeros(B, INIT_PARAMS_DTYPE)
+        params = np.zeros(len(problems), INIT_PARAMS_DTYPE)
         uvs, pns, setss, modelss = [], [], [], []
         for p, pr in enumerate(problems):
             if isinstance(pr, Initializer):
@@ -1038,13 +1043,10 @@ class ORBmatcher:
                 raise OrbxError(ORBX_E_INVALID, "problem %d: array lengths disagree: %d / %d matches, %d / %d hypotheses"
                                 % (p, len(uv), len(pn), len(sets), len(models)))
             uvs.append(uv); pns.append(pn); setss.append(sets); modelss.append(models)
-            off[p + 1] = off[p] + len(uv)
-            hyp_off[p + 1] = hyp_off[p] + len(sets)
-            mask_off[p + 1] = mask_off[p] + len(sets) * ((len(uv) + 31) // 32)
             params[p] = (np.asarray(T1, np.float32).reshape(9), np.asarray(T2, np.float32).reshape(9), np.float32(sigma))
-        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(shape, dt)
-        return (off, cat(uvs, (0, 4), np.float32), cat(pns, (0, 4), np.float32), params, hyp_off, cat(setss, (0, 8), np.int32),
-                cat(modelss, (0,), np.int32), mask_off)
+        off, hyp_off, mask_off = _hyp_offsets([(len(uv), len(sets)) for uv, sets in zip(uvs, setss)])
+        return (off, _cat(uvs, (0, 4), np.float32), _cat(pns, (0, 4), np.float32), params, hyp_off, _cat(setss, (0, 8), np.int32),
+                _cat(modelss, (0,), np.int32), mask_off)
 
     def init_hypotheses(self, problems):
         """Every H / F hypothesis of every problem in one launch (orbm_init_hypotheses; problems as in pack_init_problems).  Returns a
@@ -1055,12 +1057,7 @@ class ORBmatcher:
         sm, cnt, masks = np.zeros((max(H, 1), 10), np.float32), np.zeros(max(H, 1), np.int32), np.zeros(max(MW, 1), np.uint32)
         _mchk(self.L.orbm_init_hypotheses(self.h, B, _p(off), _p(uv), _p(pn), _p(params), _p(hyp_off), _p(sets), _p(models), _p(mask_off),
                                           _p(sm), _p(cnt), _p(masks)))
-        out = []
-        for p in range(B):
-            h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
-            W = (int(off[p + 1]) - int(off[p]) + 31) // 32
-            out.append((sm[h0:h1].copy(), cnt[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
-        return out
+        return _split_hypotheses(off, hyp_off, mask_off, sm, cnt, masks)
 
     def init_hypotheses_device(self, n_problems, total_hypotheses, off, uv, pn, params, hyp_off, sets, models, mask_off, score_M, n_inliers,
                                masks, stream=None):
@@ -1068,17 +1065,10 @@ class ORBmatcher:
         (INIT_PARAMS_DTYPE bytes), hyp_off int32 [B+1], sets int32 [H, 8], models int32 [H], mask_off int64 [B+1], score_M float32
         [H, 10], n_inliers int32 [H], masks int32 [mask words].  Nothing is copied or synchronised; stream: a torch stream, a raw
         hipStream_t or None (the handle's stream)."""
-        import torch
-        want = ((off, torch.int32), (uv, torch.float32), (pn, torch.float32), (params, torch.uint8), (hyp_off, torch.int32),
-                (sets, torch.int32), (models, torch.int32), (mask_off, torch.int64), (score_M, torch.float32), (n_inliers, torch.int32),
-                (masks, torch.int32))
-        for t, dt in want:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise OrbxError(ORBX_E_INVALID, "init_hypotheses_device wants contiguous device tensors of the documented dtypes")
-        s = getattr(stream, "cuda_stream", stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _mchk(self.L.orbm_init_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(uv), ptr(pn), ptr(params), ptr(hyp_off),
-                                                 ptr(sets), ptr(models), ptr(mask_off), ptr(score_M), ptr(n_inliers), ptr(masks), s))
+        want = ((off, "int32"), (uv, "float32"), (pn, "float32"), (params, "uint8"), (hyp_off, "int32"), (sets, "int32"), (models, "int32"),
+                (mask_off, "int64"), (score_M, "float32"), (n_inliers, "int32"), (masks, "int32"))
+        ptrs, s = _device_ptrs("init_hypotheses_device", want, stream)
+        _mchk(self.L.orbm_init_hypotheses_device(self.h, n_problems, total_hypotheses, *ptrs, s))
 
     def init_check_rt(self, uv, inliers, K, th2, Rt):
         """CheckRT's per-match part for every motion of Rt [k, 12] in one launch (orbm_init_check_rt) ->
@@ -1097,17 +1087,10 @@ class ORBmatcher:
     def init_check_rt_device(self, n, uv, inliers, K, th2, n_motions, Rt, status, cos_parallax, p3d, stream=None):
         """The same on torch tensors on the handle's device: uv float32 [n, 4], inliers uint8 [n], Rt float32 [k, 12], status uint8
         [k, n], cos_parallax float32 [k, n], p3d float32 [k, n, 3]; K = (fx, fy, cx, cy) and th2 are host values."""
-        import torch
-        want = ((uv, torch.float32), (inliers, torch.uint8), (Rt, torch.float32), (status, torch.uint8), (cos_parallax, torch.float32),
-                (p3d, torch.float32))
-        for t, dt in want:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise OrbxError(ORBX_E_INVALID, "init_check_rt_device wants contiguous device tensors of the documented dtypes")
+        want = ((uv, "float32"), (inliers, "uint8"), (Rt, "float32"), (status, "uint8"), (cos_parallax, "float32"), (p3d, "float32"))
+        (uv, inliers, Rt, status, cos_parallax, p3d), s = _device_ptrs("init_check_rt_device", want, stream)
         K = np.ascontiguousarray(K, np.float32).reshape(4)
-        s = getattr(stream, "cuda_stream", stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _mchk(self.L.orbm_init_check_rt_device(self.h, n, ptr(uv), ptr(inliers), _p(K), float(th2), n_motions, ptr(Rt), ptr(status),
-                                               ptr(cos_parallax), ptr(p3d), s))
+        _mchk(self.L.orbm_init_check_rt_device(self.h, n, uv, inliers, _p(K), float(th2), n_motions, Rt, status, cos_parallax, p3d, s))
 
     @staticmethod
     def pack_pnp_problems(problems):
@@ -1115,9 +1098,7 @@ class ORBmatcher:
         (p2d [n, 2], p3d [n, 3], max_err [n], K (fx, fy, cx, cy), set_size, samples [h, set_size]) ->
         (off int32 [B+1], p2d float32 [N, 2], p3d float32 [N, 3], max_err float32 [N], cams PNP_CAM_DTYPE [B], hyp_off int32 [B+1],
         samples int32 [H, 8] (padded with -1), mask_off int64 [B+1])."""
-        B = len(problems)
-        off, hyp_off, mask_off = np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int32), np.zeros(B + 1, np.int64)
-        cams = np.zeros(B, PNP_CAM_DTYPE)
+        cams = np.zeros(len(problems), PNP_CAM_DTYPE)
         p2s, p3s, es, sms = [], [], [], []
         for p, pr in enumerate(problems):
             if isinstance(pr, PnPsolver):
@@ -1134,14 +1115,11 @@ class ORBmatcher:
             k = min(set_size, ORBM_PNP_MAX_SET)      # a larger set is refused by the call (cams carries its true size)
             padded[:, :k] = sm[:, :k]
             p2s.append(p2d); p3s.append(p3d); es.append(e); sms.append(padded)
-            off[p + 1] = off[p] + len(p2d)
-            hyp_off[p + 1] = hyp_off[p] + len(sm)
-            mask_off[p + 1] = mask_off[p] + len(sm) * ((len(p2d) + 31) // 32)
             K = np.asarray(K, np.float32).reshape(4)
             cams[p] = (K[0], K[1], K[2], K[3], set_size)
-        cat = lambda parts, shape, dt: np.ascontiguousarray(np.concatenate(parts), dt) if parts else np.zeros(shape, dt)
-        return (off, cat(p2s, (0, 2), np.float32), cat(p3s, (0, 3), np.float32), cat(es, (0,), np.float32), cams, hyp_off,
-                cat(sms, (0, ORBM_PNP_MAX_SET), np.int32), mask_off)
+        off, hyp_off, mask_off = _hyp_offsets([(len(p2d), len(sm)) for p2d, sm in zip(p2s, sms)])
+        return (off, _cat(p2s, (0, 2), np.float32), _cat(p3s, (0, 3), np.float32), _cat(es, (0,), np.float32), cams, hyp_off,
+                _cat(sms, (0, ORBM_PNP_MAX_SET), np.int32), mask_off)
 
     def pnp_hypotheses(self, problems):
         """Every EPnP hypothesis of every problem in one launch (orbm_pnp_hypotheses; problems as in pack_pnp_problems).  Returns a
@@ -1152,12 +1130,7 @@ class ORBmatcher:
         cnt, Rt, masks = np.zeros(max(H, 1), np.int32), np.zeros((max(H, 1), 12), np.float64), np.zeros(max(MW, 1), np.uint32)
         _mchk(self.L.orbm_pnp_hypotheses(self.h, B, _p(off), _p(p2d), _p(p3d), _p(e), _p(cams), _p(hyp_off), _p(sm), _p(mask_off),
                                          _p(cnt), _p(Rt), _p(masks)))
-        out = []
-        for p in range(B):
-            h0, h1 = int(hyp_off[p]), int(hyp_off[p + 1])
-            W = (int(off[p + 1]) - int(off[p]) + 31) // 32
-            out.append((cnt[h0:h1].copy(), Rt[h0:h1].copy(), masks[mask_off[p]:mask_off[p + 1]].reshape(h1 - h0, W).copy()))
-        return out
+        return _split_hypotheses(off, hyp_off, mask_off, cnt, Rt, masks)
 
     def pnp_hypotheses_device(self, n_problems, total_hypotheses, off, p2d, p3d, max_err, cams, hyp_off, samples, mask_off, n_inliers, Rt,
                               masks, stream=None):
@@ -1165,17 +1138,10 @@ class ORBmatcher:
         [N], cams uint8 [B, 20] (PNP_CAM_DTYPE bytes), hyp_off int32 [B+1], samples int32 [H, 8], mask_off int64 [B+1], n_inliers
         int32 [H], Rt float64 [H, 12], masks int32 [mask words].  Nothing is copied or synchronised; stream: a torch stream, a raw
         hipStream_t or None (the handle's stream)."""
-        import torch
-        want = ((off, torch.int32), (p2d, torch.float32), (p3d, torch.float32), (max_err, torch.float32), (cams, torch.uint8),
-                (hyp_off, torch.int32), (samples, torch.int32), (mask_off, torch.int64), (n_inliers, torch.int32), (Rt, torch.float64),
-                (masks, torch.int32))
-        for t, dt in want:
-            if t is not None and (not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise OrbxError(ORBX_E_INVALID, "pnp_hypotheses_device wants contiguous device tensors of the documented dtypes")
-        s = getattr(stream, "cuda_stream", stream)
-        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-        _mchk(self.L.orbm_pnp_hypotheses_device(self.h, n_problems, total_hypotheses, ptr(off), ptr(p2d), ptr(p3d), ptr(max_err), ptr(cams),
-                                                ptr(hyp_off), ptr(samples), ptr(mask_off), ptr(n_inliers), ptr(Rt), ptr(masks), s))
+        want = ((off, "int32"), (p2d, "float32"), (p3d, "float32"), (max_err, "float32"), (cams, "uint8"), (hyp_off, "int32"),
+                (samples, "int32"), (mask_off, "int64"), (n_inliers, "int32"), (Rt, "float64"), (masks, "int32"))
+        ptrs, s = _device_ptrs("pnp_hypotheses_device", want, stream)
+        _mchk(self.L.orbm_pnp_hypotheses_device(self.h, n_problems, total_hypotheses, *ptrs, s))
 
     def search_local_points(self, view, skip, xw, normal, mf_max, mf_min, mp_desc, mp_obs, kps_cur, desc_cur, cur_obs, th,
                             u_right=None, viewing_cos_limit=0.5):

@@ -3,17 +3,16 @@
 // passes of ReconstructF / ReconstructH (:494-497, :698-718) in one launch (orbm_init_check_rt / _device).  The draws, the two
 // walks that keep the best score, the candidate motions and the acceptance rules stay on the host (orbp_init.cc).
 //
-// k_init_hypotheses: one wave per hypothesis = (index set, model), INIT_WAVES waves to a workgroup, hypotheses by flat index
-// (problem = binary search over hyp_off).  The solve (orbp_init_body.h, the host solver's text) is run uniformly by the wave: the
-// Jacobi's 16 x 9 / 9 x 9 matrix, its V, the column norms and their order are indexed at run time, so they live in a wave-private
-// piece of LDS (sizeof(InitWork) bytes per wave) instead of scratch; every lane reads the same address (a broadcast) and writes the
-// same value.  The lanes then stride over the problem's matches.  The score is the reference's float sum in match order, term 1 then
-// term 2 of every match: the lanes compute the terms, and the wave adds them one readlane at a time on the uniform path, so the sum
-// is the host's to the bit.  A ballot is 64 bits of the mask and its popcount adds to the count.  No workgroup barrier, no atomics;
+// k_init_hypotheses: one wave per hypothesis = (index set, model) in the frame of orbm_hyp.h (flat index, problem search, mask
+// rows, vote).  The solve (orbp_init_body.h, the host solver's text) is run uniformly by the wave: the Jacobi's 16 x 9 / 9 x 9
+// matrix, its V, the column norms and their order are indexed at run time, so they live in a wave-private piece of LDS
+// (sizeof(InitWork) bytes per wave) instead of scratch; every lane reads the same address (a broadcast) and writes the same value.
+// The score is the reference's float sum in match order, term 1 then term 2 of every match: the lanes compute the terms, and the
+// wave adds them one readlane at a time on the uniform path, so the sum is the host's to the bit.  No workgroup barrier, no atomics;
 // lane 0 writes the wave's results with vector stores.
 //
 // k_init_check_rt: one lane per (motion, match); init_motion_prepare is redone by every lane (a dozen products).
-#include "orbm_internal.h"
+#include "orbm_hyp.h"
 #include "orbp_init_body.h"
 
 #define INIT_WAVES (M_THREADS / 64)
@@ -26,20 +25,11 @@ __global__ __launch_bounds__(M_THREADS) void k_init_hypotheses(
 {
     __shared__ InitWork lds[INIT_WAVES];
     const int lane = threadIdx.x & 63;
-    const long long hl = (long long)blockIdx.x * INIT_WAVES + (threadIdx.x >> 6);
-    const int total = hyp_off[n_problems];
-    if (hl >= total) return;                    // whole waves leave
-    const int h = __builtin_amdgcn_readfirstlane((int)hl);
-    int lo = 0, hi = n_problems - 1;            // the last p with hyp_off[p] <= h (problems without hypotheses are stepped over)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (hyp_off[mid] <= h) lo = mid; else hi = mid - 1;
-    }
-    const int p = lo;
-    const long long c0 = off[p];
-    const int n = off[p + 1] - off[p];
-    const int W = (n + 31) >> 5;
-    uint32_t *mk = masks + mask_off[p] + (long long)(h - hyp_off[p]) * W;
+    const long long hl = hyp_wave_index(INIT_WAVES);
+    if (hl >= hyp_off[n_problems]) return;      // whole waves leave
+    const HypFrame f = hyp_frame(n_problems, off, hyp_off, mask_off, masks, hl);
+    const int h = f.h, p = f.p, n = f.n;
+    const long long c0 = f.c0;
     float *out = score_M + 10 * (long long)h;
     if (n <= 0) {                               // nothing to sample from: refused by the host variant
         if (lane == 0) {
@@ -83,12 +73,7 @@ __global__ __launch_bounds__(M_THREADS) void k_init_hypotheses(
             const float u1 = q[0], v1 = q[1], u2 = q[2], v2 = q[3];
             inl = is_h ? init_check_h_one(M, H12, u1, v1, u2, v2, inv_s2, s1, s2) : init_check_f_one(M, u1, v1, u2, v2, inv_s2, s1, s2);
         }
-        const unsigned long long b = __ballot(inl);
-        count += __popcll(b);
-        if (lane == 0) {
-            mk[base >> 5] = (uint32_t)b;
-            if ((base >> 5) + 1 < W) mk[(base >> 5) + 1] = (uint32_t)(b >> 32);
-        }
+        count += hyp_vote(f, inl, base, lane);
         // the reference's sum (:363, :379 / :441, :459): match order, term 1 then term 2, in float
         const int lim = min(64, n - base);
         for (int k = 0; k < lim; k++) {
@@ -125,13 +110,6 @@ __global__ __launch_bounds__(M_THREADS) void k_init_check_rt(
     p3d[3 * g] = X[0]; p3d[3 * g + 1] = X[1]; p3d[3 * g + 2] = X[2];
 }
 
-static int init_check_counts(int n_problems)
-{
-    if (n_problems < 0) return mfail(ORBX_E_INVALID, "n_problems=%d", n_problems);
-    if (n_problems > (1 << 24)) return mfail(ORBX_E_CAPACITY, "request beyond 2^24 problems");
-    return ORBX_OK;
-}
-
 static void init_launch(int n_problems, int total_hyp, const int32_t *off, const float *uv, const float *pn, const orbm_init_params *params,
                         const int32_t *hyp_off, const int32_t *sets, const int32_t *models, const int64_t *mask_off, float *score_M,
                         int32_t *n_inliers, uint32_t *masks, hipStream_t s)
@@ -144,23 +122,15 @@ extern "C" int orbm_init_hypotheses(orbm_matcher *m, int n_problems, const int32
                                     const orbm_init_params *params, const int32_t *hyp_off, const int32_t *sets, const int32_t *models,
                                     const int64_t *mask_off, float *score_M, int32_t *n_inliers, uint32_t *masks)
 {
-    MTRY(init_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (n_problems == 0) return ORBX_OK;
-    if (!off || !hyp_off || !mask_off || !params) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (off[0] != 0 || hyp_off[0] != 0 || mask_off[0] != 0) return mfail(ORBX_E_INVALID, "off[0], hyp_off[0] and mask_off[0] must be 0");
-    for (int p = 0; p < n_problems; p++) {
-        if (off[p + 1] < off[p]) return mfail(ORBX_E_INVALID, "off not monotone at %d", p);
-        if (hyp_off[p + 1] < hyp_off[p]) return mfail(ORBX_E_INVALID, "hyp_off not monotone at %d", p);
-        const int64_t W = ((int64_t)off[p + 1] - off[p] + 31) / 32;
-        if (mask_off[p + 1] != mask_off[p] + W * ((int64_t)hyp_off[p + 1] - hyp_off[p]))
-            return mfail(ORBX_E_INVALID, "mask_off[%d] is not mask_off[%d] + hypotheses * ceil(n / 32)", p + 1, p);
-    }
-    const int total = off[n_problems], H = hyp_off[n_problems];
-    const int64_t MW = mask_off[n_problems];
+    if (any_null(off, hyp_off, mask_off, params)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    int total, H;
+    int64_t MW;
+    MTRY(check_hyp_csr(n_problems, off, hyp_off, mask_off, 26, "matches", 24, total, H, MW));
     if (H == 0) return ORBX_OK;
-    if (total > (1 << 26) || H > (1 << 24) || MW > (1ll << 29)) return mfail(ORBX_E_CAPACITY, "request beyond 2^26 matches / 2^24 hypotheses / 2^29 mask words");
-    if (!sets || !models || !score_M || !n_inliers || (MW > 0 && !masks)) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (total > 0 && (!uv || !pn)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (any_null(sets, models, score_M, n_inliers) || (MW > 0 && !masks)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (total > 0 && any_null(uv, pn)) return mfail(ORBX_E_INVALID, "NULL buffer");
     for (int p = 0; p < n_problems; p++) {
         const int n = off[p + 1] - off[p];
         for (long long hh = hyp_off[p]; hh < hyp_off[p + 1]; hh++) {
@@ -174,27 +144,21 @@ extern "C" int orbm_init_hypotheses(orbm_matcher *m, int n_problems, const int32
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     // d_out holds the 10 floats per hypothesis, the counts, then the mask words
-    const size_t Hs = (size_t)H, words = 11 * Hs + (size_t)MW;
-    MTRY(orbm_grow(m, 0, 0, (long long)words));
+    const size_t B = (size_t)n_problems, N = (size_t)total, Hs = (size_t)H;
+    const OutBlock out({{score_M, Hs * 40}, {n_inliers, Hs * 4}, {masks, (size_t)MW * 4}});
+    MTRY(orbm_grow(m, 0, 0, (long long)out.words()));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    const size_t B = (size_t)n_problems, N = (size_t)total;
     InBlock in(m);
     const int pm = in.add(mask_off, (B + 1) * 8), po = in.add(off, (B + 1) * 4), pu = in.add(uv, N * 16), pp = in.add(pn, N * 16),
               pc = in.add(params, B * sizeof(orbm_init_params)), ph = in.add(hyp_off, (B + 1) * 4), ps = in.add(sets, Hs * 32),
               pmd = in.add(models, Hs * 4);
     MTRY(in.upload(s));
-    float *d_sm = reinterpret_cast<float *>(m->d_out.get());
-    int32_t *d_cnt = m->d_out + 10 * Hs;
-    uint32_t *d_masks = reinterpret_cast<uint32_t *>(m->d_out + 11 * Hs);
     init_launch(n_problems, H, in.dev_at<int32_t>(po), in.dev_at<float>(pu), in.dev_at<float>(pp), in.dev_at<orbm_init_params>(pc),
-                in.dev_at<int32_t>(ph), in.dev_at<int32_t>(ps), in.dev_at<int32_t>(pmd), in.dev_at<int64_t>(pm), d_sm, d_cnt, d_masks, s);
+                in.dev_at<int32_t>(ph), in.dev_at<int32_t>(ps), in.dev_at<int32_t>(pmd), in.dev_at<int64_t>(pm), out.dev_at<float>(m, 0),
+                out.dev_at<int32_t>(m, 1), out.dev_at<uint32_t>(m, 2), s);
     MHIPCHK(hipGetLastError());
-    void *host[3] = {score_M, n_inliers, masks};
-    const size_t parts[3] = {Hs * 40, Hs * 4, (size_t)MW * 4};
-    MTRY(orbm_d2h_split(m, host, parts, 3, m->d_out, s));
-    MTRY(orbm_sync(m, s));
-    return ORBX_OK;
+    return out.download(m, s);
 }
 
 extern "C" int orbm_init_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypotheses, const int32_t *d_off, const float *d_uv,
@@ -202,14 +166,12 @@ extern "C" int orbm_init_hypotheses_device(orbm_matcher *m, int n_problems, int 
                                            const int32_t *d_models, const int64_t *d_mask_off, float *d_score_M, int32_t *d_n_inliers,
                                            uint32_t *d_masks, void *hip_stream)
 {
-    MTRY(init_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (total_hypotheses < 0) return mfail(ORBX_E_INVALID, "total_hypotheses=%d", total_hypotheses);
     if (n_problems == 0 || total_hypotheses == 0) return ORBX_OK;
-    if (!d_off || !d_uv || !d_pn || !d_params || !d_hyp_off || !d_sets || !d_models || !d_mask_off || !d_score_M || !d_n_inliers || !d_masks)
+    if (any_null(d_off, d_uv, d_pn, d_params, d_hyp_off, d_sets, d_models, d_mask_off, d_score_M, d_n_inliers, d_masks))
         return mfail(ORBX_E_INVALID, "NULL buffer");
-    if ((((uintptr_t)d_off | (uintptr_t)d_uv | (uintptr_t)d_pn | (uintptr_t)d_params | (uintptr_t)d_hyp_off | (uintptr_t)d_sets |
-          (uintptr_t)d_models | (uintptr_t)d_score_M | (uintptr_t)d_n_inliers | (uintptr_t)d_masks) & 3) ||
-        ((uintptr_t)d_mask_off & 7))
+    if (misaligned(3, d_off, d_uv, d_pn, d_params, d_hyp_off, d_sets, d_models, d_score_M, d_n_inliers, d_masks) || misaligned(7, d_mask_off))
         return mfail(ORBX_E_INVALID, "device arrays must be 4-byte aligned, mask_off 8-byte aligned");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
@@ -240,27 +202,22 @@ extern "C" int orbm_init_check_rt(orbm_matcher *m, int n, const float *uv, const
 {
     MTRY(rt_check_counts(n, n_motions));
     if (n == 0 || n_motions == 0) return ORBX_OK;
-    if (!uv || !inliers || !K || !Rt || !status || !cos_parallax || !p3d) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (any_null(uv, inliers, K, Rt, status, cos_parallax, p3d)) return mfail(ORBX_E_INVALID, "NULL buffer");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     // d_out holds the points (3 floats per pair), the cosines, then the status bytes
-    const size_t pairs = (size_t)n * n_motions, words = 4 * pairs + (pairs + 3) / 4;
-    MTRY(orbm_grow(m, 0, 0, (long long)words));
+    const size_t pairs = (size_t)n * n_motions;
+    const OutBlock out({{p3d, pairs * 12}, {cos_parallax, pairs * 4}, {status, pairs}});
+    MTRY(orbm_grow(m, 0, 0, (long long)out.words()));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     InBlock in(m);
     const int pu = in.add(uv, (size_t)n * 16), pr = in.add(Rt, (size_t)n_motions * 48), pi = in.add(inliers, (size_t)n);
     MTRY(in.upload(s));
-    float *d_p3d = reinterpret_cast<float *>(m->d_out.get());
-    float *d_cos = d_p3d + 3 * pairs;
-    uint8_t *d_status = reinterpret_cast<uint8_t *>(d_cos + pairs);
-    rt_launch(n, n_motions, in.dev_at<float>(pu), in.dev_at<uint8_t>(pi), in.dev_at<float>(pr), K, th2, d_status, d_cos, d_p3d, s);
+    rt_launch(n, n_motions, in.dev_at<float>(pu), in.dev_at<uint8_t>(pi), in.dev_at<float>(pr), K, th2, out.dev_at<uint8_t>(m, 2),
+              out.dev_at<float>(m, 1), out.dev_at<float>(m, 0), s);
     MHIPCHK(hipGetLastError());
-    void *host[3] = {p3d, cos_parallax, status};
-    const size_t parts[3] = {pairs * 12, pairs * 4, pairs};
-    MTRY(orbm_d2h_split(m, host, parts, 3, m->d_out, s));
-    MTRY(orbm_sync(m, s));
-    return ORBX_OK;
+    return out.download(m, s);
 }
 
 extern "C" int orbm_init_check_rt_device(orbm_matcher *m, int n, const float *d_uv, const uint8_t *d_inliers, const float *K, float th2,
@@ -268,8 +225,8 @@ extern "C" int orbm_init_check_rt_device(orbm_matcher *m, int n, const float *d_
 {
     MTRY(rt_check_counts(n, n_motions));
     if (n == 0 || n_motions == 0) return ORBX_OK;
-    if (!d_uv || !d_inliers || !K || !d_Rt || !d_status || !d_cos_parallax || !d_p3d) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (((uintptr_t)d_uv | (uintptr_t)d_Rt | (uintptr_t)d_cos_parallax | (uintptr_t)d_p3d) & 3)
+    if (any_null(d_uv, d_inliers, K, d_Rt, d_status, d_cos_parallax, d_p3d)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (misaligned(3, d_uv, d_Rt, d_cos_parallax, d_p3d))
         return mfail(ORBX_E_INVALID, "device float arrays must be 4-byte aligned");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));

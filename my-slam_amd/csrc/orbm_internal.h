@@ -1,11 +1,13 @@
 // orbm_internal.h -- shared by orbm.hip, orbm_grid.hip, orbm_kf.hip, orbm_mappoint.hip, orbm_triangulate.hip, orbm_newpoints.hip,
-// orbm_frustum.hip, orbm_pose.hip, orbm_bow.hip, orbm_sim3.hip, orbm_pnp.hip and orbm_init.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h.
+// orbm_frustum.hip, orbm_pose.hip, orbm_bow.hip, orbm_sim3.hip, orbm_pnp.hip and orbm_init.hip.  The window walk of the grid searches (orbm_grid.hip, orbm_kf.hip) is in orbm_window.h,
+// the frame of the hypothesis kernels and the argument checks of the batched solver calls in orbm_hyp.h.
 #pragma once
 #include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <utility>
 #include <vector>
@@ -216,6 +218,27 @@ struct InBlock {
     }
     template <class T> T *dev_at(int part) const { return reinterpret_cast<T *>(dev + parts[part].off); }
     template <class T> const T *at(int part) const { return parts[part].bytes ? reinterpret_cast<const T *>(dev + parts[part].off) : nullptr; }
+};
+
+// The results of one call that the kernel leaves in d_out, back to back: list the parts once (host array, bytes) in the order they
+// lie there, an 8-byte type first.  words() is what d_out must hold (orbm_grow), dev_at() a part's device side (after orbm_grow:
+// growth moves d_out), download() brings all of them home in one copy and ends the call (orbm_sync).
+struct OutBlock {
+    struct Part { void *host; size_t bytes; };
+    void *host[4];
+    size_t bytes[4], off[4], total = 0;
+    int n = 0;
+    OutBlock(std::initializer_list<Part> parts)
+    {
+        for (const Part &p : parts) { host[n] = p.host; bytes[n] = p.bytes; off[n++] = total; total += p.bytes; }
+    }
+    size_t words() const { return (total + 3) / 4; }
+    template <class T> T *dev_at(orbm_matcher *m, int part) const { return reinterpret_cast<T *>(reinterpret_cast<uint8_t *>(m->d_out.get()) + off[part]); }
+    __attribute__((always_inline)) int download(orbm_matcher *m, hipStream_t s) const      // inlined: the library exports what it did
+    {
+        MTRY(orbm_d2h_split(m, host, bytes, n, m->d_out, s));
+        return orbm_sync(m, s);
+    }
 };
 
 // Rotation histogram of the matchers' orientation check (src/ORBmatcher.cc:236-246 and siblings) and the ComputeThreeMaxima cull

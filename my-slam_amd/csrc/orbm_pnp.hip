@@ -3,14 +3,12 @@
 // orbm_pnp_hypotheses / orbm_pnp_hypotheses_device (include/orbm.h).  The draws stay on the host (orbp_pnp_draw); a hypothesis is a
 // set of 4 to 8 correspondence indices of its problem.
 //
-// One wave per hypothesis, PNP_WAVES waves to a workgroup, hypotheses by flat index (problem = binary search over hyp_off).  The
-// solve is epnp_compute_pose of orbp_epnp_body.h, the host solver's text, run uniformly by the wave: its matrices (the 12 x 12
-// Jacobi's B and V, the eigenvectors, L, the small SVDs) are indexed at run time, so they live in a wave-private piece of LDS
-// (sizeof(PnpWaveLds) bytes per wave) instead of scratch; every lane reads the same address (a broadcast) and writes the same value.
-// Every sum runs in the host's order: no cross-lane reduction.  The lanes then stride over the problem's correspondences; a ballot is
-// 64 bits of the mask and its popcount adds to the count.  No workgroup barrier, no atomics; lane 0 writes the wave's results with
-// vector stores.
-#include "orbm_internal.h"
+// One wave per hypothesis in the frame of orbm_hyp.h (flat index, problem search, mask rows, vote).  The solve is
+// epnp_compute_pose of orbp_epnp_body.h, the host solver's text, run uniformly by the wave: its matrices (the 12 x 12 Jacobi's B and
+// V, the eigenvectors, L, the small SVDs) are indexed at run time, so they live in a wave-private piece of LDS (sizeof(PnpWaveLds)
+// bytes per wave) instead of scratch; every lane reads the same address (a broadcast) and writes the same value.  Every sum runs in
+// the host's order: no cross-lane reduction.  No workgroup barrier, no atomics; lane 0 writes the wave's results with vector stores.
+#include "orbm_hyp.h"
 #include "orbp_epnp_body.h"
 
 #define PNP_WAVES (M_THREADS / 64)
@@ -28,20 +26,11 @@ __global__ __launch_bounds__(M_THREADS) void k_pnp_hypotheses(
 {
     __shared__ PnpWaveLds lds[PNP_WAVES];
     const int lane = threadIdx.x & 63;
-    const long long hl = (long long)blockIdx.x * PNP_WAVES + (threadIdx.x >> 6);
-    const int total = hyp_off[n_problems];
-    if (hl >= total) return;                    // whole waves leave
-    const int h = __builtin_amdgcn_readfirstlane((int)hl);
-    int lo = 0, hi = n_problems - 1;            // the last p with hyp_off[p] <= h (problems without hypotheses are stepped over)
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (hyp_off[mid] <= h) lo = mid; else hi = mid - 1;
-    }
-    const int p = lo;
-    const long long c0 = off[p];
-    const int n = off[p + 1] - off[p];
-    const int W = (n + 31) >> 5;
-    uint32_t *mk = masks + mask_off[p] + (long long)(h - hyp_off[p]) * W;
+    const long long hl = hyp_wave_index(PNP_WAVES);
+    if (hl >= hyp_off[n_problems]) return;      // whole waves leave
+    const HypFrame f = hyp_frame(n_problems, off, hyp_off, mask_off, masks, hl);
+    const int h = f.h, p = f.p, n = f.n;
+    const long long c0 = f.c0;
     double *out = Rt + 12 * (long long)h;
     if (n <= 0) {                               // nothing to sample from: refused by the host variant
         if (lane == 0) {
@@ -69,12 +58,7 @@ __global__ __launch_bounds__(M_THREADS) void k_pnp_hypotheses(
         const int i = base + lane;
         bool inl = false;
         if (i < n) inl = epnp_check_one(R, t, e.fu, e.fv, e.uc, e.vc, p3d + 3 * (long long)i, p2d + 2 * (long long)i, err[i]);
-        const unsigned long long b = __ballot(inl);
-        count += __popcll(b);
-        if (lane == 0) {
-            mk[base >> 5] = (uint32_t)b;
-            if ((base >> 5) + 1 < W) mk[(base >> 5) + 1] = (uint32_t)(b >> 32);
-        }
+        count += hyp_vote(f, inl, base, lane);
     }
     if (lane == 0) {
         n_inliers[h] = count;
@@ -83,13 +67,6 @@ __global__ __launch_bounds__(M_THREADS) void k_pnp_hypotheses(
 #pragma unroll
         for (int i = 0; i < 3; i++) out[9 + i] = t[i];
     }
-}
-
-static int pnp_check_counts(int n_problems)
-{
-    if (n_problems < 0) return mfail(ORBX_E_INVALID, "n_problems=%d", n_problems);
-    if (n_problems > (1 << 24)) return mfail(ORBX_E_CAPACITY, "request beyond 2^24 problems");
-    return ORBX_OK;
 }
 
 static void pnp_launch(int n_problems, int total_hyp, const int32_t *off, const float *p2d, const float *p3d, const float *max_err,
@@ -104,23 +81,15 @@ extern "C" int orbm_pnp_hypotheses(orbm_matcher *m, int n_problems, const int32_
                                    const orbm_pnp_camera *cams, const int32_t *hyp_off, const int32_t *samples, const int64_t *mask_off,
                                    int32_t *n_inliers, double *Rt, uint32_t *masks)
 {
-    MTRY(pnp_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (n_problems == 0) return ORBX_OK;
-    if (!off || !hyp_off || !mask_off || !cams) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (off[0] != 0 || hyp_off[0] != 0 || mask_off[0] != 0) return mfail(ORBX_E_INVALID, "off[0], hyp_off[0] and mask_off[0] must be 0");
-    for (int p = 0; p < n_problems; p++) {
-        if (off[p + 1] < off[p]) return mfail(ORBX_E_INVALID, "off not monotone at %d", p);
-        if (hyp_off[p + 1] < hyp_off[p]) return mfail(ORBX_E_INVALID, "hyp_off not monotone at %d", p);
-        const int64_t W = ((int64_t)off[p + 1] - off[p] + 31) / 32;
-        if (mask_off[p + 1] != mask_off[p] + W * ((int64_t)hyp_off[p + 1] - hyp_off[p]))
-            return mfail(ORBX_E_INVALID, "mask_off[%d] is not mask_off[%d] + hypotheses * ceil(n / 32)", p + 1, p);
-    }
-    const int total = off[n_problems], H = hyp_off[n_problems];
-    const int64_t MW = mask_off[n_problems];
+    if (any_null(off, hyp_off, mask_off, cams)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    int total, H;
+    int64_t MW;
+    MTRY(check_hyp_csr(n_problems, off, hyp_off, mask_off, 28, "correspondences", 24, total, H, MW));
     if (H == 0) return ORBX_OK;
-    if (total > (1 << 28) || H > (1 << 24) || MW > (1ll << 29)) return mfail(ORBX_E_CAPACITY, "request beyond 2^28 correspondences / 2^24 hypotheses / 2^29 mask words");
-    if (!samples || !n_inliers || !Rt || (MW > 0 && !masks)) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (total > 0 && (!p2d || !p3d || !max_err)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (any_null(samples, n_inliers, Rt) || (MW > 0 && !masks)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (total > 0 && any_null(p2d, p3d, max_err)) return mfail(ORBX_E_INVALID, "NULL buffer");
     for (int p = 0; p < n_problems; p++) {
         if (hyp_off[p + 1] == hyp_off[p]) continue;
         const int n = off[p + 1] - off[p], set = cams[p].set_size;
@@ -137,27 +106,21 @@ extern "C" int orbm_pnp_hypotheses(orbm_matcher *m, int n_problems, const int32_
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     // d_out holds the 12 doubles per hypothesis first (8-byte aligned at its start), then the counts, then the mask words
-    const size_t Hs = (size_t)H, words = 25 * Hs + (size_t)MW;
-    MTRY(orbm_grow(m, 0, 0, (long long)words));
+    const size_t B = (size_t)n_problems, N = (size_t)total, Hs = (size_t)H;
+    const OutBlock out({{Rt, Hs * 96}, {n_inliers, Hs * 4}, {masks, (size_t)MW * 4}});
+    MTRY(orbm_grow(m, 0, 0, (long long)out.words()));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    const size_t B = (size_t)n_problems, N = (size_t)total;
     InBlock in(m);
     const int pm = in.add(mask_off, (B + 1) * 8), po = in.add(off, (B + 1) * 4), p2 = in.add(p2d, N * 8), p3 = in.add(p3d, N * 12),
               pe = in.add(max_err, N * 4), pc = in.add(cams, B * sizeof(orbm_pnp_camera)), ph = in.add(hyp_off, (B + 1) * 4),
               ps = in.add(samples, Hs * 4 * ORBM_PNP_MAX_SET);
     MTRY(in.upload(s));
-    double *d_Rt = reinterpret_cast<double *>(m->d_out.get());
-    int32_t *d_cnt = m->d_out + 24 * Hs;
-    uint32_t *d_masks = reinterpret_cast<uint32_t *>(m->d_out + 25 * Hs);
     pnp_launch(n_problems, H, in.dev_at<int32_t>(po), in.dev_at<float>(p2), in.dev_at<float>(p3), in.dev_at<float>(pe), in.dev_at<orbm_pnp_camera>(pc),
-               in.dev_at<int32_t>(ph), in.dev_at<int32_t>(ps), in.dev_at<int64_t>(pm), d_cnt, d_Rt, d_masks, s);
+               in.dev_at<int32_t>(ph), in.dev_at<int32_t>(ps), in.dev_at<int64_t>(pm), out.dev_at<int32_t>(m, 1), out.dev_at<double>(m, 0),
+               out.dev_at<uint32_t>(m, 2), s);
     MHIPCHK(hipGetLastError());
-    void *host[3] = {Rt, n_inliers, masks};
-    const size_t parts[3] = {Hs * 96, Hs * 4, (size_t)MW * 4};
-    MTRY(orbm_d2h_split(m, host, parts, 3, m->d_out, s));
-    MTRY(orbm_sync(m, s));
-    return ORBX_OK;
+    return out.download(m, s);
 }
 
 extern "C" int orbm_pnp_hypotheses_device(orbm_matcher *m, int n_problems, int total_hypotheses, const int32_t *d_off, const float *d_p2d,
@@ -165,14 +128,12 @@ extern "C" int orbm_pnp_hypotheses_device(orbm_matcher *m, int n_problems, int t
                                           const int32_t *d_samples, const int64_t *d_mask_off, int32_t *d_n_inliers, double *d_Rt,
                                           uint32_t *d_masks, void *hip_stream)
 {
-    MTRY(pnp_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (total_hypotheses < 0) return mfail(ORBX_E_INVALID, "total_hypotheses=%d", total_hypotheses);
     if (n_problems == 0 || total_hypotheses == 0) return ORBX_OK;
-    if (!d_off || !d_p2d || !d_p3d || !d_max_err || !d_cams || !d_hyp_off || !d_samples || !d_mask_off || !d_n_inliers || !d_Rt || !d_masks)
+    if (any_null(d_off, d_p2d, d_p3d, d_max_err, d_cams, d_hyp_off, d_samples, d_mask_off, d_n_inliers, d_Rt, d_masks))
         return mfail(ORBX_E_INVALID, "NULL buffer");
-    if ((((uintptr_t)d_off | (uintptr_t)d_p2d | (uintptr_t)d_p3d | (uintptr_t)d_max_err | (uintptr_t)d_cams | (uintptr_t)d_hyp_off |
-          (uintptr_t)d_samples | (uintptr_t)d_n_inliers | (uintptr_t)d_masks) & 3) ||
-        (((uintptr_t)d_mask_off | (uintptr_t)d_Rt) & 7))
+    if (misaligned(3, d_off, d_p2d, d_p3d, d_max_err, d_cams, d_hyp_off, d_samples, d_n_inliers, d_masks) || misaligned(7, d_mask_off, d_Rt))
         return mfail(ORBX_E_INVALID, "device arrays must be 4-byte aligned, Rt and mask_off 8-byte aligned");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));

@@ -18,7 +18,7 @@
 // the trial's errors").  The errors of all active edges are always those at the estimate compute_active_errors() last saw, and an
 // inactive edge is recomputed at the final estimate before it is read, so one extra estimate per problem (err_est) stands for the
 // per-edge store: an edge's error is recomputed from it where the host reads the stored one, with the same operations.
-#include "orbm_internal.h"
+#include "orbm_hyp.h"
 
 #define POSE_THREADS 256
 #define POSE_NSYS 28                            // 21 upper-triangle sums, 6 of b, the robust chi2
@@ -426,27 +426,16 @@ __global__ __launch_bounds__(POSE_THREADS) void k_pose_optimization(
     }
 }
 
-// the checks both variants share
-static int pose_check_counts(int n_problems)
-{
-    if (n_problems < 0) return mfail(ORBX_E_INVALID, "n_problems=%d", n_problems);
-    if (n_problems > (1 << 24)) return mfail(ORBX_E_CAPACITY, "request beyond 2^24 problems");
-    return ORBX_OK;
-}
-
 extern "C" int orbm_pose_optimization_batch(orbm_matcher *m, int n_problems, const int32_t *off, const float *obs, const float *u_right,
                                             const float *inv_sigma2, const float *xw, const orbm_pose_camera *cams, float *Tcw,
                                             uint8_t *outlier, int32_t *n_good)
 {
-    MTRY(pose_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (n_problems == 0) return ORBX_OK;
-    if (!off || !cams || !Tcw || !n_good) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (off[0] != 0) return mfail(ORBX_E_INVALID, "off[0] must be 0");
-    for (int p = 0; p < n_problems; p++)
-        if (off[p + 1] < off[p]) return mfail(ORBX_E_INVALID, "off not monotone at %d", p);
-    const int total = off[n_problems];
-    if (total > (1 << 28)) return mfail(ORBX_E_CAPACITY, "request beyond 2^28 observations");
-    if (total > 0 && (!obs || !inv_sigma2 || !xw || !outlier)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (any_null(off, cams, Tcw, n_good)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    int total;
+    MTRY(check_off_csr(n_problems, off, "observations", total));
+    if (total > 0 && any_null(obs, inv_sigma2, xw, outlier)) return mfail(ORBX_E_INVALID, "NULL buffer");
     if (u_right)
         for (int p = 0; p < n_problems; p++) {
             if (cams[p].bf != 0.0f) continue;
@@ -457,25 +446,19 @@ extern "C" int orbm_pose_optimization_batch(orbm_matcher *m, int n_problems, con
     MHIPCHK(hipSetDevice(m->device));
     // d_out (3 * max_q ints) holds the poses, the counts, then the flags
     const size_t B = (size_t)n_problems, N = (size_t)total;
-    const size_t words = 17 * B + (N + 3) / 4;
-    MTRY(orbm_grow(m, (long long)((words + 2) / 3), 0, 0));
+    const OutBlock out({{Tcw, B * 64}, {n_good, B * 4}, {outlier, N}});
+    MTRY(orbm_grow(m, (long long)((out.words() + 2) / 3), 0, 0));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     InBlock in(m);
     const int po = in.add(off, (B + 1) * 4), pb = in.add(obs, N * 8), pu = in.add(u_right, u_right ? N * 4 : 0), pi = in.add(inv_sigma2, N * 4),
               px = in.add(xw, N * 12), pc = in.add(cams, B * sizeof(orbm_pose_camera)), pt = in.add(Tcw, B * 64);
     MTRY(in.upload(s));
-    float *d_T = reinterpret_cast<float *>(m->d_out.get());
-    int32_t *d_good = m->d_out + 16 * B;
-    uint8_t *d_outl = reinterpret_cast<uint8_t *>(m->d_out + 17 * B);
     hipLaunchKernelGGL(k_pose_optimization, dim3(n_problems), dim3(POSE_THREADS), 0, s, in.dev_at<int32_t>(po), in.at<float>(pb), in.at<float>(pu),
-                       in.at<float>(pi), in.at<float>(px), in.dev_at<orbm_pose_camera>(pc), in.dev_at<float>(pt), d_T, d_outl, d_good);
+                       in.at<float>(pi), in.at<float>(px), in.dev_at<orbm_pose_camera>(pc), in.dev_at<float>(pt), out.dev_at<float>(m, 0),
+                       out.dev_at<uint8_t>(m, 2), out.dev_at<int32_t>(m, 1));
     MHIPCHK(hipGetLastError());
-    void *host[3] = {Tcw, n_good, outlier};
-    const size_t parts[3] = {B * 64, B * 4, N};
-    MTRY(orbm_d2h_split(m, host, parts, 3, m->d_out, s));
-    MTRY(orbm_sync(m, s));
-    return ORBX_OK;
+    return out.download(m, s);
 }
 
 extern "C" int orbm_pose_optimization_batch_device(orbm_matcher *m, int n_problems, const int32_t *d_off, const float *d_obs,
@@ -483,11 +466,10 @@ extern "C" int orbm_pose_optimization_batch_device(orbm_matcher *m, int n_proble
                                                    const orbm_pose_camera *d_cams, float *d_Tcw, uint8_t *d_outlier, int32_t *d_n_good,
                                                    void *hip_stream)
 {
-    MTRY(pose_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (n_problems == 0) return ORBX_OK;
-    if (!d_off || !d_obs || !d_inv_sigma2 || !d_xw || !d_cams || !d_Tcw || !d_outlier || !d_n_good) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (((uintptr_t)d_off | (uintptr_t)d_obs | (uintptr_t)d_u_right | (uintptr_t)d_inv_sigma2 | (uintptr_t)d_xw | (uintptr_t)d_cams |
-         (uintptr_t)d_Tcw | (uintptr_t)d_n_good) & 3)
+    if (any_null(d_off, d_obs, d_inv_sigma2, d_xw, d_cams, d_Tcw, d_outlier, d_n_good)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (misaligned(3, d_off, d_obs, d_u_right, d_inv_sigma2, d_xw, d_cams, d_Tcw, d_n_good))
         return mfail(ORBX_E_INVALID, "device arrays must be 4-byte aligned");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));

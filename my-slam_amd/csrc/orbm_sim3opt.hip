@@ -16,7 +16,7 @@
 // order from 0 (e12 before e21 within a pair), then a fixed tree: inside a wave a butterfly over the lane bits 0, 1, ..., 5 (lane l
 // adds the value of lane l ^ 1, then l ^ 2, ... l ^ 32; both partners add the same two numbers, so all 64 lanes end with the same
 // bits), then the four wave totals as (w0 + w1) + (w2 + w3).  The result depends on the problem alone, not on the batch around it.
-#include "orbm_internal.h"
+#include "orbm_hyp.h"
 #include "orbp_sim3opt_body.h"
 
 #define S3O_THREADS 256
@@ -158,36 +158,25 @@ __global__ __launch_bounds__(S3O_THREADS) void k_optimize_sim3(
     }
 }
 
-// the checks both variants share
-static int s3o_check_counts(int n_problems)
-{
-    if (n_problems < 0) return mfail(ORBX_E_INVALID, "n_problems=%d", n_problems);
-    if (n_problems > (1 << 24)) return mfail(ORBX_E_CAPACITY, "request beyond 2^24 problems");
-    return ORBX_OK;
-}
-
 extern "C" int orbm_optimize_sim3_batch(orbm_matcher *m, int n_problems, const int32_t *off, const float *x1c, const float *x2c,
                                         const float *obs1, const float *obs2, const float *inv_sigma2_1, const float *inv_sigma2_2,
                                         const float *cams, const float *th2, const int32_t *fix_scale, double *S12, uint8_t *flags,
                                         int32_t *n_in)
 {
-    MTRY(s3o_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (n_problems == 0) return ORBX_OK;
-    if (!off || !cams || !th2 || !fix_scale || !S12 || !n_in) return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (off[0] != 0) return mfail(ORBX_E_INVALID, "off[0] must be 0");
-    for (int p = 0; p < n_problems; p++)
-        if (off[p + 1] < off[p]) return mfail(ORBX_E_INVALID, "off not monotone at %d", p);
-    const int total = off[n_problems];
-    if (total > (1 << 28)) return mfail(ORBX_E_CAPACITY, "request beyond 2^28 pairs");
-    if (total > 0 && (!x1c || !x2c || !obs1 || !obs2 || !inv_sigma2_1 || !inv_sigma2_2 || !flags)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    if (any_null(off, cams, th2, fix_scale, S12, n_in)) return mfail(ORBX_E_INVALID, "NULL buffer");
+    int total;
+    MTRY(check_off_csr(n_problems, off, "pairs", total));
+    if (total > 0 && any_null(x1c, x2c, obs1, obs2, inv_sigma2_1, inv_sigma2_2, flags)) return mfail(ORBX_E_INVALID, "NULL buffer");
     for (size_t i = 0; i < 8 * (size_t)n_problems; i++)
         if (!std::isfinite(S12[i])) return mfail(ORBX_E_INVALID, "S12 of problem %d is not finite", (int)(i / 8));
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     // d_out (3 * max_q ints) holds S12 (16 words a problem), the counts, then the flags
     const size_t B = (size_t)n_problems, N = (size_t)total;
-    const size_t words = 17 * B + (N + 3) / 4;
-    MTRY(orbm_grow(m, (long long)((words + 2) / 3), 0, 0));
+    const OutBlock out({{S12, B * 64}, {n_in, B * 4}, {flags, N}});
+    MTRY(orbm_grow(m, (long long)((out.words() + 2) / 3), 0, 0));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
     InBlock in(m);
@@ -195,18 +184,12 @@ extern "C" int orbm_optimize_sim3_batch(orbm_matcher *m, int n_problems, const i
               pd = in.add(obs2, N * 8), pe = in.add(inv_sigma2_1, N * 4), pf = in.add(inv_sigma2_2, N * 4), pk = in.add(cams, B * 32),
               pt = in.add(th2, B * 4), px = in.add(fix_scale, B * 4), ps = in.add(S12, B * 64);
     MTRY(in.upload(s));
-    double *d_S = reinterpret_cast<double *>(m->d_out.get());
-    int32_t *d_nin = m->d_out + 16 * B;
-    uint8_t *d_flags = reinterpret_cast<uint8_t *>(m->d_out + 17 * B);
     hipLaunchKernelGGL(k_optimize_sim3, dim3(n_problems), dim3(S3O_THREADS), 0, s, in.dev_at<int32_t>(po), in.at<float>(pa), in.at<float>(pb),
                        in.at<float>(pc), in.at<float>(pd), in.at<float>(pe), in.at<float>(pf), in.dev_at<float>(pk), in.dev_at<float>(pt),
-                       in.dev_at<int32_t>(px), in.dev_at<double>(ps), d_S, d_flags, d_nin);
+                       in.dev_at<int32_t>(px), in.dev_at<double>(ps), out.dev_at<double>(m, 0), out.dev_at<uint8_t>(m, 2),
+                       out.dev_at<int32_t>(m, 1));
     MHIPCHK(hipGetLastError());
-    void *host[3] = {S12, n_in, flags};
-    const size_t parts[3] = {B * 64, B * 4, N};
-    MTRY(orbm_d2h_split(m, host, parts, 3, m->d_out, s));
-    MTRY(orbm_sync(m, s));
-    return ORBX_OK;
+    return out.download(m, s);
 }
 
 extern "C" int orbm_optimize_sim3_batch_device(orbm_matcher *m, int n_problems, const int32_t *d_off, const float *d_x1c, const float *d_x2c,
@@ -214,15 +197,13 @@ extern "C" int orbm_optimize_sim3_batch_device(orbm_matcher *m, int n_problems, 
                                                const float *d_inv_sigma2_2, const float *d_cams, const float *d_th2,
                                                const int32_t *d_fix_scale, double *d_S12, uint8_t *d_flags, int32_t *d_n_in, void *hip_stream)
 {
-    MTRY(s3o_check_counts(n_problems));
+    MTRY(check_problem_count(n_problems));
     if (n_problems == 0) return ORBX_OK;
-    if (!d_off || !d_x1c || !d_x2c || !d_obs1 || !d_obs2 || !d_inv_sigma2_1 || !d_inv_sigma2_2 || !d_cams || !d_th2 || !d_fix_scale ||
-        !d_S12 || !d_flags || !d_n_in)
+    if (any_null(d_off, d_x1c, d_x2c, d_obs1, d_obs2, d_inv_sigma2_1, d_inv_sigma2_2, d_cams, d_th2, d_fix_scale, d_S12, d_flags, d_n_in))
         return mfail(ORBX_E_INVALID, "NULL buffer");
-    if (((uintptr_t)d_off | (uintptr_t)d_x1c | (uintptr_t)d_x2c | (uintptr_t)d_obs1 | (uintptr_t)d_obs2 | (uintptr_t)d_inv_sigma2_1 |
-         (uintptr_t)d_inv_sigma2_2 | (uintptr_t)d_cams | (uintptr_t)d_th2 | (uintptr_t)d_fix_scale | (uintptr_t)d_n_in) & 3)
+    if (misaligned(3, d_off, d_x1c, d_x2c, d_obs1, d_obs2, d_inv_sigma2_1, d_inv_sigma2_2, d_cams, d_th2, d_fix_scale, d_n_in))
         return mfail(ORBX_E_INVALID, "device arrays must be 4-byte aligned");
-    if ((uintptr_t)d_S12 & 7) return mfail(ORBX_E_INVALID, "d_S12 must be 8-byte aligned");
+    if (misaligned(7, d_S12)) return mfail(ORBX_E_INVALID, "d_S12 must be 8-byte aligned");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : m->stream;

@@ -152,6 +152,52 @@ def test_device_pointer_form_gives_the_same_bytes(m, orbx, own_stream):
     assert e.value.code == orbx.ORBX_E_INVALID
 
 
+def test_the_frame_steps_over_empty_problems_and_zero_fills_a_problem_without_matches(m, orbx):
+    """What the kernels' shared frame (csrc/orbm_hyp.h) decides, on the device form: a problem without hypotheses first and last,
+    n = 33 with 3 hypotheses, n = 0 with 2 hypotheses (the host form refuses it; the kernel gives count 0, a zero row and no mask
+    word), n = 65 with 2 hypotheses: H = 7 leaves a partial last workgroup."""
+    import torch
+    c65 = ic.BY_NAME["general65"]
+    m33 = c65["matches12"].copy()
+    m33[np.flatnonzero(m33 >= 0)[33:]] = -1                                      # the first 33 matches of the case
+    s33, s65 = solver(orbx, dict(c65, matches12=m33)), solver(orbx, c65)
+    assert (s33.N, s65.N) == (33, 65)
+    rng = np.random.default_rng(33)
+    sets33, models33 = np.stack([rng.permutation(33)[:8] for _ in range(3)]).astype(np.int32), np.array([0, 1, 0], np.int32)
+    sets65, models65 = c65["sets"][:2], np.array([1, 0], np.int32)
+    uv33, pn33, T1, T2, sigma = s33.problem()[:5]
+    uv65, pn65, U1, U2, _ = s65.problem()[:5]
+    none8, none1 = np.zeros((0, 8), np.int32), np.zeros(0, np.int32)
+    nothing = (uv65[:9], pn65[:9], U1, U2, sigma, none8, none1)
+    problems = [nothing, (uv33, pn33, T1, T2, sigma, sets33, models33),
+                (uv65[:0], pn65[:0], U1, U2, sigma, np.zeros((2, 8), np.int32), np.array([0, 1], np.int32)),
+                (uv65, pn65, U1, U2, sigma, sets65, models65), nothing]
+    want = {1: s33.hypotheses(sets33, models33), 3: s65.hypotheses(sets65, models65)}     # the host path
+    off, uv, pn, params, hyp_off, sets, models, mask_off = orbx.ORBmatcher.pack_init_problems(problems)
+    B, H, MW = len(problems), int(hyp_off[-1]), int(mask_off[-1])
+    assert (B, H, MW) == (5, 7, 3 * 2 + 2 * 3) and list(np.diff(off)) == [9, 33, 0, 65, 9] and list(np.diff(hyp_off)) == [0, 3, 2, 2, 0]
+    dev = torch.device("cuda")
+    d_in = [torch.from_numpy(a).to(dev) for a in (off, uv, pn, np.ascontiguousarray(params.view(np.uint8).reshape(B, 76)), hyp_off, sets,
+                                                  models, mask_off)]
+    d_sm = torch.full((10 * H + 2 * PAD,), -77.0, dtype=torch.float32, device=dev)
+    d_cnt = torch.full((H + 2 * PAD,), -77, dtype=torch.int32, device=dev)
+    d_masks = torch.full((MW + 2 * PAD,), -77, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    m.init_hypotheses_device(B, H, *d_in, d_sm[PAD:PAD + 10 * H], d_cnt[PAD:PAD + H], d_masks[PAD:PAD + MW])
+    torch.cuda.synchronize()
+    sm, cnt, masks = d_sm.cpu().numpy(), d_cnt.cpu().numpy(), d_masks.cpu().numpy()
+    for a, n in ((sm, 10 * H), (cnt, H), (masks, MW)):
+        assert (a[:PAD] == -77).all() and (a[PAD + n:] == -77).all()
+    for k, w in want.items():                                                    # every mask word belongs to one of the two
+        h0, h1 = int(hyp_off[k]), int(hyp_off[k + 1])
+        got = (sm[PAD + 10 * h0:PAD + 10 * h1].reshape(-1, 10), cnt[PAD + h0:PAD + h1],
+               masks[PAD + mask_off[k]:PAD + mask_off[k + 1]].view(np.uint32).reshape(w[2].shape))
+        assert same(got, w), k
+        assert (w[0][:, 0] > 0).all()                                            # real scores
+    assert mask_off[2] == mask_off[3] and (cnt[PAD + 3:PAD + 5] == 0).all()
+    assert sm[PAD + 10 * 3:PAD + 10 * 5].tobytes() == bytes(4 * 10 * 2)
+
+
 def rt_inputs(orbx, name):
     """(solver, uv, K, th2, inlier flags, motions) of the model the case's Initialize reconstructs"""
     s = solver(orbx, ic.BY_NAME[name])

@@ -164,6 +164,40 @@ def test_device_pointer_form_gives_the_same_bytes(m, orbx, own_stream):
     assert e.value.code == orbx.ORBX_E_INVALID
 
 
+def test_the_frame_steps_over_empty_problems_and_zero_fills_a_problem_without_correspondences(m, orbx):
+    """What the kernels' shared frame (csrc/orbm_hyp.h) decides, on the device form: a problem without hypotheses first and last,
+    n = 33 with 3 hypotheses, n = 0 with 2 hypotheses (the host form refuses it; the kernel gives count 0, a zero row and no mask
+    word), n = 65 with 2 hypotheses: H = 7 leaves a partial last workgroup."""
+    import torch
+    c33, c65 = pc.BY_NAME["n33_s8"], pc.BY_NAME["n65_s6"]
+    nothing = problem(orbx, pc.BY_NAME["n64_s5"], [])
+    no_points = (np.zeros((0, 2), np.float32), np.zeros((0, 3), np.float32), np.zeros(0, np.float32), c33["K"], 4, np.zeros((2, 4), np.int32))
+    problems = [nothing, problem(orbx, c33, c33["samples"][:3]), no_points, problem(orbx, c65, c65["samples"][:2]), nothing]
+    want = {1: tuple(a[:3] for a in host(orbx, c33)), 3: tuple(a[:2] for a in host(orbx, c65))}     # the host path
+    off, p2d, p3d, e, cams, hyp_off, sm, mask_off = orbx.ORBmatcher.pack_pnp_problems(problems)
+    B, H, MW = len(problems), int(hyp_off[-1]), int(mask_off[-1])
+    assert (B, H, MW) == (5, 7, 3 * 2 + 2 * 3) and list(np.diff(off)) == [64, 33, 0, 65, 64] and list(np.diff(hyp_off)) == [0, 3, 2, 2, 0]
+    dev = torch.device("cuda")
+    d_in = [torch.from_numpy(a).to(dev) for a in (off, p2d, p3d, e, np.ascontiguousarray(cams.view(np.uint8).reshape(B, 20)), hyp_off, sm,
+                                                  mask_off)]
+    d_cnt = torch.full((H + 2 * PAD,), -77, dtype=torch.int32, device=dev)
+    d_Rt = torch.full((12 * H + 2 * PAD,), -77.0, dtype=torch.float64, device=dev)
+    d_masks = torch.full((MW + 2 * PAD,), -77, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    m.pnp_hypotheses_device(B, H, *d_in, d_cnt[PAD:PAD + H], d_Rt[PAD:PAD + 12 * H], d_masks[PAD:PAD + MW])
+    torch.cuda.synchronize()
+    cnt, Rt, masks = d_cnt.cpu().numpy(), d_Rt.cpu().numpy(), d_masks.cpu().numpy()
+    for a, n in ((cnt, H), (Rt, 12 * H), (masks, MW)):
+        assert (a[:PAD] == -77).all() and (a[PAD + n:] == -77).all()
+    for k, w in want.items():                                                    # every mask word belongs to one of the two
+        h0, h1 = int(hyp_off[k]), int(hyp_off[k + 1])
+        got = (cnt[PAD + h0:PAD + h1], Rt[PAD + 12 * h0:PAD + 12 * h1].reshape(-1, 12),
+               masks[PAD + mask_off[k]:PAD + mask_off[k + 1]].view(np.uint32).reshape(w[2].shape))
+        assert same(got, w), k
+    assert mask_off[2] == mask_off[3] and (cnt[PAD + 3:PAD + 5] == 0).all()
+    assert Rt[PAD + 12 * 3:PAD + 12 * 5].tobytes() == bytes(8 * 12 * 2)
+
+
 def test_a_small_handle_grows_and_keeps_its_grid(orbx):
     """a batch larger than the workspace grows the handle; a windowed search gives the same answer before and after"""
     h = orbx.ORBmatcher(0.8, True, max_queries=64, max_train=8192, max_pairs=64)

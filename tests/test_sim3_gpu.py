@@ -154,6 +154,44 @@ def test_device_pointer_form_gives_the_same_bytes(m, orbx, own_stream):
     assert e.value.code == orbx.ORBX_E_INVALID
 
 
+def test_the_frame_steps_over_empty_problems_and_zero_fills_a_problem_without_correspondences(m, orbx):
+    """What the kernels' shared frame (csrc/orbm_hyp.h) decides, on the device form: a problem without hypotheses first and last,
+    n = 33 with 3 hypotheses, n = 0 with 2 hypotheses (the host form refuses it; the kernel gives count 0, a zero row and no mask
+    word), n = 65 with 2 hypotheses: H = 7 leaves a partial last workgroup."""
+    import torch
+    c65 = sc.BY_NAME["n65_free"]
+    c33 = dict(c65, **{k: c65[k][:33] for k in ("x1", "x2", "sigma2_1", "sigma2_2")})     # its first 33 correspondences
+    tri33 = np.array([t for t in c65["triples"] if t.max() < 33][:3], np.int32)
+    tri65 = c65["triples"][:2]
+    assert tri33.shape == (3, 3)
+    nothing = problem(orbx, sc.BY_NAME["n21_free"], [])
+    problems = [nothing, problem(orbx, c33, tri33), problem(orbx, sc.BY_NAME["n0_free"], np.zeros((2, 3), np.int32)),
+                problem(orbx, c65, tri65), nothing]
+    want = {1: solver(orbx, c33).hypotheses(tri33), 3: solver(orbx, c65).hypotheses(tri65)}     # the host path
+    off, x1, x2, e1, e2, cams, hyp_off, tri, mask_off = orbx.ORBmatcher.pack_sim3_problems(problems)
+    B, H, MW = len(problems), int(hyp_off[-1]), int(mask_off[-1])
+    assert (B, H, MW) == (5, 7, 3 * 2 + 2 * 3) and list(np.diff(off)) == [21, 33, 0, 65, 21] and list(np.diff(hyp_off)) == [0, 3, 2, 2, 0]
+    dev = torch.device("cuda")
+    d_in = [torch.from_numpy(a).to(dev) for a in (off, x1, x2, e1, e2, np.ascontiguousarray(cams.view(np.uint8).reshape(B, 36)), hyp_off,
+                                                  tri, mask_off)]
+    d_cnt = torch.full((H + 2 * PAD,), -77, dtype=torch.int32, device=dev)
+    d_sRt = torch.full((13 * H + 2 * PAD,), -77.0, dtype=torch.float32, device=dev)
+    d_masks = torch.full((MW + 2 * PAD,), -77, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize()
+    m.sim3_hypotheses_device(B, H, *d_in, d_cnt[PAD:PAD + H], d_sRt[PAD:PAD + 13 * H], d_masks[PAD:PAD + MW])
+    torch.cuda.synchronize()
+    cnt, sRt, masks = d_cnt.cpu().numpy(), d_sRt.cpu().numpy(), d_masks.cpu().numpy()
+    for a, n in ((cnt, H), (sRt, 13 * H), (masks, MW)):
+        assert (a[:PAD] == -77).all() and (a[PAD + n:] == -77).all()
+    for k, w in want.items():                                                    # every mask word belongs to one of the two
+        h0, h1 = int(hyp_off[k]), int(hyp_off[k + 1])
+        got = (cnt[PAD + h0:PAD + h1], sRt[PAD + 13 * h0:PAD + 13 * h1].reshape(-1, 13),
+               masks[PAD + mask_off[k]:PAD + mask_off[k + 1]].view(np.uint32).reshape(w[2].shape))
+        assert same(got, w), k
+    assert mask_off[2] == mask_off[3] and (cnt[PAD + 3:PAD + 5] == 0).all()
+    assert sRt[PAD + 13 * 3:PAD + 13 * 5].tobytes() == bytes(4 * 13 * 2)
+
+
 def test_a_small_handle_grows_and_keeps_its_grid(orbx):
     """a batch larger than the workspace grows the handle; a windowed search gives the same answer before and after"""
     h = orbx.ORBmatcher(0.8, True, max_queries=256, max_train=8192, max_pairs=256)
