@@ -164,6 +164,16 @@ int orbm_search_by_projection_map(orbm_matcher *m, int n_mp, const uint8_t *in_v
  *                         grid must be in the handle.  cur_has_point in/out; cur_match[i2] = i or -1; *nmatches = return value.
  * Windows and candidate distances on the GPU in two passes, the scan on the host (it is sequential in the reference: an
  * assignment blocks the slot for every later MapPoint).
+ *
+ * Inputs the reference leaves undefined, for this search and the other projecting ones (SearchByProjection(pKF, Scw, ..), both Fuse,
+ * SearchBySim3); the reference pin ("What is pinned for the ORBmatcher") keeps them out of the comparison and
+ * its UBSan copy reports exactly this line on them:
+ *   - `int nScale = ceil(log(ratio)/mfLogScaleFactor)` (src/MapPoint.cc:393, :410) with a quotient that is NaN or infinite:
+ *     mfMaxDistance of 0, inf or NaN behind a passing distance test, mfLogScaleFactor of 0, or a distance of 0.  The last is how a
+ *     zero divisor gets there: this search has no depth test (:1502), and a point at the camera centre has zc = +-0, an infinite
+ *     invzc, u = fx*0*inf = NaN, which passes both bounds tests (:1507-1510), and dist3D = 0.
+ * The single-call entry points make no promise on them either: orbm_project_points keeps the reference's tests (a NaN passes them),
+ * orbm_predict_scale makes the same conversion; orbm_frustum and orbm_fuse_views reject such points with a status of their own.
  */
 int orbm_project_points(const float *Tcw, float fx, float fy, float cx, float cy, const float bounds[4],
                         const float *xw, int n, float *u, float *v, float *invzc, float *dist3d, uint8_t *in_image);

@@ -26,6 +26,10 @@
  *                                 the Jacobi sweeps visit their pairs in the opposite order, and the left vectors of zero singular
  *                                 values are completed from the other end of the unit vectors
  * The spread between the two is the part of the reference's answer that this choice decides.
+ *   variant C (-DCV_SHIM_ARITH_CANON)  variant A with the small float algebra of src/ORBmatcher.cc done as DESIGN.md section 2's
+ *                                 "Canonical semantics" table reads OpenCV 3.1.0 (each place cites its row).  The matcher pin
+ *                                 (oracle/_ref/ref_matcher) compares integer match tables exactly, so it cannot absorb that part in a
+ *                                 tolerance; variant A of the same driver (ref_matcher_a) is its sensitivity run.
  */
 #ifndef ORBX_CV_LINALG_HPP
 #define ORBX_CV_LINALG_HPP
@@ -72,6 +76,9 @@ inline void shim_need_f32(const Mat &m, const char *what)
 class MatExpr : public Mat {
 public:
     MatExpr(const Mat &m) : Mat(m) {}
+#ifdef CV_SHIM_ARITH_CANON
+    std::vector<float> raw;                              /* of a product: the float sums t0, row-major, for `A*B + C` (one cv::gemm) */
+#endif
 };
 
 inline Mat::Mat(int r, int c, int type, const Scalar &s) : Mat()
@@ -166,9 +173,13 @@ inline double Mat::dot(const Mat &b) const
 {
     shim_need_f32(*this, "dot is CV_32F only");
     if (b.type() != CV_32F || b.rows != rows || b.cols != cols) shim_die("dot needs two CV_32F matrices of one size");
+#ifdef CV_SHIM_ARITH_CANON
+    double s = 0;                                        /* row "`Mat::dot` of float vectors": products and sum in double (dotProd_32f) */
+#else
     shim_acc_t s = 0;
+#endif
     for (int y = 0; y < rows; y++)
-        for (int x = 0; x < cols; x++) s += (shim_acc_t)at<float>(y, x) * (shim_acc_t)b.at<float>(y, x);
+        for (int x = 0; x < cols; x++) s += (decltype(s))at<float>(y, x) * (decltype(s))b.at<float>(y, x);
     return (double)s;
 }
 
@@ -196,7 +207,12 @@ inline MatExpr operator*(double s, const Mat &m)
     shim_need_f32(m, "scalar * Mat is CV_32F only");
     Mat out(m.rows, m.cols, CV_32F);
     for (int y = 0; y < m.rows; y++)
+#ifdef CV_SHIM_ARITH_CANON
+        /* row "`Mat / s`, `s * Mat`": alpha in double, materialised by convertTo, whose 32f kernel computes x * (float)alpha + 0.0f in float */
+        for (int x = 0; x < m.cols; x++) out.at<float>(y, x) = m.at<float>(y, x) * (float)s + 0.0f;
+#else
         for (int x = 0; x < m.cols; x++) out.at<float>(y, x) = (float)(s * (double)m.at<float>(y, x));
+#endif
     return MatExpr(out);
 }
 inline MatExpr operator*(const Mat &m, double s) { return s * m; }
@@ -233,14 +249,49 @@ inline MatExpr operator*(const Mat &a, const Mat &b)
 {
     if (a.type() != CV_32F || b.type() != CV_32F || a.cols != b.rows || a.empty() || b.empty()) shim_die("Mat * Mat needs CV_32F (m x k)(k x n)");
     Mat out(a.rows, b.cols, CV_32F);
+#ifdef CV_SHIM_ARITH_CANON
+    std::vector<float> raw;
+#endif
     for (int y = 0; y < a.rows; y++)
         for (int x = 0; x < b.cols; x++) {
+#ifdef CV_SHIM_ARITH_CANON
+            float s = a.at<float>(y, 0) * b.at<float>(0, x);     /* t0 = a0*b0 + a1*b1 + ..: no leading +0, a sum of -0 stays -0 */
+            for (int k = 1; k < a.cols; k++) s += a.at<float>(y, k) * b.at<float>(k, x);
+#else
             shim_acc_t s = 0;
             for (int k = 0; k < a.cols; k++) s += (shim_acc_t)a.at<float>(y, k) * (shim_acc_t)b.at<float>(k, x);
+#endif
+#ifdef CV_SHIM_ARITH_CANON
+            /* row "`cv::Mat` products of a 3x3 and a 3x1 float matrix": cv::gemm's small-matrix path, the float sum t0 left to right,
+               then (float)(t0*alpha + c*beta) in double; without a C operand c is a static zero and beta 0, so a zero sum comes out
+               as +0.  alpha = -1 (`-Rcw.t()*tcw`, `-sR21*t12`) has been applied to the left operand, which negates t0 exactly. */
+            raw.push_back(s);
+            out.at<float>(y, x) = (float)((double)s * 1.0 + 0.0 * 0.0);
+#else
             out.at<float>(y, x) = (float)s;
+#endif
         }
+#ifdef CV_SHIM_ARITH_CANON
+    MatExpr e(out);
+    e.raw.swap(raw);
+    return e;
+#else
+    return MatExpr(out);
+#endif
+}
+
+#ifdef CV_SHIM_ARITH_CANON
+/* `A*B + C` is one cv::gemm(A, B, 1, C, 1): (float)(t0*alpha + c*beta) in double on the float sums (same row of the table) */
+inline MatExpr operator+(const MatExpr &e, const Mat &c)
+{
+    if (e.raw.empty()) return static_cast<const Mat &>(e) + c;
+    shim_same_f32(e, c, "Mat * Mat + Mat needs CV_32F matrices of one size");
+    Mat out(e.rows, e.cols, CV_32F);
+    for (int y = 0; y < e.rows; y++)
+        for (int x = 0; x < e.cols; x++) out.at<float>(y, x) = (float)((double)e.raw[(size_t)y * e.cols + x] * 1.0 + (double)c.at<float>(y, x) * 1.0);
     return MatExpr(out);
 }
+#endif
 
 /* Mat_<float>(r, c) << a, b, ...  (row-major, each value converted to float) */
 struct MatCommaInit {
