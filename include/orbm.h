@@ -939,6 +939,62 @@ int orbm_fuse_views(orbm_matcher *m, const orbm_fuse_view *views, int nviews, co
                     float *proj_u, float *proj_v, float *proj_ur, int32_t *pred_level,
                     int32_t *nfused);
 
+/*
+ * ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), LocalMapping::Run's call at src/LocalMapping.cc:82 ----
+ * The problem, outputs, `stop`, `stats` and return codes of orbp_local_bundle_adjustment (include/orbp.h), whose argument checks run
+ * first and need no handle; so does a `stop` set at entry, which launches nothing.  Everything else needs the GPU, and a NULL handle
+ * behaves as in orbm_create_new_map_points.  The kernels run the text of the host path (csrc/orbp_lba_body.h): every per-edge
+ * quantity is the host's bit for bit; the sums over edges (fixed trees instead of edge order), the device's sin / cos and the inside
+ * of the dense solve are not, so the results agree with the host's within the bar of tests/golden/lba/tolerance.json and the flags
+ * and counts are identical away from the decision boundaries.
+ *
+ * The call runs on the handle's stream: one upload through the staging arena, one download of the results at the end, and between
+ * them a Levenberg loop driven by the host over plain kernel launches in stream order.  After each trial the host reads back one
+ * 64-byte block (the trial's robust chi2, computeScale's sum, the solve's ok flag) and takes g2o's decisions in the body's own code;
+ * that is also where `stop` is read.  At most 15 iterations x 10 trials.  No cooperative launch, no grid-wide barrier, no spin-wait,
+ * no communication between workgroups other than kernel boundaries, no floating-point atomics; every kernel loop is bounded by the
+ * problem's counts.  The result is a function of the problem alone: byte-equal on a second run and on a handle that solved another
+ * problem in between.  The workspace is a block of the handle's own (grown by the rule of csrc/dev_buf.h); the grid slots and every
+ * other buffer of the handle are left as found.  The three results leave the device in one copy into the staging arena and reach
+ * the caller's arrays after the last synchronisation, so a failed call leaves every output as it was; only when the arena has no
+ * room left in this call do the copies land in the arrays directly, and a failure after that may leave them partly written.
+ *
+ * ORBX_E_CAPACITY beyond ORBM_LBA_MAX_LOCAL local key frames: the reduced system is factored by one workgroup, whose time grows
+ * with the cube of 6 n_local and which a call may run 150 times (DESIGN.md section 22 has the time at the cap); and beyond 2^28
+ * entries of the n_local x n_points table.  The host path has neither limit.
+ */
+#define ORBM_LBA_MAX_LOCAL 128
+struct orbp_lba_problem;
+struct orbp_lba_stats;
+int orbm_local_bundle_adjustment(orbm_matcher *m, const struct orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase,
+                                 const volatile uint8_t *stop, struct orbp_lba_stats *stats);
+/*
+ * The same call, measured (tools/bench_lba.py): events on the handle's stream after each group of launches.  split_ms[g] is the
+ * device time of group g summed over the call and split_count[g] the number of times it ran (both ORBM_LBA_SPLIT_N long).  A
+ * group's time runs from the end of the group before it, or from the host's return from the synchronisation before it, to its own
+ * end, so the time until the host has enqueued it counts into it.  Results and stats are those of orbm_local_bundle_adjustment,
+ * bit for bit.  ORBX_E_INVALID on a NULL split_ms or split_count.
+ */
+enum {
+    ORBM_LBA_SPLIT_UPLOAD = 0,          /* the one staged upload */
+    ORBM_LBA_SPLIT_SETUP = 1,           /* table memset, k_lba_init; k_lba_activate and its memsets (twice) */
+    ORBM_LBA_SPLIT_ERRORS = 2,          /* k_lba_errors */
+    ORBM_LBA_SPLIT_LINEARIZE = 3,       /* k_lba_linearize */
+    ORBM_LBA_SPLIT_REDUCE_POINTS = 4,   /* k_lba_reduce_points */
+    ORBM_LBA_SPLIT_REDUCE_KFS = 5,      /* k_lba_reduce_kfs */
+    ORBM_LBA_SPLIT_DINV = 6,            /* k_lba_dinv */
+    ORBM_LBA_SPLIT_SCHUR = 7,           /* k_lba_schur */
+    ORBM_LBA_SPLIT_SOLVE = 8,           /* k_lba_solve */
+    ORBM_LBA_SPLIT_UPDATE = 9,          /* k_lba_update */
+    ORBM_LBA_SPLIT_READ_BACK = 10,      /* k_lba_reduce_out and the 64-byte copy the host then waits for */
+    ORBM_LBA_SPLIT_FLAG_OUTPUT = 11,    /* k_lba_flag (both passes), k_lba_output */
+    ORBM_LBA_SPLIT_DOWNLOAD = 12,       /* the one copy of the results */
+    ORBM_LBA_SPLIT_N = 13
+};
+int orbm_local_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase,
+                                       const volatile uint8_t *stop, struct orbp_lba_stats *stats, double *split_ms,
+                                       int32_t *split_count);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

@@ -253,6 +253,63 @@ int orbp_init_plan_check_rt(orbp_init *s, int *model, float *M, uint8_t *inliers
  * ReconstructF (minParallax 1.0, minTriangulated 50).  Returns 1 and fills R21 (9), t21 (3), p3d[3 n1] = vP3D and
  * triangulated[n1] = vbTriangulated; 0 when the reference returns false (outputs untouched); < 0 on bad arguments or N < 8. */
 int orbp_init_initialize(orbp_init *s, float *R21, float *t21, float *p3d, uint8_t *triangulated);
+
+/*
+ * ---- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778), LocalMapping::Run's call at src/LocalMapping.cc:82 ----
+ * Many free vertices: the local key frames (VertexSE3Expmap) and the local points (VertexSBAPointXYZ, marginalised), joined by
+ * EdgeSE3ProjectXYZ / EdgeStereoSE3ProjectXYZ with a Huber kernel, solved by BlockSolver_6_3's Schur complement over the points
+ * under OptimizationAlgorithmLevenberg.  The g2o lines restated are listed in csrc/orbp_lba_body.h, the text the GPU call
+ * orbm_local_bundle_adjustment (include/orbm.h) runs as well; the reduced system is dense here (6K x 6K for K local key frames,
+ * Cholesky in fp64; a non-positive or non-finite pivot is "solve failed", optimization_algorithm_levenberg.cpp:126-127).
+ * Parity with g2o itself is unpinned (there is no Eigen to build it against): Eigen's product and inverse evaluation order, the
+ * elimination order of its sparse LDL^T, and the order of the unknowns (g2o: by vertex id; here: problem order).
+ *
+ * The problem is flat and gathered exactly as :455-653 walks:
+ *   n_local key frames in lLocalKeyFrames order (:456-468), local_fixed[i] != 0 for mnId == 0 (:529);
+ *   n_fixed key frames in lFixedCameras order (:489-504);
+ *   n_points points in lLocalMapPoints order (:471-486);
+ *   edges in CSR by point: point p owns the edges edge_off[p] .. edge_off[p + 1], in the order its observations map is iterated
+ *   (:585), skipping bad key frames (:589).  This is g2o's active-edge order and the host path's summation order.
+ *   Per edge: edge_kf = the key frame's index into local-then-fixed, obs = kpUn.pt (2 floats), u_right = mvuRight (< 0: monocular,
+ *   :594), inv_sigma2 = mvInvLevelSigma2[kpUn.octave].  A point holds a key frame at most once, as the map does.
+ *   Per key frame (local, then fixed): Tcw = GetPose() (row-major 4 x 4 floats) and cam = {fx, fy, cx, cy, mbf}.
+ * Outputs: Tcw_local (16 floats per local key frame) = Converter::toCvMat(SE3Quat) (:767); xw (3 floats per point, in = GetWorldPos(),
+ * out = :775); erase[e] = 1 where :715-743 pushes the edge's pair into vToErase; stats (may be NULL).
+ *
+ * Kept from the reference:
+ *   rounds: optimize(5), then the flagging pass :672-702 (chi2 > 5.991 / 7.815 on the double chi2(), or depth not positive, sets
+ *     level 1; every edge loses its robust kernel), then initializeOptimization(0) and optimize(10) from iteration 0 again;
+ *   stale errors: the final pass reads chi2() from the error the edge last stored while active (for a level-1 edge: the first
+ *     round's last computeActiveErrors, a rejected trial's included); isDepthPositive() is evaluated at the final estimates;
+ *   a point or key frame whose every edge is level 1 leaves the second round and keeps the first round's bits;
+ *   an edge to a fixed key frame (a fixed one, or a local one with mnId == 0) contributes to its point's blocks only;
+ *   stop (may be NULL): set at entry (:655-657) -> returns ORBP_LBA_STOPPED with no output written; otherwise read at the top of
+ *     every iteration and in the do ... while of the trial loop; set after the first optimize (:664-666) -> the second round is
+ *     skipped, the final pass and the write-back still run.
+ * Returns ORBP_LBA_DONE, ORBP_LBA_STOPPED, or ORBX_E_INVALID before any work on: a NULL pointer, a negative count, an edge_kf out
+ * of range or twice in a point, edge_off[0] != 0 or not monotone, a non-finite pose, point, calibration, observation or inv_sigma2.
+ * A problem without edges optimises nothing and returns ORBP_LBA_DONE (poses and points written back as the reference would).  With
+ * every key frame fixed the points alone are optimised.
+ */
+typedef struct orbp_lba_problem {
+    int32_t n_local, n_fixed, n_points;
+    const uint8_t *local_fixed;     /* n_local */
+    const float *Tcw;               /* 16 * (n_local + n_fixed) */
+    const float *cam;               /* 5 * (n_local + n_fixed) */
+    const int32_t *edge_off;        /* n_points + 1 */
+    const int32_t *edge_kf;         /* per edge */
+    const float *obs;               /* 2 per edge */
+    const float *u_right;           /* per edge */
+    const float *inv_sigma2;        /* per edge */
+} orbp_lba_problem;
+typedef struct orbp_lba_stats {
+    int32_t iterations[2], trials[2];   /* of optimize(5) and optimize(10): iterations run, Levenberg trials in them */
+    double lambda, chi2;                /* _currentLambda and the active robust chi2 after the last optimize that ran */
+    int32_t n_level1, second_round;     /* edges set to level 1 at :672-702; 1 when that pass and optimize(10) were reached */
+} orbp_lba_stats;
+enum { ORBP_LBA_DONE = 0, ORBP_LBA_STOPPED = 1 };
+int orbp_local_bundle_adjustment(const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase,
+                                 const volatile uint8_t *stop, orbp_lba_stats *stats);
 const char *orbp_last_error(void);
 
 #ifdef __cplusplus

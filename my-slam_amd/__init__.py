@@ -225,6 +225,13 @@ def _bind_pose(L):
     L.orbp_optimize_sim3.argtypes = [C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, C.c_float, C.c_int, vp, vp]
     L.orbp_sim3_from_rts.argtypes = [vp, vp, C.c_float, vp]
     L.orbp_optimize_sim3.restype = L.orbp_sim3_from_rts.restype = C.c_int
+    L.orbp_local_bundle_adjustment.argtypes = [vp] * 6
+    L.orbm_local_bundle_adjustment.argtypes = [vp] * 7
+    L.orbp_local_bundle_adjustment.restype = L.orbm_local_bundle_adjustment.restype = C.c_int
+    L.orbm_local_bundle_adjustment_split.argtypes = [vp] * 9
+    L.orbm_local_bundle_adjustment_split.restype = C.c_int
+    L.orbp_lba_set_stop_probe.argtypes = [vp, vp]
+    L.orbp_lba_set_stop_probe.restype = None
     L.orbp_last_error.restype = C.c_char_p
     for name in ("orbp_pnp_create", "orbp_pnp_set_ransac_parameters", "orbp_pnp_iterate", "orbp_pnp_find",
                  "orbp_pose_optimization", "orbp_pnp_get_problem", "orbp_pnp_draw", "orbp_pnp_queued", "orbp_pnp_hypothesis",
@@ -976,6 +983,19 @@ class ORBmatcher:
                 (th2, f32), (fix_scale, "int32"), (S12, "float64"), (flags, "uint8"), (n_in, "int32"))
         ptrs, s = _device_ptrs("optimize_sim3_batch_device", want, stream, none_ok=n_problems == 0)
         _mchk(self.L.orbm_optimize_sim3_batch_device(self.h, n_problems, *ptrs, s))
+
+    @staticmethod
+    def pack_lba_problem(problem):
+        """pack_lba_problem() of the module: the flat arrays of orbm_local_bundle_adjustment from a problem dict"""
+        return pack_lba_problem(problem)
+
+    def local_bundle_adjustment(self, problem, stop=None):
+        """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778) on the GPU: the problem, results and `stop` of
+        LocalBundleAdjustment(), through orbm_local_bundle_adjustment."""
+        rc, Tcw, xw, erase, stats = _lba_call(lambda *args: self.L.orbm_local_bundle_adjustment(self.h, *args), problem, stop)
+        if rc < 0:
+            _mchk(rc)
+        return rc, Tcw, xw, erase, stats
 
     @staticmethod
     def pack_sim3_problems(problems):
@@ -2174,3 +2194,69 @@ def PoseOptimization(obs, inv_sigma2, xw, fx, fy, cx, cy, Tcw, u_right=None, bf=
     out = np.zeros(max(len(obs), 1), np.uint8)
     n = _pchk(lib().orbp_pose_optimization(len(obs), _p(obs), _p(ur), _p(inv_sigma2), _p(xw), fx, fy, cx, cy, bf, _p(T), _p(out)))
     return T.reshape(4, 4), out[:len(obs)].astype(bool), n
+
+
+class LbaProblem(C.Structure):
+    """orbp_lba_problem (include/orbp.h)"""
+    _fields_ = [("n_local", C.c_int32), ("n_fixed", C.c_int32), ("n_points", C.c_int32), ("local_fixed", C.c_void_p),
+                ("Tcw", C.c_void_p), ("cam", C.c_void_p), ("edge_off", C.c_void_p), ("edge_kf", C.c_void_p), ("obs", C.c_void_p),
+                ("u_right", C.c_void_p), ("inv_sigma2", C.c_void_p)]
+
+
+class LbaStats(C.Structure):
+    """orbp_lba_stats (include/orbp.h)"""
+    _fields_ = [("iterations", C.c_int32 * 2), ("trials", C.c_int32 * 2), ("lambda_", C.c_double), ("chi2", C.c_double),
+                ("n_level1", C.c_int32), ("second_round", C.c_int32)]
+
+    def as_dict(self):
+        return {"iterations": tuple(self.iterations), "trials": tuple(self.trials), "lambda": self.lambda_, "chi2": self.chi2,
+                "n_level1": self.n_level1, "second_round": self.second_round}
+
+
+ORBP_LBA_DONE, ORBP_LBA_STOPPED = 0, 1
+
+
+def pack_lba_problem(problem):
+    """The flat arrays of orbp_local_bundle_adjustment / orbm_local_bundle_adjustment from a dict gathered as
+    Optimizer::LocalBundleAdjustment walks (src/Optimizer.cc:455-653): local_fixed uint8 [n_local] (mnId == 0), Tcw float32
+    [n_local + n_fixed, 4, 4] and cam float32 [n_local + n_fixed, 5] = (fx, fy, cx, cy, bf), local key frames first; xw float32
+    [n_points, 3]; edge_off int32 [n_points + 1]; per edge edge_kf int32, obs float32 [E, 2], u_right float32 (< 0: monocular),
+    inv_sigma2 float32.  -> (LbaProblem, arrays): the struct points into `arrays` (a dict of contiguous copies, xw among them),
+    which must outlive it."""
+    a = {"local_fixed": np.ascontiguousarray(problem["local_fixed"], np.uint8).reshape(-1),
+         "Tcw": np.ascontiguousarray(problem["Tcw"], np.float32).reshape(-1, 16),
+         "cam": np.ascontiguousarray(problem["cam"], np.float32).reshape(-1, 5),
+         "xw": np.array(problem["xw"], np.float32).reshape(-1, 3),
+         "edge_off": np.ascontiguousarray(problem["edge_off"], np.int32).reshape(-1),
+         "edge_kf": np.ascontiguousarray(problem["edge_kf"], np.int32).reshape(-1),
+         "obs": np.ascontiguousarray(problem["obs"], np.float32).reshape(-1, 2),
+         "u_right": np.ascontiguousarray(problem["u_right"], np.float32).reshape(-1),
+         "inv_sigma2": np.ascontiguousarray(problem["inv_sigma2"], np.float32).reshape(-1)}
+    n_local, n_kf, n_points, E = len(a["local_fixed"]), len(a["Tcw"]), len(a["xw"]), len(a["edge_kf"])
+    if len(a["cam"]) != n_kf or n_kf < n_local or len(a["edge_off"]) != n_points + 1:
+        raise OrbxError(ORBX_E_INVALID, "pack_lba_problem: key frame / point array lengths disagree")
+    if not (len(a["obs"]) == len(a["u_right"]) == len(a["inv_sigma2"]) == E) or (E and int(a["edge_off"][-1]) != E):
+        raise OrbxError(ORBX_E_INVALID, "pack_lba_problem: edge array lengths disagree")
+    s = LbaProblem(n_local, n_kf - n_local, n_points, *[a[k].ctypes.data if a[k].size else None for k in
+                                                        ("local_fixed", "Tcw", "cam", "edge_off", "edge_kf", "obs", "u_right", "inv_sigma2")])
+    s.edge_off = a["edge_off"].ctypes.data
+    return s, a
+
+
+def _lba_call(fn, problem, stop):
+    s, a = pack_lba_problem(problem)
+    E = len(a["edge_kf"])
+    Tcw = np.zeros((max(s.n_local, 1), 4, 4), np.float32)
+    erase = np.zeros(max(E, 1), np.uint8)
+    stats = LbaStats()
+    stop_arr = None if stop is None else np.ascontiguousarray(stop, np.uint8).reshape(1)
+    rc = fn(C.byref(s), _p(Tcw), _p(a["xw"]), _p(erase), _p(stop_arr), C.byref(stats))
+    return rc, Tcw[:s.n_local], a["xw"], erase[:E].astype(bool), stats.as_dict()
+
+
+def LocalBundleAdjustment(problem, stop=None):
+    """Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778) on the host over a pack_lba_problem() dict -> (code, Tcw float32
+    [n_local, 4, 4], xw float32 [n_points, 3], erase bool [E], stats dict).  code: ORBP_LBA_DONE, or ORBP_LBA_STOPPED when `stop`
+    (a uint8 [1], as pbStopFlag) was set at entry: the outputs are then zeros and the input points."""
+    rc, Tcw, xw, erase, stats = _lba_call(lib().orbp_local_bundle_adjustment, problem, stop)
+    return _pchk(rc), Tcw, xw, erase, stats

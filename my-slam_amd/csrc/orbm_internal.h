@@ -105,6 +105,8 @@ struct orbm_matcher {
     Pend pend[8]; int npend = 0;
     DevBuf<uint8_t> d_dd;           // orbm_mappoint.hip: scratch of orbm_distinctive_descriptors (lazy, its own block)
     DevBuf<uint8_t> d_fuse;         // orbm_fuse.hip: the grids of all views and the dense results of orbm_fuse_views (lazy, its own block)
+    DevBuf<uint8_t> d_lba;          // orbm_lba.hip: the workspace of orbm_local_bundle_adjustment (lazy, its own block)
+    PinBuf<uint8_t> lba_pin;        // its per-trial read-back block
     // the capacities the handle advertises are what its buffers hold
     int max_q() const { return (int)std::min(std::min(d_q.bytes() / 32, (d_off.count() ? d_off.count() - 1 : 0)), d_out.count() / 3); }
     int max_t() const { return (int)(d_t.bytes() / 32); }
@@ -118,6 +120,7 @@ int orbm_grid_ensure(orbm_matcher *m, int slot);       // the slot's arrays, siz
 int orbm_ensure_partials(orbm_matcher *m, size_t need, hipStream_t s = nullptr);          // d_part of `need` pairs
 int orbm_ensure_dd(orbm_matcher *m, size_t need, hipStream_t s);                            // d_dd of `need` bytes
 int orbm_ensure_fuse(orbm_matcher *m, size_t need);                                         // d_fuse of `need` bytes
+int orbm_ensure_lba(orbm_matcher *m, size_t need);                                          // d_lba of `need` bytes, lba_pin of 64
 // orbm_grid.hip: k_grid_build_views, one workgroup per view: view v builds d_grids[v] from the keypoints d_kps + d_off[v]
 void orbm_grid_build_views_launch(const OrbmGrid *d_grids, const int32_t *d_off, const orbx_keypoint *d_kps, int nviews, hipStream_t s);
 // orbm_grid.hip: builds a grid slot (asynchronous on the handle's stream unless it had to allocate a staging block), and the

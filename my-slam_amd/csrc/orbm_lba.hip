@@ -1,0 +1,679 @@
+// orbm_lba.hip -- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778 of WChen09/My-SLAM, on g2o) on the GPU:
+// orbm_local_bundle_adjustment (include/orbm.h).  The kernels run the text of the host path orbp_local_bundle_adjustment
+// (orbp_lba.cc): csrc/orbp_lba_body.h holds the SE3 algebra, both edges' computeError and linearizeOplus, Huber, an edge's quadratic
+// form, a point's 3x3 inverse, the Schur terms and the Levenberg loop for both; only the order of the sums over edges, the device's
+// sin / cos and the inside of the dense solve differ.
+//
+// Launch structure: one upload, then lba_optimize (the body's Levenberg loop, on the host) over plain kernel launches in stream
+// order, then one download.  A trial is six launches and one 64-byte read-back (robust chi2, computeScale's sum, the solve's ok
+// flag), where the host takes g2o's decisions and reads `stop`.  There is no cooperative launch, no grid-wide barrier, no spin-wait,
+// no communication between workgroups other than kernel boundaries and no floating-point atomic; every kernel loop is bounded by
+// the problem's counts and the host loop by 15 iterations x 10 trials.
+//
+// Sums (all in fixed orders, so the result is a function of the problem alone):
+//   a point's Hll, b_l and its back-substitution     one thread per point, its edges in ascending order (the host's order)
+//   a key frame's Hpp, b_p                           one wave per key frame over its edges in ascending order: lane l adds the
+//                                                    edges l, l + 64, ... of the list, then the butterfly over the lane bits
+//                                                    0, 1, ..., 5 of DESIGN.md section 21
+//   a block (i1 <= i2) of B Dinv B^T and of bschur   one wave per block over key frame i1's edges, the same lanes and butterfly.
+//                                                    Key frame i2's edge on the same point comes from a dense n_local x n_points
+//                                                    table of edge indices (4 bytes an entry, 1.3 MB at 40 x 8000): one load
+//                                                    instead of a search of the point's observers, and the table is rebuilt by one
+//                                                    launch a call
+//   robust chi2, computeScale, counts                one workgroup of 1024 threads: thread t adds the entries t, t + 1024, ...,
+//                                                    the butterfly inside a wave, then the 16 wave totals pairwise (8, 4, 2, 1)
+// The dense solve: one workgroup of 256 threads factors S = L L^T in place in the workspace, right-looking over 6-wide block
+// columns, then substitutes forwards and backwards; a pivot that is not positive or not finite clears the ok flag and the update.
+#include "orbm_hyp.h"
+#include "orbp_internal.h"
+#include "orbp_lba_body.h"
+#include "../../include/orbp.h"
+#include "../../include/orbm.h"
+
+#define LBA_T 256
+#define LBA_RT 1024
+
+namespace {
+struct LbaDev {
+    int K, NK, P, E, n;                     // local key frames, all key frames, points, edges, 6 K
+    // the problem
+    const float *Tcw, *cam, *xw_in, *obs, *u_right, *inv_sigma2;
+    const uint8_t *local_fixed;
+    const int32_t *edge_off, *edge_kf, *kf_off, *kf_edge;    // kf_off / kf_edge: CSR by local key frame, edges ascending
+    // state
+    double *est[2], *X[2];                  // 7 doubles a key frame, 3 a point; [cur] the estimates, [1 - cur] a trial's
+    double *err, *chi_e, *blk;              // 3, 1, LBA_NBLK an edge
+    int32_t *edge_pt, *table;               // the edge's point; table[k * P + pt] = key frame k's edge on pt or -1
+    uint8_t *level, *kf_active, *pt_active, *erase;
+    double *Hll, *bl, *Dinv, *Db, *pmax, *pterm;             // 6, 3, 9, 3, 1, 1 a point
+    double *Hpp, *bp, *kmax, *kterm;        // 21, 6, 1, 1 a local key frame
+    double *S, *bs, *xp;                    // n x n, n, n
+    double *out;                            // 8: chi2, scale, ok, maxdiag, active edges, level-1 edges
+    float *out_Tcw, *out_xw;
+};
+enum { OUT_CHI = 0, OUT_SCALE = 1, OUT_OK = 2, OUT_MAXDIAG = 3, OUT_ACTIVE = 4, OUT_LEVEL1 = 5 };
+
+__device__ __forceinline__ LbaSe3 load_se3(const double *p) { return {p[0], p[1], p[2], p[3], p[4], p[5], p[6]}; }
+__device__ __forceinline__ void store_se3(double *p, const LbaSe3 &T)
+{
+    p[0] = T.qx; p[1] = T.qy; p[2] = T.qz; p[3] = T.qw; p[4] = T.t0; p[5] = T.t1; p[6] = T.t2;
+}
+__device__ __forceinline__ LbaCam load_cam(const float *c) { return {c[0], c[1], c[2], c[3], c[4]}; }
+__device__ __forceinline__ bool kf_is_free(const LbaDev &d, int k) { return k < d.K && !d.local_fixed[k]; }
+__device__ __forceinline__ double wave_sum(double a)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
+    return a;
+}
+
+// thread i: key frame i (the estimate of its pose), point i, edge i (level 0, no stored error, its place in the table)
+__global__ __launch_bounds__(LBA_T) void k_lba_init(LbaDev d)
+{
+    const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (i < d.NK) store_se3(d.est[0] + 7 * i, lba_se3_from_Tcw(d.Tcw + 16 * i));
+    if (i < d.P) {
+        for (int j = 0; j < 3; j++) d.X[0][3 * i + j] = (double)d.xw_in[3 * i + j];
+        for (int e = d.edge_off[i]; e < d.edge_off[i + 1]; e++) {
+            d.edge_pt[e] = (int)i;
+            const int k = d.edge_kf[e];
+            if (k < d.K) d.table[(long long)k * d.P + i] = e;
+        }
+    }
+    if (i < d.E) {
+        d.level[i] = 0;
+        d.err[3 * i] = d.err[3 * i + 1] = d.err[3 * i + 2] = 0;
+    }
+}
+// initializeOptimization(0): thread i decides point i and local key frame i
+__global__ __launch_bounds__(LBA_T) void k_lba_activate(LbaDev d)
+{
+    const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (i < d.P) {
+        uint8_t a = 0;
+        for (int e = d.edge_off[i]; e < d.edge_off[i + 1]; e++) a |= !d.level[e];
+        d.pt_active[i] = a;
+    }
+    if (i < d.K) {
+        uint8_t a = 0;
+        if (!d.local_fixed[i])
+            for (int q = d.kf_off[i]; q < d.kf_off[i + 1]; q++) a |= !d.level[d.kf_edge[q]];
+        d.kf_active[i] = a;
+    }
+}
+// computeActiveErrors and every active edge's term of activeRobustChi2 at the estimates [b]
+__global__ __launch_bounds__(LBA_T) void k_lba_errors(LbaDev d, int b, int robust)
+{
+    const long long e = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (e >= d.E) return;
+    if (d.level[e]) { d.chi_e[e] = 0; return; }
+    const int k = d.edge_kf[e];
+    double pc[3], err[3];
+    lba_edge_error(load_se3(d.est[b] + 7 * (long long)k), load_cam(d.cam + 5 * (long long)k), d.X[b] + 3 * (long long)d.edge_pt[e],
+                   d.obs + 2 * e, d.u_right[e], pc, err);
+    d.err[3 * e] = err[0]; d.err[3 * e + 1] = err[1]; d.err[3 * e + 2] = err[2];
+    d.chi_e[e] = lba_edge_robust_chi2(err, (double)d.inv_sigma2[e], !(d.u_right[e] < 0), robust != 0);
+}
+// linearizeOplus + constructQuadraticForm of every active edge
+__global__ __launch_bounds__(LBA_T) void k_lba_linearize(LbaDev d, int b, int robust)
+{
+    const long long e = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (e >= d.E || d.level[e]) return;
+    const int k = d.edge_kf[e];
+    const double err[3] = {d.err[3 * e], d.err[3 * e + 1], d.err[3 * e + 2]};
+    double blk[LBA_NBLK];
+    lba_edge_blocks(load_se3(d.est[b] + 7 * (long long)k), load_cam(d.cam + 5 * (long long)k), d.X[b] + 3 * (long long)d.edge_pt[e], err,
+                    (double)d.inv_sigma2[e], !(d.u_right[e] < 0), robust != 0, kf_is_free(d, k), blk);
+    double *o = d.blk + LBA_NBLK * e;
+#pragma unroll
+    for (int i = 0; i < LBA_NBLK; i++) o[i] = blk[i];
+}
+// Hll and b_l of point i over its active edges in ascending order, and its part of computeLambdaInit's maximum
+__global__ __launch_bounds__(LBA_T) void k_lba_reduce_points(LbaDev d)
+{
+    const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (i >= d.P) return;
+    double H[6] = {0, 0, 0, 0, 0, 0}, b[3] = {0, 0, 0};
+    for (int e = d.edge_off[i]; e < d.edge_off[i + 1]; e++) {
+        if (d.level[e]) continue;
+        const double *s = d.blk + LBA_NBLK * (long long)e;
+#pragma unroll
+        for (int j = 0; j < 6; j++) H[j] += s[LBA_HLL + j];
+#pragma unroll
+        for (int j = 0; j < 3; j++) b[j] += s[LBA_BL + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 6; j++) d.Hll[6 * i + j] = H[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) d.bl[3 * i + j] = b[j];
+    d.pmax[i] = d.pt_active[i] ? fmax(fabs(H[5]), fmax(fabs(H[3]), fmax(fabs(H[0]), 0.0))) : 0.0;
+}
+// Hpp and b_p of local key frame k: one wave, lanes stride its edge list, then the butterfly
+__global__ __launch_bounds__(64) void k_lba_reduce_kfs(LbaDev d)
+{
+    const int k = blockIdx.x, lane = threadIdx.x;
+    double acc[27];
+#pragma unroll
+    for (int j = 0; j < 27; j++) acc[j] = 0;
+    if (d.kf_active[k])
+        for (int q = d.kf_off[k] + lane; q < d.kf_off[k + 1]; q += 64) {
+            const int e = d.kf_edge[q];
+            if (d.level[e]) continue;
+            const double *s = d.blk + LBA_NBLK * (long long)e;
+#pragma unroll
+            for (int j = 0; j < 27; j++) acc[j] += s[LBA_HPP + j];
+        }
+#pragma unroll
+    for (int j = 0; j < 27; j++) acc[j] = wave_sum(acc[j]);
+    if (lane == 0) {
+#pragma unroll
+        for (int j = 0; j < 21; j++) d.Hpp[21 * (long long)k + j] = acc[j];
+#pragma unroll
+        for (int j = 0; j < 6; j++) d.bp[6 * (long long)k + j] = acc[21 + j];
+        d.kmax[k] = fmax(fabs(acc[20]), fmax(fabs(acc[18]), fmax(fabs(acc[15]), fmax(fabs(acc[11]), fmax(fabs(acc[6]), fmax(fabs(acc[0]), 0.0))))));
+    }
+}
+// setLambda on a point's block, Dinv and Dinv b_l
+__global__ __launch_bounds__(LBA_T) void k_lba_dinv(LbaDev d, double lambda)
+{
+    const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (i >= d.P || !d.pt_active[i]) return;
+    double Dinv[9], Db[3];
+    lba_point_dinv(d.Hll + 6 * i, d.bl + 3 * i, lambda, Dinv, Db);
+#pragma unroll
+    for (int j = 0; j < 9; j++) d.Dinv[9 * i + j] = Dinv[j];
+#pragma unroll
+    for (int j = 0; j < 3; j++) d.Db[3 * i + j] = Db[j];
+}
+// Block (i1, i2), i1 <= i2, of S = (Hpp + lambda I) - sum B Dinv B^T, mirrored below the diagonal, and on the diagonal blocks
+// bschur = b_p - sum B Dinv b_l.  A local key frame without active edges keeps an identity block and a zero right-hand side.
+__global__ __launch_bounds__(64) void k_lba_schur(LbaDev d, double lambda)
+{
+    const int i2 = blockIdx.x, i1 = blockIdx.y, lane = threadIdx.x, n = d.n;
+    if (i1 > i2) return;
+    const bool on = d.kf_active[i1] && d.kf_active[i2];
+    double acc[36], coef[6];
+#pragma unroll
+    for (int j = 0; j < 36; j++) acc[j] = 0;
+#pragma unroll
+    for (int j = 0; j < 6; j++) coef[j] = 0;
+    if (on)
+        for (int q = d.kf_off[i1] + lane; q < d.kf_off[i1 + 1]; q += 64) {
+            const int e = d.kf_edge[q];
+            if (d.level[e]) continue;
+            const int pt = d.edge_pt[e];
+            const int e2 = i1 == i2 ? e : d.table[(long long)i2 * d.P + pt];
+            if (e2 < 0 || d.level[e2]) continue;
+            const double *W = d.blk + LBA_NBLK * (long long)e + LBA_HPL, *W2 = d.blk + LBA_NBLK * (long long)e2 + LBA_HPL;
+            double Y[18], M[36];
+            lba_mul_WD(W, d.Dinv + 9 * (long long)pt, Y);
+            lba_mul_YWt(Y, W2, M);
+#pragma unroll
+            for (int j = 0; j < 36; j++) acc[j] += M[j];
+            if (i1 == i2) {
+                double v[6];
+                lba_mul_Wd(W, d.Db + 3 * (long long)pt, v);
+#pragma unroll
+                for (int j = 0; j < 6; j++) coef[j] += v[j];
+            }
+        }
+#pragma unroll
+    for (int j = 0; j < 36; j++) acc[j] = wave_sum(acc[j]);
+    if (i1 == i2) {
+#pragma unroll
+        for (int j = 0; j < 6; j++) coef[j] = wave_sum(coef[j]);
+    }
+    if (lane != 0) return;
+    if (i1 == i2) {
+        int u = 0;
+        for (int r = 0; r < 6; r++)
+            for (int c = r; c < 6; c++, u++) {
+                const double v = on ? (d.Hpp[21 * (long long)i1 + u] + (r == c ? lambda : 0.)) - acc[6 * r + c] : (r == c ? 1. : 0.);
+                d.S[(long long)(6 * i1 + r) * n + 6 * i1 + c] = v;
+                d.S[(long long)(6 * i1 + c) * n + 6 * i1 + r] = v;
+            }
+        for (int r = 0; r < 6; r++) d.bs[6 * i1 + r] = on ? d.bp[6 * (long long)i1 + r] - coef[r] : 0.;
+    } else {
+        for (int r = 0; r < 6; r++)
+            for (int c = 0; c < 6; c++) {
+                const double v = 0. - acc[6 * r + c];
+                d.S[(long long)(6 * i1 + r) * n + 6 * i2 + c] = v;
+                d.S[(long long)(6 * i2 + c) * n + 6 * i1 + r] = v;
+            }
+    }
+}
+// S = L L^T in place (the lower triangle), right-looking over 6-wide block columns, then L y = bschur and L^T x = y in bs; x into
+// xp and the ok flag into out.  One workgroup; every barrier is reached by all of it (the failure flag is read after a barrier).
+__global__ __launch_bounds__(LBA_T) void k_lba_solve(LbaDev d)
+{
+    __shared__ int fail;
+    __shared__ double piv[6];
+    const int n = d.n, nb = d.K, tid = threadIdx.x;
+    double *A = d.S, *b = d.bs;
+    if (tid == 0) fail = 0;
+    __syncthreads();
+    for (int J = 0; J < nb; J++) {
+        const int j0 = 6 * J;
+        if (tid == 0) {                     // the diagonal block, unblocked
+            for (int j = 0; j < 6; j++) {
+                double v = A[(long long)(j0 + j) * n + j0 + j];
+                for (int k = 0; k < j; k++) v -= A[(long long)(j0 + j) * n + j0 + k] * A[(long long)(j0 + j) * n + j0 + k];
+                if (!(v > 0) || !isfinite(v)) { fail = 1; break; }
+                v = sqrt(v);
+                A[(long long)(j0 + j) * n + j0 + j] = v;
+                for (int i = j + 1; i < 6; i++) {
+                    double s = A[(long long)(j0 + i) * n + j0 + j];
+                    for (int k = 0; k < j; k++) s -= A[(long long)(j0 + i) * n + j0 + k] * A[(long long)(j0 + j) * n + j0 + k];
+                    A[(long long)(j0 + i) * n + j0 + j] = s / v;
+                }
+            }
+        }
+        __syncthreads();
+        if (fail) break;
+        for (int i = j0 + 6 + tid; i < n; i += LBA_T) {          // the panel below it: row i of L_IJ = A_IJ L_JJ^-T
+            double *row = A + (long long)i * n + j0;
+            for (int j = 0; j < 6; j++) {
+                double s = row[j];
+                for (int k = 0; k < j; k++) s -= row[k] * A[(long long)(j0 + j) * n + j0 + k];
+                row[j] = s / A[(long long)(j0 + j) * n + j0 + j];
+            }
+        }
+        __syncthreads();
+        // the trailing matrix: its lower triangle alone, row r holding the r + 1 entries c <= r.  The thread walks the entries
+        // tid, tid + 256, ... of the triangle in row order by stepping (r, c), with no division; both loops end at r == m
+        const int m = n - j0 - 6;
+        int r = 0, c = tid;
+        while (r < m && c > r) { c -= r + 1; r++; }
+        while (r < m) {
+            const int i = j0 + 6 + r, k = j0 + 6 + c;
+            const double *ri = A + (long long)i * n + j0, *rk = A + (long long)k * n + j0;
+            double s = A[(long long)i * n + k];
+#pragma unroll
+            for (int u = 0; u < 6; u++) s -= ri[u] * rk[u];
+            A[(long long)i * n + k] = s;
+            c += LBA_T;
+            while (r < m && c > r) { c -= r + 1; r++; }
+        }
+        __syncthreads();
+    }
+    const bool ok = !fail;
+    if (ok) {
+        for (int J = 0; J < nb; J++) {      // L y = b
+            const int j0 = 6 * J;
+            if (tid == 0)
+                for (int j = 0; j < 6; j++) {
+                    double s = b[j0 + j];
+                    for (int k = 0; k < j; k++) s -= A[(long long)(j0 + j) * n + j0 + k] * piv[k];
+                    piv[j] = s / A[(long long)(j0 + j) * n + j0 + j];
+                    b[j0 + j] = piv[j];
+                }
+            __syncthreads();
+            for (int i = j0 + 6 + tid; i < n; i += LBA_T) {
+                double s = b[i];
+#pragma unroll
+                for (int c = 0; c < 6; c++) s -= A[(long long)i * n + j0 + c] * piv[c];
+                b[i] = s;
+            }
+            __syncthreads();
+        }
+        for (int J = nb - 1; J >= 0; J--) { // L^T x = y
+            const int j0 = 6 * J;
+            if (tid == 0)
+                for (int j = 5; j >= 0; j--) {
+                    double s = b[j0 + j];
+                    for (int k = j + 1; k < 6; k++) s -= A[(long long)(j0 + k) * n + j0 + j] * piv[k];
+                    piv[j] = s / A[(long long)(j0 + j) * n + j0 + j];
+                    b[j0 + j] = piv[j];
+                }
+            __syncthreads();
+            for (int i = tid; i < j0; i += LBA_T) {
+                double s = b[i];
+#pragma unroll
+                for (int c = 0; c < 6; c++) s -= A[(long long)(j0 + c) * n + i] * piv[c];
+                b[i] = s;
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < n; i += LBA_T) d.xp[i] = ok ? b[i] : 0.;
+    if (tid == 0) d.out[OUT_OK] = ok ? 1. : 0.;
+}
+// x_l = Dinv (b_l - B^T x_p), update() into the trial estimates [1 - cur] and every vertex's terms of computeScale.  Thread i:
+// point i and key frame i.  A vertex outside the active set, and every vertex when the solve failed, is copied.
+__global__ __launch_bounds__(LBA_T) void k_lba_update(LbaDev d, int cur, double lambda)
+{
+    const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    const bool ok = d.out[OUT_OK] != 0.;
+    if (i < d.P) {
+        const double *x0 = d.X[cur] + 3 * i;
+        double *x1 = d.X[1 - cur] + 3 * i;
+        double term = 0;
+        if (ok && d.pt_active[i]) {
+            double cl[3] = {d.bl[3 * i], d.bl[3 * i + 1], d.bl[3 * i + 2]};
+            for (int e = d.edge_off[i]; e < d.edge_off[i + 1]; e++) {
+                const int k = d.edge_kf[e];
+                if (d.level[e] || !kf_is_free(d, k)) continue;
+                lba_sub_Wtx(d.blk + LBA_NBLK * (long long)e + LBA_HPL, d.xp + 6 * (long long)k, cl);
+            }
+            const double *D = d.Dinv + 9 * i;
+#pragma unroll
+            for (int j = 0; j < 3; j++) {
+                const double xl = D[3 * j] * cl[0] + D[3 * j + 1] * cl[1] + D[3 * j + 2] * cl[2];
+                term += lba_scale_term(xl, d.bl[3 * i + j], lambda);
+                x1[j] = x0[j] + xl;
+            }
+        } else {
+            x1[0] = x0[0]; x1[1] = x0[1]; x1[2] = x0[2];
+        }
+        d.pterm[i] = term;
+    }
+    if (i < d.NK) {
+        const LbaSe3 T = load_se3(d.est[cur] + 7 * i);
+        if (i < d.K && ok && d.kf_active[i]) {
+            double term = 0;
+#pragma unroll
+            for (int j = 0; j < 6; j++) term += lba_scale_term(d.xp[6 * i + j], d.bp[6 * i + j], lambda);
+            d.kterm[i] = term;
+            store_se3(d.est[1 - cur] + 7 * i, lba_pose_oplus(T, d.xp + 6 * i));
+        } else {
+            if (i < d.K) d.kterm[i] = 0;
+            store_se3(d.est[1 - cur] + 7 * i, T);
+        }
+    }
+}
+// One workgroup: the sums and counts the host reads after a trial (the file comment has the tree)
+__device__ __forceinline__ double lba_block_sum(double a, double *sh)
+{
+    a = wave_sum(a);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
+    __syncthreads();
+    for (int s = LBA_RT / 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
+        __syncthreads();
+    }
+    return sh[0];
+}
+__global__ __launch_bounds__(LBA_RT) void k_lba_reduce_out(LbaDev d)
+{
+    __shared__ double sh[LBA_RT / 64];
+    const int tid = threadIdx.x;
+    double chi = 0, scale = 0, scale_p = 0, active = 0, level1 = 0, mx = 0;
+    for (long long e = tid; e < d.E; e += LBA_RT) {
+        chi += d.chi_e[e];
+        if (d.level[e]) level1 += 1.; else active += 1.;
+    }
+    for (long long k = tid; k < d.K; k += LBA_RT) { scale += d.kterm[k]; mx = fmax(mx, d.kmax[k]); }
+    for (long long p = tid; p < d.P; p += LBA_RT) { scale_p += d.pterm[p]; mx = fmax(mx, d.pmax[p]); }
+    chi = lba_block_sum(chi, sh);
+    scale = lba_block_sum(scale, sh);
+    scale_p = lba_block_sum(scale_p, sh);
+    active = lba_block_sum(active, sh);         // counts: exact in double
+    level1 = lba_block_sum(level1, sh);
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) mx = fmax(mx, __shfl_xor(mx, m, 64));
+    __syncthreads();
+    if ((tid & 63) == 0) sh[tid >> 6] = mx;
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < LBA_RT / 64; w++) mx = fmax(mx, sh[w]);
+        d.out[OUT_CHI] = chi; d.out[OUT_SCALE] = scale + scale_p; d.out[OUT_MAXDIAG] = mx; d.out[OUT_ACTIVE] = active;
+        d.out[OUT_LEVEL1] = level1;
+    }
+}
+// e->chi2() > 5.991 / 7.815 || !e->isDepthPositive() on the stored error and the estimates [cur]: the level (:672-702) or the
+// erase flag (:715-743)
+__global__ __launch_bounds__(LBA_T) void k_lba_flag(LbaDev d, int cur, int final_pass)
+{
+    const long long e = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (e >= d.E) return;
+    const double err[3] = {d.err[3 * e], d.err[3 * e + 1], d.err[3 * e + 2]};
+    const bool bad = lba_chi2(err, (double)d.inv_sigma2[e]) > lba_chi2_threshold(!(d.u_right[e] < 0)) ||
+                     !lba_depth_positive(load_se3(d.est[cur] + 7 * (long long)d.edge_kf[e]), d.X[cur] + 3 * (long long)d.edge_pt[e]);
+    if (final_pass) d.erase[e] = bad ? 1 : 0;
+    else d.level[e] = bad ? 1 : 0;
+}
+// Converter::toCvMat of the local key frames' estimates and of the points (:762-777)
+__global__ __launch_bounds__(LBA_T) void k_lba_output(LbaDev d, int cur)
+{
+    const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
+    if (i < d.K) lba_se3_to_Tcw(load_se3(d.est[cur] + 7 * i), d.out_Tcw + 16 * i);
+    if (i < d.P)
+        for (int j = 0; j < 3; j++) d.out_xw[3 * i + j] = (float)d.X[cur][3 * i + j];
+}
+
+inline unsigned blocks_for(long long n) { return (unsigned)std::max<long long>((n + LBA_T - 1) / LBA_T, 1); }
+
+// orbm_local_bundle_adjustment_split: events on the call's stream between the groups of launches.  An event follows each group, so a
+// group's time runs from the end of the group before it (or from the event that opens a batch, recorded when the host comes back
+// from a synchronisation) to its own end: the idle time until the host has enqueued it counts into it.  Elapsed times are read
+// after the synchronisation that was due anyway; nothing else about the call changes.
+struct LbaProf {
+    enum { NEV = 32 };
+    bool on = false;
+    hipEvent_t ev[NEV];
+    int grp[NEV], n = 0, made = 0;
+    double *ms = nullptr;
+    int32_t *count = nullptr;
+
+    void start(double *ms_, int32_t *count_)
+    {
+        ms = ms_; count = count_;
+        for (int g = 0; g < ORBM_LBA_SPLIT_N; g++) { ms[g] = 0; count[g] = 0; }
+        for (made = 0; made < NEV; made++)
+            if (hipEventCreate(&ev[made]) != hipSuccess) return;
+        on = true;
+    }
+    ~LbaProf() { for (int i = 0; i < made; i++) (void)hipEventDestroy(ev[i]); }
+    void pre(hipStream_t s)                 // before a group: opens a batch if none is open
+    {
+        if (on && n == 0 && hipEventRecord(ev[0], s) == hipSuccess) { grp[0] = -1; n = 1; }
+    }
+    void post(int g, hipStream_t s)         // after a group's launches
+    {
+        if (on && n > 0 && n < NEV && hipEventRecord(ev[n], s) == hipSuccess) grp[n++] = g;
+    }
+    void drain()                            // after a synchronisation of the stream
+    {
+        for (int i = 1; i < n; i++) {
+            float t = 0;
+            if (hipEventElapsedTime(&t, ev[i - 1], ev[i]) == hipSuccess) { ms[grp[i]] += (double)t; count[grp[i]]++; }
+        }
+        n = 0;
+    }
+};
+#define LBA_GROUP(prof, g, s, ...) do { (prof).pre(s); __VA_ARGS__; (prof).post(g, s); } while (0)
+
+// "the passes of a problem" for lba_optimize (orbp_lba_body.h), as kernel launches on the handle's stream
+struct LbaGpu {
+    orbm_matcher *m;
+    LbaDev d;
+    hipStream_t s;
+    const volatile uint8_t *stop_flag;
+    int cur = 0, robust = 1, status = ORBX_OK;
+    double *pin;
+    LbaProf prof;
+
+    bool stop() const { return status != ORBX_OK || orbp_lba_read_stop(stop_flag); }
+    int read_out()                          // the one small block: reduce, copy, synchronise
+    {
+        prof.pre(s);
+        hipLaunchKernelGGL(k_lba_reduce_out, dim3(1), dim3(LBA_RT), 0, s, d);
+        MHIPCHK(hipGetLastError());
+        MHIPCHK(hipMemcpyAsync(pin, d.out, 64, hipMemcpyDeviceToHost, s));
+        prof.post(ORBM_LBA_SPLIT_READ_BACK, s);
+        MHIPCHK(hipStreamSynchronize(s));
+        prof.drain();
+        return ORBX_OK;
+    }
+    int activate(int &n_active, int &n_level1)
+    {
+        prof.pre(s);
+        hipLaunchKernelGGL(k_lba_activate, dim3(blocks_for(std::max(d.P, d.K))), dim3(LBA_T), 0, s, d);
+        if (d.E) MHIPCHK(hipMemsetAsync(d.chi_e, 0, sizeof(double) * (size_t)d.E, s));
+        if (d.K + d.P) {
+            MHIPCHK(hipMemsetAsync(d.kterm, 0, sizeof(double) * (size_t)(d.K + d.P), s));  // kterm, then pterm
+            MHIPCHK(hipMemsetAsync(d.kmax, 0, sizeof(double) * (size_t)(d.K + d.P), s));   // kmax, then pmax
+        }
+        prof.post(ORBM_LBA_SPLIT_SETUP, s);
+        MTRY(read_out());
+        n_active = (int)pin[OUT_ACTIVE]; n_level1 = (int)pin[OUT_LEVEL1];
+        return ORBX_OK;
+    }
+    int do_linearize(bool first, bool with_errors, double &chi, double &maxdiag)
+    {
+        if (with_errors) LBA_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
+        LBA_GROUP(prof, ORBM_LBA_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_lba_linearize, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
+        LBA_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_POINTS, s, hipLaunchKernelGGL(k_lba_reduce_points, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d));
+        if (d.K) LBA_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_KFS, s, hipLaunchKernelGGL(k_lba_reduce_kfs, dim3(d.K), dim3(64), 0, s, d));
+        MHIPCHK(hipGetLastError());
+        if (first || with_errors) {
+            MTRY(read_out());
+            chi = pin[OUT_CHI]; maxdiag = pin[OUT_MAXDIAG];
+        }
+        return ORBX_OK;
+    }
+    int do_trial(double lambda, double &chi, double &scale, bool &ok)
+    {
+        LBA_GROUP(prof, ORBM_LBA_SPLIT_DINV, s, hipLaunchKernelGGL(k_lba_dinv, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d, lambda));
+        if (d.K) LBA_GROUP(prof, ORBM_LBA_SPLIT_SCHUR, s, hipLaunchKernelGGL(k_lba_schur, dim3(d.K, d.K), dim3(64), 0, s, d, lambda));
+        LBA_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_T), 0, s, d));
+        LBA_GROUP(prof, ORBM_LBA_SPLIT_UPDATE, s, hipLaunchKernelGGL(k_lba_update, dim3(blocks_for(std::max(d.P, d.NK))), dim3(LBA_T), 0, s, d, cur, lambda));
+        LBA_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, 1 - cur, robust));
+        MHIPCHK(hipGetLastError());
+        MTRY(read_out());
+        chi = pin[OUT_CHI]; scale = pin[OUT_SCALE]; ok = pin[OUT_OK] != 0.;
+        return ORBX_OK;
+    }
+    // a failed launch or copy ends the loop through stop() and comes back as the call's status
+    void linearize(bool first, bool with_errors, double &chi, double &maxdiag) { if (status == ORBX_OK) status = do_linearize(first, with_errors, chi, maxdiag); }
+    void trial(double lambda, double &chi, double &scale, bool &ok) { if (status == ORBX_OK) status = do_trial(lambda, chi, scale, ok); }
+    void accept() { cur ^= 1; }
+    void reject() {}
+};
+}   // namespace
+
+namespace {
+int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase, const volatile uint8_t *stop,
+            orbp_lba_stats *stats, double *split_ms, int32_t *split_count)
+{
+    char text[200];
+    if (orbp_lba_check(p, Tcw_local, xw, erase, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
+    if (orbp_lba_read_stop(stop)) return ORBP_LBA_STOPPED;      // :655-657: nothing is launched
+    if (!m) return orbm_no_handle();
+    MHIPCHK(hipSetDevice(m->device));
+    const int K = p->n_local, NK = p->n_local + p->n_fixed, P = p->n_points, E = p->edge_off[P];
+    // k_lba_solve is one workgroup: its time grows with the cube of 6 K and a call runs it up to 150 times (DESIGN.md section 22
+    // has the time at the cap)
+    if ((long long)K * P > (1ll << 28) || K > ORBM_LBA_MAX_LOCAL)
+        return mfail(ORBX_E_CAPACITY, "request beyond %d local key frames / 2^28 table entries", ORBM_LBA_MAX_LOCAL);
+    // CSR by local key frame, edges ascending
+    std::vector<int32_t> kf_off((size_t)K + 1, 0), kf_edge;
+    for (int e = 0; e < E; e++)
+        if (p->edge_kf[e] < K) kf_off[p->edge_kf[e] + 1]++;
+    for (int k = 0; k < K; k++) kf_off[k + 1] += kf_off[k];
+    kf_edge.resize((size_t)kf_off[K]);
+    {
+        std::vector<int32_t> at(kf_off.begin(), kf_off.end() - 1);
+        for (int e = 0; e < E; e++)
+            if (p->edge_kf[e] < K) kf_edge[at[p->edge_kf[e]]++] = e;
+    }
+    // the workspace: 8-byte parts first
+    LbaDev d = {};
+    d.K = K; d.NK = NK; d.P = P; d.E = E; d.n = 6 * K;
+    size_t need = 0;
+    auto take = [&need](size_t bytes) { const size_t at = need; need += (bytes + 63) & ~(size_t)63; return at; };
+    const size_t n = (size_t)d.n, szd = sizeof(double);
+    const size_t o_est0 = take(7 * szd * NK), o_est1 = take(7 * szd * NK), o_X0 = take(3 * szd * P), o_X1 = take(3 * szd * P),
+                 o_err = take(3 * szd * E), o_chi = take(szd * E), o_blk = take(LBA_NBLK * szd * E), o_Hll = take(6 * szd * P),
+                 o_bl = take(3 * szd * P), o_Dinv = take(9 * szd * P), o_Db = take(3 * szd * P), o_max = take(szd * ((size_t)K + P)),
+                 o_term = take(szd * ((size_t)K + P)), o_Hpp = take(21 * szd * K), o_bp = take(6 * szd * K), o_S = take(szd * n * n),
+                 o_bs = take(szd * n), o_xp = take(szd * n), o_out = take(64),
+                 o_res = take(64 * (size_t)K + 12 * (size_t)P + (size_t)E),       // the results back to back: one copy home
+                 o_ept = take(4 * (size_t)E), o_table = take(4 * (size_t)K * P), o_level = take((size_t)E),
+                 o_ka = take((size_t)K), o_pa = take((size_t)P);
+    MTRY(orbm_ensure_lba(m, need));
+    MTRY(orbm_arena_begin(m));
+    hipStream_t s = m->stream;
+    uint8_t *w = m->d_lba;
+    d.est[0] = (double *)(w + o_est0); d.est[1] = (double *)(w + o_est1); d.X[0] = (double *)(w + o_X0); d.X[1] = (double *)(w + o_X1);
+    d.err = (double *)(w + o_err); d.chi_e = (double *)(w + o_chi); d.blk = (double *)(w + o_blk); d.Hll = (double *)(w + o_Hll);
+    d.bl = (double *)(w + o_bl); d.Dinv = (double *)(w + o_Dinv); d.Db = (double *)(w + o_Db);
+    d.kmax = (double *)(w + o_max); d.pmax = d.kmax + K; d.kterm = (double *)(w + o_term); d.pterm = d.kterm + K;
+    d.Hpp = (double *)(w + o_Hpp); d.bp = (double *)(w + o_bp); d.S = (double *)(w + o_S); d.bs = (double *)(w + o_bs);
+    d.xp = (double *)(w + o_xp); d.out = (double *)(w + o_out); d.out_Tcw = (float *)(w + o_res); d.out_xw = d.out_Tcw + 16 * (size_t)K;
+    d.erase = (uint8_t *)(d.out_xw + 3 * (size_t)P); d.edge_pt = (int32_t *)(w + o_ept); d.table = (int32_t *)(w + o_table); d.level = w + o_level;
+    d.kf_active = w + o_ka; d.pt_active = w + o_pa;
+
+    InBlock in(m);
+    const int pT = in.add(p->Tcw, 64 * (size_t)NK), pc = in.add(p->cam, 20 * (size_t)NK), pf = in.add(p->local_fixed, (size_t)K),
+              px = in.add(xw, 12 * (size_t)P), po = in.add(p->edge_off, 4 * ((size_t)P + 1)), pk = in.add(p->edge_kf, 4 * (size_t)E),
+              pb = in.add(p->obs, 8 * (size_t)E), pu = in.add(p->u_right, 4 * (size_t)E), pi = in.add(p->inv_sigma2, 4 * (size_t)E),
+              pko = in.add(kf_off.data(), 4 * ((size_t)K + 1)), pke = in.add(kf_edge.data(), 4 * kf_edge.size());
+    LbaGpu g;
+    if (split_ms && split_count) g.prof.start(split_ms, split_count);
+    g.prof.pre(s);
+    MTRY(in.upload(s));
+    g.prof.post(ORBM_LBA_SPLIT_UPLOAD, s);
+    d.Tcw = in.at<float>(pT); d.cam = in.at<float>(pc); d.local_fixed = in.at<uint8_t>(pf); d.xw_in = in.at<float>(px);
+    d.edge_off = in.dev_at<int32_t>(po); d.edge_kf = in.at<int32_t>(pk); d.obs = in.at<float>(pb); d.u_right = in.at<float>(pu);
+    d.inv_sigma2 = in.at<float>(pi); d.kf_off = in.dev_at<int32_t>(pko); d.kf_edge = in.at<int32_t>(pke);
+
+    g.m = m; g.d = d; g.s = s; g.stop_flag = stop; g.pin = (double *)m->lba_pin.get();
+    g.prof.pre(s);
+    if ((size_t)K * P) MHIPCHK(hipMemsetAsync(d.table, 0xFF, 4 * (size_t)K * P, s));
+    MHIPCHK(hipMemsetAsync(d.out, 0, 64, s));
+    hipLaunchKernelGGL(k_lba_init, dim3(blocks_for(std::max(std::max(NK, P), E))), dim3(LBA_T), 0, s, d);
+    MHIPCHK(hipGetLastError());
+    g.prof.post(ORBM_LBA_SPLIT_SETUP, s);
+
+    orbp_lba_stats st;
+    memset(&st, 0, sizeof st);
+    LbaRun run = {0, 0, 0, 0};
+    int n_active = 0, n_level1 = 0;
+    MTRY(g.activate(n_active, n_level1));                       // :659
+    if (n_active > 0) {
+        lba_optimize(g, 5, run);                                // :660
+        MTRY(g.status);
+        st.iterations[0] = run.iterations; st.trials[0] = run.trials; st.lambda = run.lambda; st.chi2 = run.chi2;
+    }
+    if (!orbp_lba_read_stop(stop)) {                            // :662-709
+        st.second_round = 1;
+        LBA_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s, hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 0));
+        g.robust = 0;
+        MTRY(g.activate(n_active, n_level1));                   // :706
+        st.n_level1 = n_level1;
+        if (n_active > 0) {
+            lba_optimize(g, 10, run);                           // :707
+            MTRY(g.status);
+            st.iterations[1] = run.iterations; st.trials[1] = run.trials; st.lambda = run.lambda; st.chi2 = run.chi2;
+        }
+    }
+    g.prof.pre(s);
+    hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 1);                  // :715-743
+    hipLaunchKernelGGL(k_lba_output, dim3(blocks_for(std::max(K, P))), dim3(LBA_T), 0, s, d, g.cur);     // :762-777
+    MHIPCHK(hipGetLastError());
+    g.prof.post(ORBM_LBA_SPLIT_FLAG_OUTPUT, s);
+    void *const host[3] = {Tcw_local, xw, erase};
+    const size_t parts[3] = {64 * (size_t)K, 12 * (size_t)P, (size_t)E};
+    MTRY(orbm_d2h_split(m, host, parts, 3, d.out_Tcw, s));      // one copy into the arena; the outputs are written at orbm_sync
+    g.prof.post(ORBM_LBA_SPLIT_DOWNLOAD, s);
+    MTRY(orbm_sync(m, s));
+    g.prof.drain();
+    if (stats) *stats = st;
+    return ORBP_LBA_DONE;
+}
+}   // namespace
+
+extern "C" int orbm_local_bundle_adjustment(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase,
+                                            const volatile uint8_t *stop, orbp_lba_stats *stats)
+{
+    return lba_run(m, p, Tcw_local, xw, erase, stop, stats, nullptr, nullptr);
+}
+extern "C" int orbm_local_bundle_adjustment_split(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase,
+                                                  const volatile uint8_t *stop, orbp_lba_stats *stats, double *split_ms,
+                                                  int32_t *split_count)
+{
+    if (!split_ms || !split_count) return mfail(ORBX_E_INVALID, "local_bundle_adjustment_split: NULL split_ms or split_count");
+    return lba_run(m, p, Tcw_local, xw, erase, stop, stats, split_ms, split_count);
+}

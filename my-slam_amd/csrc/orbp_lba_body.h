@@ -1,0 +1,390 @@
+// orbp_lba_body.h -- the arithmetic of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778 of WChen09/My-SLAM, on g2o), one text
+// for the host solver (orbp_lba.cc, plain C++) and for the kernels (orbm_lba.hip).  Restated from Thirdparty/g2o/g2o:
+//   SE3Quat                         types/se3quat.h: operator* :104-110, map :119-121, exp :223-257, normalizeRotation :280-285
+//   EdgeSE3ProjectXYZ               computeError types/types_six_dof_expmap.h:109-114, isDepthPositive :116-120,
+//                                   linearizeOplus types_six_dof_expmap.cpp:103-139, cam_project :141-147
+//   EdgeStereoSE3ProjectXYZ         computeError .h:139-144, isDepthPositive :146-150, linearizeOplus .cpp:188-235,
+//                                   cam_project with its float invz :150-157
+//   RobustKernelHuber               core/robust_kernel_impl.cpp:78-91
+//   constructQuadraticForm          core/base_binary_edge.hpp:55-120, one or both vertices free
+//   VertexSE3Expmap::oplusImpl      types_six_dof_expmap.h:62-65 (exp(update) * estimate); VertexSBAPointXYZ::oplusImpl types_sba.h (+=)
+//   BlockSolver_6_3::solve          core/block_solver.hpp:354-486 (Schur complement), setLambda :564-589
+//   OptimizationAlgorithmLevenberg  core/optimization_algorithm_levenberg.cpp:61-164 (with this fork's _nBad stop :154-161),
+//                                   computeLambdaInit :166-180, computeScale :182-189; driven by SparseOptimizer::optimize
+//                                   (core/sparse_optimizer.cpp:354-419)
+//
+// Semantics kept (include/orbp.h, orbp_local_bundle_adjustment, lists them for the caller):
+//   rounds        optimize(5); the flagging pass :672-702 (chi2 > 5.991 / 7.815 on the double chi2(), or depth not positive, sets
+//                 level 1; every edge loses its robust kernel); initializeOptimization(0) and optimize(10), which starts again at
+//                 iteration 0 (new lambda, _ni = 2, _nBad = 0)
+//   stale errors  an edge stores the error computeActiveErrors last wrote while the edge was active, a rejected trial's included;
+//                 the final pass :715-743 reads chi2() from it and evaluates isDepthPositive() at the final estimates
+//   vertices without active edges leave the second round's active set: their estimates keep the first round's bits
+//   fixed key frames contribute to the point's blocks only; a local key frame with mnId == 0 is fixed
+//   stop          read at the top of every iteration and in the do ... while of the trial loop (sparse_optimizer.cpp:376,
+//                 optimization_algorithm_levenberg.cpp:149)
+//
+// Everything is fp64 and uses + - * / sqrt alone (the build's -ffp-contract=off keeps them unfused), except lba_se3_exp, which calls
+// sin and cos of the side it is compiled for.  Every per-edge quantity (camera point, error, chi2, Huber weight, both Jacobians, the
+// 54 numbers of the edge's quadratic form) is therefore the same on host and device; the order of the sums over edges, sin / cos
+// and the inside of the dense solve are not.
+//
+// Chosen here where the flat problem does not carry what g2o orders by: g2o numbers its unknowns by vertex id (key frames by mnId,
+// points by mnId); the problem has no ids, so the unknowns stand in problem order (lLocalKeyFrames, lLocalMapPoints).  That moves
+// the order of computeScale's sum and of the elimination, nothing else.  A free key frame without active edges keeps an identity
+// block in the reduced system instead of leaving it (its update is exactly zero and is not applied).  When the solve fails the
+// update is zero (g2o applies whatever its x held before).
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define LBA_HD __host__ __device__ __forceinline__
+#else
+#define LBA_HD static inline
+#endif
+
+struct LbaSe3 { double qx, qy, qz, qw, t0, t1, t2; };       // g2o::SE3Quat: a unit quaternion (w >= 0) and a translation
+struct LbaCam { double fx, fy, cx, cy, bf; };
+
+// an edge's quadratic form: the upper triangles row-major, Hpl = B^T Omega A (6 x 3, row-major; B the pose Jacobian, A the point's)
+#define LBA_NBLK 54
+#define LBA_HPP 0               // 21
+#define LBA_BP 21               // 6
+#define LBA_HLL 27              // 6
+#define LBA_BL 33               // 3
+#define LBA_HPL 36              // 18
+#define LBA_MAX_ITERATIONS 15   // optimize(5) + optimize(10)
+#define LBA_MAX_TRIALS 10       // _maxTrialsAfterFailure
+
+// Eigen's Quaterniond(Matrix3d), the branch on the largest diagonal entry written out per case (orbp_sim3opt_body.h s3o_quat_from_R)
+LBA_HD void lba_quat_from_R(const double *R, LbaSe3 &q)
+{
+    double tr = R[0] + R[4] + R[8];
+    if (tr > 0) {
+        tr = sqrt(tr + 1.0);
+        q.qw = 0.5 * tr;
+        tr = 0.5 / tr;
+        q.qx = (R[7] - R[5]) * tr; q.qy = (R[2] - R[6]) * tr; q.qz = (R[3] - R[1]) * tr;
+    } else {
+        int i = 0;
+        if (R[4] > R[0]) i = 1;
+        if (R[8] > (i ? R[4] : R[0])) i = 2;
+        if (i == 0) {
+            tr = sqrt(R[0] - R[4] - R[8] + 1.0);
+            q.qx = 0.5 * tr; tr = 0.5 / tr;
+            q.qw = (R[7] - R[5]) * tr; q.qy = (R[3] + R[1]) * tr; q.qz = (R[6] + R[2]) * tr;
+        } else if (i == 1) {
+            tr = sqrt(R[4] - R[8] - R[0] + 1.0);
+            q.qy = 0.5 * tr; tr = 0.5 / tr;
+            q.qw = (R[2] - R[6]) * tr; q.qz = (R[7] + R[5]) * tr; q.qx = (R[1] + R[3]) * tr;
+        } else {
+            tr = sqrt(R[8] - R[0] - R[4] + 1.0);
+            q.qz = 0.5 * tr; tr = 0.5 / tr;
+            q.qw = (R[3] - R[1]) * tr; q.qx = (R[2] + R[6]) * tr; q.qy = (R[5] + R[7]) * tr;
+        }
+    }
+}
+LBA_HD void lba_quat_normalize(LbaSe3 &q)                     // se3quat.h:280-285
+{
+    if (q.qw < 0) { q.qw = -q.qw; q.qx = -q.qx; q.qy = -q.qy; q.qz = -q.qz; }
+    const double n = sqrt(q.qw * q.qw + q.qx * q.qx + q.qy * q.qy + q.qz * q.qz);
+    q.qw /= n; q.qx /= n; q.qy /= n; q.qz /= n;
+}
+// Eigen's Quaterniond * Vector3d: v + w uv + q.vec x uv with uv = 2 q.vec x v
+LBA_HD void lba_rotate(const LbaSe3 &q, const double *v, double *o)
+{
+    double u0 = q.qy * v[2] - q.qz * v[1], u1 = q.qz * v[0] - q.qx * v[2], u2 = q.qx * v[1] - q.qy * v[0];
+    u0 += u0; u1 += u1; u2 += u2;
+    o[0] = v[0] + q.qw * u0 + (q.qy * u2 - q.qz * u1);
+    o[1] = v[1] + q.qw * u1 + (q.qz * u0 - q.qx * u2);
+    o[2] = v[2] + q.qw * u2 + (q.qx * u1 - q.qy * u0);
+}
+LBA_HD void lba_quat_to_R(const LbaSe3 &q, double *R)         // Eigen's toRotationMatrix
+{
+    const double tx = 2 * q.qx, ty = 2 * q.qy, tz = 2 * q.qz;
+    const double twx = tx * q.qw, twy = ty * q.qw, twz = tz * q.qw, txx = tx * q.qx, txy = ty * q.qx, txz = tz * q.qx;
+    const double tyy = ty * q.qy, tyz = tz * q.qy, tzz = tz * q.qz;
+    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
+    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
+    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
+}
+LBA_HD void lba_map(const LbaSe3 &T, const double *x, double *o)      // se3quat.h:119-121
+{
+    lba_rotate(T, x, o);
+    o[0] += T.t0; o[1] += T.t1; o[2] += T.t2;
+}
+// Converter::toSE3Quat (src/Converter.cc:37-46) of a row-major 4 x 4 float pose: SE3Quat(R, t) normalises
+LBA_HD LbaSe3 lba_se3_from_Tcw(const float *T)
+{
+    double R[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) R[3 * i + j] = (double)T[4 * i + j];
+    LbaSe3 S;
+    lba_quat_from_R(R, S);
+    lba_quat_normalize(S);
+    S.t0 = (double)T[3]; S.t1 = (double)T[7]; S.t2 = (double)T[11];
+    return S;
+}
+// Converter::toCvMat(SE3Quat) (src/Converter.cc:48-52): to_homogeneous_matrix cast to float
+LBA_HD void lba_se3_to_Tcw(const LbaSe3 &S, float *T)
+{
+    double R[9];
+    lba_quat_to_R(S, R);
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) T[4 * i + j] = (float)R[3 * i + j];
+    T[3] = (float)S.t0; T[7] = (float)S.t1; T[11] = (float)S.t2;
+    T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
+}
+// SE3Quat::exp (se3quat.h:223-257), omega first, then upsilon; pow(theta, 3) as two multiplications on both sides
+LBA_HD LbaSe3 lba_se3_exp(const double *u)
+{
+    const double theta = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
+    const double O[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
+    double O2[9], R[9], V[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
+    if (theta < 0.00001) {
+        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0) + O[i] + O2[i]; V[i] = R[i]; }
+    } else {
+        const double sn = sin(theta), cs = cos(theta);
+        const double a = sn / theta, b = (1 - cs) / (theta * theta), c = (theta - sn) / (theta * theta * theta);
+        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0) + a * O[i] + b * O2[i]; V[i] = (i % 4 == 0) + b * O[i] + c * O2[i]; }
+    }
+    LbaSe3 T;
+    lba_quat_from_R(R, T);
+    lba_quat_normalize(T);
+    T.t0 = V[0] * u[3] + V[1] * u[4] + V[2] * u[5];
+    T.t1 = V[3] * u[3] + V[4] * u[4] + V[5] * u[5];
+    T.t2 = V[6] * u[3] + V[7] * u[4] + V[8] * u[5];
+    return T;
+}
+LBA_HD LbaSe3 lba_se3_mul(const LbaSe3 &a, const LbaSe3 &b)     // se3quat.h:104-110
+{
+    LbaSe3 r;
+    const double bt[3] = {b.t0, b.t1, b.t2};
+    double rt[3];
+    lba_rotate(a, bt, rt);
+    r.t0 = a.t0 + rt[0]; r.t1 = a.t1 + rt[1]; r.t2 = a.t2 + rt[2];
+    r.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
+    r.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
+    r.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
+    r.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
+    lba_quat_normalize(r);
+    return r;
+}
+// VertexSE3Expmap::oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
+LBA_HD LbaSe3 lba_pose_oplus(const LbaSe3 &est, const double *update) { return lba_se3_mul(lba_se3_exp(update), est); }
+
+// computeError of both edges: pc = the point in the camera frame, err = obs - cam_project(pc) (err[2] = 0 on a monocular edge).
+// The stereo cam_project divides in double and keeps the quotient as a float (types_six_dof_expmap.cpp:151).
+LBA_HD void lba_edge_error(const LbaSe3 &T, const LbaCam &c, const double *xw, const float *obs, float u_right, double *pc, double *err)
+{
+    lba_map(T, xw, pc);
+    if (u_right < 0) {
+        err[0] = (double)obs[0] - (pc[0] / pc[2] * c.fx + c.cx);
+        err[1] = (double)obs[1] - (pc[1] / pc[2] * c.fy + c.cy);
+        err[2] = 0;
+    } else {
+        const float invz = (float)(1.0 / pc[2]);
+        const double u = pc[0] * invz * c.fx + c.cx;
+        err[0] = (double)obs[0] - u;
+        err[1] = (double)obs[1] - (pc[1] * invz * c.fy + c.cy);
+        err[2] = (double)u_right - (u - c.bf * invz);
+    }
+}
+// chi2(): _error.dot(information() * _error) with information = inv_sigma2 * I
+LBA_HD double lba_chi2(const double *err, double info)
+{
+    return err[0] * (info * err[0]) + err[1] * (info * err[1]) + err[2] * (info * err[2]);
+}
+// isDepthPositive(): (v1->estimate().map(v2->estimate()))(2) > 0.0
+LBA_HD bool lba_depth_positive(const LbaSe3 &T, const double *xw)
+{
+    double pc[3];
+    lba_map(T, xw, pc);
+    return pc[2] > 0.0;
+}
+LBA_HD double lba_huber_delta(bool stereo) { return stereo ? (double)(float)sqrt(7.815) : (double)(float)sqrt(5.991); }   // :569-570
+LBA_HD double lba_chi2_threshold(bool stereo) { return stereo ? 7.815 : 5.991; }                                           // :680, :696
+LBA_HD void lba_huber(double c2, double delta, double &rho0, double &rho1)      // robust_kernel_impl.cpp:78-91
+{
+    const double dsqr = delta * delta;
+    if (c2 <= dsqr) { rho0 = c2; rho1 = 1.; }
+    else { const double s = sqrt(c2); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
+}
+// an active edge's term of activeRobustChi2 (sparse_optimizer.cpp:100-117)
+LBA_HD double lba_edge_robust_chi2(const double *err, double info, bool stereo, bool robust)
+{
+    const double c2 = lba_chi2(err, info);
+    if (!robust) return c2;
+    double rho0, rho1;
+    lba_huber(c2, lba_huber_delta(stereo), rho0, rho1);
+    return rho0;
+}
+
+// linearizeOplus + constructQuadraticForm of one edge at T and xw, with the stored error err: blk[LBA_NBLK].  The point part is
+// always formed (a point is never fixed); the pose part and Hpl only for a free key frame (else they are zero).  A monocular edge
+// carries a zero third row, so both kinds add three terms.
+LBA_HD void lba_edge_blocks(const LbaSe3 &T, const LbaCam &c, const double *xw, const double *err, double info, bool stereo, bool robust,
+                            bool kf_free, double *blk)
+{
+    double pc[3], R[9], A[3][3], B[3][6];
+    lba_map(T, xw, pc);
+    lba_quat_to_R(T, R);
+    const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z;
+    if (!stereo) {
+        // _jacobianOplusXi = -1./z * tmp * R with tmp = [fx 0 -x/z*fx; 0 fy -y/z*fy] (.cpp:115-124)
+        const double s = -1. / z;
+        const double t00 = s * c.fx, t02 = s * (-x / z * c.fx), t11 = s * c.fy, t12 = s * (-y / z * c.fy);
+        for (int k = 0; k < 3; k++) {
+            A[0][k] = t00 * R[k] + t02 * R[6 + k];
+            A[1][k] = t11 * R[3 + k] + t12 * R[6 + k];
+            A[2][k] = 0;
+        }
+    } else {
+        for (int k = 0; k < 3; k++) {                       // .cpp:202-212
+            A[0][k] = -c.fx * R[k] / z + c.fx * x * R[6 + k] / z_2;
+            A[1][k] = -c.fy * R[3 + k] / z + c.fy * y * R[6 + k] / z_2;
+            A[2][k] = A[0][k] - c.bf * R[6 + k] / z_2;
+        }
+    }
+    B[0][0] = x * y / z_2 * c.fx; B[0][1] = -(1 + (x * x / z_2)) * c.fx; B[0][2] = y / z * c.fx;
+    B[0][3] = -1. / z * c.fx; B[0][4] = 0; B[0][5] = x / z_2 * c.fx;
+    B[1][0] = (1 + y * y / z_2) * c.fy; B[1][1] = -x * y / z_2 * c.fy; B[1][2] = -x / z * c.fy;
+    B[1][3] = 0; B[1][4] = -1. / z * c.fy; B[1][5] = y / z_2 * c.fy;
+    if (stereo) {
+        B[2][0] = B[0][0] - c.bf * y / z_2; B[2][1] = B[0][1] + c.bf * x / z_2; B[2][2] = B[0][2];
+        B[2][3] = B[0][3]; B[2][4] = 0; B[2][5] = B[0][5] - c.bf / z_2;
+    } else {
+        for (int k = 0; k < 6; k++) B[2][k] = 0;
+    }
+    double w = 1.;
+    if (robust) {
+        double rho0;
+        lba_huber(lba_chi2(err, info), lba_huber_delta(stereo), rho0, w);
+    }
+    const double wi = w * info;                              // weightedOmega = rho' * Omega
+    const double r0 = -(info * err[0]) * w, r1 = -(info * err[1]) * w, r2 = -(info * err[2]) * w;      // omega_r (*= rho')
+    int u = LBA_HLL;
+    for (int a = 0; a < 3; a++) {
+        blk[LBA_BL + a] = A[0][a] * r0 + A[1][a] * r1 + A[2][a] * r2;
+        const double w0 = A[0][a] * wi, w1 = A[1][a] * wi, w2 = A[2][a] * wi;
+        for (int b = a; b < 3; b++, u++) blk[u] = w0 * A[0][b] + w1 * A[1][b] + w2 * A[2][b];
+    }
+    u = LBA_HPP;
+    for (int a = 0; a < 6; a++) {
+        const double w0 = B[0][a] * wi, w1 = B[1][a] * wi, w2 = B[2][a] * wi;
+        blk[LBA_BP + a] = kf_free ? B[0][a] * r0 + B[1][a] * r1 + B[2][a] * r2 : 0.;
+        for (int b = a; b < 6; b++, u++) blk[u] = kf_free ? w0 * B[0][b] + w1 * B[1][b] + w2 * B[2][b] : 0.;
+        for (int b = 0; b < 3; b++) blk[LBA_HPL + 3 * a + b] = kf_free ? w0 * A[0][b] + w1 * A[1][b] + w2 * A[2][b] : 0.;
+    }
+}
+
+// Dinv = (Hll + lambda I)^-1 (block_solver.hpp:389; Eigen's 3 x 3 inverse: cofactors over the determinant) and Dinv b_l (:391-395).
+// Hll is the upper triangle (00 01 02 11 12 22); Dinv comes back as a full row-major matrix
+LBA_HD void lba_point_dinv(const double *Hll, const double *bl, double lambda, double *Dinv, double *Db)
+{
+    const double m00 = Hll[0] + lambda, m01 = Hll[1], m02 = Hll[2], m11 = Hll[3] + lambda, m12 = Hll[4], m22 = Hll[5] + lambda;
+    const double c00 = m11 * m22 - m12 * m12, c01 = m02 * m12 - m01 * m22, c02 = m01 * m12 - m02 * m11;
+    const double c11 = m00 * m22 - m02 * m02, c12 = m01 * m02 - m00 * m12, c22 = m00 * m11 - m01 * m01;
+    const double invdet = 1. / (m00 * c00 + m01 * c01 + m02 * c02);
+    Dinv[0] = c00 * invdet; Dinv[1] = Dinv[3] = c01 * invdet; Dinv[2] = Dinv[6] = c02 * invdet;
+    Dinv[4] = c11 * invdet; Dinv[5] = Dinv[7] = c12 * invdet; Dinv[8] = c22 * invdet;
+    for (int i = 0; i < 3; i++) Db[i] = Dinv[3 * i] * bl[0] + Dinv[3 * i + 1] * bl[1] + Dinv[3 * i + 2] * bl[2];
+}
+// BDinv = Bi * Dinv (:407): W is an edge's Hpl (6 x 3), Y = W Dinv
+LBA_HD void lba_mul_WD(const double *W, const double *Dinv, double *Y)
+{
+    for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 3; b++) Y[3 * a + b] = W[3 * a] * Dinv[b] + W[3 * a + 1] * Dinv[3 + b] + W[3 * a + 2] * Dinv[6 + b];
+}
+// M (6 x 6, row-major) = Y W2^T, the term BDinv * Bj->transpose() of :429
+LBA_HD void lba_mul_YWt(const double *Y, const double *W2, double *M)
+{
+    for (int a = 0; a < 6; a++)
+        for (int b = 0; b < 6; b++) M[6 * a + b] = Y[3 * a] * W2[3 * b] + Y[3 * a + 1] * W2[3 * b + 1] + Y[3 * a + 2] * W2[3 * b + 2];
+}
+// v (6) = W d, the term (*Bi) * db of :413
+LBA_HD void lba_mul_Wd(const double *W, const double *d, double *v)
+{
+    for (int a = 0; a < 6; a++) v[a] = W[3 * a] * d[0] + W[3 * a + 1] * d[1] + W[3 * a + 2] * d[2];
+}
+// cl -= W^T xp, one edge's term of _HplCCS->rightMultiply(cl, -xp) (:468-477)
+LBA_HD void lba_sub_Wtx(const double *W, const double *xp, double *cl)
+{
+    for (int b = 0; b < 3; b++) {
+        double s = 0;
+        for (int a = 0; a < 6; a++) s += W[3 * a + b] * xp[a];
+        cl[b] -= s;
+    }
+}
+// one unknown's term of computeScale (optimization_algorithm_levenberg.cpp:186)
+LBA_HD double lba_scale_term(double x, double b, double lambda) { return x * (lambda * x + b); }
+
+// What one optimize() did: g2o's counters and the state the caller reports (orbp_lba_stats)
+struct LbaRun { int iterations, trials; double lambda, chi2; };
+
+// OptimizationAlgorithmLevenberg::solve inside SparseOptimizer::optimize(iterations), as s3o_optimize (orbp_sim3opt_body.h) is for
+// one vertex, over "the passes of a problem".  Host code on both paths: the host solver's passes add in edge order, the GPU path's
+// passes are kernel launches that add in their trees and hand back one small block a trial.
+//   ctx.stop()                                  terminate()
+//   ctx.linearize(first, errors, chi, maxdiag)  errors: computeActiveErrors + activeRobustChi2 into chi; always buildSystem; first:
+//                                               computeLambdaInit's maximum over the diagonals of the free poses and points.  After
+//                                               an accepted trial the edges hold that trial's errors and the chi2 g2o sums again at
+//                                               the top of the next iteration is the trial's, term for term: it is carried instead.
+//                                               After a rejected trial that ended its iteration (rho is NaN) they are computed anew.
+//   ctx.trial(lambda, chi, scale, ok)           push, setLambda, solve, update, restoreDiagonal, computeActiveErrors,
+//                                               activeRobustChi2, computeScale (without its + 1e-3)
+//   ctx.accept() / ctx.reject()                 discardTop / pop: the edges keep the trial's errors either way
+template <class Ctx>
+static inline void lba_optimize(Ctx &ctx, int iterations, LbaRun &run)
+{
+    double lambda = 0, ni = 2, current = 0;
+    int n_bad = 0;
+    bool fresh = false;                                     // the edges hold the errors of the current estimates
+    run.iterations = run.trials = 0;
+    run.lambda = run.chi2 = 0;
+    for (int it = 0; it < LBA_MAX_ITERATIONS; it++) {
+        if (it >= iterations || ctx.stop()) break;
+        double chi = 0, maxdiag = 0;
+        ctx.linearize(it == 0, !fresh, chi, maxdiag);
+        if (!fresh) current = chi;
+        if (it == 0) { lambda = 1e-5 * maxdiag; ni = 2; n_bad = 0; }                     // _tau = 1e-5
+        const double ini = current;
+        double rho = 0;
+        int qmax = 0;
+        do {
+            double temp = 0, scale = 0;
+            bool ok2 = false;
+            ctx.trial(lambda, temp, scale, ok2);
+            if (!ok2) temp = 1.7976931348623157e308;
+            rho = current - temp;
+            scale += 1e-3;
+            rho /= scale;
+            if (rho > 0 && isfinite(temp)) {
+                const double t = 2 * rho - 1;
+                double alpha = 1. - t * t * t;
+                alpha = fmin(alpha, 2. / 3.);
+                lambda *= fmax(1. / 3., alpha);
+                ni = 2;
+                current = temp;
+                fresh = true;
+                ctx.accept();
+            } else {
+                lambda *= ni;
+                ni *= 2;
+                fresh = false;
+                ctx.reject();
+            }
+            qmax++;
+            run.trials++;
+        } while (rho < 0 && qmax < LBA_MAX_TRIALS && !ctx.stop());
+        run.iterations++;
+        run.lambda = lambda;
+        run.chi2 = current;
+        if (qmax == LBA_MAX_TRIALS || rho == 0) break;
+        if ((ini - current) * 1e3 < ini) n_bad++; else n_bad = 0;
+        if (n_bad >= 3) break;
+    }
+}

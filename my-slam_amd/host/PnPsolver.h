@@ -9,8 +9,12 @@
 #pragma once
 #include <array>
 #include <cstdint>
+#include <map>
+#include <mutex>
 #include <optional>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 #include "../../include/orbm.h"
 #include "../../include/orbp.h"
@@ -328,6 +332,151 @@ public:
             P.nIn = nIn[p];
         }
         return ORBX_OK;
+    }
+
+    // ---- Optimizer::LocalBundleAdjustment (include/Optimizer.h, src/Optimizer.cc:453-778; LocalMapping::Run, src/LocalMapping.cc:82) ----
+    // The flat problem of orbp_local_bundle_adjustment (include/orbp.h) and the objects its rows stand for.
+    template <class KeyFrameT, class MapPointT>
+    struct LbaProblem {
+        std::vector<KeyFrameT *> local, fixed;              // lLocalKeyFrames, lFixedCameras
+        std::vector<MapPointT *> points;                    // lLocalMapPoints
+        std::vector<KeyFrameT *> edgeKF;                    // per edge: vpEdgeKFMono / vpEdgeKFStereo
+        std::vector<uint8_t> localFixed;
+        std::vector<float> Tcw, cam, xw, obs, uRight, invSigma2;
+        std::vector<int32_t> edgeOff, edgeKf;
+        // results
+        std::vector<float> TcwLocal;
+        std::vector<uint8_t> erase;
+        orbp_lba_stats stats{};
+        orbp_lba_problem flat() const
+        {
+            return {(int32_t)local.size(), (int32_t)fixed.size(), (int32_t)points.size(), localFixed.data(), Tcw.data(), cam.data(), edgeOff.data(),
+                    edgeKf.data(), obs.data(), uRight.data(), invSigma2.data()};
+        }
+    };
+    // The gather of :455-504 with its marks (mnBALocalForKF, mnBAFixedForKF) and isBad skips, and the edge walk :572-653
+    template <class KeyFrameT, class MapPointT>
+    static void GatherLocalBundleAdjustment(KeyFrameT *pKF, LbaProblem<KeyFrameT, MapPointT> &P)
+    {
+        P = LbaProblem<KeyFrameT, MapPointT>();
+        P.local.push_back(pKF);                                             // :458-459
+        pKF->mnBALocalForKF = pKF->mnId;
+        const std::vector<KeyFrameT *> vNeighKFs = pKF->GetVectorCovisibleKeyFrames();
+        for (int i = 0, iend = (int)vNeighKFs.size(); i < iend; i++) {      // :462-468
+            KeyFrameT *pKFi = vNeighKFs[i];
+            pKFi->mnBALocalForKF = pKF->mnId;
+            if (!pKFi->isBad()) P.local.push_back(pKFi);
+        }
+        for (KeyFrameT *pKFi : P.local) {                                   // :472-486
+            std::vector<MapPointT *> vpMPs = pKFi->GetMapPointMatches();
+            for (MapPointT *pMP : vpMPs)
+                if (pMP)
+                    if (!pMP->isBad())
+                        if (pMP->mnBALocalForKF != pKF->mnId) {
+                            P.points.push_back(pMP);
+                            pMP->mnBALocalForKF = pKF->mnId;
+                        }
+        }
+        for (MapPointT *pMP : P.points) {                                   // :490-504
+            auto observations = pMP->GetObservations();
+            for (auto mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+                KeyFrameT *pKFi = mit->first;
+                if (pKFi->mnBALocalForKF != pKF->mnId && pKFi->mnBAFixedForKF != pKF->mnId) {
+                    pKFi->mnBAFixedForKF = pKF->mnId;
+                    if (!pKFi->isBad()) P.fixed.push_back(pKFi);
+                }
+            }
+        }
+        std::map<KeyFrameT *, int32_t> index;                               // optimizer.vertex(pKFi->mnId)
+        auto addKF = [&](KeyFrameT *pKFi) {                                 // :523-546
+            index[pKFi] = (int32_t)index.size();
+            const auto T = pKFi->GetPose();
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++) P.Tcw.push_back(T.template at<float>(r, c));
+            P.cam.push_back(pKFi->fx); P.cam.push_back(pKFi->fy); P.cam.push_back(pKFi->cx); P.cam.push_back(pKFi->cy); P.cam.push_back(pKFi->mbf);
+        };
+        for (KeyFrameT *pKFi : P.local) { addKF(pKFi); P.localFixed.push_back(pKFi->mnId == 0 ? 1 : 0); }
+        for (KeyFrameT *pKFi : P.fixed) addKF(pKFi);
+        P.edgeOff.push_back(0);
+        for (MapPointT *pMP : P.points) {                                   // :572-653
+            const auto X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; r++) P.xw.push_back(X.template at<float>(r));
+            const auto observations = pMP->GetObservations();
+            for (auto mit = observations.begin(), mend = observations.end(); mit != mend; mit++) {
+                KeyFrameT *pKFi = mit->first;
+                if (pKFi->isBad()) continue;                                // :589
+                const auto it = index.find(pKFi);
+                if (it == index.end()) continue;                            // a bad key frame at :500 that is good again: no vertex
+                const auto &kpUn = pKFi->mvKeysUn[mit->second];
+                P.edgeKf.push_back(it->second);
+                P.edgeKF.push_back(pKFi);
+                P.obs.push_back(kpUn.pt.x); P.obs.push_back(kpUn.pt.y);
+                const float ur = pKFi->mvuRight[mit->second];
+                P.uRight.push_back(ur < 0 ? -1.f : ur);                     // :594
+                P.invSigma2.push_back(pKFi->mvInvLevelSigma2[kpUn.octave]);
+            }
+            P.edgeOff.push_back((int32_t)P.edgeKf.size());
+        }
+        P.TcwLocal.assign(16 * P.local.size() + 1, 0.f);
+        P.erase.assign(P.edgeKf.size() + 1, 0);
+        P.Tcw.push_back(0.f); P.cam.push_back(0.f); P.xw.push_back(0.f); P.obs.push_back(0.f); P.uRight.push_back(0.f);       // never NULL
+        P.invSigma2.push_back(0.f); P.edgeKf.push_back(0); P.localFixed.push_back(0);
+    }
+    // :745-777 in order, under pMap->mMutexMapUpdate: the erased pairs (points that turned bad during the solve are skipped as :720
+    // and :735 do), SetPose, SetWorldPos and UpdateNormalAndDepth
+    template <class KeyFrameT, class MapPointT, class MapT>
+    static void ScatterLocalBundleAdjustment(const LbaProblem<KeyFrameT, MapPointT> &P, MapT *pMap)
+    {
+        std::vector<std::pair<KeyFrameT *, MapPointT *>> vToErase;
+        for (int pass = 0; pass < 2; pass++)                                // the monocular edges first, then the stereo ones (:715-743)
+            for (size_t p = 0; p < P.points.size(); p++) {
+                if (P.points[p]->isBad()) continue;
+                for (int32_t e = P.edgeOff[p]; e < P.edgeOff[p + 1]; e++)
+                    if (P.erase[e] && (P.uRight[e] < 0) == (pass == 0)) vToErase.push_back(std::make_pair(P.edgeKF[e], P.points[p]));
+            }
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);           // :746
+        for (size_t i = 0; i < vToErase.size(); i++) {                      // :748-757
+            vToErase[i].first->EraseMapPointMatch(vToErase[i].second);
+            vToErase[i].second->EraseObservation(vToErase[i].first);
+        }
+        for (size_t k = 0; k < P.local.size(); k++) {                       // :762-768
+            auto T = P.local[k]->GetPose().clone();
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++) T.template at<float>(r, c) = P.TcwLocal[16 * k + 4 * r + c];
+            P.local[k]->SetPose(T);
+        }
+        for (size_t p = 0; p < P.points.size(); p++) {                      // :771-777
+            auto X = P.points[p]->GetWorldPos().clone();
+            for (int r = 0; r < 3; r++) X.template at<float>(r) = P.xw[3 * p + r];
+            P.points[p]->SetWorldPos(X);
+            P.points[p]->UpdateNormalAndDepth();
+        }
+    }
+    // The reference's signature, so src/LocalMapping.cc:82 compiles unchanged; on the host (orbp_local_bundle_adjustment): which
+    // path is faster at which size is in README and INTEGRATION.md 3p.  pbStopFlag is read while the solver runs, as g2o reads it.
+    template <class KeyFrameT, class MapT>
+    static void LocalBundleAdjustment(KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap)
+    {
+        (void)LocalBundleAdjustment(static_cast<orbm_matcher *>(nullptr), pKF, pbStopFlag, pMap);
+    }
+    // The same through orbm_local_bundle_adjustment on the matcher's handle (NULL: the host path).  Returns ORBP_LBA_DONE,
+    // ORBP_LBA_STOPPED (:655-657: nothing is written back) or the ORBX status; on failure nothing is changed and *err receives the text.
+    template <class KeyFrameT, class MapT>
+    static int LocalBundleAdjustment(orbm_matcher *matcher, KeyFrameT *pKF, bool *pbStopFlag, MapT *pMap, std::string *err = nullptr,
+                                     orbp_lba_stats *stats = nullptr)
+    {
+        typedef typename std::remove_pointer<typename std::decay<decltype(pKF->GetMapPointMatches()[0])>::type>::type MapPointT;
+        static_assert(sizeof(bool) == 1, "pbStopFlag is read as a byte");
+        LbaProblem<KeyFrameT, MapPointT> P;
+        GatherLocalBundleAdjustment(pKF, P);
+        const orbp_lba_problem flat = P.flat();
+        const volatile uint8_t *stop = reinterpret_cast<const volatile uint8_t *>(pbStopFlag);
+        const int rc = matcher ? orbm_local_bundle_adjustment(matcher, &flat, P.TcwLocal.data(), P.xw.data(), P.erase.data(), stop, &P.stats)
+                               : orbp_local_bundle_adjustment(&flat, P.TcwLocal.data(), P.xw.data(), P.erase.data(), stop, &P.stats);
+        if (rc < 0) { if (err) *err = matcher ? orbm_last_error() : orbp_last_error(); return rc; }
+        if (stats) *stats = P.stats;
+        if (rc == ORBP_LBA_DONE) ScatterLocalBundleAdjustment(P, pMap);
+        return rc;
     }
 
 private:
