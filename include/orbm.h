@@ -995,6 +995,47 @@ int orbm_local_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_pr
                                        const volatile uint8_t *stop, struct orbp_lba_stats *stats, double *split_ms,
                                        int32_t *split_count);
 
+/*
+ * ---- A dense symmetric positive definite solve in fp64 over many workgroups (csrc/orbm_spd.hip) ----
+ * A x = b for the symmetric positive definite n x n A (row-major; its lower triangle is read), by a blocked Cholesky
+ * factorisation: panels of 48 columns, each a diagonal-block launch of one workgroup, a panel solve over row tiles and a
+ * trailing update over the tiles of the lower triangle, then both substitutions panel by panel: 5 ceil(n / 48) - 2 launches in
+ * stream order.  No cooperative launch, no grid-wide barrier, no spin-wait, nothing between workgroups but kernel boundaries,
+ * no atomic; every loop is bounded by n; x is a function of (A, b) alone.  This is the host-array entry, for tests and
+ * measurements: it uploads into the bundle adjustment workspace of the handle, runs the device routine that
+ * orbm_bundle_adjustment runs on its reduced system, and downloads.  *ok = 1, or 0 where a pivot was not positive or not finite:
+ * x is then all zeros and the call still returns ORBX_OK (the later launches of the solve see the device flag and return at
+ * once; nothing traps and nothing is read back between the panels).
+ * ORBX_E_INVALID on a NULL argument or n < 1, ORBX_E_CAPACITY beyond ORBM_SPD_MAX_N.
+ */
+#define ORBM_SPD_MAX_N 3072
+int orbm_spd_solve_f64(orbm_matcher *m, const double *A, const double *b, int n, double *x, int *ok);
+
+/*
+ * ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (src/Optimizer.cc:41-237) on the GPU ----
+ * The problem, arguments, semantics and return codes of orbp_bundle_adjustment (include/orbp.h), whose argument checks run
+ * first and need no handle.  It is the driver of orbm_local_bundle_adjustment over the same launches, with the call's robust
+ * kernel, one optimize(n_iterations), and the solve above in place of the one-workgroup k_lba_solve: per iteration k_lba_errors /
+ * k_lba_linearize, k_lba_reduce_points, k_lba_reduce_kfs; per trial k_lba_dinv, k_lba_schur, the solve, k_lba_update,
+ * k_lba_errors, k_lba_reduce_out and its 64-byte read-back, where `stop` is read; at the end k_lba_output.  One upload, one
+ * download.  Results agree with the host path's within the bar of tests/golden/ba/tolerance.json, counts are identical away from
+ * the decision boundaries, and a second run gives the same bytes.
+ *
+ * ORBX_E_CAPACITY, decided from the counts before any allocation or launch: beyond ORBM_BA_MAX_KFS local key frames (the dense
+ * reduced system is then 75 MB) or beyond ORBM_BA_MAX_TABLE entries of the n_local x n_points table of edge indices.  Larger
+ * maps need a sparse reduced system, which is not built here.
+ * orbm_bundle_adjustment_split is the same call measured as orbm_local_bundle_adjustment_split measures: the groups are the
+ * ORBM_LBA_SPLIT_* above, ORBM_LBA_SPLIT_SOLVE holding every launch of the many-workgroup solve.
+ */
+#define ORBM_BA_MAX_KFS 512
+#define ORBM_BA_MAX_TABLE (1 << 26)
+struct orbp_ba_stats;
+int orbm_bundle_adjustment(orbm_matcher *m, const struct orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local, float *xw,
+                           const volatile uint8_t *stop, struct orbp_ba_stats *stats);
+int orbm_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local,
+                                 float *xw, const volatile uint8_t *stop, struct orbp_ba_stats *stats, double *split_ms,
+                                 int32_t *split_count);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

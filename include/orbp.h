@@ -310,6 +310,44 @@ typedef struct orbp_lba_stats {
 enum { ORBP_LBA_DONE = 0, ORBP_LBA_STOPPED = 1 };
 int orbp_local_bundle_adjustment(const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase,
                                  const volatile uint8_t *stop, orbp_lba_stats *stats);
+
+/*
+ * ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (src/Optimizer.cc:41-237) ----
+ * The calls at src/Tracking.cc:695 (CreateInitialMapMonocular, 20 iterations) and src/LoopClosing.cc:651
+ * (RunGlobalBundleAdjustment, 10 iterations, not robust).  The same vertices, edges, Schur complement and Levenberg loop as
+ * LocalBundleAdjustment above (csrc/orbp_lba_body.h, which orbm_bundle_adjustment of include/orbm.h runs as well), under a
+ * different graph walk.  This host path keeps the reduced system dense (Cholesky of 6K x 6K, time growing with (6K)^3): it is
+ * meant for the initial map and for machines without a GPU.  Parity with g2o itself is unpinned, as above.
+ *
+ * The problem is an orbp_lba_problem gathered as :71-184 walks:
+ *   the "local" key frames are the non-bad vpKFs in order (:71-83), local_fixed[i] != 0 for mnId == 0 (:79); n_fixed is
+ *   normally 0 and stays legal (key frames that only constrain points);
+ *   the points are the non-bad vpMP in order (:89-99);
+ *   a point's edges in the order GetObservations() iterates (:105), skipping bad key frames and mnId > maxKFid (:109).
+ * Outputs: Tcw_local = Converter::toCvMat(SE3Quat) of every local key frame (:199-209), xw (in = GetWorldPos(), out = :222-233).
+ *
+ * Kept from the reference:
+ *   one round: optimize(n_iterations) (:187-188) is all; no level-1 pass, no second round, no erase list;
+ *   robust != 0: RobustKernelHuber with sqrt(5.99) / sqrt(7.815) held as floats (:85-86; LocalBundleAdjustment has 5.991);
+ *     robust == 0: no kernel, rho is chi2 and the weight 1 (:129, :158);
+ *   stop (may be NULL) has no entry check (LocalBundleAdjustment has :655): it is read at the top of every iteration
+ *     (sparse_optimizer.cpp:376) and in the do ... while of the trial loop (optimization_algorithm_levenberg.cpp:149);
+ *   stop set before the first read: no iteration runs, the call returns 0, the poses come back after the toSE3Quat -> toCvMat
+ *     round trip and the points after float -> double -> float;
+ *   a point without edges (:175-179, vbNotIncludedMP) keeps its xw bits;
+ *   a key frame without edges keeps its round-tripped pose (its block of the reduced system is the identity);
+ *   n_iterations: 0 optimises nothing; above ORBP_BA_MAX_ITERATIONS -> ORBX_E_INVALID (the callers pass 20 and 10);
+ *   the fork's _nBad stop (optimization_algorithm_levenberg.cpp:154-161) applies.
+ * Returns 0, or ORBX_E_INVALID before any work on what orbp_local_bundle_adjustment refuses, a negative n_iterations or one
+ * above the bound.  stats (may be NULL): iterations run, Levenberg trials in them, _currentLambda and the active (robust) chi2.
+ */
+#define ORBP_BA_MAX_ITERATIONS 100
+typedef struct orbp_ba_stats {
+    int32_t iterations, trials;
+    double lambda, chi2;
+} orbp_ba_stats;
+int orbp_bundle_adjustment(const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local, float *xw,
+                           const volatile uint8_t *stop, orbp_ba_stats *stats);
 const char *orbp_last_error(void);
 
 #ifdef __cplusplus

@@ -230,6 +230,12 @@ def _bind_pose(L):
     L.orbp_local_bundle_adjustment.restype = L.orbm_local_bundle_adjustment.restype = C.c_int
     L.orbm_local_bundle_adjustment_split.argtypes = [vp] * 9
     L.orbm_local_bundle_adjustment_split.restype = C.c_int
+    L.orbp_bundle_adjustment.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.orbm_bundle_adjustment.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.orbm_bundle_adjustment_split.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.orbp_bundle_adjustment.restype = L.orbm_bundle_adjustment.restype = L.orbm_bundle_adjustment_split.restype = C.c_int
+    L.orbm_spd_solve_f64.argtypes = [vp, vp, vp, C.c_int, vp, ip]
+    L.orbm_spd_solve_f64.restype = C.c_int
     L.orbp_lba_set_stop_probe.argtypes = [vp, vp]
     L.orbp_lba_set_stop_probe.restype = None
     L.orbp_last_error.restype = C.c_char_p
@@ -996,6 +1002,27 @@ class ORBmatcher:
         if rc < 0:
             _mchk(rc)
         return rc, Tcw, xw, erase, stats
+
+    def bundle_adjustment(self, problem, n_iterations=5, robust=True, stop=None):
+        """Optimizer::BundleAdjustment (src/Optimizer.cc:49-237) on the GPU: the problem, arguments and results of
+        BundleAdjustment(), through orbm_bundle_adjustment (the reduced system goes to the many-workgroup solve of spd_solve)."""
+        rc, Tcw, xw, stats = _ba_call(lambda *args: self.L.orbm_bundle_adjustment(self.h, *args), problem, n_iterations, robust, stop)
+        if rc < 0:
+            _mchk(rc)
+        return rc, Tcw, xw, stats
+
+    def spd_solve(self, A, b):
+        """orbm_spd_solve_f64: A x = b for a symmetric positive definite float64 [n, n] A (its lower triangle is read) by the
+        blocked Cholesky of csrc/orbm_spd.hip -> (x float64 [n], ok bool).  ok False (a pivot not positive or not finite): x is
+        zeros."""
+        A = np.ascontiguousarray(A, np.float64)
+        b = np.ascontiguousarray(b, np.float64).reshape(-1)
+        if A.ndim != 2 or A.shape[0] != A.shape[1] or len(b) != A.shape[0]:
+            raise OrbxError(ORBX_E_INVALID, "spd_solve: A must be [n, n] and b [n]")
+        x = np.full(max(len(b), 1), np.nan)
+        ok = C.c_int(-1)
+        _mchk(self.L.orbm_spd_solve_f64(self.h, _p(A), _p(b), len(b), _p(x), C.byref(ok)))
+        return x[:len(b)], bool(ok.value)
 
     @staticmethod
     def pack_sim3_problems(problems):
@@ -2260,3 +2287,34 @@ def LocalBundleAdjustment(problem, stop=None):
     (a uint8 [1], as pbStopFlag) was set at entry: the outputs are then zeros and the input points."""
     rc, Tcw, xw, erase, stats = _lba_call(lib().orbp_local_bundle_adjustment, problem, stop)
     return _pchk(rc), Tcw, xw, erase, stats
+
+
+class BaStats(C.Structure):
+    """orbp_ba_stats (include/orbp.h)"""
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("lambda_", C.c_double), ("chi2", C.c_double)]
+
+    def as_dict(self):
+        return {"iterations": self.iterations, "trials": self.trials, "lambda": self.lambda_, "chi2": self.chi2}
+
+
+ORBP_BA_MAX_ITERATIONS = 100
+ORBM_BA_MAX_KFS, ORBM_BA_MAX_TABLE, ORBM_SPD_MAX_N = 512, 1 << 26, 3072
+
+
+def _ba_call(fn, problem, n_iterations, robust, stop):
+    s, a = pack_lba_problem(problem)
+    Tcw = np.zeros((max(s.n_local, 1), 4, 4), np.float32)
+    stats = BaStats()
+    stop_arr = None if stop is None else np.ascontiguousarray(stop, np.uint8).reshape(1)
+    rc = fn(C.byref(s), int(n_iterations), 1 if robust else 0, _p(Tcw), _p(a["xw"]), _p(stop_arr), C.byref(stats))
+    return rc, Tcw[:s.n_local], a["xw"], stats.as_dict()
+
+
+def BundleAdjustment(problem, n_iterations=5, robust=True, stop=None):
+    """Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (src/Optimizer.cc:41-237) on the host over a pack_lba_problem() dict
+    gathered as :71-184 walks (the non-bad key frames as the "local" ones, local_fixed for mnId == 0) -> (0, Tcw float32 [n_local, 4,
+    4], xw float32 [n_points, 3], stats dict: iterations, trials, lambda, chi2).  robust: Huber with sqrt(5.99) / sqrt(7.815), else no
+    kernel.  stop (a uint8 [1], as pbStopFlag) is read at every iteration's top and in the trial loop; there is no entry check.  The
+    reduced system is dense: the host path is meant for the initial map and for machines without a GPU."""
+    rc, Tcw, xw, stats = _ba_call(lib().orbp_bundle_adjustment, problem, n_iterations, robust, stop)
+    return _pchk(rc), Tcw, xw, stats

@@ -121,6 +121,9 @@ int orbm_ensure_partials(orbm_matcher *m, size_t need, hipStream_t s = nullptr);
 int orbm_ensure_dd(orbm_matcher *m, size_t need, hipStream_t s);                            // d_dd of `need` bytes
 int orbm_ensure_fuse(orbm_matcher *m, size_t need);                                         // d_fuse of `need` bytes
 int orbm_ensure_lba(orbm_matcher *m, size_t need);                                          // d_lba of `need` bytes, lba_pin of 64
+// orbm_spd.hip: A = L L^T in place in the lower triangle of the row-major n x n A, then L y = b and L^T x = y, all device memory;
+// A, b and y are overwritten.  flag: != 0 where a pivot failed (x is then zeros); ok_out (may be NULL): 1.0 / 0.0.  Enqueues only.
+int orbm_spd_solve_device(double *A, double *b, double *y, double *x, int *flag, double *ok_out, int n, hipStream_t s);
 // orbm_grid.hip: k_grid_build_views, one workgroup per view: view v builds d_grids[v] from the keypoints d_kps + d_off[v]
 void orbm_grid_build_views_launch(const OrbmGrid *d_grids, const int32_t *d_off, const orbx_keypoint *d_kps, int nviews, hipStream_t s);
 // orbm_grid.hip: builds a grid slot (asynchronous on the handle's stream unless it had to allocate a staging block), and the

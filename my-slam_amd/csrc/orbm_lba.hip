@@ -8,7 +8,7 @@
 // order, then one download.  A trial is six launches and one 64-byte read-back (robust chi2, computeScale's sum, the solve's ok
 // flag), where the host takes g2o's decisions and reads `stop`.  There is no cooperative launch, no grid-wide barrier, no spin-wait,
 // no communication between workgroups other than kernel boundaries and no floating-point atomic; every kernel loop is bounded by
-// the problem's counts and the host loop by 15 iterations x 10 trials.
+// the problem's counts and the host loop by the iterations asked for x 10 trials.
 //
 // Sums (all in fixed orders, so the result is a function of the problem alone):
 //   a point's Hll, b_l and its back-substitution     one thread per point, its edges in ascending order (the host's order)
@@ -24,6 +24,10 @@
 //                                                    the butterfly inside a wave, then the 16 wave totals pairwise (8, 4, 2, 1)
 // The dense solve: one workgroup of 256 threads factors S = L L^T in place in the workspace, right-looking over 6-wide block
 // columns, then substitutes forwards and backwards; a pivot that is not positive or not finite clears the ok flag and the update.
+//
+// orbm_bundle_adjustment (Optimizer::BundleAdjustment, src/Optimizer.cc:49-237) is the same driver over the same launches: one
+// optimize(n_iterations) with the call's robust kernel, no flagging pass, and the reduced system handed to the many-workgroup solve
+// of orbm_spd.hip instead of k_lba_solve.
 #include "orbm_hyp.h"
 #include "orbp_internal.h"
 #include "orbp_lba_body.h"
@@ -112,7 +116,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_errors(LbaDev d, int b, int robus
     lba_edge_error(load_se3(d.est[b] + 7 * (long long)k), load_cam(d.cam + 5 * (long long)k), d.X[b] + 3 * (long long)d.edge_pt[e],
                    d.obs + 2 * e, d.u_right[e], pc, err);
     d.err[3 * e] = err[0]; d.err[3 * e + 1] = err[1]; d.err[3 * e + 2] = err[2];
-    d.chi_e[e] = lba_edge_robust_chi2(err, (double)d.inv_sigma2[e], !(d.u_right[e] < 0), robust != 0);
+    d.chi_e[e] = lba_edge_robust_chi2(err, (double)d.inv_sigma2[e], !(d.u_right[e] < 0), robust);
 }
 // linearizeOplus + constructQuadraticForm of every active edge
 __global__ __launch_bounds__(LBA_T) void k_lba_linearize(LbaDev d, int b, int robust)
@@ -123,7 +127,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_linearize(LbaDev d, int b, int ro
     const double err[3] = {d.err[3 * e], d.err[3 * e + 1], d.err[3 * e + 2]};
     double blk[LBA_NBLK];
     lba_edge_blocks(load_se3(d.est[b] + 7 * (long long)k), load_cam(d.cam + 5 * (long long)k), d.X[b] + 3 * (long long)d.edge_pt[e], err,
-                    (double)d.inv_sigma2[e], !(d.u_right[e] < 0), robust != 0, kf_is_free(d, k), blk);
+                    (double)d.inv_sigma2[e], !(d.u_right[e] < 0), robust, kf_is_free(d, k), blk);
     double *o = d.blk + LBA_NBLK * e;
 #pragma unroll
     for (int i = 0; i < LBA_NBLK; i++) o[i] = blk[i];
@@ -490,8 +494,10 @@ struct LbaGpu {
     LbaDev d;
     hipStream_t s;
     const volatile uint8_t *stop_flag;
-    int cur = 0, robust = 1, status = ORBX_OK;
+    int cur = 0, robust = LBA_KERNEL_LBA, status = ORBX_OK;
     double *pin;
+    double *spd_y = nullptr;                // orbm_bundle_adjustment: the reduced system goes to orbm_spd_solve_device (orbm_spd.hip),
+    int *spd_flag = nullptr;                // whose ok flag lands where k_lba_solve writes its own
     LbaProf prof;
 
     bool stop() const { return status != ORBX_OK || orbp_lba_read_stop(stop_flag); }
@@ -537,7 +543,10 @@ struct LbaGpu {
     {
         LBA_GROUP(prof, ORBM_LBA_SPLIT_DINV, s, hipLaunchKernelGGL(k_lba_dinv, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d, lambda));
         if (d.K) LBA_GROUP(prof, ORBM_LBA_SPLIT_SCHUR, s, hipLaunchKernelGGL(k_lba_schur, dim3(d.K, d.K), dim3(64), 0, s, d, lambda));
-        LBA_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_T), 0, s, d));
+        if (spd_y && d.n > 0)
+            LBA_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, MTRY(orbm_spd_solve_device(d.S, d.bs, spd_y, d.xp, spd_flag, d.out + OUT_OK, d.n, s)));
+        else                                // without unknowns k_lba_solve only sets the ok flag
+            LBA_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_T), 0, s, d));
         LBA_GROUP(prof, ORBM_LBA_SPLIT_UPDATE, s, hipLaunchKernelGGL(k_lba_update, dim3(blocks_for(std::max(d.P, d.NK))), dim3(LBA_T), 0, s, d, cur, lambda));
         LBA_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, 1 - cur, robust));
         MHIPCHK(hipGetLastError());
@@ -554,18 +563,29 @@ struct LbaGpu {
 }   // namespace
 
 namespace {
+// what orbm_bundle_adjustment asks of the common driver (NULL: LocalBundleAdjustment)
+struct BaArgs { int n_iterations, robust; orbp_ba_stats *stats; };
+
 int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase, const volatile uint8_t *stop,
-            orbp_lba_stats *stats, double *split_ms, int32_t *split_count)
+            orbp_lba_stats *stats, double *split_ms, int32_t *split_count, const BaArgs *ba = nullptr)
 {
     char text[200];
-    if (orbp_lba_check(p, Tcw_local, xw, erase, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
-    if (orbp_lba_read_stop(stop)) return ORBP_LBA_STOPPED;      // :655-657: nothing is launched
+    if (ba) {                                                   // no entry check of `stop` (src/Optimizer.cc:49-188 has none)
+        if (orbp_ba_check(p, ba->n_iterations, Tcw_local, xw, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
+    } else {
+        if (orbp_lba_check(p, Tcw_local, xw, erase, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
+        if (orbp_lba_read_stop(stop)) return ORBP_LBA_STOPPED;      // :655-657: nothing is launched
+    }
+    const int K = p->n_local, NK = p->n_local + p->n_fixed, P = p->n_points, E = p->edge_off[P];
+    // decided from the counts, before the handle is touched
+    if (ba && (K > ORBM_BA_MAX_KFS || (long long)K * P > ORBM_BA_MAX_TABLE))
+        return mfail(ORBX_E_CAPACITY, "bundle_adjustment: beyond %d key frames / %d entries of the key frame x point table", ORBM_BA_MAX_KFS,
+                     ORBM_BA_MAX_TABLE);
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
-    const int K = p->n_local, NK = p->n_local + p->n_fixed, P = p->n_points, E = p->edge_off[P];
     // k_lba_solve is one workgroup: its time grows with the cube of 6 K and a call runs it up to 150 times (DESIGN.md section 22
     // has the time at the cap)
-    if ((long long)K * P > (1ll << 28) || K > ORBM_LBA_MAX_LOCAL)
+    if (!ba && ((long long)K * P > (1ll << 28) || K > ORBM_LBA_MAX_LOCAL))
         return mfail(ORBX_E_CAPACITY, "request beyond %d local key frames / 2^28 table entries", ORBM_LBA_MAX_LOCAL);
     // CSR by local key frame, edges ascending
     std::vector<int32_t> kf_off((size_t)K + 1, 0), kf_edge;
@@ -592,6 +612,7 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
                  o_res = take(64 * (size_t)K + 12 * (size_t)P + (size_t)E),       // the results back to back: one copy home
                  o_ept = take(4 * (size_t)E), o_table = take(4 * (size_t)K * P), o_level = take((size_t)E),
                  o_ka = take((size_t)K), o_pa = take((size_t)P);
+    const size_t o_spd_y = ba ? take(szd * n) : 0, o_spd_flag = ba ? take(64) : 0;
     MTRY(orbm_ensure_lba(m, need));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
@@ -620,6 +641,7 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
     d.inv_sigma2 = in.at<float>(pi); d.kf_off = in.dev_at<int32_t>(pko); d.kf_edge = in.at<int32_t>(pke);
 
     g.m = m; g.d = d; g.s = s; g.stop_flag = stop; g.pin = (double *)m->lba_pin.get();
+    if (ba) { g.spd_y = (double *)(w + o_spd_y); g.spd_flag = (int *)(w + o_spd_flag); }
     g.prof.pre(s);
     if ((size_t)K * P) MHIPCHK(hipMemsetAsync(d.table, 0xFF, 4 * (size_t)K * P, s));
     MHIPCHK(hipMemsetAsync(d.out, 0, 64, s));
@@ -627,10 +649,30 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
     MHIPCHK(hipGetLastError());
     g.prof.post(ORBM_LBA_SPLIT_SETUP, s);
 
-    orbp_lba_stats st;
-    memset(&st, 0, sizeof st);
     LbaRun run = {0, 0, 0, 0};
     int n_active = 0, n_level1 = 0;
+    if (ba) {                                                   // src/Optimizer.cc:187-235
+        g.robust = ba->robust ? LBA_KERNEL_BA : LBA_KERNEL_NONE;
+        MTRY(g.activate(n_active, n_level1));                   // :187
+        if (n_active > 0) {
+            lba_optimize(g, ba->n_iterations, run);             // :188
+            MTRY(g.status);
+        }
+        LBA_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s,        // a point without edges keeps its bits: float -> double -> float
+                  hipLaunchKernelGGL(k_lba_output, dim3(blocks_for(std::max(K, P))), dim3(LBA_T), 0, s, d, g.cur));
+        MHIPCHK(hipGetLastError());
+        void *const host[2] = {Tcw_local, xw};
+        const size_t parts[2] = {64 * (size_t)K, 12 * (size_t)P};
+        g.prof.pre(s);
+        MTRY(orbm_d2h_split(m, host, parts, 2, d.out_Tcw, s));
+        g.prof.post(ORBM_LBA_SPLIT_DOWNLOAD, s);
+        MTRY(orbm_sync(m, s));
+        g.prof.drain();
+        if (ba->stats) *ba->stats = {run.iterations, run.trials, run.lambda, run.chi2};
+        return ORBX_OK;
+    }
+    orbp_lba_stats st;
+    memset(&st, 0, sizeof st);
     MTRY(g.activate(n_active, n_level1));                       // :659
     if (n_active > 0) {
         lba_optimize(g, 5, run);                                // :660
@@ -640,7 +682,7 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
     if (!orbp_lba_read_stop(stop)) {                            // :662-709
         st.second_round = 1;
         LBA_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s, hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 0));
-        g.robust = 0;
+        g.robust = LBA_KERNEL_NONE;
         MTRY(g.activate(n_active, n_level1));                   // :706
         st.n_level1 = n_level1;
         if (n_active > 0) {
@@ -676,4 +718,21 @@ extern "C" int orbm_local_bundle_adjustment_split(orbm_matcher *m, const orbp_lb
 {
     if (!split_ms || !split_count) return mfail(ORBX_E_INVALID, "local_bundle_adjustment_split: NULL split_ms or split_count");
     return lba_run(m, p, Tcw_local, xw, erase, stop, stats, split_ms, split_count);
+}
+
+// Optimizer::BundleAdjustment (src/Optimizer.cc:49-237): the driver above with one optimize(n_iterations), the call's robust kernel
+// and the many-workgroup solve of orbm_spd.hip in place of k_lba_solve
+extern "C" int orbm_bundle_adjustment(orbm_matcher *m, const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local, float *xw,
+                                      const volatile uint8_t *stop, orbp_ba_stats *stats)
+{
+    const BaArgs ba = {n_iterations, robust, stats};
+    return lba_run(m, p, Tcw_local, xw, nullptr, stop, nullptr, nullptr, nullptr, &ba);
+}
+extern "C" int orbm_bundle_adjustment_split(orbm_matcher *m, const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local,
+                                            float *xw, const volatile uint8_t *stop, orbp_ba_stats *stats, double *split_ms,
+                                            int32_t *split_count)
+{
+    if (!split_ms || !split_count) return mfail(ORBX_E_INVALID, "bundle_adjustment_split: NULL split_ms or split_count");
+    const BaArgs ba = {n_iterations, robust, stats};
+    return lba_run(m, p, Tcw_local, xw, nullptr, stop, nullptr, split_ms, split_count, &ba);
 }

@@ -20,3 +20,7 @@ __attribute__((visibility("hidden"))) int orbp_lba_check(const orbp_lba_problem 
 #include <stdint.h>
 __attribute__((visibility("hidden"))) bool orbp_lba_read_stop(const volatile uint8_t *stop);
 extern "C" void orbp_lba_set_stop_probe(void (*fn)(void *), void *arg);
+// orbp_ba.cc: the argument checks of orbp_bundle_adjustment, shared with orbm_bundle_adjustment (orbm_lba.hip): those of
+// orbp_lba_check and the bound of n_iterations.
+__attribute__((visibility("hidden"))) int orbp_ba_check(const orbp_lba_problem *p, int n_iterations, const float *Tcw_local,
+                                                        const float *xw, char *text, int text_size);

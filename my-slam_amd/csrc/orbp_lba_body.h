@@ -54,7 +54,9 @@ struct LbaCam { double fx, fy, cx, cy, bf; };
 #define LBA_HLL 27              // 6
 #define LBA_BL 33               // 3
 #define LBA_HPL 36              // 18
-#define LBA_MAX_ITERATIONS 15   // optimize(5) + optimize(10)
+// the bound of lba_optimize's loop over iterations: LocalBundleAdjustment asks for 5 and 10, BundleAdjustment for up to
+// ORBP_BA_MAX_ITERATIONS (include/orbp.h, the same number); the loop runs min(iterations, this) of them
+#define LBA_MAX_ITERATIONS 100
 #define LBA_MAX_TRIALS 10       // _maxTrialsAfterFailure
 
 // Eigen's Quaterniond(Matrix3d), the branch on the largest diagonal entry written out per case (orbp_sim3opt_body.h s3o_quat_from_R)
@@ -205,7 +207,15 @@ LBA_HD bool lba_depth_positive(const LbaSe3 &T, const double *xw)
     lba_map(T, xw, pc);
     return pc[2] > 0.0;
 }
-LBA_HD double lba_huber_delta(bool stereo) { return stereo ? (double)(float)sqrt(7.815) : (double)(float)sqrt(5.991); }   // :569-570
+// An edge's robust kernel: none, RobustKernelHuber with LocalBundleAdjustment's deltas (sqrt(5.991) / sqrt(7.815) held as floats,
+// :569-570) or with BundleAdjustment's (sqrt(5.99) / sqrt(7.815), :85-86)
+#define LBA_KERNEL_NONE 0
+#define LBA_KERNEL_LBA 1
+#define LBA_KERNEL_BA 2
+LBA_HD double lba_huber_delta(bool stereo, int kernel)
+{
+    return stereo ? (double)(float)sqrt(7.815) : kernel == LBA_KERNEL_BA ? (double)(float)sqrt(5.99) : (double)(float)sqrt(5.991);
+}
 LBA_HD double lba_chi2_threshold(bool stereo) { return stereo ? 7.815 : 5.991; }                                           // :680, :696
 LBA_HD void lba_huber(double c2, double delta, double &rho0, double &rho1)      // robust_kernel_impl.cpp:78-91
 {
@@ -214,19 +224,19 @@ LBA_HD void lba_huber(double c2, double delta, double &rho0, double &rho1)      
     else { const double s = sqrt(c2); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
 }
 // an active edge's term of activeRobustChi2 (sparse_optimizer.cpp:100-117)
-LBA_HD double lba_edge_robust_chi2(const double *err, double info, bool stereo, bool robust)
+LBA_HD double lba_edge_robust_chi2(const double *err, double info, bool stereo, int robust)
 {
     const double c2 = lba_chi2(err, info);
     if (!robust) return c2;
     double rho0, rho1;
-    lba_huber(c2, lba_huber_delta(stereo), rho0, rho1);
+    lba_huber(c2, lba_huber_delta(stereo, robust), rho0, rho1);
     return rho0;
 }
 
 // linearizeOplus + constructQuadraticForm of one edge at T and xw, with the stored error err: blk[LBA_NBLK].  The point part is
 // always formed (a point is never fixed); the pose part and Hpl only for a free key frame (else they are zero).  A monocular edge
-// carries a zero third row, so both kinds add three terms.
-LBA_HD void lba_edge_blocks(const LbaSe3 &T, const LbaCam &c, const double *xw, const double *err, double info, bool stereo, bool robust,
+// carries a zero third row, so both kinds add three terms.  robust is an LBA_KERNEL_*.
+LBA_HD void lba_edge_blocks(const LbaSe3 &T, const LbaCam &c, const double *xw, const double *err, double info, bool stereo, int robust,
                             bool kf_free, double *blk)
 {
     double pc[3], R[9], A[3][3], B[3][6];
@@ -262,7 +272,7 @@ LBA_HD void lba_edge_blocks(const LbaSe3 &T, const LbaCam &c, const double *xw, 
     double w = 1.;
     if (robust) {
         double rho0;
-        lba_huber(lba_chi2(err, info), lba_huber_delta(stereo), rho0, w);
+        lba_huber(lba_chi2(err, info), lba_huber_delta(stereo, robust), rho0, w);
     }
     const double wi = w * info;                              // weightedOmega = rho' * Omega
     const double r0 = -(info * err[0]) * w, r1 = -(info * err[1]) * w, r2 = -(info * err[2]) * w;      // omega_r (*= rho')

@@ -479,6 +479,150 @@ public:
         return rc;
     }
 
+    // ---- Optimizer::BundleAdjustment / GlobalBundleAdjustemnt (include/Optimizer.h:40-44, src/Optimizer.cc:41-237;
+    // Tracking::CreateInitialMapMonocular, src/Tracking.cc:695; LoopClosing::RunGlobalBundleAdjustment, src/LoopClosing.cc:651) ----
+    // The flat problem of orbp_bundle_adjustment (include/orbp.h) and the objects its rows stand for.
+    template <class KeyFrameT, class MapPointT>
+    struct BaProblem {
+        std::vector<KeyFrameT *> kfs;                       // the non-bad vpKFs: the vertices
+        std::vector<MapPointT *> points;                    // the non-bad vpMP
+        std::vector<uint8_t> included;                      // per point: !vbNotIncludedMP (nEdges > 0, :175-183)
+        std::vector<uint8_t> localFixed;
+        std::vector<float> Tcw, cam, xw, obs, uRight, invSigma2;
+        std::vector<int32_t> edgeOff, edgeKf;
+        std::vector<float> TcwOut;
+        orbp_ba_stats stats{};
+        orbp_lba_problem flat() const
+        {
+            return {(int32_t)kfs.size(), 0, (int32_t)points.size(), localFixed.data(), Tcw.data(), cam.data(), edgeOff.data(), edgeKf.data(),
+                    obs.data(), uRight.data(), invSigma2.data()};
+        }
+    };
+    // The walk of :71-184.  An observation counts towards nEdges unless its key frame is bad or has mnId > maxKFid (:109-112); it
+    // becomes an edge only where that key frame is among the vertices (g2o's addEdge refuses an edge with a missing vertex).
+    template <class KeyFrameT, class MapPointT>
+    static void GatherBundleAdjustment(const std::vector<KeyFrameT *> &vpKFs, const std::vector<MapPointT *> &vpMP, BaProblem<KeyFrameT, MapPointT> &P)
+    {
+        P = BaProblem<KeyFrameT, MapPointT>();
+        std::map<KeyFrameT *, int32_t> index;               // optimizer.vertex(pKF->mnId)
+        long unsigned int maxKFid = 0;
+        for (size_t i = 0; i < vpKFs.size(); i++) {         // :71-83
+            KeyFrameT *pKF = vpKFs[i];
+            if (pKF->isBad()) continue;
+            index[pKF] = (int32_t)P.kfs.size();
+            P.kfs.push_back(pKF);
+            const auto T = pKF->GetPose();
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++) P.Tcw.push_back(T.template at<float>(r, c));
+            P.cam.push_back(pKF->fx); P.cam.push_back(pKF->fy); P.cam.push_back(pKF->cx); P.cam.push_back(pKF->cy); P.cam.push_back(pKF->mbf);
+            P.localFixed.push_back(pKF->mnId == 0 ? 1 : 0);
+            if (pKF->mnId > maxKFid) maxKFid = pKF->mnId;
+        }
+        P.edgeOff.push_back(0);
+        for (size_t i = 0; i < vpMP.size(); i++) {          // :89-184
+            MapPointT *pMP = vpMP[i];
+            if (pMP->isBad()) continue;
+            P.points.push_back(pMP);
+            const auto X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; r++) P.xw.push_back(X.template at<float>(r));
+            const auto observations = pMP->GetObservations();
+            int nEdges = 0;
+            for (auto mit = observations.begin(); mit != observations.end(); mit++) {
+                KeyFrameT *pKF = mit->first;
+                if (pKF->isBad() || pKF->mnId > maxKFid) continue;
+                nEdges++;
+                const auto it = index.find(pKF);
+                if (it == index.end()) continue;
+                const auto &kpUn = pKF->mvKeysUn[mit->second];
+                P.edgeKf.push_back(it->second);
+                P.obs.push_back(kpUn.pt.x); P.obs.push_back(kpUn.pt.y);
+                const float ur = pKF->mvuRight[mit->second];
+                P.uRight.push_back(ur < 0 ? -1.f : ur);     // :116
+                P.invSigma2.push_back(pKF->mvInvLevelSigma2[kpUn.octave]);
+            }
+            P.included.push_back(nEdges > 0 ? 1 : 0);
+            P.edgeOff.push_back((int32_t)P.edgeKf.size());
+        }
+        P.TcwOut.assign(16 * P.kfs.size() + 1, 0.f);
+        P.Tcw.push_back(0.f); P.cam.push_back(0.f); P.xw.push_back(0.f); P.obs.push_back(0.f); P.uRight.push_back(0.f);       // never NULL
+        P.invSigma2.push_back(0.f); P.edgeKf.push_back(0); P.localFixed.push_back(0);
+    }
+    // :190-235: SetPose / SetWorldPos + UpdateNormalAndDepth when nLoopKF == 0, else mTcwGBA / mPosGBA and mnBAGlobalForKF.  Key
+    // frames and points that turned bad during the solve are skipped, as :196 and :220 skip them.
+    template <class KeyFrameT, class MapPointT>
+    static void ScatterBundleAdjustment(const BaProblem<KeyFrameT, MapPointT> &P, const unsigned long nLoopKF)
+    {
+        for (size_t k = 0; k < P.kfs.size(); k++) {
+            KeyFrameT *pKF = P.kfs[k];
+            if (pKF->isBad()) continue;
+            auto T = pKF->GetPose().clone();
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++) T.template at<float>(r, c) = P.TcwOut[16 * k + 4 * r + c];
+            if (nLoopKF == 0) pKF->SetPose(T);
+            else {
+                pKF->mTcwGBA = T;                               // :206-207: a 4 x 4 CV_32F matrix of its own (T is a clone)
+                pKF->mnBAGlobalForKF = nLoopKF;
+            }
+        }
+        for (size_t p = 0; p < P.points.size(); p++) {
+            if (!P.included[p]) continue;
+            MapPointT *pMP = P.points[p];
+            if (pMP->isBad()) continue;
+            auto X = pMP->GetWorldPos().clone();
+            for (int r = 0; r < 3; r++) X.template at<float>(r) = P.xw[3 * p + r];
+            if (nLoopKF == 0) {
+                pMP->SetWorldPos(X);
+                pMP->UpdateNormalAndDepth();
+            } else {
+                pMP->mPosGBA = X;                               // :231-232
+                pMP->mnBAGlobalForKF = nLoopKF;
+            }
+        }
+    }
+    // Through orbm_bundle_adjustment on the matcher's handle (NULL: the host path, orbp_bundle_adjustment).  Returns 0 or the ORBX
+    // status; on failure nothing is changed and *err receives the text.  Which path to call at which size: INTEGRATION.md 3q.
+    template <class KeyFrameT, class MapPointT>
+    static int BundleAdjustment(orbm_matcher *matcher, const std::vector<KeyFrameT *> &vpKFs, const std::vector<MapPointT *> &vpMP, std::string *err,
+                                int nIterations = 5, bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true,
+                                orbp_ba_stats *stats = nullptr)
+    {
+        static_assert(sizeof(bool) == 1, "pbStopFlag is read as a byte");
+        BaProblem<KeyFrameT, MapPointT> P;
+        GatherBundleAdjustment(vpKFs, vpMP, P);
+        const orbp_lba_problem flat = P.flat();
+        const volatile uint8_t *stop = reinterpret_cast<const volatile uint8_t *>(pbStopFlag);
+        const int rc = matcher ? orbm_bundle_adjustment(matcher, &flat, nIterations, bRobust ? 1 : 0, P.TcwOut.data(), P.xw.data(), stop, &P.stats)
+                               : orbp_bundle_adjustment(&flat, nIterations, bRobust ? 1 : 0, P.TcwOut.data(), P.xw.data(), stop, &P.stats);
+        if (rc < 0) { if (err) *err = matcher ? orbm_last_error() : orbp_last_error(); return rc; }
+        if (stats) *stats = P.stats;
+        ScatterBundleAdjustment(P, nLoopKF);
+        return rc;
+    }
+    template <class MapT>
+    static int GlobalBundleAdjustemnt(orbm_matcher *matcher, MapT *pMap, std::string *err, int nIterations = 5, bool *pbStopFlag = NULL,
+                                      const unsigned long nLoopKF = 0, const bool bRobust = true, orbp_ba_stats *stats = nullptr)
+    {
+        const auto vpKFs = pMap->GetAllKeyFrames();             // :43-45
+        const auto vpMP = pMap->GetAllMapPoints();
+        return BundleAdjustment(matcher, vpKFs, vpMP, err, nIterations, pbStopFlag, nLoopKF, bRobust, stats);
+    }
+    // The reference's signatures and defaults (include/Optimizer.h:40-44), so src/Tracking.cc:695 and src/LoopClosing.cc:651 compile
+    // unchanged; on the host.
+    template <class KeyFrameT, class MapPointT>
+    static void BundleAdjustment(const std::vector<KeyFrameT *> &vpKF, const std::vector<MapPointT *> &vpMP, int nIterations = 5,
+                                 bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0, const bool bRobust = true)
+    {
+        (void)BundleAdjustment(static_cast<orbm_matcher *>(nullptr), vpKF, vpMP, static_cast<std::string *>(nullptr), nIterations, pbStopFlag,
+                               nLoopKF, bRobust);
+    }
+    template <class MapT>
+    static void GlobalBundleAdjustemnt(MapT *pMap, int nIterations = 5, bool *pbStopFlag = NULL, const unsigned long nLoopKF = 0,
+                                       const bool bRobust = true)
+    {
+        (void)GlobalBundleAdjustemnt(static_cast<orbm_matcher *>(nullptr), pMap, static_cast<std::string *>(nullptr), nIterations, pbStopFlag,
+                                     nLoopKF, bRobust);
+    }
+
 private:
     // R*X+t as one cv::gemm evaluates it: three float products summed in float, the translation added in double (Sim3Solver.h)
     template <class MatT>

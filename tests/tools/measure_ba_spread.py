@@ -1,0 +1,60 @@
+#!/usr/bin/env python3
+"""Measures the tolerance of the BundleAdjustment tests and writes tests/golden/ba/tolerance.json.  CPU only.
+
+How far two correct implementations may end apart is measured, not derived: a point that keeps few active edges has a block the
+damping alone makes invertible, and the Levenberg factors depend on rho, so rounding differences are amplified by amounts that
+depend on the scene.  Over every case of tests/ba_cases.py the oracle (tests/ba_oracle.py) runs with its sums forward and in
+reverse, and the largest difference is taken separately for the entries of the pose rotations, the pose translations, the point
+coordinates (the cases whose scale is gauge left out) and the final chi2 (relative, every case).  The bar for product-against-oracle
+and for GPU-against-host is FACTOR = 4 times that spread, the factor and the reasoning of tests/tools/measure_lba_spread.py: it
+admits a third arithmetic variant of one algorithm and not a different trial transcript, which moves the result by orders of
+magnitude more.  The product hands poses and points back as floats; the tests add that rounding to the bar (ba_cases.assert_same).
+The spread is never measured against the code under test.
+
+    python tests/tools/measure_ba_spread.py            # writes the file
+    python tests/tools/measure_ba_spread.py --check     # recomputes and compares with the file"""
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(HERE))
+import ba_cases as lc  # noqa: E402
+
+FACTOR = 4
+OUT = os.path.join(os.path.dirname(HERE), "golden", "ba", "tolerance.json")
+
+
+def measure():
+    spread = [0.0] * 4
+    worst = [""] * 4
+    for name in lc.NAMES:
+        f, r = lc.oracle(name)
+        d = lc.diffs(f["Tcw"], f["xw"], f["stats"]["chi2"], r["Tcw"], r["xw"], r["stats"]["chi2"])
+        for j, x in enumerate(d):
+            if j < 3 and name in lc.GAUGE:
+                continue
+            if x > spread[j]:
+                spread[j], worst[j] = x, name
+    return {"what": "largest |forward - reverse| of tests/ba_oracle.py over tests/ba_cases.py",
+            "script": "tests/tools/measure_ba_spread.py", "cases": len(lc.NAMES), "factor": FACTOR,
+            "spread": dict(zip(lc.KEYS, spread)), "worst_case": dict(zip(lc.KEYS, worst)),
+            "bar": {k: FACTOR * s for k, s in zip(lc.KEYS, spread)}}
+
+
+if __name__ == "__main__":
+    got = measure()
+    if "--check" in sys.argv:
+        want = json.load(open(OUT))
+        # the oracle's Schur product and its solve go through BLAS / LAPACK, whose kernels and blocking follow the CPU they run on:
+        # the recomputed spread need not equal the file's last digits, but it must reproduce the recorded one within FACTOR both
+        # ways: at most the file's bar, and at least recorded / FACTOR, so that a file whose spread is too large fails as well
+        ok = (all(want["spread"][k] / FACTOR <= got["spread"][k] <= want["bar"][k] for k in got["spread"])
+              and all(want["bar"][k] == FACTOR * want["spread"][k] for k in got["spread"]) and want["factor"] == FACTOR)
+        print(json.dumps(got["spread"]), "matches the file" if ok else "DIFFERS from the file")
+        sys.exit(0 if ok else 1)
+    os.makedirs(os.path.dirname(OUT), exist_ok=True)
+    with open(OUT, "w") as f:
+        json.dump(got, f, indent=2)
+        f.write("\n")
+    print(json.dumps(got, indent=2))
