@@ -1036,6 +1036,42 @@ int orbm_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_problem 
                                  float *xw, const volatile uint8_t *stop, struct orbp_ba_stats *stats, double *split_ms,
                                  int32_t *split_count);
 
+/*
+ * ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044) on the GPU ----
+ * The problem, arguments, semantics and return codes of orbp_optimize_essential_graph (include/orbp.h), whose argument checks
+ * run first and need no handle.  Host and kernels run one text (csrc/orbp_eg_body.h); the host drives lba_optimize as
+ * orbm_bundle_adjustment does.  Once a call k_eg_measure (the edges' measurements); per iteration k_eg_linearize (the 29 error
+ * evaluations of an edge's numeric Jacobian over 29 threads), k_eg_diag and k_eg_offdiag (one wave per vertex / per vertex pair
+ * sums its blocks in edge order into the dense 7N x 7N H0: no atomics, every sum in a fixed order); per trial k_eg_stage
+ * (H0 + lambda I and b into the work matrix), the many-workgroup solve of orbm_spd_solve_f64, k_eg_update, k_eg_errors,
+ * k_eg_reduce_out and its 64-byte read-back; at the end k_eg_output and k_eg_points.  One upload, one download.  Results agree
+ * with the host path's within the bar of tests/golden/eg/tolerance.json and a second run gives the same bytes (DESIGN.md
+ * section 24).
+ *
+ * ORBX_E_CAPACITY, decided from the counts before any allocation or launch: beyond ORBM_EG_MAX_KFS key frames, which keeps the
+ * 7 x 438 = 3066 unknowns inside ORBM_SPD_MAX_N, the range the solve has been tested and measured in.  The host path has no cap.
+ * orbm_optimize_essential_graph_split is the same call with split_ms[g] = the device time of group g summed over the call and
+ * split_count[g] the number of times it ran (both ORBM_EG_SPLIT_N long), measured as orbm_local_bundle_adjustment_split measures.
+ */
+#define ORBM_EG_MAX_KFS 438
+enum {
+    ORBM_EG_SPLIT_UPLOAD = 0,           /* the one staged upload, the memsets, k_eg_measure */
+    ORBM_EG_SPLIT_LINEARIZE = 1,        /* k_eg_linearize */
+    ORBM_EG_SPLIT_ASSEMBLE = 2,         /* k_eg_diag, k_eg_offdiag */
+    ORBM_EG_SPLIT_STAGE = 3,            /* k_eg_stage */
+    ORBM_EG_SPLIT_SOLVE = 4,            /* every launch of the many-workgroup solve */
+    ORBM_EG_SPLIT_UPDATE_ERRORS = 5,    /* k_eg_update, k_eg_errors */
+    ORBM_EG_SPLIT_READ_BACK = 6,        /* k_eg_reduce_out and the 64-byte copy the host then waits for */
+    ORBM_EG_SPLIT_OUTPUT = 7,           /* k_eg_output, k_eg_points, the one copy of the results */
+    ORBM_EG_SPLIT_N = 8
+};
+struct orbp_eg_problem;
+struct orbp_eg_stats;
+int orbm_optimize_essential_graph(orbm_matcher *m, const struct orbp_eg_problem *p, int n_iterations, float *Tcw, float *xw,
+                                  double *Scw_out, struct orbp_eg_stats *stats);
+int orbm_optimize_essential_graph_split(orbm_matcher *m, const struct orbp_eg_problem *p, int n_iterations, float *Tcw, float *xw,
+                                        double *Scw_out, struct orbp_eg_stats *stats, double *split_ms, int32_t *split_count);
+
 /* Host helpers: ComputeThreeMaxima (ind[3], -1 = none) and the histogram cull over match12.
  * orbm_rot_filter returns the number of matches left in match12 (>= 0), or ORBX_E_INVALID (negative) when the rotation
  * difference of a match falls off the histogram -- a NaN angle, or angles far outside [0, 360); the reference asserts

@@ -348,6 +348,56 @@ typedef struct orbp_ba_stats {
 } orbp_ba_stats;
 int orbp_bundle_adjustment(const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local, float *xw,
                            const volatile uint8_t *stop, orbp_ba_stats *stats);
+
+/*
+ * ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044), LoopClosing::CorrectLoop's call at src/LoopClosing.cc:568 ----
+ * A pose graph: one VertexSim3Expmap per key frame, EdgeSim3 with identity information and no robust kernel between them, numeric
+ * Jacobians (delta = 1e-9), BlockSolver_7_3 on Hpp alone (no landmarks, no Schur complement) under OptimizationAlgorithmLevenberg
+ * with setUserLambdaInit(1e-16), so the first lambda is 1e-16 and not tau * maxdiag.  The g2o lines restated are listed in
+ * csrc/orbp_eg_body.h, the text the GPU call orbm_optimize_essential_graph (include/orbm.h) runs as well; the Levenberg loop is
+ * LocalBundleAdjustment's (csrc/orbp_lba_body.h).  Parity with g2o itself is unpinned (there is no Eigen to build it against).
+ *
+ * The problem is flat:
+ *   n_kfs key frames in g2o's hessianIndex order (mnId ascending); Scw[8 i ..] = vScw[i] (:818-832) and Snc[8 i ..] = the key
+ *   frame's NonCorrectedSim3 where it has one, else a copy of Scw, both in Sim3::operator[] order qx qy qz qw tx ty tz s;
+ *   fixed = the index of pLoopKF (:834), or -1; fix_scale = bFixScale (:839);
+ *   n_edges edges in insertion order (:852-983): vertex 0 is edge_i, vertex 1 is edge_j; edge_corrected[e] = 1 where the
+ *   measurement is Scw_j * Scw_i^-1 (the LoopConnections edges, :857-867), 0 where it is Snc_j * Snc_i^-1 (:889-972);
+ *   n_points points: xw (3 floats each, in = GetWorldPos()) and ref[p] = the index of the key frame of :1020-1029, or -1.
+ * Outputs: Tcw (16 floats per key frame) = [R | t / s] of the optimised Sim3 (:999-1009, the fixed key frame's too); xw =
+ * correctedSwr.map(Srw.map(P)) (:1032-1040) with Srw from the input Scw; Scw_out (may be NULL; 8 doubles per key frame) = the
+ * optimised Sim3; stats (may be NULL).
+ *
+ * Kept from the reference: optimize(n_iterations) (the reference passes 20) with the fork's _nBad stop; a quaternion is never
+ * normalised; under fix_scale the seventh update of every vertex is exactly zero and the scales keep their bits.
+ * Chosen here: a key frame without edges stays in the system (its pivot is lambda, its update exactly zero) where g2o leaves it
+ * out of the active set; a failed solve leaves the update zero.  Two deviations the adapter (host/PnPsolver.h) relies on: a bad
+ * key frame is not part of the problem, and neither is any edge that would touch it (the reference would dereference a null
+ * vertex); a point with ref = -1 (its reference key frame has no vertex) keeps its position's bits (the reference maps it through
+ * two identities).
+ * The linear solve is an envelope (skyline) Cholesky in fp64: row r of the 7N x 7N system is stored from its first structural
+ * nonzero column, and every sum runs in the order of the dense factorisation of csrc/orbp_lba_host.h, so the result is the dense
+ * one's bit for bit at the cost of the sum of the squared row widths.  There is no cap on n_kfs.
+ * Returns 0, or ORBX_E_INVALID before any work on: a NULL pointer, a negative count, n_iterations outside
+ * [0, ORBP_BA_MAX_ITERATIONS], fixed, an edge end or a ref out of range, edge_i == edge_j, a non-finite Sim3 or a scale <= 0.
+ */
+typedef struct orbp_eg_problem {
+    int32_t n_kfs;
+    const double *Scw, *Snc;            /* 8 * n_kfs each */
+    int32_t fixed, fix_scale;
+    int32_t n_edges;
+    const int32_t *edge_i, *edge_j;     /* per edge */
+    const uint8_t *edge_corrected;      /* per edge */
+    int32_t n_points;
+    const int32_t *ref;                 /* per point */
+} orbp_eg_problem;
+typedef struct orbp_eg_stats {
+    int32_t iterations, trials;         /* iterations run, Levenberg trials in them */
+    double lambda;                      /* _currentLambda */
+    double chi2_initial, chi2_final;    /* the active chi2 at the input estimates and at the output's */
+} orbp_eg_stats;
+int orbp_optimize_essential_graph(const orbp_eg_problem *p, int n_iterations, float *Tcw, float *xw, double *Scw_out,
+                                  orbp_eg_stats *stats);
 const char *orbp_last_error(void);
 
 #ifdef __cplusplus

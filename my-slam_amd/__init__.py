@@ -234,6 +234,13 @@ def _bind_pose(L):
     L.orbm_bundle_adjustment.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     L.orbm_bundle_adjustment_split.argtypes = [vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]
     L.orbp_bundle_adjustment.restype = L.orbm_bundle_adjustment.restype = L.orbm_bundle_adjustment_split.restype = C.c_int
+    L.orbp_optimize_essential_graph.argtypes = [vp, C.c_int, vp, vp, vp, vp]
+    L.orbm_optimize_essential_graph.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp]
+    L.orbm_optimize_essential_graph_split.argtypes = [vp, vp, C.c_int, vp, vp, vp, vp, vp, vp]
+    L.orbp_optimize_essential_graph.restype = L.orbm_optimize_essential_graph.restype = C.c_int
+    L.orbm_optimize_essential_graph_split.restype = C.c_int
+    L.orbp_eg_set_dense.argtypes = [C.c_int]
+    L.orbp_eg_set_dense.restype = None
     L.orbm_spd_solve_f64.argtypes = [vp, vp, vp, C.c_int, vp, ip]
     L.orbm_spd_solve_f64.restype = C.c_int
     L.orbp_lba_set_stop_probe.argtypes = [vp, vp]
@@ -1010,6 +1017,13 @@ class ORBmatcher:
         if rc < 0:
             _mchk(rc)
         return rc, Tcw, xw, stats
+
+    def optimize_essential_graph(self, problem, n_iterations=20):
+        """Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044) on the GPU: the problem, argument and results of
+        optimize_essential_graph(), through orbm_optimize_essential_graph (the 7N x 7N system goes to the solve of spd_solve)."""
+        rc, Tcw, xw, Scw, stats = _eg_call(lambda *args: self.L.orbm_optimize_essential_graph(self.h, *args), problem, n_iterations)
+        _mchk(rc)
+        return rc, Tcw, xw, Scw, stats
 
     def spd_solve(self, A, b):
         """orbm_spd_solve_f64: A x = b for a symmetric positive definite float64 [n, n] A (its lower triangle is read) by the
@@ -2318,3 +2332,61 @@ def BundleAdjustment(problem, n_iterations=5, robust=True, stop=None):
     reduced system is dense: the host path is meant for the initial map and for machines without a GPU."""
     rc, Tcw, xw, stats = _ba_call(lib().orbp_bundle_adjustment, problem, n_iterations, robust, stop)
     return _pchk(rc), Tcw, xw, stats
+
+
+class EgProblem(C.Structure):
+    """orbp_eg_problem (include/orbp.h)"""
+    _fields_ = [("n_kfs", C.c_int32), ("Scw", C.c_void_p), ("Snc", C.c_void_p), ("fixed", C.c_int32), ("fix_scale", C.c_int32),
+                ("n_edges", C.c_int32), ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("edge_corrected", C.c_void_p),
+                ("n_points", C.c_int32), ("ref", C.c_void_p)]
+
+
+class EgStats(C.Structure):
+    """orbp_eg_stats (include/orbp.h)"""
+    _fields_ = [("iterations", C.c_int32), ("trials", C.c_int32), ("lambda_", C.c_double), ("chi2_initial", C.c_double),
+                ("chi2_final", C.c_double)]
+
+    def as_dict(self):
+        return {"iterations": self.iterations, "trials": self.trials, "lambda": self.lambda_, "chi2_initial": self.chi2_initial,
+                "chi2_final": self.chi2_final}
+
+
+ORBM_EG_MAX_KFS = 438
+
+
+def pack_eg_problem(problem):
+    """The flat arrays of orbp_optimize_essential_graph / orbm_optimize_essential_graph from a dict gathered as
+    Optimizer::OptimizeEssentialGraph walks (src/Optimizer.cc:797-983): Scw float64 [n_kfs, 8] in Sim3::operator[] order (qx qy qz
+    qw tx ty tz s), Snc the same (absent: a copy of Scw), fixed (an index or -1), fix_scale; per edge edge_i, edge_j int32 and
+    edge_corrected uint8; xw float32 [n_points, 3] and ref int32 [n_points] (-1: leave the point alone).  -> (EgProblem, arrays):
+    the struct points into `arrays` (a dict of contiguous copies, xw among them), which must outlive it."""
+    a = {"Scw": np.ascontiguousarray(problem["Scw"], np.float64).reshape(-1, 8),
+         "edge_i": np.ascontiguousarray(problem["edge_i"], np.int32).reshape(-1),
+         "edge_j": np.ascontiguousarray(problem["edge_j"], np.int32).reshape(-1),
+         "edge_corrected": np.ascontiguousarray(problem["edge_corrected"], np.uint8).reshape(-1),
+         "xw": np.array(problem.get("xw", np.zeros((0, 3))), np.float32).reshape(-1, 3),
+         "ref": np.ascontiguousarray(problem.get("ref", np.zeros(0)), np.int32).reshape(-1)}
+    a["Snc"] = np.ascontiguousarray(problem["Snc"] if problem.get("Snc") is not None else a["Scw"], np.float64).reshape(-1, 8)
+    if len(a["Snc"]) != len(a["Scw"]) or not (len(a["edge_i"]) == len(a["edge_j"]) == len(a["edge_corrected"])) or len(a["ref"]) != len(a["xw"]):
+        raise OrbxError(ORBX_E_INVALID, "pack_eg_problem: array lengths disagree")
+    ptr = {k: (v.ctypes.data if v.size else None) for k, v in a.items()}
+    s = EgProblem(len(a["Scw"]), ptr["Scw"], ptr["Snc"], int(problem.get("fixed", -1)), 1 if problem.get("fix_scale") else 0,
+                  len(a["edge_i"]), ptr["edge_i"], ptr["edge_j"], ptr["edge_corrected"], len(a["xw"]), ptr["ref"])
+    return s, a
+
+
+def _eg_call(fn, problem, n_iterations):
+    s, a = pack_eg_problem(problem)
+    Tcw = np.zeros((max(s.n_kfs, 1), 4, 4), np.float32)
+    Scw = np.zeros((max(s.n_kfs, 1), 8), np.float64)
+    stats = EgStats()
+    rc = fn(C.byref(s), int(n_iterations), _p(Tcw), _p(a["xw"]), _p(Scw), C.byref(stats))
+    return rc, Tcw[:s.n_kfs], a["xw"], Scw[:s.n_kfs], stats.as_dict()
+
+
+def optimize_essential_graph(problem, n_iterations=20):
+    """Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044) on the host over a pack_eg_problem() dict -> (0, Tcw float32
+    [n_kfs, 4, 4] = [R | t / s], xw float32 [n_points, 3], Scw float64 [n_kfs, 8] = the optimised Sim3, stats dict: iterations,
+    trials, lambda, chi2_initial, chi2_final).  The 7N x 7N system is an envelope Cholesky: there is no cap on n_kfs."""
+    rc, Tcw, xw, Scw, stats = _eg_call(lib().orbp_optimize_essential_graph, problem, n_iterations)
+    return _pchk(rc), Tcw, xw, Scw, stats

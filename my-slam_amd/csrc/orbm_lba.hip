@@ -29,6 +29,7 @@
 // optimize(n_iterations) with the call's robust kernel, no flagging pass, and the reduced system handed to the many-workgroup solve
 // of orbm_spd.hip instead of k_lba_solve.
 #include "orbm_hyp.h"
+#include "orbm_prof.h"
 #include "orbp_internal.h"
 #include "orbp_lba_body.h"
 #include "../../include/orbp.h"
@@ -448,46 +449,6 @@ __global__ __launch_bounds__(LBA_T) void k_lba_output(LbaDev d, int cur)
 
 inline unsigned blocks_for(long long n) { return (unsigned)std::max<long long>((n + LBA_T - 1) / LBA_T, 1); }
 
-// orbm_local_bundle_adjustment_split: events on the call's stream between the groups of launches.  An event follows each group, so a
-// group's time runs from the end of the group before it (or from the event that opens a batch, recorded when the host comes back
-// from a synchronisation) to its own end: the idle time until the host has enqueued it counts into it.  Elapsed times are read
-// after the synchronisation that was due anyway; nothing else about the call changes.
-struct LbaProf {
-    enum { NEV = 32 };
-    bool on = false;
-    hipEvent_t ev[NEV];
-    int grp[NEV], n = 0, made = 0;
-    double *ms = nullptr;
-    int32_t *count = nullptr;
-
-    void start(double *ms_, int32_t *count_)
-    {
-        ms = ms_; count = count_;
-        for (int g = 0; g < ORBM_LBA_SPLIT_N; g++) { ms[g] = 0; count[g] = 0; }
-        for (made = 0; made < NEV; made++)
-            if (hipEventCreate(&ev[made]) != hipSuccess) return;
-        on = true;
-    }
-    ~LbaProf() { for (int i = 0; i < made; i++) (void)hipEventDestroy(ev[i]); }
-    void pre(hipStream_t s)                 // before a group: opens a batch if none is open
-    {
-        if (on && n == 0 && hipEventRecord(ev[0], s) == hipSuccess) { grp[0] = -1; n = 1; }
-    }
-    void post(int g, hipStream_t s)         // after a group's launches
-    {
-        if (on && n > 0 && n < NEV && hipEventRecord(ev[n], s) == hipSuccess) grp[n++] = g;
-    }
-    void drain()                            // after a synchronisation of the stream
-    {
-        for (int i = 1; i < n; i++) {
-            float t = 0;
-            if (hipEventElapsedTime(&t, ev[i - 1], ev[i]) == hipSuccess) { ms[grp[i]] += (double)t; count[grp[i]]++; }
-        }
-        n = 0;
-    }
-};
-#define LBA_GROUP(prof, g, s, ...) do { (prof).pre(s); __VA_ARGS__; (prof).post(g, s); } while (0)
-
 // "the passes of a problem" for lba_optimize (orbp_lba_body.h), as kernel launches on the handle's stream
 struct LbaGpu {
     orbm_matcher *m;
@@ -498,7 +459,7 @@ struct LbaGpu {
     double *pin;
     double *spd_y = nullptr;                // orbm_bundle_adjustment: the reduced system goes to orbm_spd_solve_device (orbm_spd.hip),
     int *spd_flag = nullptr;                // whose ok flag lands where k_lba_solve writes its own
-    LbaProf prof;
+    SplitProf prof;
 
     bool stop() const { return status != ORBX_OK || orbp_lba_read_stop(stop_flag); }
     int read_out()                          // the one small block: reduce, copy, synchronise
@@ -528,10 +489,10 @@ struct LbaGpu {
     }
     int do_linearize(bool first, bool with_errors, double &chi, double &maxdiag)
     {
-        if (with_errors) LBA_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
-        LBA_GROUP(prof, ORBM_LBA_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_lba_linearize, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
-        LBA_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_POINTS, s, hipLaunchKernelGGL(k_lba_reduce_points, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d));
-        if (d.K) LBA_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_KFS, s, hipLaunchKernelGGL(k_lba_reduce_kfs, dim3(d.K), dim3(64), 0, s, d));
+        if (with_errors) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_lba_linearize, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_POINTS, s, hipLaunchKernelGGL(k_lba_reduce_points, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d));
+        if (d.K) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_KFS, s, hipLaunchKernelGGL(k_lba_reduce_kfs, dim3(d.K), dim3(64), 0, s, d));
         MHIPCHK(hipGetLastError());
         if (first || with_errors) {
             MTRY(read_out());
@@ -541,14 +502,14 @@ struct LbaGpu {
     }
     int do_trial(double lambda, double &chi, double &scale, bool &ok)
     {
-        LBA_GROUP(prof, ORBM_LBA_SPLIT_DINV, s, hipLaunchKernelGGL(k_lba_dinv, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d, lambda));
-        if (d.K) LBA_GROUP(prof, ORBM_LBA_SPLIT_SCHUR, s, hipLaunchKernelGGL(k_lba_schur, dim3(d.K, d.K), dim3(64), 0, s, d, lambda));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_DINV, s, hipLaunchKernelGGL(k_lba_dinv, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d, lambda));
+        if (d.K) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_SCHUR, s, hipLaunchKernelGGL(k_lba_schur, dim3(d.K, d.K), dim3(64), 0, s, d, lambda));
         if (spd_y && d.n > 0)
-            LBA_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, MTRY(orbm_spd_solve_device(d.S, d.bs, spd_y, d.xp, spd_flag, d.out + OUT_OK, d.n, s)));
+            SPLIT_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, MTRY(orbm_spd_solve_device(d.S, d.bs, spd_y, d.xp, spd_flag, d.out + OUT_OK, d.n, s)));
         else                                // without unknowns k_lba_solve only sets the ok flag
-            LBA_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_T), 0, s, d));
-        LBA_GROUP(prof, ORBM_LBA_SPLIT_UPDATE, s, hipLaunchKernelGGL(k_lba_update, dim3(blocks_for(std::max(d.P, d.NK))), dim3(LBA_T), 0, s, d, cur, lambda));
-        LBA_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, 1 - cur, robust));
+            SPLIT_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_T), 0, s, d));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_UPDATE, s, hipLaunchKernelGGL(k_lba_update, dim3(blocks_for(std::max(d.P, d.NK))), dim3(LBA_T), 0, s, d, cur, lambda));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, 1 - cur, robust));
         MHIPCHK(hipGetLastError());
         MTRY(read_out());
         chi = pin[OUT_CHI]; scale = pin[OUT_SCALE]; ok = pin[OUT_OK] != 0.;
@@ -632,7 +593,7 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
               pb = in.add(p->obs, 8 * (size_t)E), pu = in.add(p->u_right, 4 * (size_t)E), pi = in.add(p->inv_sigma2, 4 * (size_t)E),
               pko = in.add(kf_off.data(), 4 * ((size_t)K + 1)), pke = in.add(kf_edge.data(), 4 * kf_edge.size());
     LbaGpu g;
-    if (split_ms && split_count) g.prof.start(split_ms, split_count);
+    if (split_ms && split_count) g.prof.start(split_ms, split_count, ORBM_LBA_SPLIT_N);
     g.prof.pre(s);
     MTRY(in.upload(s));
     g.prof.post(ORBM_LBA_SPLIT_UPLOAD, s);
@@ -658,7 +619,7 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
             lba_optimize(g, ba->n_iterations, run);             // :188
             MTRY(g.status);
         }
-        LBA_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s,        // a point without edges keeps its bits: float -> double -> float
+        SPLIT_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s,        // a point without edges keeps its bits: float -> double -> float
                   hipLaunchKernelGGL(k_lba_output, dim3(blocks_for(std::max(K, P))), dim3(LBA_T), 0, s, d, g.cur));
         MHIPCHK(hipGetLastError());
         void *const host[2] = {Tcw_local, xw};
@@ -681,7 +642,7 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
     }
     if (!orbp_lba_read_stop(stop)) {                            // :662-709
         st.second_round = 1;
-        LBA_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s, hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 0));
+        SPLIT_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s, hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 0));
         g.robust = LBA_KERNEL_NONE;
         MTRY(g.activate(n_active, n_level1));                   // :706
         st.n_level1 = n_level1;

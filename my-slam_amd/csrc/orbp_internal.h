@@ -24,3 +24,10 @@ extern "C" void orbp_lba_set_stop_probe(void (*fn)(void *), void *arg);
 // orbp_lba_check and the bound of n_iterations.
 __attribute__((visibility("hidden"))) int orbp_ba_check(const orbp_lba_problem *p, int n_iterations, const float *Tcw_local,
                                                         const float *xw, char *text, int text_size);
+// orbp_eg.cc: the argument checks of orbp_optimize_essential_graph, shared with orbm_optimize_essential_graph (orbm_eg.hip).
+struct orbp_eg_problem;
+__attribute__((visibility("hidden"))) int orbp_eg_check(const orbp_eg_problem *p, int n_iterations, const float *Tcw, const float *xw,
+                                                        char *text, int text_size);
+// orbp_eg.cc, a hook for tests/test_eg_cpu.py only: dense != 0 makes every row of the envelope start at column 0 (per thread),
+// which is the dense factorisation the envelope must reproduce bit for bit.
+extern "C" void orbp_eg_set_dense(int dense);

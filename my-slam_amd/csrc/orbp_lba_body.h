@@ -347,8 +347,10 @@ struct LbaRun { int iterations, trials; double lambda, chi2; };
 //   ctx.trial(lambda, chi, scale, ok)           push, setLambda, solve, update, restoreDiagonal, computeActiveErrors,
 //                                               activeRobustChi2, computeScale (without its + 1e-3)
 //   ctx.accept() / ctx.reject()                 discardTop / pop: the edges keep the trial's errors either way
+// user_lambda_init > 0 is setUserLambdaInit's value, which computeLambdaInit returns instead of tau * maxdiag (:168-169;
+// OptimizeEssentialGraph sets 1e-16, orbp_eg_body.h).
 template <class Ctx>
-static inline void lba_optimize(Ctx &ctx, int iterations, LbaRun &run)
+static inline void lba_optimize(Ctx &ctx, int iterations, LbaRun &run, double user_lambda_init = 0)
 {
     double lambda = 0, ni = 2, current = 0;
     int n_bad = 0;
@@ -360,7 +362,7 @@ static inline void lba_optimize(Ctx &ctx, int iterations, LbaRun &run)
         double chi = 0, maxdiag = 0;
         ctx.linearize(it == 0, !fresh, chi, maxdiag);
         if (!fresh) current = chi;
-        if (it == 0) { lambda = 1e-5 * maxdiag; ni = 2; n_bad = 0; }                     // _tau = 1e-5
+        if (it == 0) { lambda = user_lambda_init > 0 ? user_lambda_init : 1e-5 * maxdiag; ni = 2; n_bad = 0; }    // _tau = 1e-5
         const double ini = current;
         double rho = 0;
         int qmax = 0;

@@ -7,11 +7,13 @@
 // cv::Mat the reference returns.  PnPsolver::EvaluateAll is the one addition to the reference's interface: the EPnP
 // hypotheses of all Relocalization candidates in one GPU call (orbm_pnp_hypotheses), replayed by iterate.
 #pragma once
+#include <algorithm>
 #include <array>
 #include <cstdint>
 #include <map>
 #include <mutex>
 #include <optional>
+#include <set>
 #include <string>
 #include <type_traits>
 #include <utility>
@@ -621,6 +623,181 @@ public:
     {
         (void)GlobalBundleAdjustemnt(static_cast<orbm_matcher *>(nullptr), pMap, static_cast<std::string *>(nullptr), nIterations, pbStopFlag,
                                      nLoopKF, bRobust);
+    }
+
+    // ---- Optimizer::OptimizeEssentialGraph (include/Optimizer.h, src/Optimizer.cc:781-1044; LoopClosing::CorrectLoop,
+    // src/LoopClosing.cc:568) ----
+    // The flat problem of orbp_optimize_essential_graph (include/orbp.h) and the objects its rows stand for.
+    template <class KeyFrameT, class MapPointT>
+    struct EgProblem {
+        std::vector<KeyFrameT *> kfs;                       // the non-bad vpKFs by mnId ascending (g2o's hessianIndex order): the vertices
+        std::vector<MapPointT *> points;                    // the non-bad vpMPs
+        std::vector<double> Scw, Snc;
+        std::vector<int32_t> edgeI, edgeJ, ref;
+        std::vector<uint8_t> edgeCorrected;
+        std::vector<float> xw, TcwOut;
+        int32_t fixed = -1;
+        bool fixScale = false;
+        orbp_eg_stats stats{};
+        orbp_eg_problem flat() const
+        {
+            return {(int32_t)kfs.size(), Scw.data(), Snc.data(), fixed, fixScale ? 1 : 0, (int32_t)(edgeI.size() - 1), edgeI.data(), edgeJ.data(),
+                    edgeCorrected.data(), (int32_t)points.size(), ref.data()};
+        }
+    };
+    // The walk of :797-983 and :1013-1029.  Sim3 values are read through operator[] only.  Two deviations (include/orbp.h): a bad key
+    // frame gets no vertex and every edge or point that would touch a missing vertex is skipped (the reference dereferences a null
+    // vertex there; GetAllKeyFrames returns no bad key frame in practice), and a point whose reference has no vertex gets ref = -1.
+    template <class MapT, class KeyFrameT, class MapPointT, class PoseMapT, class ConnT>
+    static void GatherEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const PoseMapT &NonCorrectedSim3,
+                                     const PoseMapT &CorrectedSim3, const ConnT &LoopConnections, const bool bFixScale,
+                                     EgProblem<KeyFrameT, MapPointT> &P)
+    {
+        P = EgProblem<KeyFrameT, MapPointT>();
+        P.fixScale = bFixScale;
+        const std::vector<KeyFrameT *> vpKFs = pMap->GetAllKeyFrames();
+        const std::vector<MapPointT *> vpMPs = pMap->GetAllMapPoints();
+        const int minFeat = 100;
+        std::map<unsigned long, KeyFrameT *> byId;          // :809-844
+        for (size_t i = 0; i < vpKFs.size(); i++)
+            if (!vpKFs[i]->isBad()) byId[vpKFs[i]->mnId] = vpKFs[i];
+        std::map<unsigned long, int32_t> index;             // optimizer.vertex(mnId)
+        for (auto it = byId.begin(); it != byId.end(); it++) {
+            KeyFrameT *pKF = it->second;
+            index[it->first] = (int32_t)P.kfs.size();
+            if (pKF == pLoopKF) P.fixed = (int32_t)P.kfs.size();
+            P.kfs.push_back(pKF);
+            double S[8];
+            const auto itc = CorrectedSim3.find(pKF);
+            if (itc != CorrectedSim3.end()) {
+                for (int k = 0; k < 8; k++) S[k] = itc->second[k];
+            } else {
+                const auto R = pKF->GetRotation(), t = pKF->GetTranslation();
+                float Rf[9], tf[3];
+                for (int r = 0; r < 3; r++) {
+                    for (int c = 0; c < 3; c++) Rf[3 * r + c] = R.template at<float>(r, c);
+                    tf[r] = t.template at<float>(r);
+                }
+                (void)orbp_sim3_from_rts(Rf, tf, 1.0f, S);
+            }
+            P.Scw.insert(P.Scw.end(), S, S + 8);
+            const auto itn = NonCorrectedSim3.find(pKF);
+            if (itn != NonCorrectedSim3.end())
+                for (int k = 0; k < 8; k++) S[k] = itn->second[k];
+            P.Snc.insert(P.Snc.end(), S, S + 8);
+        }
+        const auto vertex = [&index](KeyFrameT *pKF) {
+            const auto it = index.find(pKF->mnId);
+            return it == index.end() || pKF->isBad() ? (int32_t)-1 : it->second;
+        };
+        const auto add = [&P](int32_t i, int32_t j, uint8_t corrected) {
+            P.edgeI.push_back(i); P.edgeJ.push_back(j); P.edgeCorrected.push_back(corrected);
+        };
+        std::set<std::pair<long unsigned int, long unsigned int>> sInsertedEdges;
+        for (auto mit = LoopConnections.begin(), mend = LoopConnections.end(); mit != mend; mit++) {       // :852-880
+            KeyFrameT *pKF = mit->first;
+            const long unsigned int nIDi = pKF->mnId;
+            for (auto sit = mit->second.begin(), send = mit->second.end(); sit != send; sit++) {
+                const long unsigned int nIDj = (*sit)->mnId;
+                if ((nIDi != pCurKF->mnId || nIDj != pLoopKF->mnId) && pKF->GetWeight(*sit) < minFeat) continue;
+                const int32_t vi = vertex(pKF), vj = vertex(*sit);
+                if (vi < 0 || vj < 0 || vi == vj) continue;
+                add(vi, vj, 1);
+                sInsertedEdges.insert(std::make_pair(std::min(nIDi, nIDj), std::max(nIDi, nIDj)));
+            }
+        }
+        for (size_t i = 0; i < vpKFs.size(); i++) {         // :883-983
+            KeyFrameT *pKF = vpKFs[i];
+            const int32_t vi = vertex(pKF);
+            if (vi < 0) continue;
+            KeyFrameT *pParentKF = pKF->GetParent();
+            if (pParentKF && vertex(pParentKF) >= 0 && vertex(pParentKF) != vi) add(vi, vertex(pParentKF), 0);     // :901-923
+            const std::set<KeyFrameT *> sLoopEdges = pKF->GetLoopEdges();
+            for (auto sit = sLoopEdges.begin(), send = sLoopEdges.end(); sit != send; sit++) {                    // :926-949
+                KeyFrameT *pLKF = *sit;
+                if (pLKF->mnId < pKF->mnId && vertex(pLKF) >= 0) add(vi, vertex(pLKF), 0);
+            }
+            const std::vector<KeyFrameT *> vpConnectedKFs = pKF->GetCovisiblesByWeight(minFeat);
+            for (auto vit = vpConnectedKFs.begin(); vit != vpConnectedKFs.end(); vit++) {                         // :952-982
+                KeyFrameT *pKFn = *vit;
+                if (pKFn && pKFn != pParentKF && !pKF->hasChild(pKFn) && !sLoopEdges.count(pKFn)) {
+                    if (!pKFn->isBad() && pKFn->mnId < pKF->mnId) {
+                        if (sInsertedEdges.count(std::make_pair(std::min(pKF->mnId, pKFn->mnId), std::max(pKF->mnId, pKFn->mnId)))) continue;
+                        if (vertex(pKFn) >= 0) add(vi, vertex(pKFn), 0);
+                    }
+                }
+            }
+        }
+        for (size_t i = 0; i < vpMPs.size(); i++) {         // :1013-1036
+            MapPointT *pMP = vpMPs[i];
+            if (pMP->isBad()) continue;
+            long unsigned int nIDr;
+            if (pMP->mnCorrectedByKF == pCurKF->mnId) nIDr = pMP->mnCorrectedReference;
+            else nIDr = pMP->GetReferenceKeyFrame()->mnId;
+            const auto it = index.find(nIDr);
+            P.points.push_back(pMP);
+            P.ref.push_back(it == index.end() ? -1 : it->second);
+            const auto X = pMP->GetWorldPos();
+            for (int r = 0; r < 3; r++) P.xw.push_back(X.template at<float>(r));
+        }
+        P.TcwOut.assign(16 * P.kfs.size() + 1, 0.f);
+        P.Scw.push_back(0.); P.Snc.push_back(0.); P.xw.push_back(0.f); P.ref.push_back(-1);      // never NULL
+        add(0, 0, 0);                                       // flat() leaves this last entry out of n_edges
+    }
+    // :989-1043 under the map's update lock: SetPose for every vertex, SetWorldPos + UpdateNormalAndDepth for every non-bad point
+    template <class MapT, class KeyFrameT, class MapPointT>
+    static void ScatterEssentialGraph(const EgProblem<KeyFrameT, MapPointT> &P, MapT *pMap)
+    {
+        std::unique_lock<std::mutex> lock(pMap->mMutexMapUpdate);
+        for (size_t k = 0; k < P.kfs.size(); k++) {
+            auto T = P.kfs[k]->GetPose().clone();
+            for (int r = 0; r < 4; r++)
+                for (int c = 0; c < 4; c++) T.template at<float>(r, c) = P.TcwOut[16 * k + 4 * r + c];
+            P.kfs[k]->SetPose(T);
+        }
+        for (size_t p = 0; p < P.points.size(); p++) {
+            MapPointT *pMP = P.points[p];
+            if (pMP->isBad()) continue;
+            auto X = pMP->GetWorldPos().clone();
+            for (int r = 0; r < 3; r++) X.template at<float>(r) = P.xw[3 * p + r];
+            pMP->SetWorldPos(X);
+            pMP->UpdateNormalAndDepth();
+        }
+    }
+    // Through orbm_optimize_essential_graph on the matcher's handle (NULL: the host path, orbp_optimize_essential_graph).  A map
+    // beyond ORBM_EG_MAX_KFS key frames falls back to the host path, which has no cap; *err then holds the GPU call's reason.
+    // Returns 0 or the ORBX status; on failure nothing is changed and *err receives the text.  Which path to call at which size:
+    // INTEGRATION.md 3r.
+    template <class MapT, class KeyFrameT, class PoseMapT, class ConnT>
+    static int OptimizeEssentialGraph(orbm_matcher *matcher, MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const PoseMapT &NonCorrectedSim3,
+                                      const PoseMapT &CorrectedSim3, const ConnT &LoopConnections, const bool &bFixScale,
+                                      std::string *err = nullptr, orbp_eg_stats *stats = nullptr, int nIterations = 20)
+    {
+        typedef typename std::remove_pointer<typename decltype(pMap->GetAllMapPoints())::value_type>::type MapPointT;
+        EgProblem<KeyFrameT, MapPointT> P;
+        GatherEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections, bFixScale, P);
+        const orbp_eg_problem flat = P.flat();
+        int rc = ORBX_E_CAPACITY;
+        if (matcher) {
+            rc = orbm_optimize_essential_graph(matcher, &flat, nIterations, P.TcwOut.data(), P.xw.data(), nullptr, &P.stats);
+            if (rc < 0 && err) *err = orbm_last_error();
+        }
+        if (rc == ORBX_E_CAPACITY) {
+            rc = orbp_optimize_essential_graph(&flat, nIterations, P.TcwOut.data(), P.xw.data(), nullptr, &P.stats);
+            if (rc < 0 && err) *err = orbp_last_error();
+        }
+        if (rc < 0) return rc;
+        if (stats) *stats = P.stats;
+        ScatterEssentialGraph(P, pMap);
+        return rc;
+    }
+    // The reference's signature (include/Optimizer.h:47-51), so src/LoopClosing.cc:568 compiles unchanged; on the host.
+    template <class MapT, class KeyFrameT, class PoseMapT, class ConnT>
+    static void OptimizeEssentialGraph(MapT *pMap, KeyFrameT *pLoopKF, KeyFrameT *pCurKF, const PoseMapT &NonCorrectedSim3,
+                                       const PoseMapT &CorrectedSim3, const ConnT &LoopConnections, const bool &bFixScale)
+    {
+        (void)OptimizeEssentialGraph(static_cast<orbm_matcher *>(nullptr), pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3, LoopConnections,
+                                     bFixScale);
     }
 
 private:
