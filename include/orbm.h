@@ -1006,7 +1006,8 @@ int orbm_local_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_pr
  * orbm_bundle_adjustment runs on its reduced system, and downloads.  *ok = 1, or 0 where a pivot was not positive or not finite:
  * x is then all zeros and the call still returns ORBX_OK (the later launches of the solve see the device flag and return at
  * once; nothing traps and nothing is read back between the panels).
- * ORBX_E_INVALID on a NULL argument or n < 1, ORBX_E_CAPACITY beyond ORBM_SPD_MAX_N.
+ * ORBX_E_INVALID on a NULL argument or n < 1, ORBX_E_CAPACITY beyond ORBM_SPD_MAX_N.  tests/test_spd_gpu.py runs the solve up to
+ * and at ORBM_SPD_MAX_N: against Higham's backward error bound, and on systems whose exact solution it must return byte for byte.
  */
 #define ORBM_SPD_MAX_N 3072
 int orbm_spd_solve_f64(orbm_matcher *m, const double *A, const double *b, int n, double *x, int *ok);
@@ -1049,7 +1050,8 @@ int orbm_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_problem 
  * section 24).
  *
  * ORBX_E_CAPACITY, decided from the counts before any allocation or launch: beyond ORBM_EG_MAX_KFS key frames, which keeps the
- * 7 x 438 = 3066 unknowns inside ORBM_SPD_MAX_N, the range the solve has been tested and measured in.  The host path has no cap.
+ * 7 x 438 = 3066 unknowns inside ORBM_SPD_MAX_N, the range the solve has been tested and measured in (tests/test_spd_gpu.py at
+ * n = 3066 and 3072; tests/test_eg_gpu.py holds this call to the oracle at 438 key frames).  The host path has no cap.
  * orbm_optimize_essential_graph_split is the same call with split_ms[g] = the device time of group g summed over the call and
  * split_count[g] the number of times it ran (both ORBM_EG_SPLIT_N long), measured as orbm_local_bundle_adjustment_split measures.
  */

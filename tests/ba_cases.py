@@ -6,7 +6,8 @@ src/Optimizer.cc:71-184 walks: every key frame is "local", the one with mnId == 
 The shapes follow the solver of csrc/orbm_spd.hip, whose panel is NB = 48 unknowns = B = 8 key frames: 1, B - 1, B, B + 1 and
 3 B + 1 free key frames (with the fixed one 2, 8, 9, 10 and 26 blocks of the reduced system: one panel exactly filled, one row
 over, and four panels with a ragged last one); a point's observers are a random subset of all key frames, so the off-diagonal panels
-of the largest case are not empty.  Points: 0, 1, 63 / 64 / 65, 400.
+of the largest case are not empty.  Points: 0, 1, 63 / 64 / 65, 400.  SCALE_SPECS, further down, holds three dense cases of 49,
+89 and 512 blocks: a group of its own with bars of its own.
 
 Condition on every case, asserted when it is built: in the oracle (tests/ba_oracle.py), in both summation orders, every decision
 stays at least 1e-3 (relative) from its boundary, both orders give the same transcript and counts, and the case's own predicate
@@ -30,11 +31,12 @@ NB, B = 48, 8                        # SPD_NB of csrc/orbm_spd.hip and the key f
 KEYS, FLOAT_ULP, diffs = lc.KEYS, lc.FLOAT_ULP, lc.diffs
 
 
-def scene(rng, n_free, n_points, kinds="mixed", outliers=0.0, fixed_at=None, n_fixed=0, id0=True, all_fixed=False, empty=False):
+def scene(rng, n_free, n_points, kinds="mixed", outliers=0.0, fixed_at=None, n_fixed=0, id0=True, all_fixed=False, empty=False,
+          observers=None):
     """lba_cases.scene() with the mnId == 0 key frame moved to position fixed_at of the list (None: the end, where scene() puts
     it).  empty: one more free key frame and one more point, both without edges, the point in the middle of the list."""
     pr = lc.scene(rng, n_free=n_free, n_fixed=n_fixed, n_points=n_points, kinds=kinds, outliers=outliers, local_id0=id0,
-                  all_local_fixed=all_fixed)
+                  all_local_fixed=all_fixed, observers=observers)
     pr = {k: v for k, v in pr.items() if k not in ("k_bad", "k_behind")}
     K = len(pr["local_fixed"])
     if id0 and fixed_at is not None and fixed_at != K - 1:
@@ -121,6 +123,34 @@ GAUGE = ("init_map_mono", "no_fixed_gauge")
 TOLERANCE_NAMES = tuple(n for n in NAMES if n not in GAUGE)
 LARGEST = "k25_p400_mixed"
 
+
+# The scale cases: reduced systems that csrc/orbm_spd.hip solves with a second and a third workgroup of k_spd_backward (49 and 89
+# blocks: 294 and 534 unknowns) and at ORBM_BA_MAX_KFS (512 blocks, 3072 unknowns = ORBM_SPD_MAX_N), this time with edges.  A group
+# of its own: the stop sweeps, the spread over NAMES and the case count of tolerance.json stay as they are, and each has bars of
+# its own there under "scale" (4 x the spread of the oracle's two orders on that case alone: the spread grows with the condition
+# of the system, and a pooled bar would let the small cases hide behind the large ones).
+# Density is a condition of these cases (dense_enough): lba_cases.scene() gives a point about six observers, which at 512 key
+# frames leaves S almost block-diagonal; here 300 points are each seen by a third of all key frames.
+# One iteration at the larger two; two at the smallest, so that an accepted step feeds a second linearisation.
+density = lc.density
+
+
+def dense_enough(pr, f):
+    """no key frame without edges, every key frame with more than 64 (the lane stride of k_lba_reduce_kfs and k_lba_schur wraps),
+    at least a quarter of S's tiles below the diagonal occupied, and an iteration that ran"""
+    fewest, tiles = density(pr)
+    return fewest > 64 and tiles >= 0.25 and ran_all(pr, f)
+
+
+SCALE_POINTS = 300
+SCALE_SPECS = {
+    "scale_k49": (2000, dict(n_free=48, n_points=SCALE_POINTS, kinds="mixed", fixed_at=20, observers=49 // 3), 2, False, dense_enough),
+    "scale_k89": (2100, dict(n_free=88, n_points=SCALE_POINTS, kinds="mixed", fixed_at=50, observers=89 // 3), 1, True, dense_enough),
+    "scale_k512": (2200, dict(n_free=511, n_points=SCALE_POINTS, kinds="mixed", fixed_at=300, observers=512 // 3), 1, False, dense_enough),
+}
+SCALE_NAMES = tuple(SCALE_SPECS)
+AT_THE_CAP = "scale_k512"
+
 _CASES = {}
 _HOST = {}
 
@@ -132,11 +162,12 @@ def case(name):
     """(problem, n_iterations, robust)"""
     if name not in _CASES:
         group = SAME_PROBLEM if name in SAME_PROBLEM else (name,)
-        seed, args = SPECS[group[0]][:2]
-        assert all(SPECS[n][:2] == (seed, args) for n in group)
-        pr = checked(seed, lambda rng: scene(rng, **args), [SPECS[n][2:] for n in group])
+        specs = SCALE_SPECS if name in SCALE_SPECS else SPECS
+        seed, args = specs[group[0]][:2]
+        assert all(specs[n][:2] == (seed, args) for n in group)
+        pr = checked(seed, lambda rng: scene(rng, **args), [specs[n][2:] for n in group])
         for n in group:
-            _CASES[n] = (pr, SPECS[n][2], SPECS[n][3])
+            _CASES[n] = (pr, specs[n][2], specs[n][3])
     return _CASES[name]
 
 

@@ -12,7 +12,8 @@ The shapes are the smallest at which each piece can go wrong: 2 key frames; 6 an
 the solve's 48-column panel); 14 with a loop; 30 as a chain plus a band plus long loop rows (the envelope); the fixed key frame
 first, in the middle, last and absent; two and three edges on a pair; a key frame without edges; the fixed key frame in both roles;
 fix_scale; the four branches of Sim3::log and a consistent graph; budgets 0, 1, 2, 3 and 20; a rejected trial; 0, 1, 63, 64 and 65
-points with ref = -1 and ref = the fixed key frame among them.
+points with ref = -1 and ref = the fixed key frame among them.  SCALE_SPECS, further down, holds the four graphs at which the GPU
+path's launches take more than one workgroup: a group of its own with bars of its own.
 
 Counts: after convergence accept / reject is decided by noise.  Iteration and trial counts are compared exactly on the cases whose
 every oracle decision (tests/eg_oracle.py: rho against 0, the _nBad quantity against 0) stays at least MARGIN_FACTOR x its own
@@ -146,13 +147,38 @@ CONVERGED = ("chain30", "no_fixed", "consistent", "budget_20")
 BRANCH_OF = {"log_small_angle_unit_scale": (True, True), "log_small_angle_scaled": (False, True),
              "log_angle_unit_scale": (True, False), "log_angle_scaled": (False, False)}
 
+
+
+def _scale(n, n_iterations, **more):
+    """n key frames, the first fixed, as a chain plus a band of 10 plus a loop of 10 edges (the shape of tools/bench_eg.py)"""
+    return (dict(seed=n, n=n, fixed=0, corrected_from=n - 10, band=10, loop_connections=tuple((n - 1 - k, k) for k in range(10)), **more),
+            n_iterations)
+
+
+# The scale cases: what only a launch over several workgroups reaches (N = 7 free key frames unknowns).  They are a group of their
+# own: they take no part in the common spread, the CONVERGED list or the case count of tolerance.json, and each has bars of its
+# own there under "scale", made as the common ones are (4 x the spread of the oracle's six variants on that case alone): the
+# spread grows with the condition of the system, and a pooled bar would let the small cases hide behind the large ones.
+# One iteration at the large sizes: a second one of such a graph runs into rejected trials decided by noise.  Every one of them
+# must keep decisions_clear(), so its counts are compared exactly.
+SCALE_SPECS = {
+    "scale_kf43": _scale(43, 2),                      # N = 294: k_eg_stage's second column block, k_spd_backward's second workgroup
+    "scale_kf78": _scale(78, 1),                      # N = 539: k_spd_backward's third workgroup
+    # more than 256 key frames, 2555 edges and N = 1813: k_eg_update / k_eg_output / k_eg_measure / k_eg_errors beyond one
+    # workgroup, k_eg_reduce_out's loop strides twice; 300 points over all key frames: k_eg_points beyond one workgroup
+    "scale_kf260": _scale(260, 1, n_points=300),
+    "scale_kf438": _scale(438, 1),                    # ORBM_EG_MAX_KFS, N = 3059
+}
+SCALE_NAMES = tuple(SCALE_SPECS)
+AT_THE_CAP = "scale_kf438"
+
 _CASES, _ORACLE, _HOST = {}, {}, {}
 
 
 def case(name):
     """(problem, n_iterations)"""
     if name not in _CASES:
-        args, n_it = SPECS[name]
+        args, n_it = SPECS[name] if name in SPECS else SCALE_SPECS[name]
         _CASES[name] = (graph(**args), n_it)
     return _CASES[name]
 
@@ -229,6 +255,8 @@ def absolute_chi2_bar(pr):
 
 def bars(name):
     tol = json.load(open(TOLERANCE))
+    if name in SCALE_SPECS:
+        return tol["scale"][name]["bar"]
     return tol["ill_conditioned"][name]["bar"] if name in ILL_CONDITIONED else tol["bar"]
 
 

@@ -48,8 +48,9 @@ def project(R, t, cam, X):
 
 
 def scene(rng, n_free, n_fixed, n_points, kinds="mixed", outliers=0.0, local_id0=False, all_local_fixed=False, min_degree=2,
-          bad_point=False, bad_kf=False, behind=False, mild=0.0):
-    """kinds: "mono", "stereo" or "mixed" (each observation is stereo with probability 1/2).  local_id0: one more local key frame,
+          bad_point=False, bad_kf=False, behind=False, mild=0.0, observers=None):
+    """observers: every point is seen by that many key frames (None: about six, drawn per point, and the first point by all).
+    kinds: "mono", "stereo" or "mixed" (each observation is stereo with probability 1/2).  local_id0: one more local key frame,
     fixed (mnId == 0).  bad_kf: one more free local key frame that sees 8 points at random pixels.  behind: one more free local
     key frame 13 m ahead of the others; a point 8 m ahead is behind it and is "observed" where the projection formula puts it."""
     n_local = n_free + (1 if local_id0 else 0) + (1 if bad_kf else 0) + (1 if behind else 0)
@@ -82,7 +83,9 @@ def scene(rng, n_free, n_fixed, n_points, kinds="mixed", outliers=0.0, local_id0
         inv.append(1.0 / SIGMA2[rng.integers(0, 8) if level is None else level])
 
     for p in range(n_points):
-        if p == 0:
+        if observers is not None:
+            deg = min(observers, top)
+        elif p == 0:
             deg = top                                          # one point seen by every key frame
         elif p == 1:
             deg = min(min_degree, top)
@@ -229,6 +232,37 @@ SPECS = {
     "gauge_mono": (1400, dict(n_free=3, n_fixed=0, n_points=100, kinds="mono", local_id0=True), None),
 }
 NAMES = tuple(SPECS)
+
+
+def density(pr, B=8):
+    """(fewest edges of a key frame, share of the 6 B x 6 B tiles strictly below the diagonal of S that hold a non-zero 6 x 6 block):
+    block (a, b) of S is non-zero where key frames a and b see a common point"""
+    K = len(pr["local_fixed"])
+    sees = np.zeros((K, len(pr["xw"])), bool)
+    point_of = np.repeat(np.arange(len(pr["xw"])), np.diff(pr["edge_off"]))
+    local = pr["edge_kf"] < K
+    sees[pr["edge_kf"][local], point_of[local]] = True
+    share = (sees.astype(np.int32) @ sees.T.astype(np.int32)) > 0
+    T = (K + B - 1) // B
+    tiles = [share[B * i:B * i + B, B * j:B * j + B].any() for i in range(T) for j in range(i)]
+    return int(np.bincount(pr["edge_kf"], minlength=K)[:K].min()), float(np.mean(tiles))
+
+
+def dense_and_ran_ten(pr, f):
+    """no key frame without edges, every key frame with more than 64 (the lane stride of k_lba_reduce_kfs and k_lba_schur wraps),
+    at least a quarter of S's tiles below the diagonal occupied, and a second round that ran after outliers were flagged"""
+    fewest, tiles = density(pr)
+    return fewest > 64 and tiles >= 0.25 and ran_ten(pr, f)
+
+
+# The scale case: ORBM_LBA_MAX_LOCAL = 128 local key frames, all free (768 unknowns: three strides of the 256 threads of the
+# one-workgroup k_lba_solve, a trailing triangle of 290 thousand entries), 8 fixed ones, 300 points each seen by a third of all key
+# frames, a tenth of the observations gross outliers as in the `mixed` cases above.  A group of its own: it takes no part in the
+# common spread or the case count of tolerance.json and has bars of its own there under "scale", made the same way.
+SCALE_SPECS = {
+    "scale_k128": (1500, dict(n_free=128, n_fixed=8, n_points=300, kinds="mixed", outliers=0.1, observers=136 // 3), dense_and_ran_ten),
+}
+SCALE_NAMES = tuple(SCALE_SPECS)
 GAUGE = ("gauge_mono",)             # compared on flags, counts and final chi2 only
 TOLERANCE_NAMES = tuple(n for n in NAMES if n not in GAUGE)
 
@@ -238,7 +272,7 @@ _HOST = {}
 
 def case(name):
     if name not in _CASES:
-        seed, args, pred = SPECS[name]
+        seed, args, pred = SPECS[name] if name in SPECS else SCALE_SPECS[name]
         _CASES[name] = checked(seed, lambda rng: scene(rng, **args), pred)
     return _CASES[name]
 

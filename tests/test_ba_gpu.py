@@ -54,6 +54,28 @@ def test_the_gpu_call_equals_the_host(m, orbx, name):
     bc.assert_same(gpu(m, name), want[1], want[2], want[3], BARS, "gpu " + name, coordinates=name not in bc.GAUGE, float_roundings=2)
 
 
+@pytest.mark.parametrize("name", bc.SCALE_NAMES)
+def test_the_gpu_call_equals_the_oracle_where_the_solve_spans_workgroups(m, name):
+    """the scale cases of tests/ba_cases.py (dense reduced systems of 294, 534 and 3072 unknowns) against the oracle's forward
+    result: identical counts; poses, points and final chi2 within that case's own bars plus the float rounding of the one output"""
+    f = bc.oracle(name)[0]
+    bars = tuple(TOL["scale"][name]["bar"][k] for k in bc.KEYS)
+    bc.assert_same(gpu(m, name), f["Tcw"], f["xw"], f["stats"], bars, "gpu " + name, float_roundings=1)
+
+
+def test_the_scale_cases_keep_their_bytes(m, orbx):
+    """512 key frames with edges give the same bytes on a second run, and 49 the same bytes before and after them on one handle,
+    whose workspace grows in between"""
+    h = orbx.ORBmatcher(0.8, True, max_queries=64, max_train=64, max_pairs=256)
+    try:
+        first = run(h, "scale_k49")
+        assert same_bytes(first, gpu(m, "scale_k49"))
+        assert same_bytes(run(h, bc.AT_THE_CAP), gpu(m, bc.AT_THE_CAP))
+        assert same_bytes(first, run(h, "scale_k49"))
+    finally:
+        h.close()
+
+
 def test_vertices_without_edges_and_robust(m):
     pr = bc.case("empty_vertices")[0]
     xw = gpu(m, "empty_vertices")[2]

@@ -57,6 +57,15 @@ def test_the_tolerance_file_is_what_the_script_measures():
         assert TOL["bar"][k] == 4 * TOL["spread"][k] and 0 < TOL["spread"][k] < 1e-4 and TOL["worst_case"][k] in ec.NAMES
     assert TOL["bar"]["chi2_initial_relative"] < 1e-13          # the tight bar: error evaluation and edge gather, no Jacobian in the way
     assert set(TOL["ill_conditioned"]) == set(ec.ILL_CONDITIONED)
+    assert set(TOL["scale"]) == set(ec.SCALE_NAMES)             # each scale case has bars of its own, made the same way
+    for name in ec.SCALE_NAMES:
+        s = TOL["scale"][name]
+        for k in ("rotation", "translation", "scale", "chi2_final_relative", "chi2_initial_relative"):
+            assert s["bar"][k] == 4 * s["spread"][k] and 0 < s["spread"][k] and s["worst_case"][k] == name
+        # a step of these graphs moves the corrected key frames by the correction itself (a translation of 2, an angle of 0.3): a
+        # key frame that a launch left out misses every one of these bars by more than an order of magnitude
+        assert s["bar"]["translation"] < 0.1 and s["bar"]["rotation"] < 1e-3 and s["bar"]["scale"] < 1e-3
+        assert s["bar"]["chi2_initial_relative"] < 1e-13
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tools", "measure_eg_spread.py"), "--check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
 
@@ -99,7 +108,26 @@ def test_the_cases_cover_what_they_should():
             assert c[0]["ref"][0] == -1 and c[0]["ref"][-1] == c[0]["fixed"]
 
 
-@pytest.mark.parametrize("name", ec.NAMES)
+def test_the_scale_cases_reach_what_they_should():
+    """the sizes at which the launches of csrc/orbm_eg.hip and csrc/orbm_spd.hip take a second and a third workgroup or stride, each
+    with every decision of the oracle clear of noise in all six variants, so that the counts are compared exactly"""
+    cs = {n: ec.case(n) for n in ec.SCALE_NAMES}
+    N = {n: 7 * (len(c[0]["Scw"]) - 1) for n, c in cs.items()}
+    assert N == {"scale_kf43": 294, "scale_kf78": 539, "scale_kf260": 1813, "scale_kf438": 3059}
+    assert 256 < N["scale_kf43"] <= 512 < N["scale_kf78"] <= 768          # two and three workgroups of k_spd_backward, 256 entries each
+    big = cs["scale_kf260"][0]
+    assert len(big["Scw"]) > 256 and len(big["edge_i"]) == 2555 > 2 * 1024 and N["scale_kf260"] > 1024
+    assert len(big["xw"]) == 300 > 256 and len(set(big["ref"][1:-1].tolist())) > 150 and big["ref"][1:-1].max() > 256
+    assert len(cs[ec.AT_THE_CAP][0]["Scw"]) == 438 and len(cs[ec.AT_THE_CAP][0]["edge_i"]) == 4335
+    assert [cs[n][1] for n in ec.SCALE_NAMES] == [2, 1, 1, 1]
+    for n, (pr, n_it) in cs.items():
+        assert pr["fixed"] == 0 and not pr["fix_scale"], n
+        assert ec.decisions_clear(n), n
+        stats = ec.oracle(n)["stats"]
+        assert stats["iterations"] == n_it and all(ec.oracle(n, *v)["stats"][k] == stats[k] for v in ec.VARIANTS for k in ("iterations", "trials")), n
+
+
+@pytest.mark.parametrize("name", ec.NAMES + ec.SCALE_NAMES)
 def test_the_host_path_equals_the_oracle(built, name):
     o = ec.oracle(name)
     ec.assert_same(name, ec.host(built, name), o["Tcw"], o["Scw"][:, 7], o["xw"], o["stats"], "host " + name,

@@ -4,7 +4,8 @@ variants, measured by tests/tools/measure_eg_spread.py) plus the float rounding 
 counts identical on the cases whose decisions are clear of noise.  Host and kernels run one text (csrc/orbp_eg_body.h); the
 device's acos / sin / cos / log / exp, the trees of the chi2 and computeScale sums and the solve (csrc/orbm_spd.hip here, the
 envelope Cholesky there) are what differs.  Also: the bytes of a second run and of a run after a bundle_adjustment on the same
-handle (the solve's workspace is shared), fix_scale's exact zeros, the bits of ref = -1, the cap."""
+handle (the solve's workspace is shared), fix_scale's exact zeros, the bits of ref = -1, the cap.  The scale cases (43, 78, 260
+and 438 key frames: every launch of csrc/orbm_eg.hip beyond one workgroup) are held to the oracle itself, each within its own bars."""
 import ctypes as C
 
 import numpy as np
@@ -48,6 +49,26 @@ def test_the_gpu_call_equals_the_host(m, orbx, name):
     want = ec.host(orbx, name)
     ec.assert_same(name, gpu(m, name), ec.tcw_of(want[3]), want[3][:, 7], want[2], want[4], "gpu " + name,
                    counts=name not in ec.CONVERGED, float_sides=2)
+
+
+@pytest.mark.parametrize("name", ec.SCALE_NAMES)
+def test_the_gpu_call_equals_the_oracle_where_launches_span_workgroups(m, name):
+    """the scale cases of tests/eg_cases.py against the oracle's forward result: identical counts, Scw in double, Tcw, the scale,
+    the points (scale_kf260 carries 300) and both chi2 within that case's own bars"""
+    o = ec.oracle(name)
+    ec.assert_same(name, gpu(m, name), o["Tcw"], o["Scw"][:, 7], o["xw"], o["stats"], "gpu " + name, counts=True, float_sides=1)
+
+
+def test_the_small_scale_case_keeps_its_bytes_after_the_cap(m):
+    """43 key frames before and after 438 on the same handle: the workspace grows from 0.7 MB to 75 MB in between"""
+    h = m.__class__(0.8, True, max_queries=64, max_train=64, max_pairs=256)
+    try:
+        first = run(h, "scale_kf43")
+        assert same_bytes(first, gpu(m, "scale_kf43"))
+        assert same_bytes(run(h, ec.AT_THE_CAP), gpu(m, ec.AT_THE_CAP))
+        assert same_bytes(first, run(h, "scale_kf43"))
+    finally:
+        h.close()
 
 
 def test_the_bytes_depend_on_the_problem_alone(m):
@@ -96,12 +117,15 @@ def test_beyond_the_capacity(m, orbx):
 def test_at_the_cap_with_edges(m, orbx):
     """438 key frames as a chain plus a band of 10 plus a loop of 10 edges (the largest shape of tools/bench_eg.py, 3059 unknowns),
     one iteration: the same counts as the host, the initial chi2 (4335 edges, no Jacobian in it), and a step that Levenberg
-    accepted.  The estimates are not compared: the bars were measured on graphs of at most 30 key frames.  The initial chi2 is a sum
+    accepted.  The initial chi2 is a sum
     of E non-negative terms, in edge order on the host and by a tree on the device: each order is within (E - 1) eps / 2 of the exact
-    sum, so the two lie within (E - 1) eps of each other, on top of the bar, which covers what the terms themselves may differ by."""
+    sum, so the two lie within (E - 1) eps of each other, on top of the bar, which covers what the terms themselves may differ by.
+    The graph is the case scale_kf438 of tests/eg_cases.py: the estimates of the GPU and of the host are each held to the oracle's
+    within that case's own bars."""
     n = orbx.ORBM_EG_MAX_KFS
-    pr = ec.graph(seed=n, n=n, fixed=0, corrected_from=n - 10, band=10, loop_connections=tuple((n - 1 - k, k) for k in range(10)))
-    host, got = orbx.optimize_essential_graph(pr, 1), m.optimize_essential_graph(pr, 1)
+    pr, n_it = ec.case(ec.AT_THE_CAP)
+    assert len(pr["Scw"]) == n and n_it == 1
+    host, got = ec.host(orbx, ec.AT_THE_CAP), gpu(m, ec.AT_THE_CAP)
     assert got[0] == host[0] == 0 and got[4]["iterations"] == host[4]["iterations"] == 1 and got[4]["trials"] == host[4]["trials"] == 1
     rel = abs(got[4]["chi2_initial"] - host[4]["chi2_initial"]) / host[4]["chi2_initial"]
     print("chi2_initial %.17g, relative difference %.3g; chi2_final gpu %.9g host %.9g" % (host[4]["chi2_initial"], rel, got[4]["chi2_final"],
@@ -109,3 +133,6 @@ def test_at_the_cap_with_edges(m, orbx):
     assert rel <= ec.bars("free6")["chi2_initial_relative"] + (len(pr["edge_i"]) - 1) * np.finfo(np.float64).eps
     assert np.isfinite(got[3]).all() and 0 <= got[4]["chi2_final"] < got[4]["chi2_initial"]
     assert got[3][0].tobytes() == np.asarray(pr["Scw"])[0].tobytes()
+    o = ec.oracle(ec.AT_THE_CAP)
+    for what, res in (("gpu", got), ("host", host)):
+        ec.assert_same(ec.AT_THE_CAP, res, o["Tcw"], o["Scw"][:, 7], o["xw"], o["stats"], what + " at the cap", counts=True, float_sides=1)

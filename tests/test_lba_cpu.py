@@ -48,6 +48,11 @@ def test_the_tolerance_file_is_what_the_script_measures():
     assert TOL["factor"] == 4
     for k in lc.KEYS:
         assert TOL["bar"][k] == 4 * TOL["spread"][k] and 0 < TOL["spread"][k] < 1e-3
+    assert set(TOL["scale"]) == set(lc.SCALE_NAMES)                     # each scale case has bars of its own, made the same way
+    for name in lc.SCALE_NAMES:
+        for k in lc.KEYS:
+            s = TOL["scale"][name]
+            assert s["bar"][k] == 4 * s["spread"][k] and 0 < s["spread"][k] < 1e-3 and s["worst_case"][k] == name
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "tools", "measure_lba_spread.py"), "--check"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
 
@@ -80,10 +85,28 @@ def test_the_cases_cover_what_they_should():
         assert min(f["margin"], r["margin"]) > lc.MARGIN and f["transcript"] == r["transcript"], name
 
 
-@pytest.mark.parametrize("name", lc.NAMES)
+def test_the_scale_case_is_at_the_cap_and_dense(built):
+    """ORBM_LBA_MAX_LOCAL free key frames (768 unknowns: three strides of k_lba_solve's 256 threads), some fixed ones, every key frame
+    with more than 64 edges, every tile of S occupied, a tenth gross outliers that the first round flags, and a second round"""
+    pr = lc.case("scale_k128")
+    f, r = lc.oracle("scale_k128")
+    cap = int(re.search(r"#define\s+ORBM_LBA_MAX_LOCAL\s+(\d+)", open(os.path.join(ROOT, "include", "orbm.h")).read()).group(1))
+    assert len(pr["local_fixed"]) == cap == 128 and pr["local_fixed"].sum() == 0 and len(pr["Tcw"]) == cap + 8 and 6 * cap == 3 * 256
+    fewest, tiles = lc.density(pr)
+    assert fewest > 64 and tiles >= 0.25
+    assert min(f["margin"], r["margin"]) > lc.MARGIN and f["transcript"] == r["transcript"]
+    assert f["stats"]["n_level1"] >= len(pr["edge_kf"]) // 20 and f["stats"]["iterations"][1] >= 1 and f["stats"]["second_round"] == 1
+
+
+def scale_bars(name):
+    return tuple(TOL["scale"][name]["bar"][k] for k in lc.KEYS)
+
+
+@pytest.mark.parametrize("name", lc.NAMES + lc.SCALE_NAMES)
 def test_host_equals_oracle(built, name):
     f = lc.oracle(name)[0]
-    lc.assert_same(lc.host(built, name), f["Tcw"], f["xw"], f["erase"], f["stats"], BARS, name, coordinates=name not in lc.GAUGE)
+    bars = scale_bars(name) if name in lc.SCALE_NAMES else BARS
+    lc.assert_same(lc.host(built, name), f["Tcw"], f["xw"], f["erase"], f["stats"], bars, name, coordinates=name not in lc.GAUGE)
 
 
 def test_stale_errors_decide_the_final_pass(built):

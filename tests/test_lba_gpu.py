@@ -53,6 +53,16 @@ def test_the_gpu_call_equals_the_host(m, orbx, name):
     against_host(orbx, gpu(m, name), name)
 
 
+@pytest.mark.parametrize("name", lc.SCALE_NAMES)
+def test_the_gpu_call_equals_the_oracle_at_the_cap(m, name):
+    """128 free local key frames with edges: k_lba_solve's 256 threads stride three times over the 768 unknowns and walk a trailing
+    triangle of 290 thousand entries.  Against the oracle's forward result within the case's own bars, and a second run's bytes."""
+    f = lc.oracle(name)[0]
+    bars = tuple(TOL["scale"][name]["bar"][k] for k in lc.KEYS)
+    lc.assert_same(gpu(m, name), f["Tcw"], f["xw"], f["erase"], f["stats"], bars, "gpu " + name)
+    assert same_bytes(gpu(m, name), m.local_bundle_adjustment(lc.case(name))), name
+
+
 def test_a_second_run_gives_the_same_bytes(m):
     for name in ("k11_p257_mixed", "bad_kf", "no_free"):
         assert same_bytes(gpu(m, name), m.local_bundle_adjustment(lc.case(name))), name

@@ -18,7 +18,11 @@ beside its sources to cite here.  The product hands poses and points back as flo
 The file also lists the cases whose counts are decided by noise (eg_cases.decisions_clear is False); eg_cases.CONVERGED must name
 exactly those.
 
+The scale cases (eg_cases.SCALE_SPECS) are measured the same way, each by itself, into the file's "scale" entry; they take no part
+in the common spread.
+
     python tests/tools/measure_eg_spread.py            # writes the file
+    python tests/tools/measure_eg_spread.py --scale     # measures the scale cases alone and puts them into the file as it is
     python tests/tools/measure_eg_spread.py --check     # recomputes and compares with the file"""
 import json
 import os
@@ -64,13 +68,38 @@ def measure():
     got.update(spread_over([n for n in ec.NAMES if n not in ec.ILL_CONDITIONED]))
     got["ill_conditioned"] = {n: spread_over([n]) for n in ec.ILL_CONDITIONED}
     got["converged"] = [n for n in ec.NAMES if not ec.decisions_clear(n)]
+    got["scale"] = measure_scale()
     return got
 
 
+def measure_scale():
+    """the scale cases, each by itself: a pooled bar would let the small ones hide behind the large ones"""
+    for n in ec.SCALE_NAMES:
+        assert ec.decisions_clear(n), "%s: a decision of the oracle is not clear of noise" % n
+    return {n: spread_over([n]) for n in ec.SCALE_NAMES}
+
+
+def scale_matches(want, got):
+    return (set(want) == set(got) and
+            all(want[n]["spread"][k] / FACTOR <= got[n]["spread"][k] <= want[n]["bar"][k] and want[n]["bar"][k] == FACTOR * want[n]["spread"][k]
+                for n in got for k in got[n]["spread"]))
+
+
 if __name__ == "__main__":
+    if "--scale" in sys.argv:                   # the scale cases alone, added to the file as it is: every other entry keeps its digits
+        want = json.load(open(ec.TOLERANCE))
+        want["scale"] = measure_scale()
+        with open(ec.TOLERANCE, "w") as f:
+            json.dump(want, f, indent=2)
+            f.write("\n")
+        print(json.dumps(want["scale"], indent=2))
+        sys.exit(0)
     got = measure()
     if "--check" in sys.argv:
         want = json.load(open(ec.TOLERANCE))
+        if not scale_matches(want.get("scale", {}), got["scale"]):
+            print(json.dumps({n: s["spread"] for n, s in got["scale"].items()}), "the scale cases DIFFER from the file")
+            sys.exit(1)
         # the oracle's solves go through LAPACK, whose kernels follow the CPU they run on: the recomputed spread must reproduce the
         # recorded one within FACTOR both ways
         ok = (all(want["spread"][k] / FACTOR <= got["spread"][k] <= want["bar"][k] for k in got["spread"])
