@@ -1002,7 +1002,7 @@ int orbm_local_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_pr
  * trailing update over the tiles of the lower triangle, then both substitutions panel by panel: 5 ceil(n / 48) - 2 launches in
  * stream order.  No cooperative launch, no grid-wide barrier, no spin-wait, nothing between workgroups but kernel boundaries,
  * no atomic; every loop is bounded by n; x is a function of (A, b) alone.  This is the host-array entry, for tests and
- * measurements: it uploads into the bundle adjustment workspace of the handle, runs the device routine that
+ * measurements: it uploads into the optimizer workspace of the handle, runs the device routine that
  * orbm_bundle_adjustment runs on its reduced system, and downloads.  *ok = 1, or 0 where a pivot was not positive or not finite:
  * x is then all zeros and the call still returns ORBX_OK (the later launches of the solve see the device flag and return at
  * once; nothing traps and nothing is read back between the panels).
@@ -1040,7 +1040,7 @@ int orbm_bundle_adjustment_split(orbm_matcher *m, const struct orbp_lba_problem 
 /*
  * ---- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044) on the GPU ----
  * The problem, arguments, semantics and return codes of orbp_optimize_essential_graph (include/orbp.h), whose argument checks
- * run first and need no handle.  Host and kernels run one text (csrc/orbp_eg_body.h); the host drives lba_optimize as
+ * run first and need no handle.  Host and kernels run one text (csrc/orbp_eg_body.h); the host drives lm_optimize as
  * orbm_bundle_adjustment does.  Once a call k_eg_measure (the edges' measurements); per iteration k_eg_linearize (the 29 error
  * evaluations of an edge's numeric Jacobian over 29 threads), k_eg_diag and k_eg_offdiag (one wave per vertex / per vertex pair
  * sums its blocks in edge order into the dense 7N x 7N H0: no atomics, every sum in a fixed order); per trial k_eg_stage

@@ -355,7 +355,7 @@ int orbp_bundle_adjustment(const orbp_lba_problem *p, int n_iterations, int robu
  * Jacobians (delta = 1e-9), BlockSolver_7_3 on Hpp alone (no landmarks, no Schur complement) under OptimizationAlgorithmLevenberg
  * with setUserLambdaInit(1e-16), so the first lambda is 1e-16 and not tau * maxdiag.  The g2o lines restated are listed in
  * csrc/orbp_eg_body.h, the text the GPU call orbm_optimize_essential_graph (include/orbm.h) runs as well; the Levenberg loop is
- * LocalBundleAdjustment's (csrc/orbp_lba_body.h).  Parity with g2o itself is unpinned (there is no Eigen to build it against).
+ * LocalBundleAdjustment's (csrc/orbp_lm_body.h).  Parity with g2o itself is unpinned (there is no Eigen to build it against).
  *
  * The problem is flat:
  *   n_kfs key frames in g2o's hessianIndex order (mnId ascending); Scw[8 i ..] = vScw[i] (:818-832) and Snc[8 i ..] = the key

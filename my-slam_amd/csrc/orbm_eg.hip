@@ -1,7 +1,7 @@
 // orbm_eg.hip -- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044 of WChen09/My-SLAM, on g2o) on the GPU:
 // orbm_optimize_essential_graph (include/orbm.h) over the flat problem of orbp_optimize_essential_graph (include/orbp.h).  Host and
-// kernels run one text for the edges (orbp_eg_body.h); the host drives lba_optimize (orbp_lba_body.h) with launches as its passes,
-// as orbm_bundle_adjustment does, and the 7N x 7N system goes to the many-workgroup solve of orbm_spd.hip.
+// kernels run one text for the edges (orbp_eg_body.h); the host drives lm_optimize (orbp_lm_body.h) with launches as its passes, as
+// orbm_bundle_adjustment does (orbm_opt.h: what they share), and the 7N x 7N system goes to orbm_spd.hip's many-workgroup solve.
 //
 //   once          k_eg_measure     a thread an edge: Sji = Sjw * Swi from Scw or Snc (:857-867, :889-972)
 //   an iteration  k_eg_linearize   32 lanes an edge, 8 edges a workgroup: lane k < 29 evaluates entry k of the numeric
@@ -14,8 +14,8 @@
 //                 orbm_spd_solve_device
 //                 k_eg_update      a thread a vertex: the trial's estimate Sim3(x_v) * estimate into the other buffer
 //                 k_eg_errors      a thread an edge: e . e at the trial's estimates
-//                 k_eg_reduce_out  one workgroup: chi2 and computeScale's x . (lambda x + b), each a fixed tree, into the 64 bytes
-//                                  the host reads
+//                 k_eg_reduce_out  one workgroup: chi2 and computeScale's x . (lambda x + b), each by opt_block_sum (orbm_opt.h has
+//                                  the tree), into the 64 bytes the host reads
 //   at the end    k_eg_output, k_eg_points, one copy home
 // H0 is zeroed once a call: the graph does not change, so every iteration rewrites the same blocks.  The estimates are double
 // buffered ([cur] and the trial's), so accept is a flip and reject nothing.
@@ -23,11 +23,11 @@
 // Kept because the machines are shared (DESIGN.md sections 22 to 24): plain launches in stream order, no cooperative launch, no
 // grid-wide barrier, no spin-wait, nothing between workgroups but kernel boundaries, no atomic; every loop is bounded by a count
 // known at launch; a failed pivot leaves x = 0 through the solve's flag and nothing traps.
-#include "orbm_internal.h"
-#include "orbm_prof.h"
+#include "orbm_opt.h"
+#include "ws_layout.h"
 #include "orbp_internal.h"
 #include "orbp_eg_body.h"
-#include "orbp_lba_body.h"
+#include "orbp_lm_body.h"
 #include "../../include/orbp.h"
 #include "../../include/orbm.h"
 
@@ -57,25 +57,6 @@ struct EgDev {
     double *out_S;
 };
 enum { OUT_CHI = 0, OUT_SCALE = 1, OUT_OK = 2 };
-
-__device__ __forceinline__ double eg_wave_sum(double a)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
-    return a;
-}
-__device__ __forceinline__ double eg_block_sum(double a, double *sh)
-{
-    a = eg_wave_sum(a);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-    __syncthreads();
-    for (int s = EG_RT / 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
 
 __global__ __launch_bounds__(EG_T) void k_eg_measure(EgDev d)
 {
@@ -189,9 +170,9 @@ __global__ __launch_bounds__(EG_RT) void k_eg_reduce_out(EgDev d, double lambda)
     const int tid = threadIdx.x;
     double chi = 0, scale = 0;
     for (int e = tid; e < d.E; e += EG_RT) chi += d.chi_e[e];
-    for (int i = tid; i < d.N; i += EG_RT) scale += lba_scale_term(d.x[i], d.b0[i], lambda);
-    chi = eg_block_sum(chi, sh);
-    scale = eg_block_sum(scale, sh);
+    for (int i = tid; i < d.N; i += EG_RT) scale += lm_scale_term(d.x[i], d.b0[i], lambda);
+    chi = opt_block_sum<EG_RT>(chi, sh);
+    scale = opt_block_sum<EG_RT>(scale, sh);
     if (tid == 0) { d.out[OUT_CHI] = chi; d.out[OUT_SCALE] = scale; }
 }
 
@@ -213,40 +194,29 @@ __global__ __launch_bounds__(EG_T) void k_eg_points(EgDev d, int cur)
     d.out_xw[3 * q] = x[0]; d.out_xw[3 * q + 1] = x[1]; d.out_xw[3 * q + 2] = x[2];
 }
 
-inline unsigned eg_blocks(long long n, int per = EG_T) { return (unsigned)std::max<long long>((n + per - 1) / per, 1); }
-
-// "the passes of a problem" for lba_optimize (orbp_lba_body.h), as kernel launches on the handle's stream
-struct EgGpu {
-    EgDev d;
-    hipStream_t s;
-    int cur = 0, status = ORBX_OK;
-    double *pin, *spd_y;
-    int *spd_flag;
+// "the passes of a problem" for lm_optimize (orbp_lm_body.h), as kernel launches on the handle's stream (OptGpu, orbm_opt.h)
+struct EgGpu : OptGpu {
+    EgDev d = {};
+    int *spd_flag = nullptr;                // orbm_spd_solve_device's; its y is d.y
     double chi2_initial = 0;
-    SplitProf prof;
 
     bool stop() const { return status != ORBX_OK; }
     int read_out(double lambda)             // the one small block: reduce, copy, synchronise
     {
         prof.pre(s);
         hipLaunchKernelGGL(k_eg_reduce_out, dim3(1), dim3(EG_RT), 0, s, d, lambda);
-        MHIPCHK(hipGetLastError());
-        MHIPCHK(hipMemcpyAsync(pin, d.out, 64, hipMemcpyDeviceToHost, s));
-        prof.post(ORBM_EG_SPLIT_READ_BACK, s);
-        MHIPCHK(hipStreamSynchronize(s));
-        prof.drain();
-        return ORBX_OK;
+        return read_back(ORBM_EG_SPLIT_READ_BACK);
     }
     int errors_now(double &chi)             // computeActiveErrors + activeChi2 at the current estimates
     {
-        SPLIT_GROUP(prof, ORBM_EG_SPLIT_UPDATE_ERRORS, s, hipLaunchKernelGGL(k_eg_errors, dim3(eg_blocks(d.E)), dim3(EG_T), 0, s, d, cur));
+        SPLIT_GROUP(prof, ORBM_EG_SPLIT_UPDATE_ERRORS, s, hipLaunchKernelGGL(k_eg_errors, dim3(opt_blocks(d.E, EG_T)), dim3(EG_T), 0, s, d, cur));
         MTRY(read_out(0.));
         chi = pin[OUT_CHI];
         return ORBX_OK;
     }
     int do_linearize(bool first, bool with_errors, double &chi)
     {
-        SPLIT_GROUP(prof, ORBM_EG_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_eg_linearize, dim3(eg_blocks(d.E, EG_EPB)), dim3(EG_T), 0, s, d, cur));
+        SPLIT_GROUP(prof, ORBM_EG_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_eg_linearize, dim3(opt_blocks(d.E, EG_EPB)), dim3(EG_T), 0, s, d, cur));
         prof.pre(s);
         hipLaunchKernelGGL(k_eg_diag, dim3(d.nf), dim3(64), 0, s, d);
         if (d.npairs) hipLaunchKernelGGL(k_eg_offdiag, dim3(d.npairs), dim3(64), 0, s, d);
@@ -261,26 +231,22 @@ struct EgGpu {
     }
     int do_trial(double lambda, double &chi, double &scale, bool &ok)
     {
-        SPLIT_GROUP(prof, ORBM_EG_SPLIT_STAGE, s, hipLaunchKernelGGL(k_eg_stage, dim3(eg_blocks(d.N), d.N), dim3(EG_T), 0, s, d, lambda));
-        SPLIT_GROUP(prof, ORBM_EG_SPLIT_SOLVE, s, MTRY(orbm_spd_solve_device(d.W, d.bw, spd_y, d.x, spd_flag, d.out + OUT_OK, d.N, s)));
+        SPLIT_GROUP(prof, ORBM_EG_SPLIT_STAGE, s, hipLaunchKernelGGL(k_eg_stage, dim3(opt_blocks(d.N, EG_T), d.N), dim3(EG_T), 0, s, d, lambda));
+        SPLIT_GROUP(prof, ORBM_EG_SPLIT_SOLVE, s, MTRY(orbm_spd_solve_device(d.W, d.bw, d.y, d.x, spd_flag, d.out + OUT_OK, d.N, s)));
         prof.pre(s);
-        hipLaunchKernelGGL(k_eg_update, dim3(eg_blocks(d.n)), dim3(EG_T), 0, s, d, cur);
-        hipLaunchKernelGGL(k_eg_errors, dim3(eg_blocks(d.E)), dim3(EG_T), 0, s, d, 1 - cur);
+        hipLaunchKernelGGL(k_eg_update, dim3(opt_blocks(d.n, EG_T)), dim3(EG_T), 0, s, d, cur);
+        hipLaunchKernelGGL(k_eg_errors, dim3(opt_blocks(d.E, EG_T)), dim3(EG_T), 0, s, d, 1 - cur);
         prof.post(ORBM_EG_SPLIT_UPDATE_ERRORS, s);
-        MHIPCHK(hipGetLastError());
-        MTRY(read_out(lambda));
+        MTRY(read_out(lambda));             // checks the launches above as well
         chi = pin[OUT_CHI]; scale = pin[OUT_SCALE]; ok = pin[OUT_OK] != 0.;
         return ORBX_OK;
     }
-    // a failed launch or copy ends the loop through stop() and comes back as the call's status
     void linearize(bool first, bool with_errors, double &chi, double &maxdiag)
     {
         maxdiag = 0;                        // computeLambdaInit returns the user's value
         if (status == ORBX_OK) status = do_linearize(first, with_errors, chi);
     }
     void trial(double lambda, double &chi, double &scale, bool &ok) { if (status == ORBX_OK) status = do_trial(lambda, chi, scale, ok); }
-    void accept() { cur ^= 1; }
-    void reject() {}
 };
 
 int eg_run(orbm_matcher *m, const orbp_eg_problem *p, int n_iterations, float *Tcw, float *xw, double *Scw_out, orbp_eg_stats *stats,
@@ -324,25 +290,20 @@ int eg_run(orbm_matcher *m, const orbp_eg_problem *p, int n_iterations, float *T
     }
     const int npairs = (int)pair_hi.size();
 
-    EgDev d = {};
+    EgGpu g; EgDev &d = g.d;
     d.n = n; d.fixed = p->fixed; d.nf = nf; d.N = 7 * nf; d.E = E; d.P = P; d.npairs = npairs; d.fix_scale = p->fix_scale;
-    size_t need = 0;
-    auto take = [&need](size_t bytes) { const size_t at = need; need += (bytes + 63) & ~(size_t)63; return at; };
-    const size_t N = (size_t)d.N, szd = sizeof(double);
-    const size_t o_meas = take(8 * szd * E), o_est0 = take(8 * szd * n), o_est1 = take(8 * szd * n), o_err = take(7 * szd * E),
-                 o_Ji = take(49 * szd * E), o_Jj = take(49 * szd * E), o_chi = take(szd * E), o_H0 = take(szd * N * N),
-                 o_b0 = take(szd * N), o_W = take(szd * N * N), o_bw = take(szd * N), o_y = take(szd * N), o_x = take(szd * N),
-                 o_out = take(64), o_flag = take(64),
-                 o_res = take(64 * (size_t)n + 64 * (size_t)n + 12 * (size_t)P);     // the results back to back: one copy home
-    MTRY(orbm_ensure_lba(m, need));
+    const size_t N = (size_t)d.N, szd = sizeof(double), sn = (size_t)n, sE = (size_t)E;
+    WsLayout ws;
+    ws.take(d.meas, 8 * sE); ws.take(d.est[0], 8 * sn); ws.take(d.est[1], 8 * sn); ws.take(d.err, 7 * sE);
+    ws.take(d.Ji, 49 * sE); ws.take(d.Jj, 49 * sE); ws.take(d.chi_e, sE); ws.take(d.H0, N * N);
+    ws.take(d.b0, N); ws.take(d.W, N * N); ws.take(d.bw, N); ws.take(d.y, N); ws.take(d.x, N); ws.take(d.out, 8); ws.take(g.spd_flag, 16);
+    uint8_t *res = nullptr;
+    ws.take(res, 64 * sn + 64 * sn + 12 * (size_t)P);           // the results back to back: one copy home
+    MTRY(orbm_ensure_opt(m, ws.bytes()));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    uint8_t *w = m->d_lba;
-    d.meas = (double *)(w + o_meas); d.est[0] = (double *)(w + o_est0); d.est[1] = (double *)(w + o_est1); d.err = (double *)(w + o_err);
-    d.Ji = (double *)(w + o_Ji); d.Jj = (double *)(w + o_Jj); d.chi_e = (double *)(w + o_chi); d.H0 = (double *)(w + o_H0);
-    d.b0 = (double *)(w + o_b0); d.W = (double *)(w + o_W); d.bw = (double *)(w + o_bw); d.y = (double *)(w + o_y);
-    d.x = (double *)(w + o_x); d.out = (double *)(w + o_out);
-    d.out_S = (double *)(w + o_res); d.out_Tcw = (float *)(d.out_S + 8 * (size_t)n); d.out_xw = d.out_Tcw + 16 * (size_t)n;
+    ws.bind(m->d_opt.get());
+    d.out_S = (double *)res; d.out_Tcw = (float *)(d.out_S + 8 * sn); d.out_xw = d.out_Tcw + 16 * sn;
 
     InBlock in(m);
     const int pS = in.add(p->Scw, 64 * (size_t)n), pN = in.add(p->Snc, 64 * (size_t)n), pi = in.add(p->edge_i, 4 * (size_t)E),
@@ -351,7 +312,7 @@ int eg_run(orbm_matcher *m, const orbp_eg_problem *p, int n_iterations, float *T
               pve = in.add(vtx_edge.data(), 4 * vtx_edge.size()), ppo = in.add(pair_off.data(), 4 * pair_off.size()),
               ppe = in.add(pair_edge.data(), 4 * pair_edge.size()), pph = in.add(pair_hi.data(), 4 * (size_t)npairs),
               ppl = in.add(pair_lo.data(), 4 * (size_t)npairs);
-    EgGpu g;
+    g.m = m; g.s = s; g.pin = (double *)m->opt_pin.get(); g.out = d.out;
     if (split_ms && split_count) g.prof.start(split_ms, split_count, ORBM_EG_SPLIT_N);
     g.prof.pre(s);
     MTRY(in.upload(s));
@@ -363,29 +324,23 @@ int eg_run(orbm_matcher *m, const orbp_eg_problem *p, int n_iterations, float *T
     if (N) MHIPCHK(hipMemsetAsync(d.x, 0, szd * N, s));
     MHIPCHK(hipMemsetAsync(d.out, 0, 64, s));
     if (n) MHIPCHK(hipMemcpyAsync(d.est[0], d.Scw, 64 * (size_t)n, hipMemcpyDeviceToDevice, s));
-    if (E) hipLaunchKernelGGL(k_eg_measure, dim3(eg_blocks(E)), dim3(EG_T), 0, s, d);
+    if (E) hipLaunchKernelGGL(k_eg_measure, dim3(opt_blocks(E, EG_T)), dim3(EG_T), 0, s, d);
     MHIPCHK(hipGetLastError());
     g.prof.post(ORBM_EG_SPLIT_UPLOAD, s);
 
-    g.d = d; g.s = s; g.pin = (double *)m->lba_pin.get(); g.spd_y = d.y; g.spd_flag = (int *)(w + o_flag);
-    LbaRun run = {0, 0, 0, 0};
+    LmRun run = {0, 0, 0, 0};
     if (E > 0 && nf > 0) {
-        lba_optimize(g, n_iterations, run, 1e-16);              // :794, :986-987
+        lm_optimize(g, n_iterations, run, 1e-16);               // :794, :986-987
         MTRY(g.status);
     }
     if (run.iterations == 0 && E > 0) MTRY(g.errors_now(g.chi2_initial));
     g.prof.pre(s);
-    if (n) hipLaunchKernelGGL(k_eg_output, dim3(eg_blocks(n)), dim3(EG_T), 0, s, d, g.cur);           // :992-1010
-    if (P) hipLaunchKernelGGL(k_eg_points, dim3(eg_blocks(P)), dim3(EG_T), 0, s, d, g.cur);           // :1013-1043
+    if (n) hipLaunchKernelGGL(k_eg_output, dim3(opt_blocks(n, EG_T)), dim3(EG_T), 0, s, d, g.cur);    // :992-1010
+    if (P) hipLaunchKernelGGL(k_eg_points, dim3(opt_blocks(P, EG_T)), dim3(EG_T), 0, s, d, g.cur);    // :1013-1043
     MHIPCHK(hipGetLastError());
     std::vector<double> unread;
-    if (!Scw_out) { unread.resize(8 * (size_t)n + 1); Scw_out = unread.data(); }
-    void *const host[3] = {Scw_out, Tcw, xw};
-    const size_t parts[3] = {64 * (size_t)n, 64 * (size_t)n, 12 * (size_t)P};
-    MTRY(orbm_d2h_split(m, host, parts, 3, d.out_S, s));
-    g.prof.post(ORBM_EG_SPLIT_OUTPUT, s);
-    MTRY(orbm_sync(m, s));
-    g.prof.drain();
+    if (!Scw_out) { unread.resize(8 * sn + 1); Scw_out = unread.data(); }
+    MTRY(g.download({Scw_out, Tcw, xw}, {64 * sn, 64 * sn, 12 * (size_t)P}, d.out_S, ORBM_EG_SPLIT_OUTPUT));
     if (stats) *stats = {run.iterations, run.trials, run.lambda, g.chi2_initial, run.iterations ? run.chi2 : g.chi2_initial};
     return ORBX_OK;
 }

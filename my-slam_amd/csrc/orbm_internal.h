@@ -105,8 +105,8 @@ struct orbm_matcher {
     Pend pend[8]; int npend = 0;
     DevBuf<uint8_t> d_dd;           // orbm_mappoint.hip: scratch of orbm_distinctive_descriptors (lazy, its own block)
     DevBuf<uint8_t> d_fuse;         // orbm_fuse.hip: the grids of all views and the dense results of orbm_fuse_views (lazy, its own block)
-    DevBuf<uint8_t> d_lba;          // orbm_lba.hip: the workspace of orbm_local_bundle_adjustment (lazy, its own block)
-    PinBuf<uint8_t> lba_pin;        // its per-trial read-back block
+    DevBuf<uint8_t> d_opt;          // the workspace of LBA, BA (orbm_lba.hip), EG (orbm_eg.hip) and both SPD entry points (lazy)
+    PinBuf<uint8_t> opt_pin;        // the 64 bytes the three optimizers read back after a trial (OptGpu, orbm_opt.h)
     // the capacities the handle advertises are what its buffers hold
     int max_q() const { return (int)std::min(std::min(d_q.bytes() / 32, (d_off.count() ? d_off.count() - 1 : 0)), d_out.count() / 3); }
     int max_t() const { return (int)(d_t.bytes() / 32); }
@@ -120,7 +120,7 @@ int orbm_grid_ensure(orbm_matcher *m, int slot);       // the slot's arrays, siz
 int orbm_ensure_partials(orbm_matcher *m, size_t need, hipStream_t s = nullptr);          // d_part of `need` pairs
 int orbm_ensure_dd(orbm_matcher *m, size_t need, hipStream_t s);                            // d_dd of `need` bytes
 int orbm_ensure_fuse(orbm_matcher *m, size_t need);                                         // d_fuse of `need` bytes
-int orbm_ensure_lba(orbm_matcher *m, size_t need);                                          // d_lba of `need` bytes, lba_pin of 64
+int orbm_ensure_opt(orbm_matcher *m, size_t need);                                          // d_opt of `need` bytes, opt_pin of 64
 // orbm_spd.hip: A = L L^T in place in the lower triangle of the row-major n x n A, then L y = b and L^T x = y, all device memory;
 // A, b and y are overwritten.  flag: != 0 where a pivot failed (x is then zeros); ok_out (may be NULL): 1.0 / 0.0.  Enqueues only.
 int orbm_spd_solve_device(double *A, double *b, double *y, double *x, int *flag, double *ok_out, int n, hipStream_t s);

@@ -1,10 +1,10 @@
 // orbm_lba.hip -- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778 of WChen09/My-SLAM, on g2o) on the GPU:
 // orbm_local_bundle_adjustment (include/orbm.h).  The kernels run the text of the host path orbp_local_bundle_adjustment
 // (orbp_lba.cc): csrc/orbp_lba_body.h holds the SE3 algebra, both edges' computeError and linearizeOplus, Huber, an edge's quadratic
-// form, a point's 3x3 inverse, the Schur terms and the Levenberg loop for both; only the order of the sums over edges, the device's
-// sin / cos and the inside of the dense solve differ.
+// form, a point's 3x3 inverse and the Schur terms for both, csrc/orbp_lm_body.h the Levenberg loop; only the order of the sums over
+// edges, the device's sin / cos and the inside of the dense solve differ.
 //
-// Launch structure: one upload, then lba_optimize (the body's Levenberg loop, on the host) over plain kernel launches in stream
+// Launch structure: one upload, then lm_optimize (the Levenberg loop, on the host) over plain kernel launches in stream
 // order, then one download.  A trial is six launches and one 64-byte read-back (robust chi2, computeScale's sum, the solve's ok
 // flag), where the host takes g2o's decisions and reads `stop`.  There is no cooperative launch, no grid-wide barrier, no spin-wait,
 // no communication between workgroups other than kernel boundaries and no floating-point atomic; every kernel loop is bounded by
@@ -13,23 +13,23 @@
 // Sums (all in fixed orders, so the result is a function of the problem alone):
 //   a point's Hll, b_l and its back-substitution     one thread per point, its edges in ascending order (the host's order)
 //   a key frame's Hpp, b_p                           one wave per key frame over its edges in ascending order: lane l adds the
-//                                                    edges l, l + 64, ... of the list, then the butterfly over the lane bits
-//                                                    0, 1, ..., 5 of DESIGN.md section 21
+//                                                    edges l, l + 64, ... of the list, then opt_wave_sum (orbm_opt.h)
 //   a block (i1 <= i2) of B Dinv B^T and of bschur   one wave per block over key frame i1's edges, the same lanes and butterfly.
 //                                                    Key frame i2's edge on the same point comes from a dense n_local x n_points
 //                                                    table of edge indices (4 bytes an entry, 1.3 MB at 40 x 8000): one load
 //                                                    instead of a search of the point's observers, and the table is rebuilt by one
 //                                                    launch a call
 //   robust chi2, computeScale, counts                one workgroup of 1024 threads: thread t adds the entries t, t + 1024, ...,
-//                                                    the butterfly inside a wave, then the 16 wave totals pairwise (8, 4, 2, 1)
+//                                                    then opt_block_sum (orbm_opt.h has the tree)
 // The dense solve: one workgroup of 256 threads factors S = L L^T in place in the workspace, right-looking over 6-wide block
 // columns, then substitutes forwards and backwards; a pivot that is not positive or not finite clears the ok flag and the update.
 //
-// orbm_bundle_adjustment (Optimizer::BundleAdjustment, src/Optimizer.cc:49-237) is the same driver over the same launches: one
-// optimize(n_iterations) with the call's robust kernel, no flagging pass, and the reduced system handed to the many-workgroup solve
-// of orbm_spd.hip instead of k_lba_solve.
+// orbm_bundle_adjustment (Optimizer::BundleAdjustment, src/Optimizer.cc:49-237) is a second short driver over the same set-up and
+// the same launches: one optimize(n_iterations) with the call's robust kernel, no flagging pass, and the reduced system handed to the
+// many-workgroup solve of orbm_spd.hip instead of k_lba_solve.
 #include "orbm_hyp.h"
-#include "orbm_prof.h"
+#include "orbm_opt.h"
+#include "ws_layout.h"
 #include "orbp_internal.h"
 #include "orbp_lba_body.h"
 #include "../../include/orbp.h"
@@ -65,12 +65,6 @@ __device__ __forceinline__ void store_se3(double *p, const LbaSe3 &T)
 }
 __device__ __forceinline__ LbaCam load_cam(const float *c) { return {c[0], c[1], c[2], c[3], c[4]}; }
 __device__ __forceinline__ bool kf_is_free(const LbaDev &d, int k) { return k < d.K && !d.local_fixed[k]; }
-__device__ __forceinline__ double wave_sum(double a)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);
-    return a;
-}
 
 // thread i: key frame i (the estimate of its pose), point i, edge i (level 0, no stored error, its place in the table)
 __global__ __launch_bounds__(LBA_T) void k_lba_init(LbaDev d)
@@ -169,7 +163,7 @@ __global__ __launch_bounds__(64) void k_lba_reduce_kfs(LbaDev d)
             for (int j = 0; j < 27; j++) acc[j] += s[LBA_HPP + j];
         }
 #pragma unroll
-    for (int j = 0; j < 27; j++) acc[j] = wave_sum(acc[j]);
+    for (int j = 0; j < 27; j++) acc[j] = opt_wave_sum(acc[j]);
     if (lane == 0) {
 #pragma unroll
         for (int j = 0; j < 21; j++) d.Hpp[21 * (long long)k + j] = acc[j];
@@ -223,10 +217,10 @@ __global__ __launch_bounds__(64) void k_lba_schur(LbaDev d, double lambda)
             }
         }
 #pragma unroll
-    for (int j = 0; j < 36; j++) acc[j] = wave_sum(acc[j]);
+    for (int j = 0; j < 36; j++) acc[j] = opt_wave_sum(acc[j]);
     if (i1 == i2) {
 #pragma unroll
-        for (int j = 0; j < 6; j++) coef[j] = wave_sum(coef[j]);
+        for (int j = 0; j < 6; j++) coef[j] = opt_wave_sum(coef[j]);
     }
     if (lane != 0) return;
     if (i1 == i2) {
@@ -364,7 +358,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_update(LbaDev d, int cur, double 
 #pragma unroll
             for (int j = 0; j < 3; j++) {
                 const double xl = D[3 * j] * cl[0] + D[3 * j + 1] * cl[1] + D[3 * j + 2] * cl[2];
-                term += lba_scale_term(xl, d.bl[3 * i + j], lambda);
+                term += lm_scale_term(xl, d.bl[3 * i + j], lambda);
                 x1[j] = x0[j] + xl;
             }
         } else {
@@ -377,7 +371,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_update(LbaDev d, int cur, double 
         if (i < d.K && ok && d.kf_active[i]) {
             double term = 0;
 #pragma unroll
-            for (int j = 0; j < 6; j++) term += lba_scale_term(d.xp[6 * i + j], d.bp[6 * i + j], lambda);
+            for (int j = 0; j < 6; j++) term += lm_scale_term(d.xp[6 * i + j], d.bp[6 * i + j], lambda);
             d.kterm[i] = term;
             store_se3(d.est[1 - cur] + 7 * i, lba_pose_oplus(T, d.xp + 6 * i));
         } else {
@@ -386,19 +380,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_update(LbaDev d, int cur, double 
         }
     }
 }
-// One workgroup: the sums and counts the host reads after a trial (the file comment has the tree)
-__device__ __forceinline__ double lba_block_sum(double a, double *sh)
-{
-    a = wave_sum(a);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = a;
-    __syncthreads();
-    for (int s = LBA_RT / 128; s > 0; s >>= 1) {
-        if ((int)threadIdx.x < s) sh[threadIdx.x] += sh[threadIdx.x + s];
-        __syncthreads();
-    }
-    return sh[0];
-}
+// One workgroup: the sums and counts the host reads after a trial (orbm_opt.h has the trees)
 __global__ __launch_bounds__(LBA_RT) void k_lba_reduce_out(LbaDev d)
 {
     __shared__ double sh[LBA_RT / 64];
@@ -410,18 +392,13 @@ __global__ __launch_bounds__(LBA_RT) void k_lba_reduce_out(LbaDev d)
     }
     for (long long k = tid; k < d.K; k += LBA_RT) { scale += d.kterm[k]; mx = fmax(mx, d.kmax[k]); }
     for (long long p = tid; p < d.P; p += LBA_RT) { scale_p += d.pterm[p]; mx = fmax(mx, d.pmax[p]); }
-    chi = lba_block_sum(chi, sh);
-    scale = lba_block_sum(scale, sh);
-    scale_p = lba_block_sum(scale_p, sh);
-    active = lba_block_sum(active, sh);         // counts: exact in double
-    level1 = lba_block_sum(level1, sh);
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) mx = fmax(mx, __shfl_xor(mx, m, 64));
-    __syncthreads();
-    if ((tid & 63) == 0) sh[tid >> 6] = mx;
-    __syncthreads();
+    chi = opt_block_sum<LBA_RT>(chi, sh);
+    scale = opt_block_sum<LBA_RT>(scale, sh);
+    scale_p = opt_block_sum<LBA_RT>(scale_p, sh);
+    active = opt_block_sum<LBA_RT>(active, sh); // counts: exact in double
+    level1 = opt_block_sum<LBA_RT>(level1, sh);
+    mx = opt_block_max<LBA_RT>(mx, sh);
     if (tid == 0) {
-        for (int w = 1; w < LBA_RT / 64; w++) mx = fmax(mx, sh[w]);
         d.out[OUT_CHI] = chi; d.out[OUT_SCALE] = scale + scale_p; d.out[OUT_MAXDIAG] = mx; d.out[OUT_ACTIVE] = active;
         d.out[OUT_LEVEL1] = level1;
     }
@@ -447,36 +424,24 @@ __global__ __launch_bounds__(LBA_T) void k_lba_output(LbaDev d, int cur)
         for (int j = 0; j < 3; j++) d.out_xw[3 * i + j] = (float)d.X[cur][3 * i + j];
 }
 
-inline unsigned blocks_for(long long n) { return (unsigned)std::max<long long>((n + LBA_T - 1) / LBA_T, 1); }
-
-// "the passes of a problem" for lba_optimize (orbp_lba_body.h), as kernel launches on the handle's stream
-struct LbaGpu {
-    orbm_matcher *m;
-    LbaDev d;
-    hipStream_t s;
-    const volatile uint8_t *stop_flag;
-    int cur = 0, robust = LBA_KERNEL_LBA, status = ORBX_OK;
-    double *pin;
+// "the passes of a problem" for lm_optimize (orbp_lm_body.h), as kernel launches on the handle's stream (OptGpu, orbm_opt.h)
+struct LbaGpu : OptGpu {
+    LbaDev d = {};
+    const volatile uint8_t *stop_flag = nullptr;
+    int robust = LBA_KERNEL_LBA;
     double *spd_y = nullptr;                // orbm_bundle_adjustment: the reduced system goes to orbm_spd_solve_device (orbm_spd.hip),
     int *spd_flag = nullptr;                // whose ok flag lands where k_lba_solve writes its own
-    SplitProf prof;
-
     bool stop() const { return status != ORBX_OK || orbp_lba_read_stop(stop_flag); }
     int read_out()                          // the one small block: reduce, copy, synchronise
     {
         prof.pre(s);
         hipLaunchKernelGGL(k_lba_reduce_out, dim3(1), dim3(LBA_RT), 0, s, d);
-        MHIPCHK(hipGetLastError());
-        MHIPCHK(hipMemcpyAsync(pin, d.out, 64, hipMemcpyDeviceToHost, s));
-        prof.post(ORBM_LBA_SPLIT_READ_BACK, s);
-        MHIPCHK(hipStreamSynchronize(s));
-        prof.drain();
-        return ORBX_OK;
+        return read_back(ORBM_LBA_SPLIT_READ_BACK);
     }
     int activate(int &n_active, int &n_level1)
     {
         prof.pre(s);
-        hipLaunchKernelGGL(k_lba_activate, dim3(blocks_for(std::max(d.P, d.K))), dim3(LBA_T), 0, s, d);
+        hipLaunchKernelGGL(k_lba_activate, dim3(opt_blocks(std::max(d.P, d.K), LBA_T)), dim3(LBA_T), 0, s, d);
         if (d.E) MHIPCHK(hipMemsetAsync(d.chi_e, 0, sizeof(double) * (size_t)d.E, s));
         if (d.K + d.P) {
             MHIPCHK(hipMemsetAsync(d.kterm, 0, sizeof(double) * (size_t)(d.K + d.P), s));  // kterm, then pterm
@@ -489,9 +454,9 @@ struct LbaGpu {
     }
     int do_linearize(bool first, bool with_errors, double &chi, double &maxdiag)
     {
-        if (with_errors) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
-        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_lba_linearize, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, cur, robust));
-        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_POINTS, s, hipLaunchKernelGGL(k_lba_reduce_points, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d));
+        if (with_errors) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(opt_blocks(d.E, LBA_T)), dim3(LBA_T), 0, s, d, cur, robust));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_LINEARIZE, s, hipLaunchKernelGGL(k_lba_linearize, dim3(opt_blocks(d.E, LBA_T)), dim3(LBA_T), 0, s, d, cur, robust));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_POINTS, s, hipLaunchKernelGGL(k_lba_reduce_points, dim3(opt_blocks(d.P, LBA_T)), dim3(LBA_T), 0, s, d));
         if (d.K) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_REDUCE_KFS, s, hipLaunchKernelGGL(k_lba_reduce_kfs, dim3(d.K), dim3(64), 0, s, d));
         MHIPCHK(hipGetLastError());
         if (first || with_errors) {
@@ -502,52 +467,29 @@ struct LbaGpu {
     }
     int do_trial(double lambda, double &chi, double &scale, bool &ok)
     {
-        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_DINV, s, hipLaunchKernelGGL(k_lba_dinv, dim3(blocks_for(d.P)), dim3(LBA_T), 0, s, d, lambda));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_DINV, s, hipLaunchKernelGGL(k_lba_dinv, dim3(opt_blocks(d.P, LBA_T)), dim3(LBA_T), 0, s, d, lambda));
         if (d.K) SPLIT_GROUP(prof, ORBM_LBA_SPLIT_SCHUR, s, hipLaunchKernelGGL(k_lba_schur, dim3(d.K, d.K), dim3(64), 0, s, d, lambda));
         if (spd_y && d.n > 0)
             SPLIT_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, MTRY(orbm_spd_solve_device(d.S, d.bs, spd_y, d.xp, spd_flag, d.out + OUT_OK, d.n, s)));
         else                                // without unknowns k_lba_solve only sets the ok flag
             SPLIT_GROUP(prof, ORBM_LBA_SPLIT_SOLVE, s, hipLaunchKernelGGL(k_lba_solve, dim3(1), dim3(LBA_T), 0, s, d));
-        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_UPDATE, s, hipLaunchKernelGGL(k_lba_update, dim3(blocks_for(std::max(d.P, d.NK))), dim3(LBA_T), 0, s, d, cur, lambda));
-        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(blocks_for(d.E)), dim3(LBA_T), 0, s, d, 1 - cur, robust));
-        MHIPCHK(hipGetLastError());
-        MTRY(read_out());
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_UPDATE, s, hipLaunchKernelGGL(k_lba_update, dim3(opt_blocks(std::max(d.P, d.NK), LBA_T)), dim3(LBA_T), 0, s, d, cur, lambda));
+        SPLIT_GROUP(prof, ORBM_LBA_SPLIT_ERRORS, s, hipLaunchKernelGGL(k_lba_errors, dim3(opt_blocks(d.E, LBA_T)), dim3(LBA_T), 0, s, d, 1 - cur, robust));
+        MTRY(read_out());                   // checks the launches above as well
         chi = pin[OUT_CHI]; scale = pin[OUT_SCALE]; ok = pin[OUT_OK] != 0.;
         return ORBX_OK;
     }
-    // a failed launch or copy ends the loop through stop() and comes back as the call's status
     void linearize(bool first, bool with_errors, double &chi, double &maxdiag) { if (status == ORBX_OK) status = do_linearize(first, with_errors, chi, maxdiag); }
     void trial(double lambda, double &chi, double &scale, bool &ok) { if (status == ORBX_OK) status = do_trial(lambda, chi, scale, ok); }
-    void accept() { cur ^= 1; }
-    void reject() {}
 };
-}   // namespace
 
-namespace {
-// what orbm_bundle_adjustment asks of the common driver (NULL: LocalBundleAdjustment)
-struct BaArgs { int n_iterations, robust; orbp_ba_stats *stats; };
-
-int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase, const volatile uint8_t *stop,
-            orbp_lba_stats *stats, double *split_ms, int32_t *split_count, const BaArgs *ba = nullptr)
+// What both drivers do between their checks and their first activate(): the CSR by local key frame, the workspace, the upload and
+// k_lba_init.  with_spd: also the two parts orbm_spd_solve_device asks for (BundleAdjustment).  `in` outlives the call's orbm_sync().
+int lba_setup(orbm_matcher *m, LbaGpu &g, InBlock &in, const orbp_lba_problem *p, const float *xw, const volatile uint8_t *stop,
+              bool with_spd, double *split_ms, int32_t *split_count)
 {
-    char text[200];
-    if (ba) {                                                   // no entry check of `stop` (src/Optimizer.cc:49-188 has none)
-        if (orbp_ba_check(p, ba->n_iterations, Tcw_local, xw, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
-    } else {
-        if (orbp_lba_check(p, Tcw_local, xw, erase, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
-        if (orbp_lba_read_stop(stop)) return ORBP_LBA_STOPPED;      // :655-657: nothing is launched
-    }
+    LbaDev &d = g.d;
     const int K = p->n_local, NK = p->n_local + p->n_fixed, P = p->n_points, E = p->edge_off[P];
-    // decided from the counts, before the handle is touched
-    if (ba && (K > ORBM_BA_MAX_KFS || (long long)K * P > ORBM_BA_MAX_TABLE))
-        return mfail(ORBX_E_CAPACITY, "bundle_adjustment: beyond %d key frames / %d entries of the key frame x point table", ORBM_BA_MAX_KFS,
-                     ORBM_BA_MAX_TABLE);
-    if (!m) return orbm_no_handle();
-    MHIPCHK(hipSetDevice(m->device));
-    // k_lba_solve is one workgroup: its time grows with the cube of 6 K and a call runs it up to 150 times (DESIGN.md section 22
-    // has the time at the cap)
-    if (!ba && ((long long)K * P > (1ll << 28) || K > ORBM_LBA_MAX_LOCAL))
-        return mfail(ORBX_E_CAPACITY, "request beyond %d local key frames / 2^28 table entries", ORBM_LBA_MAX_LOCAL);
     // CSR by local key frame, edges ascending
     std::vector<int32_t> kf_off((size_t)K + 1, 0), kf_edge;
     for (int e = 0; e < E; e++)
@@ -560,39 +502,28 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
             if (p->edge_kf[e] < K) kf_edge[at[p->edge_kf[e]]++] = e;
     }
     // the workspace: 8-byte parts first
-    LbaDev d = {};
     d.K = K; d.NK = NK; d.P = P; d.E = E; d.n = 6 * K;
-    size_t need = 0;
-    auto take = [&need](size_t bytes) { const size_t at = need; need += (bytes + 63) & ~(size_t)63; return at; };
-    const size_t n = (size_t)d.n, szd = sizeof(double);
-    const size_t o_est0 = take(7 * szd * NK), o_est1 = take(7 * szd * NK), o_X0 = take(3 * szd * P), o_X1 = take(3 * szd * P),
-                 o_err = take(3 * szd * E), o_chi = take(szd * E), o_blk = take(LBA_NBLK * szd * E), o_Hll = take(6 * szd * P),
-                 o_bl = take(3 * szd * P), o_Dinv = take(9 * szd * P), o_Db = take(3 * szd * P), o_max = take(szd * ((size_t)K + P)),
-                 o_term = take(szd * ((size_t)K + P)), o_Hpp = take(21 * szd * K), o_bp = take(6 * szd * K), o_S = take(szd * n * n),
-                 o_bs = take(szd * n), o_xp = take(szd * n), o_out = take(64),
-                 o_res = take(64 * (size_t)K + 12 * (size_t)P + (size_t)E),       // the results back to back: one copy home
-                 o_ept = take(4 * (size_t)E), o_table = take(4 * (size_t)K * P), o_level = take((size_t)E),
-                 o_ka = take((size_t)K), o_pa = take((size_t)P);
-    const size_t o_spd_y = ba ? take(szd * n) : 0, o_spd_flag = ba ? take(64) : 0;
-    MTRY(orbm_ensure_lba(m, need));
+    const size_t n = (size_t)d.n, sK = (size_t)K, sNK = (size_t)NK, sP = (size_t)P, sE = (size_t)E;
+    WsLayout ws;
+    ws.take(d.est[0], 7 * sNK); ws.take(d.est[1], 7 * sNK); ws.take(d.X[0], 3 * sP); ws.take(d.X[1], 3 * sP);
+    ws.take(d.err, 3 * sE); ws.take(d.chi_e, sE); ws.take(d.blk, LBA_NBLK * sE); ws.take(d.Hll, 6 * sP);
+    ws.take(d.bl, 3 * sP); ws.take(d.Dinv, 9 * sP); ws.take(d.Db, 3 * sP);
+    ws.take(d.kmax, sK + sP); ws.take(d.kterm, sK + sP);            // the key frames', then the points': pmax and pterm below
+    ws.take(d.Hpp, 21 * sK); ws.take(d.bp, 6 * sK); ws.take(d.S, n * n); ws.take(d.bs, n); ws.take(d.xp, n); ws.take(d.out, 8);
+    uint8_t *res = nullptr;
+    ws.take(res, 64 * sK + 12 * sP + sE);   // the results back to back: one copy home
+    ws.take(d.edge_pt, sE); ws.take(d.table, sK * sP); ws.take(d.level, sE); ws.take(d.kf_active, sK); ws.take(d.pt_active, sP);
+    if (with_spd) { ws.take(g.spd_y, n); ws.take(g.spd_flag, 16); }
+    MTRY(orbm_ensure_opt(m, ws.bytes()));
     MTRY(orbm_arena_begin(m));
     hipStream_t s = m->stream;
-    uint8_t *w = m->d_lba;
-    d.est[0] = (double *)(w + o_est0); d.est[1] = (double *)(w + o_est1); d.X[0] = (double *)(w + o_X0); d.X[1] = (double *)(w + o_X1);
-    d.err = (double *)(w + o_err); d.chi_e = (double *)(w + o_chi); d.blk = (double *)(w + o_blk); d.Hll = (double *)(w + o_Hll);
-    d.bl = (double *)(w + o_bl); d.Dinv = (double *)(w + o_Dinv); d.Db = (double *)(w + o_Db);
-    d.kmax = (double *)(w + o_max); d.pmax = d.kmax + K; d.kterm = (double *)(w + o_term); d.pterm = d.kterm + K;
-    d.Hpp = (double *)(w + o_Hpp); d.bp = (double *)(w + o_bp); d.S = (double *)(w + o_S); d.bs = (double *)(w + o_bs);
-    d.xp = (double *)(w + o_xp); d.out = (double *)(w + o_out); d.out_Tcw = (float *)(w + o_res); d.out_xw = d.out_Tcw + 16 * (size_t)K;
-    d.erase = (uint8_t *)(d.out_xw + 3 * (size_t)P); d.edge_pt = (int32_t *)(w + o_ept); d.table = (int32_t *)(w + o_table); d.level = w + o_level;
-    d.kf_active = w + o_ka; d.pt_active = w + o_pa;
-
-    InBlock in(m);
-    const int pT = in.add(p->Tcw, 64 * (size_t)NK), pc = in.add(p->cam, 20 * (size_t)NK), pf = in.add(p->local_fixed, (size_t)K),
-              px = in.add(xw, 12 * (size_t)P), po = in.add(p->edge_off, 4 * ((size_t)P + 1)), pk = in.add(p->edge_kf, 4 * (size_t)E),
-              pb = in.add(p->obs, 8 * (size_t)E), pu = in.add(p->u_right, 4 * (size_t)E), pi = in.add(p->inv_sigma2, 4 * (size_t)E),
-              pko = in.add(kf_off.data(), 4 * ((size_t)K + 1)), pke = in.add(kf_edge.data(), 4 * kf_edge.size());
-    LbaGpu g;
+    ws.bind(m->d_opt.get());
+    d.pmax = d.kmax + K; d.pterm = d.kterm + K;
+    d.out_Tcw = (float *)res; d.out_xw = d.out_Tcw + 16 * sK; d.erase = (uint8_t *)(d.out_xw + 3 * sP);
+    const int pT = in.add(p->Tcw, 64 * sNK), pc = in.add(p->cam, 20 * sNK), pf = in.add(p->local_fixed, sK), px = in.add(xw, 12 * sP),
+              po = in.add(p->edge_off, 4 * (sP + 1)), pk = in.add(p->edge_kf, 4 * sE), pb = in.add(p->obs, 8 * sE),
+              pu = in.add(p->u_right, 4 * sE), pi = in.add(p->inv_sigma2, 4 * sE), pko = in.add(kf_off.data(), 4 * (sK + 1)),
+              pke = in.add(kf_edge.data(), 4 * kf_edge.size());
     if (split_ms && split_count) g.prof.start(split_ms, split_count, ORBM_LBA_SPLIT_N);
     g.prof.pre(s);
     MTRY(in.upload(s));
@@ -600,71 +531,94 @@ int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float 
     d.Tcw = in.at<float>(pT); d.cam = in.at<float>(pc); d.local_fixed = in.at<uint8_t>(pf); d.xw_in = in.at<float>(px);
     d.edge_off = in.dev_at<int32_t>(po); d.edge_kf = in.at<int32_t>(pk); d.obs = in.at<float>(pb); d.u_right = in.at<float>(pu);
     d.inv_sigma2 = in.at<float>(pi); d.kf_off = in.dev_at<int32_t>(pko); d.kf_edge = in.at<int32_t>(pke);
-
-    g.m = m; g.d = d; g.s = s; g.stop_flag = stop; g.pin = (double *)m->lba_pin.get();
-    if (ba) { g.spd_y = (double *)(w + o_spd_y); g.spd_flag = (int *)(w + o_spd_flag); }
+    g.m = m; g.s = s; g.stop_flag = stop; g.pin = (double *)m->opt_pin.get(); g.out = d.out;
     g.prof.pre(s);
-    if ((size_t)K * P) MHIPCHK(hipMemsetAsync(d.table, 0xFF, 4 * (size_t)K * P, s));
+    if (sK * sP) MHIPCHK(hipMemsetAsync(d.table, 0xFF, 4 * sK * sP, s));
     MHIPCHK(hipMemsetAsync(d.out, 0, 64, s));
-    hipLaunchKernelGGL(k_lba_init, dim3(blocks_for(std::max(std::max(NK, P), E))), dim3(LBA_T), 0, s, d);
+    hipLaunchKernelGGL(k_lba_init, dim3(opt_blocks(std::max(std::max(NK, P), E), LBA_T)), dim3(LBA_T), 0, s, d);
     MHIPCHK(hipGetLastError());
     g.prof.post(ORBM_LBA_SPLIT_SETUP, s);
+    return ORBX_OK;
+}
 
-    LbaRun run = {0, 0, 0, 0};
-    int n_active = 0, n_level1 = 0;
-    if (ba) {                                                   // src/Optimizer.cc:187-235
-        g.robust = ba->robust ? LBA_KERNEL_BA : LBA_KERNEL_NONE;
-        MTRY(g.activate(n_active, n_level1));                   // :187
-        if (n_active > 0) {
-            lba_optimize(g, ba->n_iterations, run);             // :188
-            MTRY(g.status);
-        }
-        SPLIT_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s,        // a point without edges keeps its bits: float -> double -> float
-                  hipLaunchKernelGGL(k_lba_output, dim3(blocks_for(std::max(K, P))), dim3(LBA_T), 0, s, d, g.cur));
-        MHIPCHK(hipGetLastError());
-        void *const host[2] = {Tcw_local, xw};
-        const size_t parts[2] = {64 * (size_t)K, 12 * (size_t)P};
-        g.prof.pre(s);
-        MTRY(orbm_d2h_split(m, host, parts, 2, d.out_Tcw, s));
-        g.prof.post(ORBM_LBA_SPLIT_DOWNLOAD, s);
-        MTRY(orbm_sync(m, s));
-        g.prof.drain();
-        if (ba->stats) *ba->stats = {run.iterations, run.trials, run.lambda, run.chi2};
-        return ORBX_OK;
-    }
+// Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778): two rounds, the flagging passes, three result parts
+int lba_run(orbm_matcher *m, const orbp_lba_problem *p, float *Tcw_local, float *xw, uint8_t *erase, const volatile uint8_t *stop,
+            orbp_lba_stats *stats, double *split_ms, int32_t *split_count)
+{
+    char text[200];
+    if (orbp_lba_check(p, Tcw_local, xw, erase, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
+    if (orbp_lba_read_stop(stop)) return ORBP_LBA_STOPPED;          // :655-657: nothing is launched
+    if (!m) return orbm_no_handle();
+    MHIPCHK(hipSetDevice(m->device));
+    // k_lba_solve is one workgroup: its time grows with the cube of 6 K and a call runs it up to 150 times (DESIGN.md section 22
+    // has the time at the cap)
+    if ((long long)p->n_local * p->n_points > (1ll << 28) || p->n_local > ORBM_LBA_MAX_LOCAL)
+        return mfail(ORBX_E_CAPACITY, "request beyond %d local key frames / 2^28 table entries", ORBM_LBA_MAX_LOCAL);
+    InBlock in(m); LbaGpu g;
+    MTRY(lba_setup(m, g, in, p, xw, stop, false, split_ms, split_count));
+    const LbaDev &d = g.d; hipStream_t s = g.s;
     orbp_lba_stats st;
     memset(&st, 0, sizeof st);
+    LmRun run = {0, 0, 0, 0};
+    int n_active = 0, n_level1 = 0;
     MTRY(g.activate(n_active, n_level1));                       // :659
     if (n_active > 0) {
-        lba_optimize(g, 5, run);                                // :660
+        lm_optimize(g, 5, run);                                 // :660
         MTRY(g.status);
         st.iterations[0] = run.iterations; st.trials[0] = run.trials; st.lambda = run.lambda; st.chi2 = run.chi2;
     }
     if (!orbp_lba_read_stop(stop)) {                            // :662-709
         st.second_round = 1;
-        SPLIT_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s, hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 0));
+        SPLIT_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s, hipLaunchKernelGGL(k_lba_flag, dim3(opt_blocks(d.E, LBA_T)), dim3(LBA_T), 0, s, d, g.cur, 0));
         g.robust = LBA_KERNEL_NONE;
         MTRY(g.activate(n_active, n_level1));                   // :706
         st.n_level1 = n_level1;
         if (n_active > 0) {
-            lba_optimize(g, 10, run);                           // :707
+            lm_optimize(g, 10, run);                            // :707
             MTRY(g.status);
             st.iterations[1] = run.iterations; st.trials[1] = run.trials; st.lambda = run.lambda; st.chi2 = run.chi2;
         }
     }
     g.prof.pre(s);
-    hipLaunchKernelGGL(k_lba_flag, dim3(blocks_for(E)), dim3(LBA_T), 0, s, d, g.cur, 1);                  // :715-743
-    hipLaunchKernelGGL(k_lba_output, dim3(blocks_for(std::max(K, P))), dim3(LBA_T), 0, s, d, g.cur);     // :762-777
+    hipLaunchKernelGGL(k_lba_flag, dim3(opt_blocks(d.E, LBA_T)), dim3(LBA_T), 0, s, d, g.cur, 1);          // :715-743
+    hipLaunchKernelGGL(k_lba_output, dim3(opt_blocks(std::max(d.K, d.P), LBA_T)), dim3(LBA_T), 0, s, d, g.cur);     // :762-777
     MHIPCHK(hipGetLastError());
     g.prof.post(ORBM_LBA_SPLIT_FLAG_OUTPUT, s);
-    void *const host[3] = {Tcw_local, xw, erase};
-    const size_t parts[3] = {64 * (size_t)K, 12 * (size_t)P, (size_t)E};
-    MTRY(orbm_d2h_split(m, host, parts, 3, d.out_Tcw, s));      // one copy into the arena; the outputs are written at orbm_sync
-    g.prof.post(ORBM_LBA_SPLIT_DOWNLOAD, s);
-    MTRY(orbm_sync(m, s));
-    g.prof.drain();
+    MTRY(g.download({Tcw_local, xw, erase}, {64 * (size_t)d.K, 12 * (size_t)d.P, (size_t)d.E}, d.out_Tcw, ORBM_LBA_SPLIT_DOWNLOAD));
     if (stats) *stats = st;
     return ORBP_LBA_DONE;
+}
+
+// Optimizer::BundleAdjustment (src/Optimizer.cc:49-237): one round with the call's robust kind, the many-workgroup solve of
+// orbm_spd.hip in place of k_lba_solve, two result parts
+int ba_run(orbm_matcher *m, const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local, float *xw,
+           const volatile uint8_t *stop, orbp_ba_stats *stats, double *split_ms, int32_t *split_count)
+{
+    char text[200];                                             // no entry check of `stop` (src/Optimizer.cc:49-188 has none)
+    if (orbp_ba_check(p, n_iterations, Tcw_local, xw, text, (int)sizeof text) != ORBX_OK) return mfail(ORBX_E_INVALID, "%s", text);
+    // decided from the counts, before the handle is touched
+    if (p->n_local > ORBM_BA_MAX_KFS || (long long)p->n_local * p->n_points > ORBM_BA_MAX_TABLE)
+        return mfail(ORBX_E_CAPACITY, "bundle_adjustment: beyond %d key frames / %d entries of the key frame x point table", ORBM_BA_MAX_KFS,
+                     ORBM_BA_MAX_TABLE);
+    if (!m) return orbm_no_handle();
+    MHIPCHK(hipSetDevice(m->device));
+    InBlock in(m); LbaGpu g;
+    MTRY(lba_setup(m, g, in, p, xw, stop, true, split_ms, split_count));
+    const LbaDev &d = g.d; hipStream_t s = g.s;
+    LmRun run = {0, 0, 0, 0};                                   // src/Optimizer.cc:187-235
+    int n_active = 0, n_level1 = 0;
+    g.robust = robust ? LBA_KERNEL_BA : LBA_KERNEL_NONE;
+    MTRY(g.activate(n_active, n_level1));                       // :187
+    if (n_active > 0) {
+        lm_optimize(g, n_iterations, run);                      // :188
+        MTRY(g.status);
+    }
+    SPLIT_GROUP(g.prof, ORBM_LBA_SPLIT_FLAG_OUTPUT, s,            // a point without edges keeps its bits: float -> double -> float
+              hipLaunchKernelGGL(k_lba_output, dim3(opt_blocks(std::max(d.K, d.P), LBA_T)), dim3(LBA_T), 0, s, d, g.cur));
+    MHIPCHK(hipGetLastError());
+    MTRY(g.download({Tcw_local, xw}, {64 * (size_t)d.K, 12 * (size_t)d.P}, d.out_Tcw, ORBM_LBA_SPLIT_DOWNLOAD));
+    if (stats) *stats = {run.iterations, run.trials, run.lambda, run.chi2};
+    return ORBX_OK;
 }
 }   // namespace
 
@@ -680,20 +634,15 @@ extern "C" int orbm_local_bundle_adjustment_split(orbm_matcher *m, const orbp_lb
     if (!split_ms || !split_count) return mfail(ORBX_E_INVALID, "local_bundle_adjustment_split: NULL split_ms or split_count");
     return lba_run(m, p, Tcw_local, xw, erase, stop, stats, split_ms, split_count);
 }
-
-// Optimizer::BundleAdjustment (src/Optimizer.cc:49-237): the driver above with one optimize(n_iterations), the call's robust kernel
-// and the many-workgroup solve of orbm_spd.hip in place of k_lba_solve
 extern "C" int orbm_bundle_adjustment(orbm_matcher *m, const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local, float *xw,
                                       const volatile uint8_t *stop, orbp_ba_stats *stats)
 {
-    const BaArgs ba = {n_iterations, robust, stats};
-    return lba_run(m, p, Tcw_local, xw, nullptr, stop, nullptr, nullptr, nullptr, &ba);
+    return ba_run(m, p, n_iterations, robust, Tcw_local, xw, stop, stats, nullptr, nullptr);
 }
 extern "C" int orbm_bundle_adjustment_split(orbm_matcher *m, const orbp_lba_problem *p, int n_iterations, int robust, float *Tcw_local,
                                             float *xw, const volatile uint8_t *stop, orbp_ba_stats *stats, double *split_ms,
                                             int32_t *split_count)
 {
     if (!split_ms || !split_count) return mfail(ORBX_E_INVALID, "bundle_adjustment_split: NULL split_ms or split_count");
-    const BaArgs ba = {n_iterations, robust, stats};
-    return lba_run(m, p, Tcw_local, xw, nullptr, stop, nullptr, split_ms, split_count, &ba);
+    return ba_run(m, p, n_iterations, robust, Tcw_local, xw, stop, stats, split_ms, split_count);
 }

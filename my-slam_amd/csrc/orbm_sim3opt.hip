@@ -36,6 +36,7 @@ __device__ __forceinline__ void s3o_reduce(double *acc, S3oShared &sh)
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
     for (int v = 0; v < NV; v++) {
+        // the butterfly of opt_wave_sum (orbm_opt.h), written out: as a call it leaves this kernel another register allocation
         double a = acc[v];
 #pragma unroll
         for (int m = 1; m < 64; m <<= 1) a += __shfl_xor(a, m, 64);

@@ -28,6 +28,7 @@
 // by LDS), and at n = 3072 the first trailing update is 2016 tiles for 256 CUs.  A wider panel makes k_spd_diag, the one
 // single-workgroup step, longer; a narrower one adds launches, which dominate below n of about 1000.
 #include "orbm_internal.h"
+#include "ws_layout.h"
 #include "../../include/orbm.h"
 
 #define SPD_NB 48
@@ -262,24 +263,24 @@ extern "C" int orbm_spd_solve_timed(orbm_matcher *m, const double *A, const doub
         return mfail(ORBX_E_INVALID, "spd_solve_timed: bad argument");
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
-    const size_t nn = (size_t)n * n * sizeof(double), nv = ((size_t)n * sizeof(double) + 63) & ~(size_t)63;
-    MTRY(orbm_ensure_lba(m, 2 * nn + 4 * nv + 64));
+    const size_t sn = (size_t)n, nn = sn * sn * sizeof(double);
+    SpdDev d = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n};
+    double *dA0 = nullptr, *db0 = nullptr;  // the uploaded system: every repetition starts from a copy of it
+    WsLayout ws;
+    ws.take(d.A, sn * sn); ws.take(dA0, sn * sn); ws.take(d.b, sn); ws.take(db0, sn); ws.take(d.y, sn); ws.take(d.x, sn); ws.take(d.flag, 16);
+    MTRY(orbm_ensure_opt(m, ws.bytes()));
     hipStream_t s = m->stream;
-    uint8_t *w = m->d_lba;
-    double *dA = (double *)w, *dA0 = (double *)(w + nn), *db = (double *)(w + 2 * nn), *db0 = (double *)(w + 2 * nn + nv),
-           *dy = (double *)(w + 2 * nn + 2 * nv), *dx = (double *)(w + 2 * nn + 3 * nv);
-    int *flag = (int *)(w + 2 * nn + 4 * nv);
+    ws.bind(m->d_opt.get());
     MHIPCHK(hipMemcpyAsync(dA0, A, nn, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemcpyAsync(db0, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
+    MHIPCHK(hipMemcpyAsync(db0, b, sn * sizeof(double), hipMemcpyHostToDevice, s));
     hipEvent_t ev[3];
     for (int i = 0; i < 3; i++) MHIPCHK(hipEventCreate(&ev[i]));
     std::vector<float> tf, ts;
-    const SpdDev d = {dA, db, dy, dx, flag, nullptr, n};
     int rc = ORBX_OK;
     for (int r = 0; r < reps && rc == ORBX_OK; r++) {
-        hipError_t e = hipMemcpyAsync(dA, dA0, nn, hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemcpyAsync(db, db0, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, s);
-        if (e == hipSuccess) e = hipMemsetAsync(flag, 0, sizeof(int), s);
+        hipError_t e = hipMemcpyAsync(d.A, dA0, nn, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemcpyAsync(d.b, db0, sn * sizeof(double), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipMemsetAsync(d.flag, 0, sizeof(int), s);
         if (e == hipSuccess) e = hipEventRecord(ev[0], s);
         spd_factor(d, s);
         if (e == hipSuccess) e = hipEventRecord(ev[1], s);
@@ -306,18 +307,19 @@ extern "C" int orbm_spd_solve_f64(orbm_matcher *m, const double *A, const double
     if (n > ORBM_SPD_MAX_N) return mfail(ORBX_E_CAPACITY, "spd_solve: n = %d beyond %d", n, ORBM_SPD_MAX_N);
     if (!m) return orbm_no_handle();
     MHIPCHK(hipSetDevice(m->device));
-    const size_t nn = (size_t)n * n * sizeof(double), nv = ((size_t)n * sizeof(double) + 63) & ~(size_t)63;
-    MTRY(orbm_ensure_lba(m, nn + 3 * nv + 64));
+    const size_t sn = (size_t)n;
+    SpdDev d = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, n};
+    WsLayout ws;
+    ws.take(d.A, sn * sn); ws.take(d.b, sn); ws.take(d.y, sn); ws.take(d.x, sn); ws.take(d.flag, 16);
+    MTRY(orbm_ensure_opt(m, ws.bytes()));
     hipStream_t s = m->stream;
-    uint8_t *w = m->d_lba;
-    double *dA = (double *)w, *db = (double *)(w + nn), *dy = (double *)(w + nn + nv), *dx = (double *)(w + nn + 2 * nv);
-    int *flag = (int *)(w + nn + 3 * nv);
-    MHIPCHK(hipMemcpyAsync(dA, A, nn, hipMemcpyHostToDevice, s));
-    MHIPCHK(hipMemcpyAsync(db, b, (size_t)n * sizeof(double), hipMemcpyHostToDevice, s));
-    MTRY(orbm_spd_solve_device(dA, db, dy, dx, flag, nullptr, n, s));
+    ws.bind(m->d_opt.get());
+    MHIPCHK(hipMemcpyAsync(d.A, A, sn * sn * sizeof(double), hipMemcpyHostToDevice, s));
+    MHIPCHK(hipMemcpyAsync(d.b, b, sn * sizeof(double), hipMemcpyHostToDevice, s));
+    MTRY(orbm_spd_solve_device(d.A, d.b, d.y, d.x, d.flag, nullptr, n, s));
     int failed = 0;
-    MHIPCHK(hipMemcpyAsync(x, dx, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    MHIPCHK(hipMemcpyAsync(&failed, flag, sizeof(int), hipMemcpyDeviceToHost, s));
+    MHIPCHK(hipMemcpyAsync(x, d.x, sn * sizeof(double), hipMemcpyDeviceToHost, s));
+    MHIPCHK(hipMemcpyAsync(&failed, d.flag, sizeof(int), hipMemcpyDeviceToHost, s));
     MHIPCHK(hipStreamSynchronize(s));
     *ok = failed ? 0 : 1;
     return ORBX_OK;

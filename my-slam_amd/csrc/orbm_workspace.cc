@@ -135,10 +135,10 @@ int orbm_ensure_fuse(orbm_matcher *m, size_t need)
     MHIPCHK(hipStreamSynchronize(m->stream));
     return m->d_fuse.grow(need + need / 2, mfail, "Fuse batch workspace");
 }
-int orbm_ensure_lba(orbm_matcher *m, size_t need)
+int orbm_ensure_opt(orbm_matcher *m, size_t need)
 {
-    MTRY(m->lba_pin.grow(64, mfail, "bundle adjustment read-back block"));
-    if (need <= m->d_lba.bytes()) return ORBX_OK;
+    MTRY(m->opt_pin.grow(64, mfail, "optimizer read-back block"));
+    if (need <= m->d_opt.bytes()) return ORBX_OK;
     MHIPCHK(hipStreamSynchronize(m->stream));
-    return m->d_lba.grow(need + need / 2, mfail, "bundle adjustment workspace");
+    return m->d_opt.grow(need + need / 2, mfail, "optimizer workspace");
 }

@@ -1,7 +1,7 @@
 // orbp_ba.cc -- Optimizer::BundleAdjustment (src/Optimizer.cc:49-237 of WChen09/My-SLAM, on g2o) over the flat problem of
 // include/orbp.h: orbp_bundle_adjustment.  One optimize(n_iterations) of the graph LocalBundleAdjustment also builds: the edges,
-// Huber, the Schur terms and the Levenberg loop are csrc/orbp_lba_body.h, the sums in edge order and the dense Cholesky
-// csrc/orbp_lba_host.h.  This file owns the call's own semantics: no entry check of `stop`, the robust switch, the one round.
+// Huber and the Schur terms are csrc/orbp_lba_body.h, the Levenberg loop csrc/orbp_lm_body.h, the sums in edge order and the dense
+// Cholesky csrc/orbp_lba_host.h.  This file owns the call's semantics: no entry check of `stop`, the robust switch, the one round.
 #include <cstdio>
 #include <cstring>
 #include "../../include/orbp.h"
@@ -10,7 +10,7 @@
 #include "orbp_lba_body.h"
 #include "orbp_lba_host.h"
 
-static_assert(ORBP_BA_MAX_ITERATIONS == LBA_MAX_ITERATIONS, "lba_optimize's loop bound is the bound of n_iterations");
+static_assert(ORBP_BA_MAX_ITERATIONS == LM_MAX_ITERATIONS, "lm_optimize's loop bound is the bound of n_iterations");
 
 int orbp_ba_check(const orbp_lba_problem *p, int n_iterations, const float *Tcw_local, const float *xw, char *text, int text_size)
 {
@@ -38,9 +38,9 @@ extern "C" int orbp_bundle_adjustment(const orbp_lba_problem *p, int n_iteration
     LbaHost h;
     h.prepare(p, xw, stop);
     h.robust = robust ? LBA_KERNEL_BA : LBA_KERNEL_NONE;        // :129-134, :158-163
-    LbaRun run = {0, 0, 0, 0};
+    LmRun run = {0, 0, 0, 0};
     h.activate();                                               // :187
-    if (h.n_active > 0) lba_optimize(h, n_iterations, run);     // :188
+    if (h.n_active > 0) lm_optimize(h, n_iterations, run);      // :188
     for (int k = 0; k < h.K; k++) lba_se3_to_Tcw(h.est[k], Tcw_local + 16 * (size_t)k);    // :193-210
     for (int pt = 0; pt < h.P; pt++)                            // :213-235; a point without edges is vbNotIncludedMP
         if (p->edge_off[pt + 1] > p->edge_off[pt])

@@ -1,6 +1,6 @@
 // orbp_eg.cc -- Optimizer::OptimizeEssentialGraph (src/Optimizer.cc:781-1044 of WChen09/My-SLAM, on g2o) over the flat problem of
-// include/orbp.h: orbp_optimize_essential_graph.  The edges' arithmetic is csrc/orbp_eg_body.h, the Levenberg loop lba_optimize
-// (csrc/orbp_lba_body.h) with the user's initial lambda of :794.  This file owns the argument checks, the sums in edge order (g2o's
+// include/orbp.h: orbp_optimize_essential_graph.  The edges' arithmetic is csrc/orbp_eg_body.h, the Levenberg loop lm_optimize
+// (csrc/orbp_lm_body.h) with the user's initial lambda of :794.  This file owns the argument checks, the sums in edge order (g2o's
 // active edges are sorted by id, which is insertion order) and the linear solve: BlockSolver_7_3 has Hpp alone, and the essential
 // graph's Hpp is a band (spanning tree and covisibility) plus a few long rows (loop edges), so it is kept as an envelope.
 #include <algorithm>
@@ -11,7 +11,7 @@
 #include "../../include/orbx.h"
 #include "orbp_internal.h"
 #include "orbp_eg_body.h"
-#include "orbp_lba_body.h"
+#include "orbp_lm_body.h"
 
 int orbp_eg_check(const orbp_eg_problem *p, int n_iterations, const float *Tcw, const float *xw, char *text, int text_size)
 {
@@ -46,7 +46,7 @@ static thread_local int eg_dense = 0;
 extern "C" void orbp_eg_set_dense(int dense) { eg_dense = dense; }
 
 namespace {
-// "the passes of a problem" for lba_optimize on the host
+// "the passes of a problem" for lm_optimize on the host
 struct EgHost {
     const orbp_eg_problem *p;
     int n, nf, N, E;                        // key frames, free ones, unknowns = 7 nf, edges
@@ -141,7 +141,7 @@ struct EgHost {
         }
     }
     // (H + lambda I) = L L^T inside the envelope, L y = b, L^T x = y; every entry and every sum as the dense factorisation of
-    // orbp_lba_host.h computes them, minus the terms that are structurally zero
+    // the bundle adjustments (LbaHost::cholesky_solve) computes them, minus the terms that are structurally zero
     bool solve(double lambda)
     {
         for (int i = 0; i < N; i++) {
@@ -179,7 +179,7 @@ struct EgHost {
         ok = solve(lambda);
         if (!ok) std::fill(x.begin(), x.end(), 0.);
         scale = 0;
-        for (int i = 0; i < N; i++) scale += lba_scale_term(x[i], b[i], lambda);
+        for (int i = 0; i < N; i++) scale += lm_scale_term(x[i], b[i], lambda);
         for (int k = 0; k < n; k++)
             if (free_of[k] >= 0) est[k] = s3o_oplus(est[k], &x[7 * (size_t)free_of[k]], fix_scale);
         chi = errors();
@@ -199,8 +199,8 @@ extern "C" int orbp_optimize_essential_graph(const orbp_eg_problem *p, int n_ite
     }
     EgHost h;
     h.prepare(p);
-    LbaRun run = {0, 0, 0, 0};
-    if (h.E > 0 && h.nf > 0) lba_optimize(h, n_iterations, run, 1e-16);     // :794, :986-987
+    LmRun run = {0, 0, 0, 0};
+    if (h.E > 0 && h.nf > 0) lm_optimize(h, n_iterations, run, 1e-16);      // :794, :986-987
     if (run.iterations == 0) h.chi2_initial = h.errors();
     for (int k = 0; k < h.n; k++) {                                         // :992-1010
         eg_to_Tcw(h.est[k], Tcw + 16 * (size_t)k);

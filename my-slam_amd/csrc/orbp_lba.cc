@@ -1,8 +1,8 @@
 // orbp_lba.cc -- Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778 of WChen09/My-SLAM, on g2o) over the flat problem of
-// include/orbp.h: orbp_local_bundle_adjustment.  The arithmetic of an edge, of a point's 3x3 block, the Schur terms and the Levenberg
-// loop are csrc/orbp_lba_body.h, the text the kernels of orbm_lba.hip run as well; csrc/orbp_lba_host.h owns the order of the sums (edge
-// order, as g2o's active edges are sorted by id) and the dense Cholesky of the reduced system, for this file and orbp_ba.cc; this file
-// owns the two rounds, the two flagging passes and the argument checks.
+// include/orbp.h: orbp_local_bundle_adjustment.  The arithmetic of an edge, of a point's 3x3 block and the Schur terms
+// (csrc/orbp_lba_body.h) and the Levenberg loop (csrc/orbp_lm_body.h) are the text orbm_lba.hip runs as well; csrc/orbp_lba_host.h
+// owns the order of the sums (edge order, as g2o's active edges are sorted by id) and the dense Cholesky of the reduced system,
+// for this file and orbp_ba.cc; this file owns the two rounds, the two flagging passes and the argument checks.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -78,11 +78,11 @@ extern "C" int orbp_local_bundle_adjustment(const orbp_lba_problem *p, float *Tc
 
     orbp_lba_stats st;
     memset(&st, 0, sizeof st);
-    LbaRun run = {0, 0, 0, 0};
+    LmRun run = {0, 0, 0, 0};
     h.robust = LBA_KERNEL_LBA;
     h.activate();                                               // :659
     if (h.n_active > 0) {
-        lba_optimize(h, 5, run);                                // :660
+        lm_optimize(h, 5, run);                                 // :660
         st.iterations[0] = run.iterations; st.trials[0] = run.trials; st.lambda = run.lambda; st.chi2 = run.chi2;
     }
     if (!orbp_lba_read_stop(stop)) {                            // :662-709
@@ -92,7 +92,7 @@ extern "C" int orbp_local_bundle_adjustment(const orbp_lba_problem *p, float *Tc
         h.robust = LBA_KERNEL_NONE;
         h.activate();                                           // :706
         if (h.n_active > 0) {
-            lba_optimize(h, 10, run);                           // :707
+            lm_optimize(h, 10, run);                            // :707
             st.iterations[1] = run.iterations; st.trials[1] = run.trials; st.lambda = run.lambda; st.chi2 = run.chi2;
         }
     }

@@ -9,9 +9,7 @@
 //   constructQuadraticForm          core/base_binary_edge.hpp:55-120, one or both vertices free
 //   VertexSE3Expmap::oplusImpl      types_six_dof_expmap.h:62-65 (exp(update) * estimate); VertexSBAPointXYZ::oplusImpl types_sba.h (+=)
 //   BlockSolver_6_3::solve          core/block_solver.hpp:354-486 (Schur complement), setLambda :564-589
-//   OptimizationAlgorithmLevenberg  core/optimization_algorithm_levenberg.cpp:61-164 (with this fork's _nBad stop :154-161),
-//                                   computeLambdaInit :166-180, computeScale :182-189; driven by SparseOptimizer::optimize
-//                                   (core/sparse_optimizer.cpp:354-419)
+//   OptimizationAlgorithmLevenberg  the loop itself, lm_optimize, is orbp_lm_body.h
 //
 // Semantics kept (include/orbp.h, orbp_local_bundle_adjustment, lists them for the caller):
 //   rounds        optimize(5); the flagging pass :672-702 (chi2 > 5.991 / 7.815 on the double chi2(), or depth not positive, sets
@@ -37,6 +35,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "orbp_lm_body.h"
 
 #if defined(__HIPCC__)
 #define LBA_HD __host__ __device__ __forceinline__
@@ -54,10 +53,6 @@ struct LbaCam { double fx, fy, cx, cy, bf; };
 #define LBA_HLL 27              // 6
 #define LBA_BL 33               // 3
 #define LBA_HPL 36              // 18
-// the bound of lba_optimize's loop over iterations: LocalBundleAdjustment asks for 5 and 10, BundleAdjustment for up to
-// ORBP_BA_MAX_ITERATIONS (include/orbp.h, the same number); the loop runs min(iterations, this) of them
-#define LBA_MAX_ITERATIONS 100
-#define LBA_MAX_TRIALS 10       // _maxTrialsAfterFailure
 
 // Eigen's Quaterniond(Matrix3d), the branch on the largest diagonal entry written out per case (orbp_sim3opt_body.h s3o_quat_from_R)
 LBA_HD void lba_quat_from_R(const double *R, LbaSe3 &q)
@@ -327,76 +322,5 @@ LBA_HD void lba_sub_Wtx(const double *W, const double *xp, double *cl)
         double s = 0;
         for (int a = 0; a < 6; a++) s += W[3 * a + b] * xp[a];
         cl[b] -= s;
-    }
-}
-// one unknown's term of computeScale (optimization_algorithm_levenberg.cpp:186)
-LBA_HD double lba_scale_term(double x, double b, double lambda) { return x * (lambda * x + b); }
-
-// What one optimize() did: g2o's counters and the state the caller reports (orbp_lba_stats)
-struct LbaRun { int iterations, trials; double lambda, chi2; };
-
-// OptimizationAlgorithmLevenberg::solve inside SparseOptimizer::optimize(iterations), as s3o_optimize (orbp_sim3opt_body.h) is for
-// one vertex, over "the passes of a problem".  Host code on both paths: the host solver's passes add in edge order, the GPU path's
-// passes are kernel launches that add in their trees and hand back one small block a trial.
-//   ctx.stop()                                  terminate()
-//   ctx.linearize(first, errors, chi, maxdiag)  errors: computeActiveErrors + activeRobustChi2 into chi; always buildSystem; first:
-//                                               computeLambdaInit's maximum over the diagonals of the free poses and points.  After
-//                                               an accepted trial the edges hold that trial's errors and the chi2 g2o sums again at
-//                                               the top of the next iteration is the trial's, term for term: it is carried instead.
-//                                               After a rejected trial that ended its iteration (rho is NaN) they are computed anew.
-//   ctx.trial(lambda, chi, scale, ok)           push, setLambda, solve, update, restoreDiagonal, computeActiveErrors,
-//                                               activeRobustChi2, computeScale (without its + 1e-3)
-//   ctx.accept() / ctx.reject()                 discardTop / pop: the edges keep the trial's errors either way
-// user_lambda_init > 0 is setUserLambdaInit's value, which computeLambdaInit returns instead of tau * maxdiag (:168-169;
-// OptimizeEssentialGraph sets 1e-16, orbp_eg_body.h).
-template <class Ctx>
-static inline void lba_optimize(Ctx &ctx, int iterations, LbaRun &run, double user_lambda_init = 0)
-{
-    double lambda = 0, ni = 2, current = 0;
-    int n_bad = 0;
-    bool fresh = false;                                     // the edges hold the errors of the current estimates
-    run.iterations = run.trials = 0;
-    run.lambda = run.chi2 = 0;
-    for (int it = 0; it < LBA_MAX_ITERATIONS; it++) {
-        if (it >= iterations || ctx.stop()) break;
-        double chi = 0, maxdiag = 0;
-        ctx.linearize(it == 0, !fresh, chi, maxdiag);
-        if (!fresh) current = chi;
-        if (it == 0) { lambda = user_lambda_init > 0 ? user_lambda_init : 1e-5 * maxdiag; ni = 2; n_bad = 0; }    // _tau = 1e-5
-        const double ini = current;
-        double rho = 0;
-        int qmax = 0;
-        do {
-            double temp = 0, scale = 0;
-            bool ok2 = false;
-            ctx.trial(lambda, temp, scale, ok2);
-            if (!ok2) temp = 1.7976931348623157e308;
-            rho = current - temp;
-            scale += 1e-3;
-            rho /= scale;
-            if (rho > 0 && isfinite(temp)) {
-                const double t = 2 * rho - 1;
-                double alpha = 1. - t * t * t;
-                alpha = fmin(alpha, 2. / 3.);
-                lambda *= fmax(1. / 3., alpha);
-                ni = 2;
-                current = temp;
-                fresh = true;
-                ctx.accept();
-            } else {
-                lambda *= ni;
-                ni *= 2;
-                fresh = false;
-                ctx.reject();
-            }
-            qmax++;
-            run.trials++;
-        } while (rho < 0 && qmax < LBA_MAX_TRIALS && !ctx.stop());
-        run.iterations++;
-        run.lambda = lambda;
-        run.chi2 = current;
-        if (qmax == LBA_MAX_TRIALS || rho == 0) break;
-        if ((ini - current) * 1e3 < ini) n_bad++; else n_bad = 0;
-        if (n_bad >= 3) break;
     }
 }

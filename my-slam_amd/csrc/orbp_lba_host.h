@@ -1,4 +1,4 @@
-// orbp_lba_host.h -- "the passes of a problem" for lba_optimize (orbp_lba_body.h) on the host, shared by orbp_lba.cc
+// orbp_lba_host.h -- "the passes of a problem" for lm_optimize (orbp_lm_body.h) on the host, shared by orbp_lba.cc
 // (Optimizer::LocalBundleAdjustment) and orbp_ba.cc (Optimizer::BundleAdjustment): the sums in edge order, as g2o's active edges
 // are sorted by id, and the dense Cholesky of the reduced system.  prepare() sets the graph up from the flat problem.
 #pragma once
@@ -185,10 +185,10 @@ struct LbaHost {
             }
             for (int k = 0; k < K; k++)         // computeScale: the poses, then the points
                 if (kf_active[k])
-                    for (int j = 0; j < 6; j++) scale += lba_scale_term(xp[6 * (size_t)k + j], bp[6 * (size_t)k + j], lambda);
+                    for (int j = 0; j < 6; j++) scale += lm_scale_term(xp[6 * (size_t)k + j], bp[6 * (size_t)k + j], lambda);
             for (int pt = 0; pt < P; pt++)
                 if (pt_active[pt])
-                    for (int j = 0; j < 3; j++) scale += lba_scale_term(xl[3 * (size_t)pt + j], bl[3 * (size_t)pt + j], lambda);
+                    for (int j = 0; j < 3; j++) scale += lm_scale_term(xl[3 * (size_t)pt + j], bl[3 * (size_t)pt + j], lambda);
             for (int k = 0; k < K; k++)         // update
                 if (kf_active[k]) est[k] = lba_pose_oplus(est[k], &xp[6 * (size_t)k]);
             for (int pt = 0; pt < P; pt++)
