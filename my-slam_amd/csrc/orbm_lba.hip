@@ -58,7 +58,7 @@ struct LbaDev {
 };
 enum { OUT_CHI = 0, OUT_SCALE = 1, OUT_OK = 2, OUT_MAXDIAG = 3, OUT_ACTIVE = 4, OUT_LEVEL1 = 5 };
 
-__device__ __forceinline__ LbaSe3 load_se3(const double *p) { return {p[0], p[1], p[2], p[3], p[4], p[5], p[6]}; }
+__device__ __forceinline__ LbaSe3 load_se3(const double *p) { return {{p[0], p[1], p[2], p[3]}, p[4], p[5], p[6]}; }
 __device__ __forceinline__ void store_se3(double *p, const LbaSe3 &T)
 {
     p[0] = T.qx; p[1] = T.qy; p[2] = T.qz; p[3] = T.qw; p[4] = T.t0; p[5] = T.t1; p[6] = T.t2;
@@ -70,7 +70,7 @@ __device__ __forceinline__ bool kf_is_free(const LbaDev &d, int k) { return k < 
 __global__ __launch_bounds__(LBA_T) void k_lba_init(LbaDev d)
 {
     const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
-    if (i < d.NK) store_se3(d.est[0] + 7 * i, lba_se3_from_Tcw(d.Tcw + 16 * i));
+    if (i < d.NK) store_se3(d.est[0] + 7 * i, se3_from_Tcw(d.Tcw + 16 * i));
     if (i < d.P) {
         for (int j = 0; j < 3; j++) d.X[0][3 * i + j] = (double)d.xw_in[3 * i + j];
         for (int e = d.edge_off[i]; e < d.edge_off[i + 1]; e++) {
@@ -419,7 +419,7 @@ __global__ __launch_bounds__(LBA_T) void k_lba_flag(LbaDev d, int cur, int final
 __global__ __launch_bounds__(LBA_T) void k_lba_output(LbaDev d, int cur)
 {
     const long long i = (long long)blockIdx.x * LBA_T + threadIdx.x;
-    if (i < d.K) lba_se3_to_Tcw(load_se3(d.est[cur] + 7 * i), d.out_Tcw + 16 * i);
+    if (i < d.K) se3_to_Tcw(load_se3(d.est[cur] + 7 * i), d.out_Tcw + 16 * i);
     if (i < d.P)
         for (int j = 0; j < 3; j++) d.out_xw[3 * i + j] = (float)d.X[cur][3 * i + j];
 }

@@ -116,7 +116,7 @@ __global__ __launch_bounds__(S3O_THREADS) void k_optimize_sim3(
     double *Sout = S12_out + 8 * (long long)p;
 
     for (int i = tid; i < n; i += S3O_THREADS) flags[i] = 0;
-    S3oSim est = {Sin[0], Sin[1], Sin[2], Sin[3], Sin[4], Sin[5], Sin[6], Sin[7]};
+    S3oSim est = {{Sin[0], Sin[1], Sin[2], Sin[3]}, Sin[4], Sin[5], Sin[6], Sin[7]};
     const S3oSim init = est;
     S3oSim err_est = est;
     if (n > 0) s3o_optimize(P, est, err_est, P.fix_scale, 5);                      // :1182

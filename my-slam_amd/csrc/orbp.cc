@@ -1,9 +1,9 @@
-// orbp.cc -- host-side pose solvers behind include/orbp.h (EPnP RANSAC + motion-only pose optimisation).
+// orbp.cc -- the host-side PnP solver behind include/orbp.h (EPnP RANSAC) and the error text of all of orbp.h.
 // Plain C++, fp64, no device code.  Each function names the reference lines it follows; the linear algebra the reference borrows
 // from OpenCV / Eigen is written here.  One EPnP hypothesis (csrc/orbp_epnp_body.h) is shared with the kernel of orbm_pnp.hip, which
-// evaluates the hypotheses of all Relocalization candidates at once; the RANSAC state machine, Refine and PoseOptimization stay here.
+// evaluates the hypotheses of all Relocalization candidates at once; the RANSAC state machine and Refine stay here.  The motion-only
+// pose optimisation is orbp_pose.cc.
 #include <algorithm>
-#include <cfloat>
 #include <climits>
 #include <cmath>
 #include <cstdarg>
@@ -345,337 +345,4 @@ extern "C" int orbp_pnp_find(orbp_pnp *s, uint8_t *inliers, int *n_inliers, floa
     int flag = 0;
     if (!s) return pfail(ORBX_E_INVALID, "solver is NULL");
     return orbp_pnp_iterate(s, s->max_its, &flag, inliers, n_inliers, Tcw);
-}
-
-// -------------------------------------------------------------------------------------------------
-// Motion-only pose optimisation (Optimizer.cc:239-451 on g2o)
-// -------------------------------------------------------------------------------------------------
-namespace {
-struct Quat { double w, x, y, z; };
-struct Se3 { Quat r; double t[3]; };
-
-static Quat quat_from_R(const double R[9])    // Eigen's Quaterniond(Matrix3d) (Shepperd), as g2o::SE3Quat(R, t) uses
-{
-    Quat q;
-    double tr = R[0] + R[4] + R[8];
-    if (tr > 0) {
-        tr = std::sqrt(tr + 1.0);
-        q.w = 0.5 * tr;
-        tr = 0.5 / tr;
-        q.x = (R[7] - R[5]) * tr; q.y = (R[2] - R[6]) * tr; q.z = (R[3] - R[1]) * tr;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > R[4 * i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        double v[3];
-        tr = std::sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
-        v[i] = 0.5 * tr;
-        tr = 0.5 / tr;
-        q.w = (R[3 * k + j] - R[3 * j + k]) * tr;
-        v[j] = (R[3 * j + i] + R[3 * i + j]) * tr;
-        v[k] = (R[3 * k + i] + R[3 * i + k]) * tr;
-        q.x = v[0]; q.y = v[1]; q.z = v[2];
-    }
-    return q;
-}
-static void quat_normalize(Quat &q)           // se3quat.h:280-285
-{
-    if (q.w < 0) { q.w = -q.w; q.x = -q.x; q.y = -q.y; q.z = -q.z; }
-    const double n = std::sqrt(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
-    q.w /= n; q.x /= n; q.y /= n; q.z /= n;
-}
-static Quat quat_mul(const Quat &a, const Quat &b)
-{
-    return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
-            a.w * b.y + a.y * b.w + a.z * b.x - a.x * b.z, a.w * b.z + a.z * b.w + a.x * b.y - a.y * b.x};
-}
-static void quat_rotate(const Quat &q, const double v[3], double out[3])      // Eigen: v + w uv + q.vec x uv, uv = 2 q.vec x v
-{
-    double uv[3] = {q.y * v[2] - q.z * v[1], q.z * v[0] - q.x * v[2], q.x * v[1] - q.y * v[0]};
-    uv[0] += uv[0]; uv[1] += uv[1]; uv[2] += uv[2];
-    out[0] = v[0] + q.w * uv[0] + (q.y * uv[2] - q.z * uv[1]);
-    out[1] = v[1] + q.w * uv[1] + (q.z * uv[0] - q.x * uv[2]);
-    out[2] = v[2] + q.w * uv[2] + (q.x * uv[1] - q.y * uv[0]);
-}
-static void quat_to_R(const Quat &q, double R[9])
-{
-    const double tx = 2 * q.x, ty = 2 * q.y, tz = 2 * q.z;
-    const double twx = tx * q.w, twy = ty * q.w, twz = tz * q.w, txx = tx * q.x, txy = ty * q.x, txz = tz * q.x;
-    const double tyy = ty * q.y, tyz = tz * q.y, tzz = tz * q.z;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-static void se3_map(const Se3 &T, const double x[3], double out[3])
-{
-    quat_rotate(T.r, x, out);
-    out[0] += T.t[0]; out[1] += T.t[1]; out[2] += T.t[2];
-}
-static Se3 se3_exp(const double u[6])          // se3quat.h:223-257 (omega first, then upsilon)
-{
-    const double om[3] = {u[0], u[1], u[2]}, up[3] = {u[3], u[4], u[5]};
-    const double theta = std::sqrt(om[0] * om[0] + om[1] * om[1] + om[2] * om[2]);
-    const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
-    double O2[9], R[9], V[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    if (theta < 0.00001) {
-        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0) + O[i] + O2[i]; V[i] = R[i]; }
-    } else {
-        const double a = std::sin(theta) / theta, b = (1 - std::cos(theta)) / (theta * theta);
-        const double c = (theta - std::sin(theta)) / std::pow(theta, 3);
-        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0) + a * O[i] + b * O2[i]; V[i] = (i % 4 == 0) + b * O[i] + c * O2[i]; }
-    }
-    Se3 T;
-    T.r = quat_from_R(R);
-    quat_normalize(T.r);
-    for (int i = 0; i < 3; i++) T.t[i] = V[3 * i] * up[0] + V[3 * i + 1] * up[1] + V[3 * i + 2] * up[2];
-    return T;
-}
-static Se3 se3_mul(const Se3 &a, const Se3 &b)  // se3quat.h:104-110
-{
-    Se3 r = a;
-    double rt[3];
-    quat_rotate(a.r, b.t, rt);
-    r.t[0] += rt[0]; r.t[1] += rt[1]; r.t[2] += rt[2];
-    r.r = quat_mul(a.r, b.r);
-    quat_normalize(r.r);
-    return r;
-}
-
-// 6x6 symmetric positive definite solve (the reference: Eigen LDLT inside g2o::LinearSolverDense)
-static bool ldlt_solve6(const double H[36], const double b[6], double x[6])
-{
-    double L[36] = {0}, D[6];
-    for (int j = 0; j < 6; j++) {
-        double d = H[6 * j + j];
-        for (int k = 0; k < j; k++) d -= L[6 * j + k] * L[6 * j + k] * D[k];
-        if (!(std::fabs(d) > 0) || !std::isfinite(d)) return false;
-        D[j] = d;
-        L[6 * j + j] = 1;
-        for (int i = j + 1; i < 6; i++) {
-            double s = H[6 * i + j];
-            for (int k = 0; k < j; k++) s -= L[6 * i + k] * L[6 * j + k] * D[k];
-            L[6 * i + j] = s / d;
-        }
-    }
-    double y[6];
-    for (int i = 0; i < 6; i++) { double s = b[i]; for (int k = 0; k < i; k++) s -= L[6 * i + k] * y[k]; y[i] = s; }
-    for (int i = 0; i < 6; i++) y[i] /= D[i];
-    for (int i = 5; i >= 0; i--) { double s = y[i]; for (int k = i + 1; k < 6; k++) s -= L[6 * k + i] * x[k]; x[i] = s; }
-    return true;
-}
-
-struct Edge {
-    int idx; bool stereo;
-    double obs[3], xw[3], info;
-    double err[3];         // _error: refreshed only where g2o refreshes it
-    double pc[3];          // the point in the camera frame at the estimate compute_error last saw
-    bool robust; int level;
-};
-
-struct PoseProblem {
-    double fx, fy, cx, cy, bf;
-    std::vector<Edge> edges;
-    std::vector<int> active;
-    Se3 est;
-    double delta_mono, delta_stereo;
-
-    void compute_error(Edge &e) const         // types_six_dof_expmap.h:153-157,184-188; .cpp:290-306
-    {
-        double *p = e.pc;
-        se3_map(est, e.xw, p);
-        if (!e.stereo) {
-            e.err[0] = e.obs[0] - (p[0] / p[2] * fx + cx);
-            e.err[1] = e.obs[1] - (p[1] / p[2] * fy + cy);
-            e.err[2] = 0;
-        } else {
-            const float invz = 1.0f / (float)p[2];
-            const double u = p[0] * invz * fx + cx;
-            e.err[0] = e.obs[0] - u;
-            e.err[1] = e.obs[1] - (p[1] * invz * fy + cy);
-            e.err[2] = e.obs[2] - (u - bf * invz);
-        }
-    }
-    static double chi2(const Edge &e) { return (e.err[0] * e.err[0] + e.err[1] * e.err[1] + e.err[2] * e.err[2]) * e.info; }
-    void huber(const Edge &e, double c2, double rho[2]) const      // robust_kernel_impl.cpp:78-91
-    {
-        const double delta = e.stereo ? delta_stereo : delta_mono, dsqr = delta * delta;
-        if (c2 <= dsqr) { rho[0] = c2; rho[1] = 1.; }
-        else { const double s = std::sqrt(c2); rho[0] = 2 * s * delta - dsqr; rho[1] = delta / s; }
-    }
-    void compute_active_errors() { for (int k : active) compute_error(edges[k]); }
-    double active_robust_chi2() const
-    {
-        double sum = 0;
-        for (int k : active) {
-            const Edge &e = edges[k];
-            const double c2 = chi2(e);
-            if (e.robust) { double rho[2]; huber(e, c2, rho); sum += rho[0]; }
-            else sum += c2;
-        }
-        return sum;
-    }
-    // linearizeOplus (.cpp:266-288,335-364) + constructQuadraticForm (base_unary_edge.hpp:43-72).  Called right after
-    // compute_active_errors() at the same estimate, so the camera-frame points cached there are the ones g2o maps again.
-    void build_system(double H[36], double b[6]) const
-    {
-        double Hu[21] = {0};
-        for (int i = 0; i < 6; i++) b[i] = 0;
-        for (int k : active) {
-            const Edge &e = edges[k];
-            const double x = e.pc[0], y = e.pc[1], invz = 1.0 / e.pc[2], invz_2 = invz * invz;
-            double J[3][6];
-            J[0][0] = x * y * invz_2 * fx; J[0][1] = -(1 + (x * x * invz_2)) * fx; J[0][2] = y * invz * fx;
-            J[0][3] = -invz * fx; J[0][4] = 0; J[0][5] = x * invz_2 * fx;
-            J[1][0] = (1 + y * y * invz_2) * fy; J[1][1] = -x * y * invz_2 * fy; J[1][2] = -x * invz * fy;
-            J[1][3] = 0; J[1][4] = -invz * fy; J[1][5] = y * invz_2 * fy;
-            if (e.stereo) {
-                J[2][0] = J[0][0] - bf * y * invz_2; J[2][1] = J[0][1] + bf * x * invz_2; J[2][2] = J[0][2];
-                J[2][3] = J[0][3]; J[2][4] = 0; J[2][5] = J[0][5] - bf * invz_2;
-            }
-            double w = 1.0;
-            if (e.robust) { double rho[2]; huber(e, chi2(e), rho); w = rho[1]; }
-            const double wi = w * e.info;
-            // b -= rho' J^T Omega e and H += J^T (rho' Omega) J, upper triangle; written out per row count so the
-            // compiler sees fixed trip counts (the sums keep the order 0 + row0 + row1 (+ row2))
-            double wJ[3][6];
-            for (int r = 0; r < 6; r++) { wJ[0][r] = J[0][r] * wi; wJ[1][r] = J[1][r] * wi; }
-            if (!e.stereo) {
-                int u = 0;
-                for (int r = 0; r < 6; r++) {
-                    const double g = J[0][r] * e.info * e.err[0] + J[1][r] * e.info * e.err[1];
-                    b[r] -= w * g;
-                    for (int c = r; c < 6; c++, u++) Hu[u] += wJ[0][r] * J[0][c] + wJ[1][r] * J[1][c];
-                }
-            } else {
-                for (int r = 0; r < 6; r++) wJ[2][r] = J[2][r] * wi;
-                int u = 0;
-                for (int r = 0; r < 6; r++) {
-                    const double g = J[0][r] * e.info * e.err[0] + J[1][r] * e.info * e.err[1] + J[2][r] * e.info * e.err[2];
-                    b[r] -= w * g;
-                    for (int c = r; c < 6; c++, u++) Hu[u] += wJ[0][r] * J[0][c] + wJ[1][r] * J[1][c] + wJ[2][r] * J[2][c];
-                }
-            }
-        }
-        int u = 0;
-        for (int r = 0; r < 6; r++)
-            for (int c = r; c < 6; c++, u++) H[6 * r + c] = H[6 * c + r] = Hu[u];
-    }
-
-    // OptimizationAlgorithmLevenberg::solve driven by SparseOptimizer::optimize (sparse_optimizer.cpp:354-420)
-    void optimize(int iterations)
-    {
-        double lambda = 0, ni = 2;
-        int n_bad = 0;
-        // g2o recomputes the active errors and their robust chi2 at the top of every iteration; right after an accepted
-        // step they are exactly what the trial left on the edges, so that pass is skipped (same values, same sum)
-        bool fresh = false;
-        double carried = 0;
-        for (int it = 0; it < iterations; it++) {
-            if (!fresh) { compute_active_errors(); carried = active_robust_chi2(); }
-            double current = carried, temp = current;
-            const double ini = current;
-            double H[36], b[6], x[6];
-            build_system(H, b);
-            if (it == 0) {
-                double mx = 0;
-                for (int j = 0; j < 6; j++) mx = std::max(std::fabs(H[7 * j]), mx);
-                lambda = 1e-5 * mx; ni = 2; n_bad = 0;
-            }
-            double rho = 0;
-            int qmax = 0;
-            do {
-                const Se3 backup = est;
-                double Hl[36];
-                memcpy(Hl, H, sizeof Hl);
-                for (int j = 0; j < 6; j++) Hl[7 * j] += lambda;
-                for (int j = 0; j < 6; j++) x[j] = 0;
-                const bool ok2 = ldlt_solve6(Hl, b, x);
-                est = se3_mul(se3_exp(x), est);
-                compute_active_errors();
-                temp = active_robust_chi2();
-                if (!ok2) temp = DBL_MAX;
-                rho = current - temp;
-                double scale = 0;
-                for (int j = 0; j < 6; j++) scale += x[j] * (lambda * x[j] + b[j]);
-                scale += 1e-3;
-                rho /= scale;
-                if (rho > 0 && std::isfinite(temp)) {
-                    double alpha = 1. - std::pow((2 * rho - 1), 3);
-                    alpha = std::min(alpha, 2. / 3.);
-                    lambda *= std::max(1. / 3., alpha);
-                    ni = 2;
-                    current = temp;
-                    fresh = true; carried = temp;
-                } else {
-                    lambda *= ni;
-                    ni *= 2;
-                    est = backup;          // the edges keep the trial's errors, as in g2o
-                    fresh = false;
-                }
-                qmax++;
-            } while (rho < 0 && qmax < 10);
-            if (qmax == 10 || rho == 0) return;
-            if ((ini - current) * 1e3 < ini) n_bad++; else n_bad = 0;
-            if (n_bad >= 3) return;
-        }
-    }
-};
-}   // namespace
-
-extern "C" int orbp_pose_optimization(int n, const float *obs, const float *u_right, const float *inv_sigma2, const float *xw,
-                                      float fx, float fy, float cx, float cy, float bf, float *Tcw, uint8_t *outlier)
-{
-    if (n < 0 || !Tcw || !outlier || (n > 0 && (!obs || !inv_sigma2 || !xw))) return pfail(ORBX_E_INVALID, "bad arguments");
-    PoseProblem P;
-    P.fx = fx; P.fy = fy; P.cx = cx; P.cy = cy; P.bf = bf;
-    P.delta_mono = (float)std::sqrt(5.991); P.delta_stereo = (float)std::sqrt(7.815);     // const float delta* (:270-271)
-    double R0[9], t0[3];
-    for (int i = 0; i < 3; i++) { for (int j = 0; j < 3; j++) R0[3 * i + j] = Tcw[4 * i + j]; t0[i] = Tcw[4 * i + 3]; }
-    Se3 init;
-    init.r = quat_from_R(R0);
-    quat_normalize(init.r);
-    memcpy(init.t, t0, sizeof t0);
-    P.est = init;
-    P.edges.resize(n);
-    for (int i = 0; i < n; i++) {
-        Edge &e = P.edges[i];
-        e.idx = i; e.stereo = u_right && u_right[i] >= 0;
-        e.obs[0] = obs[2 * i]; e.obs[1] = obs[2 * i + 1]; e.obs[2] = e.stereo ? u_right[i] : 0;
-        for (int j = 0; j < 3; j++) e.xw[j] = xw[3 * i + j];
-        e.info = inv_sigma2[i];
-        e.err[0] = e.err[1] = e.err[2] = 0;
-        e.robust = true; e.level = 0;
-        outlier[i] = 0;
-    }
-    if (n < 3) return 0;                        // :363-364
-    const float chi2_mono = 5.991f, chi2_stereo = 7.815f;
-    int n_bad = 0;
-    for (int it = 0; it < 4; it++) {
-        P.est = init;                           // every round restarts from pFrame->mTcw (:375)
-        P.active.clear();
-        for (int i = 0; i < n; i++)
-            if (P.edges[i].level == 0) P.active.push_back(i);
-        if (!P.active.empty()) P.optimize(10);
-        n_bad = 0;
-        for (int i = 0; i < n; i++) {
-            Edge &e = P.edges[i];
-            if (outlier[i]) P.compute_error(e);
-            const float c2 = (float)PoseProblem::chi2(e);
-            if (c2 > (e.stereo ? chi2_stereo : chi2_mono)) { outlier[i] = 1; e.level = 1; n_bad++; }
-            else { outlier[i] = 0; e.level = 0; }
-            if (it == 2) e.robust = false;
-        }
-        if (n < 10) break;                      // optimizer.edges().size() < 10 (:443-444)
-    }
-    double R[9];
-    quat_to_R(P.est.r, R);
-    for (int i = 0; i < 16; i++) Tcw[i] = (i % 5 == 0) ? 1.f : 0.f;
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) Tcw[4 * i + j] = (float)R[3 * i + j];
-        Tcw[4 * i + 3] = (float)P.est.t[i];
-    }
-    return n - n_bad;
 }

@@ -41,7 +41,7 @@ extern "C" int orbp_bundle_adjustment(const orbp_lba_problem *p, int n_iteration
     LmRun run = {0, 0, 0, 0};
     h.activate();                                               // :187
     if (h.n_active > 0) lm_optimize(h, n_iterations, run);      // :188
-    for (int k = 0; k < h.K; k++) lba_se3_to_Tcw(h.est[k], Tcw_local + 16 * (size_t)k);    // :193-210
+    for (int k = 0; k < h.K; k++) se3_to_Tcw(h.est[k], Tcw_local + 16 * (size_t)k);    // :193-210
     for (int pt = 0; pt < h.P; pt++)                            // :213-235; a point without edges is vbNotIncludedMP
         if (p->edge_off[pt + 1] > p->edge_off[pt])
             for (int j = 0; j < 3; j++) xw[3 * (size_t)pt + j] = (float)h.xw[3 * (size_t)pt + j];

@@ -16,20 +16,10 @@
 
 #define EG_NLIN 29              // the estimates, then +delta and -delta along the 7 axes of vertex 0, then of vertex 1
 
-S3O_HD S3oSim eg_load(const double *p) { return {p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7]}; }     // Sim3::operator[] order
+S3O_HD S3oSim eg_load(const double *p) { return {{p[0], p[1], p[2], p[3]}, p[4], p[5], p[6], p[7]}; }     // Sim3::operator[] order
 S3O_HD void eg_store(double *p, const S3oSim &S)
 {
     p[0] = S.qx; p[1] = S.qy; p[2] = S.qz; p[3] = S.qw; p[4] = S.t0; p[5] = S.t1; p[6] = S.t2; p[7] = S.s;
-}
-// Eigen's Quaterniond::toRotationMatrix: nothing is normalised (g2o::Sim3 never normalises its r)
-S3O_HD void eg_quat_to_R(const S3oSim &q, double *R)
-{
-    const double tx = 2 * q.qx, ty = 2 * q.qy, tz = 2 * q.qz;
-    const double twx = tx * q.qw, twy = ty * q.qw, twz = tz * q.qw, txx = tx * q.qx, txy = ty * q.qx, txz = tz * q.qx;
-    const double tyy = ty * q.qy, tyz = tz * q.qy, tzz = tz * q.qz;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
 }
 // W.lu().solve(t) (sim3.h:217): Eigen's PartialPivLU of a 3 x 3 matrix, unblocked -- per column the first row of largest
 // magnitude comes up, a zero pivot skips its division -- then the permuted t through the unit lower and the upper triangle
@@ -70,7 +60,7 @@ S3O_HD void eg_log(const S3oSim &S, double *res)
 {
     const double sigma = log(S.s);
     double R[9];
-    eg_quat_to_R(S, R);
+    quat_to_R(S, R);
     const double d = 0.5 * (R[0] + R[4] + R[8] - 1);
     const double dR[3] = {R[7] - R[5], R[2] - R[6], R[3] - R[1]};       // deltaR
     const double eps = 0.00001;
@@ -164,7 +154,7 @@ S3O_HD double eg_h_term(const double *J, const double *K, int a, int b)
 S3O_HD void eg_to_Tcw(const S3oSim &S, float *T)
 {
     double R[9];
-    eg_quat_to_R(S, R);
+    quat_to_R(S, R);
     const double f = 1. / S.s;
     S3O_UNROLL
     for (int i = 0; i < 3; i++)

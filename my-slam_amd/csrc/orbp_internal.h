@@ -1,4 +1,4 @@
-// orbp_internal.h -- shared by orbp.cc, orbp_sim3.cc and orbp_init.cc; nothing here is part of the C ABI of include/orbp.h.
+// orbp_internal.h -- shared by the host solvers (orbp*.cc) and the GPU drivers that use their checks; nothing here is part of the C ABI of include/orbp.h.
 #pragma once
 
 // orbp.cc: sets the thread-local text that orbp_last_error() returns (not exported from liborbx.so)

@@ -97,7 +97,7 @@ extern "C" int orbp_local_bundle_adjustment(const orbp_lba_problem *p, float *Tc
         }
     }
     for (int e = 0; e < h.E; e++) erase[e] = h.flagged(e) ? 1 : 0;      // :715-743
-    for (int k = 0; k < h.K; k++) lba_se3_to_Tcw(h.est[k], Tcw_local + 16 * (size_t)k);    // :762-768
+    for (int k = 0; k < h.K; k++) se3_to_Tcw(h.est[k], Tcw_local + 16 * (size_t)k);    // :762-768
     for (size_t i = 0; i < h.xw.size(); i++) xw[i] = (float)h.xw[i];                       // :771-777
     if (stats) *stats = st;
     return ORBP_LBA_DONE;

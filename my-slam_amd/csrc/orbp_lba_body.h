@@ -1,11 +1,10 @@
 // orbp_lba_body.h -- the arithmetic of Optimizer::LocalBundleAdjustment (src/Optimizer.cc:453-778 of WChen09/My-SLAM, on g2o), one text
 // for the host solver (orbp_lba.cc, plain C++) and for the kernels (orbm_lba.hip).  Restated from Thirdparty/g2o/g2o:
-//   SE3Quat                         types/se3quat.h: operator* :104-110, map :119-121, exp :223-257, normalizeRotation :280-285
+//   SE3Quat, RobustKernelHuber      orbp_se3_body.h
 //   EdgeSE3ProjectXYZ               computeError types/types_six_dof_expmap.h:109-114, isDepthPositive :116-120,
 //                                   linearizeOplus types_six_dof_expmap.cpp:103-139, cam_project :141-147
 //   EdgeStereoSE3ProjectXYZ         computeError .h:139-144, isDepthPositive :146-150, linearizeOplus .cpp:188-235,
 //                                   cam_project with its float invz :150-157
-//   RobustKernelHuber               core/robust_kernel_impl.cpp:78-91
 //   constructQuadraticForm          core/base_binary_edge.hpp:55-120, one or both vertices free
 //   VertexSE3Expmap::oplusImpl      types_six_dof_expmap.h:62-65 (exp(update) * estimate); VertexSBAPointXYZ::oplusImpl types_sba.h (+=)
 //   BlockSolver_6_3::solve          core/block_solver.hpp:354-486 (Schur complement), setLambda :564-589
@@ -22,7 +21,7 @@
 //   stop          read at the top of every iteration and in the do ... while of the trial loop (sparse_optimizer.cpp:376,
 //                 optimization_algorithm_levenberg.cpp:149)
 //
-// Everything is fp64 and uses + - * / sqrt alone (the build's -ffp-contract=off keeps them unfused), except lba_se3_exp, which calls
+// Everything is fp64 and uses + - * / sqrt alone (the build's -ffp-contract=off keeps them unfused), except se3_exp, which calls
 // sin and cos of the side it is compiled for.  Every per-edge quantity (camera point, error, chi2, Huber weight, both Jacobians, the
 // 54 numbers of the edge's quadratic form) is therefore the same on host and device; the order of the sums over edges, sin / cos
 // and the inside of the dense solve are not.
@@ -36,6 +35,7 @@
 #include <math.h>
 #include <stdint.h>
 #include "orbp_lm_body.h"
+#include "orbp_se3_body.h"
 
 #if defined(__HIPCC__)
 #define LBA_HD __host__ __device__ __forceinline__
@@ -43,7 +43,7 @@
 #define LBA_HD static inline
 #endif
 
-struct LbaSe3 { double qx, qy, qz, qw, t0, t1, t2; };       // g2o::SE3Quat: a unit quaternion (w >= 0) and a translation
+typedef Se3 LbaSe3;                                     // the group itself is orbp_se3_body.h
 struct LbaCam { double fx, fy, cx, cy, bf; };
 
 // an edge's quadratic form: the upper triangles row-major, Hpl = B^T Omega A (6 x 3, row-major; B the pose Jacobian, A the point's)
@@ -54,130 +54,14 @@ struct LbaCam { double fx, fy, cx, cy, bf; };
 #define LBA_BL 33               // 3
 #define LBA_HPL 36              // 18
 
-// Eigen's Quaterniond(Matrix3d), the branch on the largest diagonal entry written out per case (orbp_sim3opt_body.h s3o_quat_from_R)
-LBA_HD void lba_quat_from_R(const double *R, LbaSe3 &q)
-{
-    double tr = R[0] + R[4] + R[8];
-    if (tr > 0) {
-        tr = sqrt(tr + 1.0);
-        q.qw = 0.5 * tr;
-        tr = 0.5 / tr;
-        q.qx = (R[7] - R[5]) * tr; q.qy = (R[2] - R[6]) * tr; q.qz = (R[3] - R[1]) * tr;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > (i ? R[4] : R[0])) i = 2;
-        if (i == 0) {
-            tr = sqrt(R[0] - R[4] - R[8] + 1.0);
-            q.qx = 0.5 * tr; tr = 0.5 / tr;
-            q.qw = (R[7] - R[5]) * tr; q.qy = (R[3] + R[1]) * tr; q.qz = (R[6] + R[2]) * tr;
-        } else if (i == 1) {
-            tr = sqrt(R[4] - R[8] - R[0] + 1.0);
-            q.qy = 0.5 * tr; tr = 0.5 / tr;
-            q.qw = (R[2] - R[6]) * tr; q.qz = (R[7] + R[5]) * tr; q.qx = (R[1] + R[3]) * tr;
-        } else {
-            tr = sqrt(R[8] - R[0] - R[4] + 1.0);
-            q.qz = 0.5 * tr; tr = 0.5 / tr;
-            q.qw = (R[3] - R[1]) * tr; q.qx = (R[2] + R[6]) * tr; q.qy = (R[5] + R[7]) * tr;
-        }
-    }
-}
-LBA_HD void lba_quat_normalize(LbaSe3 &q)                     // se3quat.h:280-285
-{
-    if (q.qw < 0) { q.qw = -q.qw; q.qx = -q.qx; q.qy = -q.qy; q.qz = -q.qz; }
-    const double n = sqrt(q.qw * q.qw + q.qx * q.qx + q.qy * q.qy + q.qz * q.qz);
-    q.qw /= n; q.qx /= n; q.qy /= n; q.qz /= n;
-}
-// Eigen's Quaterniond * Vector3d: v + w uv + q.vec x uv with uv = 2 q.vec x v
-LBA_HD void lba_rotate(const LbaSe3 &q, const double *v, double *o)
-{
-    double u0 = q.qy * v[2] - q.qz * v[1], u1 = q.qz * v[0] - q.qx * v[2], u2 = q.qx * v[1] - q.qy * v[0];
-    u0 += u0; u1 += u1; u2 += u2;
-    o[0] = v[0] + q.qw * u0 + (q.qy * u2 - q.qz * u1);
-    o[1] = v[1] + q.qw * u1 + (q.qz * u0 - q.qx * u2);
-    o[2] = v[2] + q.qw * u2 + (q.qx * u1 - q.qy * u0);
-}
-LBA_HD void lba_quat_to_R(const LbaSe3 &q, double *R)         // Eigen's toRotationMatrix
-{
-    const double tx = 2 * q.qx, ty = 2 * q.qy, tz = 2 * q.qz;
-    const double twx = tx * q.qw, twy = ty * q.qw, twz = tz * q.qw, txx = tx * q.qx, txy = ty * q.qx, txz = tz * q.qx;
-    const double tyy = ty * q.qy, tyz = tz * q.qy, tzz = tz * q.qz;
-    R[0] = 1 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
-    R[3] = txy + twz; R[4] = 1 - (txx + tzz); R[5] = tyz - twx;
-    R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1 - (txx + tyy);
-}
-LBA_HD void lba_map(const LbaSe3 &T, const double *x, double *o)      // se3quat.h:119-121
-{
-    lba_rotate(T, x, o);
-    o[0] += T.t0; o[1] += T.t1; o[2] += T.t2;
-}
-// Converter::toSE3Quat (src/Converter.cc:37-46) of a row-major 4 x 4 float pose: SE3Quat(R, t) normalises
-LBA_HD LbaSe3 lba_se3_from_Tcw(const float *T)
-{
-    double R[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) R[3 * i + j] = (double)T[4 * i + j];
-    LbaSe3 S;
-    lba_quat_from_R(R, S);
-    lba_quat_normalize(S);
-    S.t0 = (double)T[3]; S.t1 = (double)T[7]; S.t2 = (double)T[11];
-    return S;
-}
-// Converter::toCvMat(SE3Quat) (src/Converter.cc:48-52): to_homogeneous_matrix cast to float
-LBA_HD void lba_se3_to_Tcw(const LbaSe3 &S, float *T)
-{
-    double R[9];
-    lba_quat_to_R(S, R);
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) T[4 * i + j] = (float)R[3 * i + j];
-    T[3] = (float)S.t0; T[7] = (float)S.t1; T[11] = (float)S.t2;
-    T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
-}
-// SE3Quat::exp (se3quat.h:223-257), omega first, then upsilon; pow(theta, 3) as two multiplications on both sides
-LBA_HD LbaSe3 lba_se3_exp(const double *u)
-{
-    const double theta = sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    const double O[9] = {0, -u[2], u[1], u[2], 0, -u[0], -u[1], u[0], 0};
-    double O2[9], R[9], V[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++) O2[3 * i + j] = O[3 * i] * O[j] + O[3 * i + 1] * O[3 + j] + O[3 * i + 2] * O[6 + j];
-    if (theta < 0.00001) {
-        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0) + O[i] + O2[i]; V[i] = R[i]; }
-    } else {
-        const double sn = sin(theta), cs = cos(theta);
-        const double a = sn / theta, b = (1 - cs) / (theta * theta), c = (theta - sn) / (theta * theta * theta);
-        for (int i = 0; i < 9; i++) { R[i] = (i % 4 == 0) + a * O[i] + b * O2[i]; V[i] = (i % 4 == 0) + b * O[i] + c * O2[i]; }
-    }
-    LbaSe3 T;
-    lba_quat_from_R(R, T);
-    lba_quat_normalize(T);
-    T.t0 = V[0] * u[3] + V[1] * u[4] + V[2] * u[5];
-    T.t1 = V[3] * u[3] + V[4] * u[4] + V[5] * u[5];
-    T.t2 = V[6] * u[3] + V[7] * u[4] + V[8] * u[5];
-    return T;
-}
-LBA_HD LbaSe3 lba_se3_mul(const LbaSe3 &a, const LbaSe3 &b)     // se3quat.h:104-110
-{
-    LbaSe3 r;
-    const double bt[3] = {b.t0, b.t1, b.t2};
-    double rt[3];
-    lba_rotate(a, bt, rt);
-    r.t0 = a.t0 + rt[0]; r.t1 = a.t1 + rt[1]; r.t2 = a.t2 + rt[2];
-    r.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
-    r.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
-    r.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
-    r.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
-    lba_quat_normalize(r);
-    return r;
-}
 // VertexSE3Expmap::oplusImpl: setEstimate(SE3Quat::exp(update) * estimate())
-LBA_HD LbaSe3 lba_pose_oplus(const LbaSe3 &est, const double *update) { return lba_se3_mul(lba_se3_exp(update), est); }
+LBA_HD LbaSe3 lba_pose_oplus(const LbaSe3 &est, const double *update) { return se3_mul(se3_exp(update), est); }
 
 // computeError of both edges: pc = the point in the camera frame, err = obs - cam_project(pc) (err[2] = 0 on a monocular edge).
 // The stereo cam_project divides in double and keeps the quotient as a float (types_six_dof_expmap.cpp:151).
 LBA_HD void lba_edge_error(const LbaSe3 &T, const LbaCam &c, const double *xw, const float *obs, float u_right, double *pc, double *err)
 {
-    lba_map(T, xw, pc);
+    se3_map(T, xw, pc);
     if (u_right < 0) {
         err[0] = (double)obs[0] - (pc[0] / pc[2] * c.fx + c.cx);
         err[1] = (double)obs[1] - (pc[1] / pc[2] * c.fy + c.cy);
@@ -199,7 +83,7 @@ LBA_HD double lba_chi2(const double *err, double info)
 LBA_HD bool lba_depth_positive(const LbaSe3 &T, const double *xw)
 {
     double pc[3];
-    lba_map(T, xw, pc);
+    se3_map(T, xw, pc);
     return pc[2] > 0.0;
 }
 // An edge's robust kernel: none, RobustKernelHuber with LocalBundleAdjustment's deltas (sqrt(5.991) / sqrt(7.815) held as floats,
@@ -212,19 +96,13 @@ LBA_HD double lba_huber_delta(bool stereo, int kernel)
     return stereo ? (double)(float)sqrt(7.815) : kernel == LBA_KERNEL_BA ? (double)(float)sqrt(5.99) : (double)(float)sqrt(5.991);
 }
 LBA_HD double lba_chi2_threshold(bool stereo) { return stereo ? 7.815 : 5.991; }                                           // :680, :696
-LBA_HD void lba_huber(double c2, double delta, double &rho0, double &rho1)      // robust_kernel_impl.cpp:78-91
-{
-    const double dsqr = delta * delta;
-    if (c2 <= dsqr) { rho0 = c2; rho1 = 1.; }
-    else { const double s = sqrt(c2); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
-}
 // an active edge's term of activeRobustChi2 (sparse_optimizer.cpp:100-117)
 LBA_HD double lba_edge_robust_chi2(const double *err, double info, bool stereo, int robust)
 {
     const double c2 = lba_chi2(err, info);
     if (!robust) return c2;
     double rho0, rho1;
-    lba_huber(c2, lba_huber_delta(stereo, robust), rho0, rho1);
+    huber(c2, lba_huber_delta(stereo, robust), rho0, rho1);
     return rho0;
 }
 
@@ -235,8 +113,8 @@ LBA_HD void lba_edge_blocks(const LbaSe3 &T, const LbaCam &c, const double *xw, 
                             bool kf_free, double *blk)
 {
     double pc[3], R[9], A[3][3], B[3][6];
-    lba_map(T, xw, pc);
-    lba_quat_to_R(T, R);
+    se3_map(T, xw, pc);
+    quat_to_R(T, R);
     const double x = pc[0], y = pc[1], z = pc[2], z_2 = z * z;
     if (!stereo) {
         // _jacobianOplusXi = -1./z * tmp * R with tmp = [fx 0 -x/z*fx; 0 fy -y/z*fy] (.cpp:115-124)
@@ -267,7 +145,7 @@ LBA_HD void lba_edge_blocks(const LbaSe3 &T, const LbaCam &c, const double *xw, 
     double w = 1.;
     if (robust) {
         double rho0;
-        lba_huber(lba_chi2(err, info), lba_huber_delta(stereo, robust), rho0, w);
+        huber(lba_chi2(err, info), lba_huber_delta(stereo, robust), rho0, w);
     }
     const double wi = w * info;                              // weightedOmega = rho' * Omega
     const double r0 = -(info * err[0]) * w, r1 = -(info * err[1]) * w, r2 = -(info * err[2]) * w;      // omega_r (*= rho')

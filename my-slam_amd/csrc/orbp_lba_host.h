@@ -33,7 +33,7 @@ struct LbaHost {
         K = p->n_local; NK = p->n_local + p->n_fixed; P = p->n_points; E = p->edge_off[p->n_points];
         est.resize(NK); cam.resize(NK); kf_free.assign(NK, 0); kf_active.assign(NK, 0);
         for (int k = 0; k < NK; k++) {
-            est[k] = lba_se3_from_Tcw(p->Tcw + 16 * (size_t)k);
+            est[k] = se3_from_Tcw(p->Tcw + 16 * (size_t)k);
             const float *c = p->cam + 5 * (size_t)k;
             cam[k] = {c[0], c[1], c[2], c[3], c[4]};
             kf_free[k] = k < K && !p->local_fixed[k];

@@ -3,6 +3,13 @@
 // core/sparse_optimizer.cpp:354-419): one text for the host solvers (orbp_lba/ba/eg.cc) and the GPU drivers (orbm_lba/eg.hip)
 #pragma once
 #include <math.h>
+#if defined(__HIPCC__)
+#define LM_HD __host__ __device__ __forceinline__
+#define LM_UNROLL _Pragma("unroll")
+#else
+#define LM_HD static inline
+#define LM_UNROLL
+#endif
 // the bound of lm_optimize's loop over iterations: LocalBundleAdjustment asks for 5 and 10, BundleAdjustment for up to
 // ORBP_BA_MAX_ITERATIONS (include/orbp.h, the same number); the loop runs min(iterations, this) of them
 #define LM_MAX_ITERATIONS 100
@@ -76,4 +83,58 @@ static inline void lm_optimize(Ctx &ctx, int iterations, LmRun &run, double user
         if ((ini - current) * 1e3 < ini) n_bad++; else n_bad = 0;
         if (n_bad >= 3) break;
     }
+}
+
+// N x N LDL^T solve of (H + lambda I) x = b on the upper triangle Hu, row-major (the reference: Eigen's LDLT inside
+// g2o::LinearSolverDense), for the one vertex of PoseOptimization (N = 6) and of OptimizeSim3 (N = 7); false, and x = 0, where a
+// pivot is zero or not finite
+template <int N>
+LM_HD bool lm_ldlt_solve(const double *Hu, double lambda, const double *b, double *x)
+{
+    double H[N * N], L[N * N], D[N], y[N];
+    {
+        int u = 0;
+        LM_UNROLL
+        for (int r = 0; r < N; r++)
+            LM_UNROLL
+            for (int c = r; c < N; c++, u++) H[N * r + c] = H[N * c + r] = Hu[u];
+    }
+    LM_UNROLL
+    for (int j = 0; j < N; j++) H[(N + 1) * j] += lambda;
+    bool ok = true;
+    LM_UNROLL
+    for (int j = 0; j < N; j++) {
+        double d = H[N * j + j];
+        LM_UNROLL
+        for (int k = 0; k < j; k++) d -= L[N * j + k] * L[N * j + k] * D[k];
+        if (!(fabs(d) > 0) || !isfinite(d)) ok = false;
+        D[j] = d;
+        LM_UNROLL
+        for (int i = j + 1; i < N; i++) {
+            double s = H[N * i + j];
+            LM_UNROLL
+            for (int k = 0; k < j; k++) s -= L[N * i + k] * L[N * j + k] * D[k];
+            L[N * i + j] = s / d;
+        }
+    }
+    LM_UNROLL
+    for (int i = 0; i < N; i++) {
+        double s = b[i];
+        LM_UNROLL
+        for (int k = 0; k < i; k++) s -= L[N * i + k] * y[k];
+        y[i] = s;
+    }
+    LM_UNROLL
+    for (int i = 0; i < N; i++) y[i] /= D[i];
+    LM_UNROLL
+    for (int i = N - 1; i >= 0; i--) {
+        double s = y[i];
+        LM_UNROLL
+        for (int k = i + 1; k < N; k++) s -= L[N * k + i] * x[k];
+        x[i] = s;
+    }
+    if (!ok)
+        LM_UNROLL
+        for (int i = 0; i < N; i++) x[i] = 0;
+    return ok;
 }

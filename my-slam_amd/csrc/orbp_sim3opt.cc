@@ -62,7 +62,7 @@ extern "C" int orbp_sim3_from_rts(const float *R, const float *t, float s, doubl
     double Rd[9];
     for (int i = 0; i < 9; i++) Rd[i] = R[i];          // Converter::toMatrix3d
     S3oSim S;
-    s3o_quat_from_R(Rd, S);                            // Sim3(const Matrix3d &, ...) (sim3.h:64-67): Quaterniond(R), not normalised
+    quat_from_R(Rd, S);                            // Sim3(const Matrix3d &, ...) (sim3.h:64-67): Quaterniond(R), not normalised
     out[0] = S.qx; out[1] = S.qy; out[2] = S.qz; out[3] = S.qw;
     for (int i = 0; i < 3; i++) out[4 + i] = t[i];     // Converter::toVector3d
     out[7] = s;
@@ -87,7 +87,7 @@ extern "C" int orbp_optimize_sim3(int n, const float *x1c, const float *x2c, con
     P.fix_scale = fix_scale != 0;
     P.removed = flags;
     for (int i = 0; i < n; i++) flags[i] = 0;
-    S3oSim est = {S12[0], S12[1], S12[2], S12[3], S12[4], S12[5], S12[6], S12[7]};
+    S3oSim est = {{S12[0], S12[1], S12[2], S12[3]}, S12[4], S12[5], S12[6], S12[7]};
     S3oSim err_est = est;
     // a problem without edges optimises nothing (sparse_optimizer.cpp: optimize() returns on an empty active set)
     if (n > 0) s3o_optimize(P, est, err_est, P.fix_scale, 5);                      // :1182

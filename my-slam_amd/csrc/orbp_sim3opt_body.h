@@ -10,6 +10,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include "orbp_lm_body.h"
+#include "orbp_se3_body.h"
 
 #if defined(__HIPCC__)
 #define S3O_HD __host__ __device__ __forceinline__
@@ -27,61 +29,21 @@
 #define S3O_NLIN 15             // the estimate, then +delta and -delta along each of the 7 axes
 
 // g2o::Sim3: r (Eigen's coefficient order x, y, z, w; never normalised), t, s
-struct S3oSim { double qx, qy, qz, qw, t0, t1, t2, s; };
+struct S3oSim : Quat { double t0, t1, t2, s; };
 struct S3oCam { double fx, fy, cx, cy; };
 
-// Eigen's Quaterniond(Matrix3d) (orbp.cc quat_from_R), the branch on the largest diagonal entry written out per case
-S3O_HD void s3o_quat_from_R(const double *R, S3oSim &q)
-{
-    double tr = R[0] + R[4] + R[8];
-    if (tr > 0) {
-        tr = sqrt(tr + 1.0);
-        q.qw = 0.5 * tr;
-        tr = 0.5 / tr;
-        q.qx = (R[7] - R[5]) * tr; q.qy = (R[2] - R[6]) * tr; q.qz = (R[3] - R[1]) * tr;
-    } else {
-        int i = 0;
-        if (R[4] > R[0]) i = 1;
-        if (R[8] > (i ? R[4] : R[0])) i = 2;
-        if (i == 0) {               // j = 1, k = 2
-            tr = sqrt(R[0] - R[4] - R[8] + 1.0);
-            q.qx = 0.5 * tr; tr = 0.5 / tr;
-            q.qw = (R[7] - R[5]) * tr; q.qy = (R[3] + R[1]) * tr; q.qz = (R[6] + R[2]) * tr;
-        } else if (i == 1) {        // j = 2, k = 0
-            tr = sqrt(R[4] - R[8] - R[0] + 1.0);
-            q.qy = 0.5 * tr; tr = 0.5 / tr;
-            q.qw = (R[2] - R[6]) * tr; q.qz = (R[7] + R[5]) * tr; q.qx = (R[1] + R[3]) * tr;
-        } else {                    // j = 0, k = 1
-            tr = sqrt(R[8] - R[0] - R[4] + 1.0);
-            q.qz = 0.5 * tr; tr = 0.5 / tr;
-            q.qw = (R[3] - R[1]) * tr; q.qx = (R[2] + R[6]) * tr; q.qy = (R[5] + R[7]) * tr;
-        }
-    }
-}
-// Eigen's Quaterniond * Vector3d: v + w uv + q.vec x uv with uv = 2 q.vec x v (exact only for a unit quaternion; g2o's is not)
-S3O_HD void s3o_rotate(const S3oSim &q, double v0, double v1, double v2, double &o0, double &o1, double &o2)
-{
-    double u0 = q.qy * v2 - q.qz * v1, u1 = q.qz * v0 - q.qx * v2, u2 = q.qx * v1 - q.qy * v0;
-    u0 += u0; u1 += u1; u2 += u2;
-    o0 = v0 + q.qw * u0 + (q.qy * u2 - q.qz * u1);
-    o1 = v1 + q.qw * u1 + (q.qz * u0 - q.qx * u2);
-    o2 = v2 + q.qw * u2 + (q.qx * u1 - q.qy * u0);
-}
 // Sim3::map (sim3.h:144-146): s * (r * xyz) + t
 S3O_HD void s3o_map(const S3oSim &S, double x0, double x1, double x2, double &o0, double &o1, double &o2)
 {
     double r0, r1, r2;
-    s3o_rotate(S, x0, x1, x2, r0, r1, r2);
+    quat_rotate(S, x0, x1, x2, r0, r1, r2);
     o0 = S.s * r0 + S.t0; o1 = S.s * r1 + S.t1; o2 = S.s * r2 + S.t2;
 }
 // Sim3::operator* (sim3.h:266-272): nothing is normalised
 S3O_HD S3oSim s3o_mul(const S3oSim &a, const S3oSim &b)
 {
     S3oSim r;
-    r.qw = a.qw * b.qw - a.qx * b.qx - a.qy * b.qy - a.qz * b.qz;
-    r.qx = a.qw * b.qx + a.qx * b.qw + a.qy * b.qz - a.qz * b.qy;
-    r.qy = a.qw * b.qy + a.qy * b.qw + a.qz * b.qx - a.qx * b.qz;
-    r.qz = a.qw * b.qz + a.qz * b.qw + a.qx * b.qy - a.qy * b.qx;
+    quat_mul(a, b, r);
     s3o_map(a, b.t0, b.t1, b.t2, r.t0, r.t1, r.t2);
     r.s = a.s * b.s;
     return r;
@@ -92,7 +54,7 @@ S3O_HD S3oSim s3o_inverse(const S3oSim &a)
     S3oSim r;
     r.qx = -a.qx; r.qy = -a.qy; r.qz = -a.qz; r.qw = a.qw;
     const double f = -1. / a.s;
-    s3o_rotate(r, f * a.t0, f * a.t1, f * a.t2, r.t0, r.t1, r.t2);
+    quat_rotate(r, f * a.t0, f * a.t1, f * a.t2, r.t0, r.t1, r.t2);
     r.s = 1. / a.s;
     return r;
 }
@@ -144,7 +106,7 @@ S3O_HD S3oSim s3o_exp(const double *u)
             B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
         }
     }
-    s3o_quat_from_R(R, S);
+    quat_from_R(R, S);
     double W[9];
     S3O_UNROLL
     for (int i = 0; i < 9; i++) W[i] = (A * O[i] + B * O2[i]) + C * (i % 4 == 0);
@@ -189,13 +151,6 @@ S3O_HD void s3o_error(const S3oSim &S, const S3oCam &cam, const float *x, const 
     e1 = (double)obs[1] - (p1 / p2 * cam.fy + cam.cy);
 }
 S3O_HD double s3o_chi2(double e0, double e1, double info) { return (e0 * e0 + e1 * e1) * info; }
-// RobustKernelHuber::robustify (robust_kernel_impl.cpp:78-91): rho and rho'
-S3O_HD void s3o_huber(double c2, double delta, double &rho0, double &rho1)
-{
-    const double dsqr = delta * delta;
-    if (c2 <= dsqr) { rho0 = c2; rho1 = 1.; }
-    else { const double s = sqrt(c2); rho0 = 2 * s * delta - dsqr; rho1 = delta / s; }
-}
 
 // One edge: its robust chi2 into acc[S3O_CHI] and, with SYSTEM, the numeric Jacobian over lin[1..14] (scaled by 1 / (2 delta)) and
 // constructQuadraticForm: b += J^T (rho' * -(Omega e)), H += J^T (rho' Omega) J, upper triangle.  lin is the e or the inv array of a
@@ -208,7 +163,7 @@ S3O_HD void s3o_edge(const S3oSim *lin, const S3oCam &cam, const float *x, const
 {
     double e0, e1, rho0, rho1;
     s3o_error(lin[0], cam, x, obs, e0, e1);
-    s3o_huber(s3o_chi2(e0, e1, info), huber_delta, rho0, rho1);
+    huber(s3o_chi2(e0, e1, info), huber_delta, rho0, rho1);
     acc[SYSTEM ? S3O_CHI : 0] += rho0;
     if (!SYSTEM) return;
     const double scalar = 1.0 / (2 * 1e-9);
@@ -253,61 +208,9 @@ S3O_HD bool s3o_pair_bad(const S3oSim &S, const S3oSim &Sinv, const S3oCam &cam1
     return s3o_chi2(a0, a1, (double)inv_sigma2_1) > (double)th2 || s3o_chi2(b0, b1, (double)inv_sigma2_2) > (double)th2;
 }
 
-// 7x7 LDL^T solve of (H + lambda I) x = b on the upper triangle Hu (the reference: Eigen's LDLT inside g2o::LinearSolverDense), in
-// the manner of orbp.cc's ldlt_solve6; false, and x = 0, where a pivot is zero or not finite
-S3O_HD bool s3o_ldlt_solve7(const double *Hu, double lambda, const double *b, double *x)
-{
-    double H[49], L[49], D[7], y[7];
-    {
-        int u = 0;
-        S3O_UNROLL
-        for (int r = 0; r < 7; r++)
-            S3O_UNROLL
-            for (int c = r; c < 7; c++, u++) H[7 * r + c] = H[7 * c + r] = Hu[u];
-    }
-    S3O_UNROLL
-    for (int j = 0; j < 7; j++) H[8 * j] += lambda;
-    bool ok = true;
-    S3O_UNROLL
-    for (int j = 0; j < 7; j++) {
-        double d = H[7 * j + j];
-        S3O_UNROLL
-        for (int k = 0; k < j; k++) d -= L[7 * j + k] * L[7 * j + k] * D[k];
-        if (!(fabs(d) > 0) || !isfinite(d)) ok = false;
-        D[j] = d;
-        S3O_UNROLL
-        for (int i = j + 1; i < 7; i++) {
-            double s = H[7 * i + j];
-            S3O_UNROLL
-            for (int k = 0; k < j; k++) s -= L[7 * i + k] * L[7 * j + k] * D[k];
-            L[7 * i + j] = s / d;
-        }
-    }
-    S3O_UNROLL
-    for (int i = 0; i < 7; i++) {
-        double s = b[i];
-        S3O_UNROLL
-        for (int k = 0; k < i; k++) s -= L[7 * i + k] * y[k];
-        y[i] = s;
-    }
-    S3O_UNROLL
-    for (int i = 0; i < 7; i++) y[i] /= D[i];
-    S3O_UNROLL
-    for (int i = 6; i >= 0; i--) {
-        double s = y[i];
-        S3O_UNROLL
-        for (int k = i + 1; k < 7; k++) s -= L[7 * k + i] * x[k];
-        x[i] = s;
-    }
-    if (!ok)
-        S3O_UNROLL
-        for (int i = 0; i < 7; i++) x[i] = 0;
-    return ok;
-}
-
 // OptimizationAlgorithmLevenberg::solve (core/optimization_algorithm_levenberg.cpp:66-170, with this fork's _nBad stop :157-164)
-// driven by SparseOptimizer::optimize(iterations) (core/sparse_optimizer.cpp:354-420), as orbp.cc's PoseProblem::optimize restates
-// it, for the one 7-dof vertex.  ctx.system(T, sys) is computeActiveErrors + linearizeOplus + constructQuadraticForm at T with the
+// driven by SparseOptimizer::optimize(iterations) (core/sparse_optimizer.cpp:354-420), as pose_optimize (orbp_pose_body.h) restates
+// it for six unknowns, for the one 7-dof vertex.  ctx.system(T, sys) is computeActiveErrors + linearizeOplus + constructQuadraticForm at T with the
 // robust chi2 of the active edges in sys[S3O_CHI]; ctx.chi2(T) is computeActiveErrors + activeRobustChi2.  err_est follows the
 // estimate the errors on the active edges were last computed at: a rejected trial restores the vertex, not the edges
 // ("Edge state without per-edge storage").  The bounds are fixed: at most 10 iterations of at most 10 trials.
@@ -334,7 +237,7 @@ S3O_HD void s3o_optimize(Ctx &ctx, S3oSim &est, S3oSim &err_est, bool fix_scale,
         int qmax = 0;
         do {
             const S3oSim backup = est;
-            const bool ok2 = s3o_ldlt_solve7(sys, lambda, sys + S3O_B0, x);
+            const bool ok2 = lm_ldlt_solve<7>(sys, lambda, sys + S3O_B0, x);
             est = s3o_oplus(est, x, fix_scale);
             temp = ctx.chi2(est);
             err_est = est;

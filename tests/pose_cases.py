@@ -25,11 +25,14 @@ SINGLE_SIZES = (0, 2, 3, 9, 10, 63, 64, 65, 255, 256, 257, 1500)
 MIXED_SIZES = (0, 300, 2, 1500, 9, 64, 10, 257, 3, 30, 0, 200, 65)
 
 
-def scene(rng, n, noise=0.0, n_wrong=0, K=KITTI):
+def scene(rng, n, noise=0.0, n_wrong=0, K=KITTI, rot=None):
+    """rot = (axis, angle) sets the true rotation; without it the axis is random and the angle below 0.5 rad"""
     fx, fy, cx, cy = K
     ax = rng.normal(size=3)
     ax /= np.linalg.norm(ax)
     ang = rng.uniform(0, 0.5)
+    if rot is not None:
+        ax, ang = np.asarray(rot[0], np.float64) / np.linalg.norm(rot[0]), rot[1]
     Kx = po._skew(ax)
     R = np.eye(3) + math.sin(ang) * Kx + (1 - math.cos(ang)) * Kx @ Kx
     t = rng.uniform(-1, 1, 3)
@@ -48,11 +51,11 @@ def T_of(R, t):
     return T
 
 
-def problem(rng, n, trial, K=KITTI, bf=BF_KITTI, n_wrong=None):
+def problem(rng, n, trial, K=KITTI, bf=BF_KITTI, n_wrong=None, rot=None):
     """one trial of test_pose_optimization_equals_oracle; n_wrong overrides the n/5 of the odd trials"""
     if n_wrong is None:
         n_wrong = n // 5 if trial % 2 else 0
-    R, t, pw, u = scene(rng, n, noise=0.7, n_wrong=n_wrong, K=K)
+    R, t, pw, u = scene(rng, n, noise=0.7, n_wrong=n_wrong, K=K, rot=rot)
     inv_s2 = (1.0 / SIGMA2[rng.integers(0, 8, n)]).astype(np.float32)
     dR, dt = po._se3_exp(np.concatenate([rng.normal(size=3) * 0.02, rng.normal(size=3) * 0.1]))
     T0 = T_of(dR @ R, dR @ t + dt)
@@ -96,6 +99,23 @@ def fixed_point():
     return (u.astype(np.float32), np.ones(100, np.float32), pw.astype(np.float32), *KITTI, T_of(R, t), None, 0.0)
 
 
+LARGE_ANGLES = (2.2, 2.9, 3.1)
+
+
+def large_rotation():
+    """18 problems of 64 observations whose true rotation is LARGE_ANGLES about axes 0.05 off x, y and z, clean and with n/5
+    outliers: the trace of R is negative, so Quaterniond(Matrix3d) takes its three branches on the largest diagonal entry, which
+    no rotation below 0.5 rad reaches"""
+    rng = np.random.default_rng(29)
+    out = []
+    for a in range(3):
+        ax = np.zeros(3)
+        ax[a], ax[(a + 1) % 3] = 1.0, 0.05
+        for ang in LARGE_ANGLES:
+            out += [problem(rng, 64, trial, rot=(ax, ang)) for trial in (0, 1)]
+    return out
+
+
 def bench_problems(B, n, seed=1):
     """B problems of n observations in the tracking regime: a fifth of them outliers in every other problem, stereo in every third"""
     rng = np.random.default_rng(seed)
@@ -108,6 +128,7 @@ def all_cases():
     cases["mixed"] = mixed()
     cases["all_outliers"] = [all_outliers()]
     cases["fixed_point"] = [fixed_point()]
+    cases["large_rotation"] = large_rotation()
     return cases
 
 

@@ -76,6 +76,11 @@ def test_all_outliers_and_the_fixed_point(m, orbx):
     assert got[0][2] == 100 and not got[0][1].any() and np.abs(got[0][0] - pr[7]).max() < 1e-5
 
 
+def test_large_rotations_equal_the_host(m, orbx):
+    """rotations of 2.2, 2.9 and 3.1 rad about x, y and z: the three branches of Quaterniond(Matrix3d) below a positive trace"""
+    against_host(orbx, m.pose_optimization_batch(pc.cases()["large_rotation"]), "large_rotation")
+
+
 def test_a_result_depends_on_its_problem_alone(m):
     """the batch is byte-equal to B single-problem calls, to a second run and to the same problems in reversed order"""
     problems = pc.cases()["mixed"]
