@@ -26,7 +26,7 @@
  *                                 the Jacobi sweeps visit their pairs in the opposite order, and the left vectors of zero singular
  *                                 values are completed from the other end of the unit vectors
  * The spread between the two is the part of the reference's answer that this choice decides.
- *   variant C (-DCV_SHIM_ARITH_CANON)  variant A with the small float algebra of src/ORBmatcher.cc done as DESIGN.md section 2's
+ *   variant C (-DCV_SHIM_ARITH_CANON)  variant A with the small float algebra of src/ORBmatcher.cc and src/LocalMapping.cc done as DESIGN.md section 2's
  *                                 "Canonical semantics" table reads OpenCV 3.1.0 (each place cites its row).  The matcher pin
  *                                 (oracle/_ref/ref_matcher) compares integer match tables exactly, so it cannot absorb that part in a
  *                                 tolerance; variant A of the same driver (ref_matcher_a) is its sensitivity run.
@@ -75,9 +75,15 @@ inline void shim_need_f32(const Mat &m, const char *what)
 
 class MatExpr : public Mat {
 public:
+#ifdef CV_SHIM_ARITH_CANON
+    MatExpr(const Mat &m) : Mat(m), alpha(0) {}
+#else
     MatExpr(const Mat &m) : Mat(m) {}
+#endif
 #ifdef CV_SHIM_ARITH_CANON
     std::vector<float> raw;                              /* of a product: the float sums t0, row-major, for `A*B + C` (one cv::gemm) */
+    Mat scaled;                                          /* of `s * Mat`: the matrix and s, for `s*A - B` (one cv::addWeighted) */
+    double alpha;
 #endif
 };
 
@@ -213,7 +219,14 @@ inline MatExpr operator*(double s, const Mat &m)
 #else
         for (int x = 0; x < m.cols; x++) out.at<float>(y, x) = (float)(s * (double)m.at<float>(y, x));
 #endif
+#ifdef CV_SHIM_ARITH_CANON
+    MatExpr e(out);
+    e.scaled = m;
+    e.alpha = s;
+    return e;
+#else
     return MatExpr(out);
+#endif
 }
 inline MatExpr operator*(const Mat &m, double s) { return s * m; }
 inline MatExpr operator/(const Mat &m, double s) { return (1.0 / s) * m; }       /* OpenCV scales by the reciprocal */
@@ -226,6 +239,22 @@ inline MatExpr operator-(const Mat &a, const Mat &b)
         for (int x = 0; x < a.cols; x++) out.at<float>(y, x) = a.at<float>(y, x) - b.at<float>(y, x);
     return MatExpr(out);
 }
+
+#ifdef CV_SHIM_ARITH_CANON
+/* row "`alpha*row - row`": `s*A - B` is one MatOp_AddEx with alpha = s and beta = -1, cv::addWeighted(A, s, B, -1, 0), whose 32f kernel
+   computes (float)(a*alpha + b*beta + gamma) in double; alpha == 1 is cv::subtract in float (MatOp_AddEx::assign) */
+inline MatExpr operator-(const MatExpr &e, const Mat &b)
+{
+    if (e.scaled.empty()) return static_cast<const Mat &>(e) - b;
+    shim_same_f32(e.scaled, b, "s * Mat - Mat needs two CV_32F matrices of one size");
+    if (e.alpha == 1.0) return e.scaled - b;
+    Mat out(b.rows, b.cols, CV_32F);
+    for (int y = 0; y < b.rows; y++)
+        for (int x = 0; x < b.cols; x++)
+            out.at<float>(y, x) = (float)(((double)e.scaled.at<float>(y, x) * e.alpha + (double)b.at<float>(y, x) * -1.0) + 0.0);
+    return MatExpr(out);
+}
+#endif
 
 inline MatExpr operator+(const Mat &a, const Mat &b)
 {
